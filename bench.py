@@ -15,14 +15,21 @@ per rank); `--shard` picks how the (member, image-shard) grid is dealt to the ra
 `images` keeps every member on every rank.  value = N * batch * K / t.
 
 The round-1 variant (the step starts from decoded RGB u8 pixels already resident in HBM: the metric's "inputs resident" form) is
-`--workload ensemble8-resident`; the default run times it as well and reports it under "detail".
+`--workload ensemble8-resident`; a `--full` run times it as well and reports it under "detail".
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the `--steps` steps and prints the line (`roofline`, `cpu_baseline` and `detail` are null).
+`--full` adds the measurements that take runs of their own, on the JSON line:
   roofline     — the dominant kernel family, timed live with HIP events on the launch stream; `peak` is the vendor figure of
                  MI355X_MICROARCH.md, `peak_measured` the on-box probe (vip_microbench_*), both fractions are given;
   cpu_baseline — the fp32 CPU oracle ("port": the reference's TF path cannot run anywhere here) on a bounded sample of the same
                  workload with the protocol of SURVEY.md section 8(d) (batch 128, first batch discarded, >= 3 timed batches, all host
-                 cores of the box's share, Pillow decode + oracle resize + every member), rank 0, N = 1 only.
+                 cores of the box's share, Pillow decode + oracle resize + every member), rank 0, N = 1 only;
+  detail       — per-family kernel times, the resident-input variant, the strict-precision leg (checked in-run against the fast leg),
+                 the batch sweep and the measured peaks.
+
+`--dump-outputs DIR` writes what the last timed step returned, after the timed steps: DIR/scores.npy (float32 [images], the ensemble
+mean per image) and DIR/member_scores.npy (float32 [members, images], rows in the order of config.members).  The inputs are seeded: the same arguments
+give the same inputs in every run.
 """
 import argparse
 import json
@@ -30,7 +37,9 @@ import os
 import sys
 import time
 
-import torch
+T_START = time.perf_counter()
+
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -63,12 +72,33 @@ def parse():
     ap.add_argument("--cpu-batch", type=int, default=48, help="images per timed CPU batch (SURVEY 8(d) protocol: 128)")
     ap.add_argument("--cpu-warm", type=int, default=8, help="images of the discarded CPU warm-up batch (SURVEY 8(d) protocol: 128)")
     ap.add_argument("--no-resident-leg", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the resident-input and strict-precision legs, the batch sweep, the peak probes + roofline and the CPU "
+                         "baseline (each still subject to its --no-* switch); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores as DIR/scores.npy and DIR/member_scores.npy (float32)")
     return ap.parse_args()
 
 
 def note(msg: str):
-    """progress on stderr (stdout carries only the JSON line)"""
-    print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+    """progress on stderr (stdout carries only the JSON line), with the seconds since the process started"""
+    print(f"[bench {time.strftime('%H:%M:%S')} +{time.perf_counter() - T_START:.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def last_outputs(wl):
+    """what the last timed step returned to its caller, copied to the host: {name: float32 array}"""
+    out = {"scores": wl.scores}
+    if getattr(wl, "member_scores", None) is not None:
+        out["member_scores"] = wl.member_scores
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(d: str, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+    note(f"outputs of the last timed step written to {d}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in arrays.items()))
 
 
 def host_cores() -> int:
@@ -214,6 +244,8 @@ def main():
         wl = workloads.FakeWorkload(a.batch, rank, world)
         dt = timed_steps(wl, dist, a.steps, a.warmup)
         if rank == 0:
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, last_outputs(wl))
             print(json.dumps({"metric": "images/sec (200x200, full ensemble)", "value": a.batch * world * a.steps / dt, "unit": "images/sec",
                               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
                               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "none", "data": "fake",
@@ -245,10 +277,12 @@ def main():
     dt = timed_steps(wl, dist, a.steps, a.warmup)
     if rank == 0:
         note(f"{a.batch * world * a.steps / dt:.0f} images/s, {dt / a.steps * 1e3:.2f} ms/step")
+        if a.dump_outputs:              # before anything below steps `wl` again (the roofline's instrumented step)
+            dump_outputs(a.dump_outputs, last_outputs(wl))
 
     # the metric's "inputs already resident in HBM" form of the same step, for the record (never `value` here)
     resident = None
-    if not wl.resident and not a.no_resident_leg:
+    if a.full and not wl.resident and not a.no_resident_leg:
         wr = workloads.Workload(wl.name, wl.members, a.batch, rank, world, a.shard, resident=True, jpegs=wl.jpegs, models=wl.models,
                                 precision=mode, costs=costs)
         wr.member_streams = wl.member_streams                                # same resident members, same stream assignment
@@ -259,7 +293,7 @@ def main():
     # the price of the stated tolerance, driver-timed: the same step in STRICT precision (packed fp16-pair storage, three MFMAs per
     # product) - checked IN THE RUN against the fast leg on the same batch (a strict step that mis-dispatched would still print img/s)
     strict = None
-    if mode == "fast" and not a.no_strict_leg and a.shard == "images":
+    if a.full and mode == "fast" and not a.no_strict_leg and a.shard == "images":
         if rank == 0:
             note("strict-precision leg: building packed-strict members")
         one = [wl.jpeg_batches[0]]
@@ -305,7 +339,7 @@ def main():
 
     # batch sweep for the default step (the deep stages run at M = B x 49 rows: larger batches fill the chip better)
     sweep = None
-    if not a.no_batch_sweep and world == 1 and not wl.resident:
+    if a.full and not a.no_batch_sweep and world == 1 and not wl.resident:
         sweep = {str(a.batch): {"images_per_sec": a.batch * a.steps / dt, "ms_per_step": dt / a.steps * 1e3}}
         for bsz in (512, 1024):
             if bsz == a.batch:
@@ -323,7 +357,7 @@ def main():
             torch.cuda.empty_cache()
 
     roof, peaks = None, None
-    if rank == 0:
+    if a.full and rank == 0:
         note("peak probes + instrumented step")
         peaks = {"mfma_tflops": PEAK_MFMA_F16_TFLOPS, "hbm_gbs": PEAK_HBM_GBS}
         peaks.update(workloads.measure_peaks())
@@ -342,7 +376,7 @@ def main():
                 roof["flop_weighted"] = lv["flop_weighted"]
                 roof["levels_definition"] = lv["definition"]
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(wl, max(1, a.cpu_batches), max(1, a.cpu_batch), max(1, a.cpu_warm))
 
     if rank == 0:
@@ -364,15 +398,18 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
         }
-        detail = {"kernel_families": wl.extra(), "resident_input_variant": resident, "strict_precision": strict,
-                  "batch_sweep": sweep,
-                  "peaks": {"vendor": {"mfma_f16_tflops": PEAK_MFMA_F16_TFLOPS, "hbm_gbs": PEAK_HBM_GBS},
-                            "measured_on_box": {k: (round(v, 1) if isinstance(v, float) else v) for k, v in peaks.items() if k.endswith("_measured")},
-                            "guide_achievable_hbm_gbs": 6290.0,
-                            "note": "peak_measured (HBM) = the best of three copy probes on THIS box (vip_microbench_copy_variant); "
-                                    "MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy"}}
-        if world > 1:
-            detail["shard_plan"] = wl.plan.describe()
+        detail = None
+        if a.full:
+            detail = {"kernel_families": wl.extra(), "resident_input_variant": resident, "strict_precision": strict,
+                      "batch_sweep": sweep,
+                      "peaks": {"vendor": {"mfma_f16_tflops": PEAK_MFMA_F16_TFLOPS, "hbm_gbs": PEAK_HBM_GBS},
+                                "measured_on_box": {k: (round(v, 1) if isinstance(v, float) else v) for k, v in peaks.items()
+                                                    if k.endswith("_measured")},
+                                "guide_achievable_hbm_gbs": 6290.0,
+                                "note": "peak_measured (HBM) = the best of three copy probes on THIS box (vip_microbench_copy_variant); "
+                                        "MI355X_MICROARCH.md quotes 6.29 TB/s for a float4 copy"}}
+            if world > 1:
+                detail["shard_plan"] = wl.plan.describe()
         line["detail"] = detail
         print(json.dumps(line))
     wl.close()

@@ -36,6 +36,22 @@ def test_bench_single_rank_runs_in_process():
     assert "launching" not in r.stderr                    # no child launcher for one rank
 
 
+def test_bench_dump_outputs_writes_the_last_step(tmp_path):
+    """`--dump-outputs DIR`: the scores of the last timed step as float32 .npy, identical for identical arguments; the JSON line unchanged"""
+    import numpy as np
+    got = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--workload", "fake", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 2 and line["detail"]["steps_seen"] == 3 and line["ms_per_step"] > 0
+        a = np.load(d / "scores.npy")
+        assert a.dtype == np.float32 and a.tolist() == [1.0] * 4 + [2.0] * 4      # both ranks' payloads, written once (rank 0)
+        got.append(a)
+    assert np.array_equal(got[0], got[1])
+
+
 def test_bench_under_an_outer_launcher_does_not_relaunch():
     """the driver's N > 1 form: torch.distributed.run sets WORLD_SIZE - bench.py must join that world, not start another"""
     import socket
