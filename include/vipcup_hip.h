@@ -32,7 +32,8 @@ typedef enum vip_status {
     VIP_ERR_ALIGNMENT = -2,    /* channel count / stride not a multiple of 8 halfs   */
     VIP_ERR_UNSUPPORTED = -3,  /* shape outside what the kernel family implements    */
     VIP_ERR_LAUNCH = -4,       /* hipGetLastError() != hipSuccess after the launch   */
-    VIP_ERR_JPEG = -5          /* stream is not a baseline JPEG this decoder accepts */
+    VIP_ERR_JPEG = -5,         /* stream is not a baseline JPEG this decoder accepts */
+    VIP_ERR_PNG = -6           /* stream is not a PNG this decoder accepts           */
 } vip_status;
 
 /* activation codes shared by every epilogue */
@@ -327,6 +328,42 @@ int vip_jpeg_entropy_decode_h(const uint8_t* const* jpeg_h, const size_t* len_h,
  * left untouched). */
 int vip_jpeg_idct_rgb_u8(const int16_t* coef, const vip_jpeg_desc* desc, int n, int max_blocks,
                          uint8_t* planes_ws, uint8_t* rgb_u8, int maxH, int maxW, void* stream);
+
+/* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
+ * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
+typedef struct vip_png_desc {
+    int32_t width, height;            /* image size                                                      */
+    int32_t bit_depth;                /* 1, 2, 4, 8 or 16                                                */
+    int32_t color_type;               /* 0 gray, 2 RGB, 3 palette, 4 gray+alpha, 6 RGBA                  */
+    int32_t interlace;                /* 0 none, 1 Adam7                                                 */
+    int32_t channels;                 /* samples per pixel (1, 3, 1, 2, 4)                               */
+    int32_t bpp;                      /* filter distance in bytes: max(1, channels * bit_depth / 8)      */
+    int32_t palette_size;             /* PLTE entries (0 when the image has no palette)                  */
+    int64_t stream_off;               /* byte offset of the image's filtered scanlines in the batch buffer */
+    int64_t pass_off[7];              /* offset of each pass relative to stream_off (pass 0 only when not
+                                         interlaced; an empty Adam7 pass has no bytes)                   */
+    int32_t pass_w[7], pass_h[7];     /* pixels per row / rows of each pass (0 = empty or absent pass)   */
+    uint8_t palette[256][3];          /* PLTE entries as RGB, unused entries zero                         */
+} vip_png_desc;
+
+/* Host: walk the chunks (signature, critical-chunk CRCs are checked by vip_png_inflate_h), validate IHDR and fill the
+ * descriptor (stream_off = 0); *stream_bytes_h = the size of the filtered scanline stream, (1 + rowbytes) per row of every
+ * pass.  The per-image pixel cap VIP_MAX_JPEG_PIXELS (environment, default 64 Mi) applies: larger -> VIP_ERR_PNG. */
+int vip_png_probe_h(const uint8_t* png_h, size_t len, vip_png_desc* desc_h, size_t* stream_bytes_h);
+
+/* Host, multithreaded: check critical-chunk CRCs, inflate (RFC 1950/1951) the concatenated IDAT data of n PNG byte streams
+ * and pack the still-filtered scanlines back to back in stream_h; desc_h[i].stream_off are offsets into stream_h.  Filter
+ * types are validated (0..4).  Replaces the zlib half of tf.image.decode_png (dataset/dataset.py:30). */
+int vip_png_inflate_h(const uint8_t* const* png_h, const size_t* len_h, int n, vip_png_desc* desc_h, uint8_t* stream_h,
+                      size_t stream_cap, size_t* stream_used_h, int threads);
+
+/* Device: undo the scanline filters (None, Sub, Up, Average, Paeth) IN PLACE in `filtered` (a device copy of what
+ * vip_png_inflate_h produced) and expand to 8-bit RGB like libpng for channels=3: gray 1/2/4 bits by bit replication,
+ * palette by PLTE lookup (an index past the palette is black), alpha dropped, 16-bit samples reduced to round(v / 257)
+ * (png_set_scale_16).  Adam7 passes are scattered to their pixel positions.  rgb_u8 [n][maxH][maxW][3]; pixels beyond an
+ * image's size are left untouched. */
+int vip_png_unfilter_rgb_u8(uint8_t* filtered, const vip_png_desc* desc, int n, uint8_t* rgb_u8, int maxH, int maxW,
+                            void* stream);
 
 /* Host: the 1025x2 coefficient table of TensorFlow's legacy bicubic kernel (Keys a = -0.5). */
 int vip_bicubic_table_f32(float* table_h);

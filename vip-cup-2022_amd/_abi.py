@@ -33,6 +33,14 @@ class JpegDesc(C.Structure):
                 ("coef_off", C.c_int64 * 3), ("qt", (C.c_uint16 * 64) * 3), ("rgb_coded", C.c_int32)]
 
 
+class PngDesc(C.Structure):
+    """mirror of vip_png_desc (include/vipcup_hip.h)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32),
+                ("interlace", C.c_int32), ("channels", C.c_int32), ("bpp", C.c_int32), ("palette_size", C.c_int32),
+                ("stream_off", C.c_int64), ("pass_off", C.c_int64 * 7), ("pass_w", C.c_int32 * 7), ("pass_h", C.c_int32 * 7),
+                ("palette", (C.c_uint8 * 3) * 256)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/vipcup_hip.h declares
@@ -78,6 +86,9 @@ SIGNATURES = {
     "vip_jpeg_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_jpeg_entropy_decode_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_jpeg_idct_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
+    "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
+    "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
     "vip_bicubic_table_f32": (_i, [_vp]),
     "vip_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tta_augment_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

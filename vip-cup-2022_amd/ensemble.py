@@ -188,7 +188,7 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
                 shard: str = "images", costs: Optional[Sequence[float]] = None) -> np.ndarray:
     """Score images [0, n_images) with every member; returns ``[M, n_images]`` fp32 probabilities on every rank.
 
-    ``jpegs_for(lo, hi)`` returns the JPEG byte strings of images lo..hi-1 (read lazily, per batch).
+    ``jpegs_for(lo, hi)`` returns the JPEG / PNG byte strings of images lo..hi-1 (read lazily, per batch).
     ``members`` = [(spec, model)] with ``spec.input_hw`` and ``model.predict(x) -> [n, C]``.
     ``tta`` > 1: every image is scored ``tta`` times under ``apply_augment`` draws and the predictions are averaged
     (main.py:92,109-111, ``CFG.agg = 'mean'``); the JPEGs are still decoded once.
@@ -205,12 +205,12 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
             work.append((s, plan.units[rank][s], b0, min(b0 + batch_size, hi)))
 
     def host_stage(item):
-        """file read + Huffman decode of one batch (C++ threads, the GIL is released inside the ctypes call)"""
+        """file read + Huffman decode / inflate of one batch (C++ threads, the GIL is released inside the ctypes call)"""
         raws = jpegs_for(item[2], item[3])
         if scorer is not None:
             return raws
         from . import pipeline
-        return pipeline.entropy_decode(raws, pinned=True)
+        return pipeline.host_decode(raws, pinned=True)
 
     # read-ahead (the overlap the reference gets from tf.data's prefetch, dataset/dataset.py:101): while the GPU scores batch i the
     # host stage of batch i+2 runs on a worker thread, and the DEVICE half of batch i+1 (H2D of the coefficients, IDCT, colour) is
@@ -236,7 +236,7 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
                 from . import pipeline
                 st = futs.popleft().result()
                 submit_next()
-                decoded[0] = pipeline.decode_entropy(st)
+                decoded[0] = pipeline.decode_staged(st)
 
         for i, (s, midx, b0, b1) in enumerate(work):
             if decoded[0] is not None:
@@ -389,13 +389,13 @@ class MemberStreams:
 
 
 def measure_costs(members, raws: Sequence[bytes], dist=None, rank: int = 0) -> List[float]:
-    """ms per image of every member on a sample batch (JPEG byte strings), timed on rank 0 (a serial pass, the one
+    """ms per image of every member on a sample batch (JPEG / PNG byte strings), timed on rank 0 (a serial pass, the one
     ``MemberStreams._calibrate`` makes) and broadcast so that every rank derives the SAME hybrid ShardPlan.  Set-up traffic
     (one float per member), not part of the per-image data path."""
     from . import pipeline
     costs = torch.zeros((len(members),), dtype=torch.float64, device="cuda")
     if rank == 0:
-        batch = pipeline.decode_jpegs(list(raws))
+        batch = pipeline.decode_images(list(raws))
         inputs = member_inputs(batch, members)
         ms = MemberStreams(2)
         ms._calibrate(members, inputs)          # warm-up: first-launch costs (module load, attribute calls)
@@ -415,7 +415,7 @@ _MEMBER_STREAMS: Optional[MemberStreams] = None
 
 
 def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork=None) -> torch.Tensor:
-    """``staged`` = ``pipeline.entropy_decode(raws)`` (or the raw JPEG byte strings, or an already decoded batch).  ``after_fork``:
+    """``staged`` = ``pipeline.host_decode(raws)`` (or the raw JPEG / PNG byte strings, or an already decoded batch).  ``after_fork``:
     called once, between the fork and the join of the member streams (see ``MemberStreams.predict_all``).  Decode once -> per member: resize
     to its resolution, predict, multi->binary.  Returns [M, n] (device).
     ``flags`` bool [tta, n, 3] (hflip, vflip, gray): one pass per row over augmented copies of the resized batch, mean
@@ -424,7 +424,8 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
     else:
-        batch = pipeline.decode_entropy(staged) if isinstance(staged, tuple) else pipeline.decode_jpegs(staged)
+        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
+            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
     hook = [after_fork]
     global _MEMBER_STREAMS
     if _MEMBER_STREAMS is None:

@@ -101,10 +101,11 @@ def main(argv=None):
     calib = None
     if a.calibration_images and mode == "fast" and not a.no_bias_calibration:
         files = sorted(glob(os.path.join(a.calibration_images, "*.jpg")) + glob(os.path.join(a.calibration_images, "*.jpeg")) +
-                       glob(os.path.join(a.calibration_images, "*.JPG")))[:32]
+                       glob(os.path.join(a.calibration_images, "*.JPG")) + glob(os.path.join(a.calibration_images, "*.png")) +
+                       glob(os.path.join(a.calibration_images, "*.PNG")))[:32]
         if not files:
-            raise ValueError(f"--calibration-images {a.calibration_images}: no *.jpg / *.jpeg files")
-        calib = pipeline.decode_jpegs([open(f, "rb").read() for f in files])
+            raise ValueError(f"--calibration-images {a.calibration_images}: no *.jpg / *.jpeg / *.png files")
+        calib = pipeline.decode_images([open(f, "rb").read() for f in files])
         if rank == 0:
             print(f"> BIAS CALIBRATION on {len(files)} images from {a.calibration_images}")
     build = dict(bias_calibration=not a.no_bias_calibration, precision=mode, calibration_batch=calib)

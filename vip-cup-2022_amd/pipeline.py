@@ -8,7 +8,8 @@ re-decodes the files for every model.
 """
 import ctypes as C
 import os
-from typing import Dict, List, Sequence, Tuple
+import re
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,7 +29,8 @@ def bicubic_table(device) -> torch.Tensor:
     return _TABLE_DEV[key]
 
 
-MAX_JPEG_PIXELS = int(os.environ.get("VIP_MAX_JPEG_PIXELS", str(64 << 20)))   # per image; the task's images are 200 x 200
+# per image, JPEG and PNG (csrc/png_host.cpp reads the same variable); the task's images are 200 x 200
+MAX_JPEG_PIXELS = int(os.environ.get("VIP_MAX_JPEG_PIXELS", str(64 << 20)))
 
 
 def entropy_decode(jpegs: Sequence[bytes], threads: int = 0, pinned: bool = False):
@@ -83,6 +85,161 @@ class DecodedBatch:
                                      maxH, maxW, _p(out), out_h, out_w, c_out, _stream())
         _abi.check(st, fn)
         return out
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+class PngStage:
+    """What ``inflate_pngs`` returns: ``desc`` (ctypes array of PngDesc) and the still-filtered scanlines of the batch
+    (uint8 numpy array, or a page-locked torch tensor), padded to whole 4-byte words (the device kernel reads words)."""
+
+    def __init__(self, desc, stream):
+        self.desc, self.stream = desc, stream
+
+    def __len__(self):
+        return len(self.desc)
+
+
+class MixedStage:
+    """``host_decode`` of a batch that holds PNGs: the PNG subset inflated, the JPEG subset (if any) entropy-decoded,
+    and where each image of the batch sits in them."""
+
+    def __init__(self, n, png_idx, png, jpeg_idx, jpeg):
+        self.n, self.png_idx, self.png, self.jpeg_idx, self.jpeg = n, png_idx, png, jpeg_idx, jpeg
+
+    def __len__(self):
+        return self.n
+
+
+def _remap_index(msg: str, index: Optional[Sequence[int]]) -> str:
+    if index is None:
+        return msg
+    return re.sub(r"png image (\d+)", lambda m: f"png image {index[int(m.group(1))]}", msg)
+
+
+def inflate_pngs(pngs: Sequence[bytes], threads: int = 0, pinned: bool = False,
+                 index: Optional[Sequence[int]] = None) -> PngStage:
+    """Host stage of the PNG path, the twin of ``entropy_decode``: chunk walk + CRC checks + inflate (C++ threads, the
+    GIL is released inside the ctypes call) into the still-filtered scanline stream of the batch.  ``index``: the batch
+    position of every PNG, used in error messages.  Raises VipError (naming the image) for a stream that is not a valid
+    PNG or whose size exceeds VIP_MAX_JPEG_PIXELS."""
+    lib = _abi.lib()
+    n = len(pngs)
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in pngs]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in pngs])
+    desc = (_abi.PngDesc * n)()
+    total = 0
+    tmp = _abi.PngDesc()
+    need = C.c_size_t(0)
+    for i in range(n):
+        where = i if index is None else index[i]
+        st = lib.vip_png_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
+        if st != 0:
+            raise _abi.VipError(f"png image {where}: vip_png_probe_h failed with vip_status {st}: "
+                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
+        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"png image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+        total += need.value
+    size = (total + 3) // 4 * 4 + 4                 # whole words, and never empty
+    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
+    stream = stream_t.numpy() if pinned else np.empty((size,), dtype=np.uint8)
+    used = C.c_size_t(0)
+    st = lib.vip_png_inflate_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
+    if st != 0:
+        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
+        raise _abi.VipError(f"vip_png_inflate_h failed with vip_status {st}: {msg}")
+    return PngStage(desc, stream_t if pinned else stream)
+
+
+def _png_into(stage: PngStage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
+    """Launch the unfilter + expand kernel for the PNGs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
+    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
+    full = (_abi.PngDesc * n)()                       # the other rows get all-zero descriptors: no pass, nothing written
+    for k, i in enumerate(slots):
+        full[i] = stage.desc[k]
+    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
+    if isinstance(stage.stream, torch.Tensor):
+        stream_d = stage.stream.to(device, non_blocking=True)
+    else:
+        stream_d = torch.from_numpy(stage.stream).to(device)
+    st = _abi.lib().vip_png_unfilter_rgb_u8(_p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW, _stream())
+    _abi.check(st, "vip_png_unfilter_rgb_u8")
+
+
+def decode_png_stage(staged: PngStage, device="cuda") -> DecodedBatch:
+    """Device half of the PNG path, the twin of ``decode_entropy``: ``staged`` = ``inflate_pngs(...)``.  Undoes the
+    scanline filters and expands to 8-bit RGB like ``tf.image.decode_png(channels=3)`` (dataset/dataset.py:30): gray
+    1/2/4 bits by bit replication, palette through PLTE (an index past it is black), alpha dropped (tRNS ignored), 16-bit
+    samples reduced to round(v / 257) (libpng ``png_set_scale_16``), Adam7 passes scattered to their pixels."""
+    n = len(staged.desc)
+    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
+    maxH = max(h for h, _ in sizes_host)
+    maxW = max(w for _, w in sizes_host)
+    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
+    _png_into(staged, range(n), n, rgb, device)
+    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
+    return DecodedBatch(rgb, sizes, sizes_host)
+
+
+def image_format(raw: bytes, i: int = 0) -> str:
+    """"jpeg" or "png", from the magic bytes (not the file name); anything else raises VipError naming image ``i``."""
+    if raw[:2] == b"\xff\xd8":
+        return "jpeg"
+    if raw[:8] == PNG_SIGNATURE:
+        return "png"
+    raise _abi.VipError(f"image {i}: neither a JPEG (FF D8) nor a PNG (89 50 4E 47 0D 0A 1A 0A) signature")
+
+
+def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False):
+    """Host stage of ``decode_images``: picks the format of every image by its magic bytes.  An all-JPEG batch returns
+    exactly what ``entropy_decode`` returns (same calls, same buffers); a batch with PNGs returns a ``MixedStage``."""
+    kinds = [image_format(r, i) for i, r in enumerate(raws)]
+    if "png" not in kinds:
+        return entropy_decode(raws, threads, pinned)
+    png_idx = [i for i, k in enumerate(kinds) if k == "png"]
+    jpeg_idx = [i for i, k in enumerate(kinds) if k == "jpeg"]
+    png = inflate_pngs([raws[i] for i in png_idx], threads, pinned, index=png_idx)
+    jpeg = entropy_decode([raws[i] for i in jpeg_idx], threads, pinned) if jpeg_idx else None
+    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg)
+
+
+def decode_staged(staged, device="cuda") -> DecodedBatch:
+    """Device half of ``decode_images``: ``staged`` = ``host_decode(...)`` (or ``entropy_decode`` / ``inflate_pngs``).  In a
+    mixed batch the PNG kernel writes straight into the batch's pixels and the JPEG subset, decoded as ``decode_entropy``
+    does, is copied into its rows."""
+    if isinstance(staged, tuple):
+        return decode_entropy(staged, device)
+    if isinstance(staged, PngStage):
+        return decode_png_stage(staged, device)
+    n = staged.n
+    sizes_host: List[Tuple[int, int]] = [(0, 0)] * n
+    for k, i in enumerate(staged.png_idx):
+        d = staged.png.desc[k]
+        sizes_host[i] = (int(d.height), int(d.width))
+    jb = None
+    if staged.jpeg is not None:
+        jb = decode_entropy(staged.jpeg, device)
+        for k, i in enumerate(staged.jpeg_idx):
+            sizes_host[i] = jb.sizes_host[k]
+    maxH = max(h for h, _ in sizes_host)
+    maxW = max(w for _, w in sizes_host)
+    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
+    _png_into(staged.png, staged.png_idx, n, rgb, device)
+    if jb is not None:
+        rows = torch.tensor(staged.jpeg_idx, dtype=torch.long, device=device)
+        rgb[rows, :jb.rgb.shape[1], :jb.rgb.shape[2]] = jb.rgb
+    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
+    return DecodedBatch(rgb, sizes, sizes_host)
+
+
+def decode_images(raws: Sequence[bytes], device="cuda", threads: int = 0) -> DecodedBatch:
+    """``build_decoder(ext=...)`` for a batch of JPEG and / or PNG byte strings (dataset/dataset.py:22-30), the format
+    of each image picked from its content."""
+    return decode_staged(host_decode(raws, threads), device)
 
 
 def decode_jpegs(jpegs: Sequence[bytes], device="cuda", threads: int = 0) -> DecodedBatch:
@@ -180,7 +337,7 @@ class Dataset:
             yield buf.pop(int(rng.integers(len(buf))))
 
     def _host_stage(self, items):
-        """read + entropy-decode the images of one batch that are not cached (runs on the read-ahead thread)"""
+        """read + entropy-decode / inflate the images of one batch that are not cached (runs on the read-ahead thread)"""
         todo = [i for i, _ in items if i not in self._cached]
         todo = list(dict.fromkeys(todo))
         if not todo:
@@ -191,7 +348,7 @@ class Dataset:
         for i in todo:
             with open(self.paths[i], "rb") as f:            # tf.io.read_file (dataset.py:24)
                 raws.append(f.read())
-        return todo, entropy_decode(raws, self.threads, pinned=torch.cuda.is_available())
+        return todo, host_decode(raws, self.threads, pinned=torch.cuda.is_available())
 
     def _device_stage(self, items, staged):
         from . import ops
@@ -201,7 +358,7 @@ class Dataset:
             if self.decode_fn is not None:
                 x = ops.to_device_nhwc8(torch.from_numpy(np.stack(host)), self.device, self.dtype)
             else:
-                x = decode_entropy(host, self.device).resized(self.img_size[0], self.img_size[1], dtype=self.dtype)
+                x = decode_staged(host, self.device).resized(self.img_size[0], self.img_size[1], dtype=self.dtype)
             fresh = {i: x[j] for j, i in enumerate(todo)}
             if self.cache:
                 self._cached.update(fresh)
