@@ -111,6 +111,23 @@ int vip_gemm_bias_act_f16(const void* A, const void* W, const float* bias, const
                           void* C, int M, int N, int K, int lda, int ldw, int ldc, int ldr,
                           int act_pre, int act_post, void* stream);
 
+/* The same with a LayerNorm over K folded into the activation operand:
+ *   C[M,N] = act_post(act_pre(LN(A[M,K]; gamma, beta, eps) @ W[N,K]^T + bias) + residual)
+ * in ONE launch: the row is normalised in the registers of the GEMM that consumes it (fp32 two-pass statistics, the normalised
+ * operand rounded to fp16 exactly where vip_layernorm_f16 would have stored it), so LN(A) is neither written nor read back.
+ * ln_gamma, ln_beta [K] f32; the other arguments and the epilogue modes ((activation) or (residual [+ post-ReLU])) as
+ * vip_gemm_bias_act_f16.  vip_ln_gemm_supported(M, K, N, act_pre) != 0 for the shapes it takes: what the kernel can run (64 < K <= 384,
+ * K % 8 == 0, M >= 16384, N >= 256) less the shapes that measured no faster than the two launches (M < 65536 with N > 512: too few
+ * workgroups for the chip; VIP_LN_GEMM_ALL=1 lifts this for A/B runs and tests).  Anything else returns VIP_ERR_UNSUPPORTED - use
+ * vip_layernorm_f16 + vip_gemm_bias_act_f16.
+ * Replaces LayerNormalization -> Dense of models/tfimm/architectures/convnext.py:220-229 (norm -> fc1, stage 2) and
+ * models/gcvit/layers/block.py:60-81 (level 1 norm2 -> fc1, level 2 norm1 -> qkv with a global query); the same pattern of
+ * vit.py:170-227 (norm1 -> qkv, norm2 -> fc1) and the other level 2 layers of GCViT are shapes the policy leaves on two launches. */
+int vip_ln_gemm_supported(int M, int K, int N, int act);
+int vip_ln_gemm_bias_act_f16(const void* A, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* W,
+                             const float* bias, const void* residual, void* C, int M, int N, int K, int lda, int ldw,
+                             int ldc, int ldr, int act_pre, int act_post, void* stream);
+
 /* Few-row Dense with a SPLIT fp16 output:  v = act(A[M,K] @ W[N,K]^T + bias);  C[m][0][n] = fp16(v), C[m][1][n] =
  * fp16(v - fp16(v)), C is [M][2][N] f16.  For the last layer of a squeeze-excite block whose matrices are too large for
  * vip_se_gate_f16 (resnet_rs_model.py:167-180 at 1024/2048 channels): the gate keeps ~22 bits.  M <= 256, N % 4 == 0. */

@@ -51,6 +51,8 @@ SIGNATURES = {
     "vip_conv2d_gated_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_conv2d_hilo_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
+    "vip_ln_gemm_supported": (_i, [_i, _i, _i, _i]),
+    "vip_ln_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 4 + [_i] * 9 + [_vp]),
     "vip_mlp_fused_supported": (_i, [_i, _i, _i, _i]),
     "vip_mlp_fused_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 6 + [_i] * 9 + [_vp]),
     "vip_se_gate_f16": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),

@@ -75,6 +75,9 @@ struct ConvArgs {
     int gate_hw;       // pixels per image (image index of pixel m = m / gate_hw)
     float out_scale;   // H2: 1 / (power-of-two scale folded into the weights AND the bias), applied to the accumulators
     int* status;       // H2: device word raised to VIP_H2_OVERFLOW when an output does not fit the fp16 range (may be NULL)
+    const float* ln_g; // pwx_ln_kernel: LayerNorm scale / shift [K] fp32 over the input row, applied to the activation fragments (else NULL)
+    const float* ln_b;
+    float ln_eps;
 };
 
 // ---- H2 epilogue core: 8 consecutive channels of one pixel (two accumulator quads) -> activation -> (+ residual) -> post -> packed
@@ -450,7 +453,7 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
             U4H8 r;
             if constexpr (RES)
                 r.u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                    rb_res, ok ? (unsigned)((m * a.ldr + a.res_off + n) * 2) : OOB, 0, 0));
+                                                    rb_res, ok ? ((unsigned)m * (unsigned)a.ldr + (unsigned)(a.res_off + n)) * 2u : OOB, 0, 0));
             U4H8 o;
 #pragma unroll
             for (int j = 0; j < 8; j += 2) {
@@ -463,7 +466,7 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
             }
             __builtin_amdgcn_raw_buffer_store_b128(
                 __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o.u), rb_y,
-                ok ? (unsigned)((m * a.ldy + a.cout_off + n) * 2) : OOB, 0, 0);
+                ok ? ((unsigned)m * (unsigned)a.ldy + (unsigned)(a.cout_off + n)) * 2u : OOB, 0, 0);      // (unsigned: spans < 4 GiB, m * ld * 2 may pass 2^31)
         }
     }
 }
@@ -936,8 +939,15 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode
 // (KSC 64-half chunks: <= 64 VGPRs at 32 pixels per wave) and walks over every 128-channel tile of N: the weight chunks of
 // (tile, chunk) pairs stream through the same double-buffered LDS image back to back - the prefetch of tile t+1's first chunk is issued
 // under tile t's last MFMAs, so there is one fill per workgroup instead of one per 128 channels - and the activations are read once.
-template <int KSC, int PT>
-__global__ __launch_bounds__(256, 2) void pwx_kernel(ConvArgs a, int mode) {
+//
+// LN = true (pwx_ln_kernel, vip_ln_gemm_bias_act_f16): the rows are LayerNorm-ed over K on their way in.  A row's K channels sit in the
+// four lanes (l15, lq = 0..3) of its pixel, so once the fragments have landed the statistics are in-lane sums over the lane's 8-channel
+// groups plus two lane exchanges (as ln_fragments of mlp_fused.hip): fp32 two-pass mean / variance and the expression of layernorm_kernel
+// (pointwise.hip), and the normalised row is rounded to fp16 IN PLACE - the MFMA operand is what the stand-alone launch would have
+// stored, without its write and the read back (2 x M x K x 2 bytes per layer).  Replaces LayerNormalization -> Dense of the reference
+// (tfimm vit.py:170-227 norm1 -> qkv and norm2 -> fc1, convnext.py:220-229 norm -> fc1, gcvit/layers/block.py:60-81).
+template <int KSC, int PT, bool LN>
+__device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
     constexpr int NG = 2, NB = 64 * NG, ROWB = 160;
     constexpr int STAGE = NB * ROWB;
     constexpr int W_IT = NB / 32;
@@ -995,7 +1005,8 @@ __global__ __launch_bounds__(256, 2) void pwx_kernel(ConvArgs a, int mode) {
 #pragma unroll
     for (int p = 0; p < PT; ++p) {
         const int m = m0 + p * 16 + l15;
-        const unsigned xo = m < a.M ? (unsigned)((m * a.ldx + lq * (H2 ? 16 : 8)) * 2) : 0xFFFF0000u;
+        // (unsigned: m * ldx * 2 passes 2^31 on the large maps; the span is checked < 4 GiB by the host)
+        const unsigned xo = m < a.M ? ((unsigned)m * (unsigned)a.ldx + (unsigned)(lq * (H2 ? 16 : 8))) * 2u : 0xFFFF0000u;
 #pragma unroll
         for (int kc = 0; kc < KSC; ++kc)
 #pragma unroll
@@ -1004,6 +1015,82 @@ __global__ __launch_bounds__(256, 2) void pwx_kernel(ConvArgs a, int mode) {
                 xf[2 * kc + ks][p].u = __builtin_bit_cast(
                     uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? xo + kc * 128 + ks * (H2 ? 16 : 64) : OOB, 0, 0));
             }
+    }
+    if constexpr (LN && !H2) {
+        // fragment i = 2 kc + ks of a lane holds channels 64 kc + 32 ks + 8 lq + 0..7.  Channels beyond K (the K tail, and whole
+        // chunks when K < 64 KSC) were loaded as zeros: they add nothing to the sum, are left out of the squared deviations, and
+        // must STAY zero - their gamma and beta are staged as zeros, so a masked channel gets d * 0 + 0 = 0 (d is finite)
+        // (beta must not leak into a channel whose weights are only zero in LDS: see the note at xf).  Rows beyond M are all
+        // zeros: mean 0, rstd = rsqrt(eps), finite, and never stored.
+        // gamma / beta: staged once per workgroup (zeros beyond K), read back per fragment with the lane's own 8-channel offsets
+        __shared__ __attribute__((aligned(16))) float lnp[2][64 * KSC];
+        for (int c = tid; c < 64 * KSC; c += 256) {
+            lnp[0][c] = c < a.K ? a.ln_g[c] : 0.f;
+            lnp[1][c] = c < a.K ? a.ln_b[c] : 0.f;
+        }
+        __syncthreads();
+        const float fk = (float)a.K;
+        float mean[PT], rstd[PT];
+        // the fp16 fragments are converted again in every pass: opaque between the passes, or the compiler keeps the fp32 copies of the
+        // whole tile live (2 x 8 KSC x PT registers) and spills
+        auto pin = [&]() {
+#pragma unroll
+            for (int i = 0; i < 2 * KSC; ++i)
+#pragma unroll
+                for (int p = 0; p < PT; ++p) {
+                    unsigned t0 = xf[i][p].u.x, t1 = xf[i][p].u.y, t2 = xf[i][p].u.z, t3 = xf[i][p].u.w;
+                    asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
+                    xf[i][p].u = make_uint4(t0, t1, t2, t3);
+                }
+        };
+#pragma unroll
+        for (int p = 0; p < PT; ++p) {
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2 * KSC; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sum += (float)xf[i][p].e[j];
+            sum += __shfl_xor(sum, 16, 64);
+            sum += __shfl_xor(sum, 32, 64);
+            mean[p] = sum / fk;
+            pin();
+            float sq = 0.f;
+#pragma unroll
+            for (int i = 0; i < 2 * KSC; ++i) {
+                const bool ok = (i >> 1) * 64 + (i & 1) * 32 + lq * 8 < a.K;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float d = ok ? (float)xf[i][p].e[j] - mean[p] : 0.f;
+                    sq += d * d;
+                }
+            }
+            sq += __shfl_xor(sq, 16, 64);
+            sq += __shfl_xor(sq, 32, 64);
+            rstd[p] = rsqrtf(sq / fk + a.ln_eps);
+            pin();
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * KSC; ++i) {
+            const int c0 = (i >> 1) * 64 + (i & 1) * 32 + lq * 8;
+            const f32x4 g0 = *reinterpret_cast<const f32x4*>(&lnp[0][c0]), g1 = *reinterpret_cast<const f32x4*>(&lnp[0][c0 + 4]);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(&lnp[1][c0]), b1 = *reinterpret_cast<const f32x4*>(&lnp[1][c0 + 4]);
+#pragma unroll
+            for (int p = 0; p < PT; ++p)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float gg = j < 4 ? g0[j & 3] : g1[j & 3], bb = j < 4 ? b0[j & 3] : b1[j & 3];
+                    xf[i][p].e[j] = (f16)(((float)xf[i][p].e[j] - mean[p]) * rstd[p] * gg + bb);
+                }
+            // one fragment pair at a time: left alone, every gamma / beta read (16 registers per pair) is hoisted above the arithmetic
+            // and spills.  The finished fragments are operands of an opaque statement the next pair's LDS reads cannot cross.
+#pragma unroll
+            for (int p = 0; p < PT; ++p) {
+                unsigned t0 = xf[i][p].u.x, t1 = xf[i][p].u.y, t2 = xf[i][p].u.z, t3 = xf[i][p].u.w;
+                asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3) : : "memory");
+                xf[i][p].u = make_uint4(t0, t1, t2, t3);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the prologue is over before the weight pipeline starts
     }
 
     f32x4 acc[NG][PT][4];
@@ -1104,12 +1191,31 @@ __global__ __launch_bounds__(256, 2) void pwx_kernel(ConvArgs a, int mode) {
 }
 
 template <int KSC, int PT>
+__global__ __launch_bounds__(256, 2) void pwx_kernel(ConvArgs a, int mode) {
+    pwx_body<KSC, PT, false>(a, mode);
+}
+
+template <int KSC, int PT>
+__global__ __launch_bounds__(256, 2) void pwx_ln_kernel(ConvArgs a, int mode) {
+    pwx_body<KSC, PT, true>(a, mode);
+}
+
+template <int KSC, int PT>
 int launch_pwx(const ConvArgs& a0, int mode, hipStream_t s) {
     ConvArgs a = a0;
     a.m_blocks = (a.M + 64 * PT - 1) / (64 * PT);
     a.n_blocks = 1;
     hipLaunchKernelGGL((pwx_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
     return vip_launch_status("vip_conv2d_nhwc_f16(pwx)");
+}
+
+template <int KSC, int PT>
+int launch_pwx_ln(const ConvArgs& a0, int mode, hipStream_t s) {
+    ConvArgs a = a0;
+    a.m_blocks = (a.M + 64 * PT - 1) / (64 * PT);
+    a.n_blocks = 1;
+    hipLaunchKernelGGL((pwx_ln_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
+    return vip_launch_status("vip_ln_gemm_bias_act_f16");
 }
 
 #if VIP_BUILD_EXPERIMENTS
@@ -1750,7 +1856,7 @@ static thread_local const char* g_pick = "";
 
 static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
                        const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
-                       int* status = nullptr) {
+                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
     VIP_REQUIRE(x && w && y && d, VIP_ERR_BAD_ARG, "vip_conv2d_nhwc_f16: null pointer");
     VIP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kh > 0 && d->kw > 0 &&
                     d->sh > 0 && d->sw > 0 && d->Ho > 0 && d->Wo > 0 && d->groups > 0 && d->pt >= 0 && d->pl >= 0,
@@ -1800,7 +1906,27 @@ static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void
     a.gate = (const f16*)gate;
     a.gate_hw = d->Ho * d->Wo;
     a.y_lo_off = y_lo_off;
+    a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
     hipStream_t s = (hipStream_t)stream;
+#if !VIP_GEMM_H2
+    if (ln_g) {     // vip_ln_gemm_bias_act_f16: the one kernel with the LayerNorm prologue, no fall-back (a missing kernel is an error)
+        int mode = -1;
+        if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
+        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
+        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
+        VIP_REQUIRE(mode >= 0 && ln_b && !w_lo && !gate && !y_lo_off && !x_split && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 &&
+                        d->sw == 1 && d->pt == 0 && d->pl == 0 && d->Ho == d->H && d->Wo == d->W && d->cin_off == 0 &&
+                        vip_ln_gemm_supported((int)M, a.K, cout_g, d->act_pre) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K,
+                    VIP_ERR_UNSUPPORTED,
+                    "vip_ln_gemm_bias_act_f16: M=%ld K=%d N=%d act=%d/%d%s not taken (vip_ln_gemm_supported; (activation) or "
+                    "(residual [+ReLU]) epilogue)", M, a.K, cout_g, d->act_pre, d->act_post, residual ? " +res" : "");
+        const int ksc = (a.K + 63) >> 6;
+        if (ksc <= 2) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<2, 2>(a, mode, s)));
+        if (ksc <= 3) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<3, 2>(a, mode, s)));
+        if (ksc <= 4) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<4, 2>(a, mode, s)));
+        VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<6, 2>(a, mode, s)));
+    }
+#endif
     // HBM-bound shapes (short K): a smaller M tile -> 24-48 KB LDS and half the accumulators -> 3-5 workgroups per
     // CU in flight instead of 2, which is what hides the load -> MFMA -> store latency chain of a 1-4 k-tile block.
     // (Tried and measured SLOWER on these shapes: a two-deep register prefetch (+40 VGPRs), an LDS-transposed
@@ -1968,6 +2094,39 @@ extern "C" int vip_gemm_bias_act_f16(const void* A, const void* W, const float* 
     d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = ldc; d.cout_off = 0; d.ldr = ldr;
     d.res_off = 0; d.ldw = ldw; d.act_pre = act_pre; d.act_post = act_post;
     return vip_conv2d_nhwc_f16(A, W, bias, residual, C, &d, stream);
+}
+
+/* LayerNorm folded into the GEMM that consumes it (pwx_ln_kernel).  Shapes: the row must fit the kernel's resident fragments
+ * (K <= 384: 96 fragment + 64 accumulator registers at 32 pixels per wave, no scratch; K = 512 would leave 16 pixels per wave and has
+ * no call site with M >= 16384 in the ensemble), and the activation-resident form needs enough rows and channel tiles to pay
+ * (M >= 16384, N >= 256: the limits of pwx_kernel). */
+extern "C" int vip_ln_gemm_supported(int M, int K, int N, int act) {
+    if (M < 16384 || N < 256 || N % 8 != 0 || K % 8 != 0 || K <= 64 || K > 384 || (unsigned)act > 4u) return 0;
+    // what follows is POLICY, not capability: call sites that measured no faster than the two launches.  VIP_LN_GEMM_ALL=1 (read per
+    // call: the A/B driver and the kernel's tests set it) lifts it, so that every shape the kernel can run stays measurable and tested.
+    const char* all = getenv("VIP_LN_GEMM_ALL");
+    if (all && atoi(all)) return 1;
+    // Measured per call site against layernorm_kernel + the GEMM ops.dense picks (tools/bench_ln_gemm.py, eight rounds per side,
+    // profiles/ln_gemm_per_site_ab.log).  A workgroup owns 128 rows and every channel tile of N, so M / 128 workgroups run on the chip's
+    // 512 slots (256 CUs x 2).  Where they fill them the fused launch wins outside the spread of the rounds - ConvNeXt-T stage 2 fc1
+    // (147456 x 384 x 1536 gelu), GCViT-T level 1 fc1 (200704 x 128 x 384 gelu) - and so does the one under-filled site with few
+    // channel tiles, GCViT-T level 2 qkv with a global query (50176 x 256 x 512).  With ~50 000 rows (392-394 workgroups) and N >= 768 -
+    // ViT-S qkv / fc1 (50432 x 384 x 1152 / 1536), GCViT-T level 2 qkv / fc1 (50176 x 256 x 768) - the direct kernel's split over N
+    // makes up for the LayerNorm pass it cannot fold: fused and two launches overlap, no gain shown, they keep the two launches.
+    if (M < 65536 && N > 512) return 0;
+    return 1;
+}
+
+extern "C" int vip_ln_gemm_bias_act_f16(const void* A, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* W,
+                                        const float* bias, const void* residual, void* C, int M, int N, int K, int lda, int ldw,
+                                        int ldc, int ldr, int act_pre, int act_post, void* stream) {
+    VIP_REQUIRE(ln_gamma && ln_beta, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: null LayerNorm parameters");
+    VIP_REQUIRE(ln_eps > 0.f, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: eps must be positive");
+    vip_conv_desc d;
+    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
+    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = ldc; d.cout_off = 0; d.ldr = ldr;
+    d.res_off = 0; d.ldw = ldw; d.act_pre = act_pre; d.act_post = act_post;
+    return conv2d_impl(A, nullptr, 0, W, bias, residual, C, &d, stream, nullptr, false, 1.f, nullptr, ln_gamma, ln_beta, ln_eps);
 }
 
 extern "C" int vip_gemm_split_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda,

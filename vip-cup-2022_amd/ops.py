@@ -690,6 +690,50 @@ def dense(x: torch.Tensor, cw: ConvWeight, act=None, act_post=None, residual: Op
     return out
 
 
+_LN_GEMM = os.environ.get("VIP_LN_GEMM", "1") != "0"
+
+
+def ln_gemm_fused(x: torch.Tensor, cw: ConvWeight, act=None, act_post=None, residual: Optional[torch.Tensor] = None) -> bool:
+    """whether ``ln_dense`` runs as ONE launch (``vip_ln_gemm_bias_act_f16``) for these operands"""
+    if (not _LN_GEMM or _UNFUSED or _CALIB or _EXACT or x.dtype != torch.float16 or not x.is_contiguous() or cw.kind != "f16"
+            or cw.groups != 1 or cw.kh != 1 or cw.kw != 1 or cw.cin != x.shape[-1] or 2 * x.numel() >= 0xFFFF0000 - 2 * x.shape[-1]):
+        return False
+    if residual is not None and (act is not None or act_post not in (None, "relu")):
+        return False
+    if residual is None and act_post is not None:
+        return False
+    K = x.shape[-1]
+    return bool(_abi.lib().vip_ln_gemm_supported(x.numel() // K, K, cw.cout, _act(act)))
+
+
+def ln_dense(x: torch.Tensor, ln, cw: ConvWeight, act=None, act_post=None, residual: Optional[torch.Tensor] = None):
+    """``dense(layernorm(x), cw, ...)`` with ``ln = (gamma, beta, eps)``: on the fp16 storage ONE launch where the C ABI takes the shape
+    (``vip_ln_gemm_supported``: the row is normalised in the registers of the GEMM, LN(x) never goes to memory), otherwise - and always
+    on the strict storages and inside ``unfused()`` / ``calibration()`` / ``exact_weights()`` - LayerNorm then Dense, two launches.
+    Same arithmetic either way: the normalised operand is rounded to fp16 where the separate launch stored it."""
+    if not ln_gemm_fused(x, cw, act, act_post, residual):
+        return dense(layernorm(x, ln[0], ln[1], float(ln[2])), cw, act=act, act_post=act_post, residual=residual)
+    lead, K = x.shape[:-1], x.shape[-1]
+    M = x.numel() // K
+    out = torch.empty((*lead, cw.cout), dtype=torch.float16, device=x.device)
+    ldr = 0
+    if residual is not None:
+        _chk16(residual, "ln_dense.residual")
+        assert residual.shape == out.shape and residual.is_contiguous()
+        ldr = cw.cout
+    tok = None
+    if _PROF is not None:       # bytes: x in, y out (+ residual), the weights - no LN(x) round trip
+        tok = _PROF.start("pwx_ln_kernel", 2.0 * M * cw.cout * K,
+                          2.0 * (M * K + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()) + 8.0 * K,
+                          f"M={M} N={cw.cout} K={K} ln+dense{' res' if residual is not None else ''} act={act}")
+    st = _abi.lib().vip_ln_gemm_bias_act_f16(_p(x), _p(ln[0]), _p(ln[1]), float(ln[2]), _p(cw.w), _p(cw.bias), _p(residual), _p(out),
+                                             M, cw.cout, K, K, cw.ldw, cw.cout, ldr, _act(act), _act(act_post), _stream())
+    if tok is not None:
+        _PROF.stop(tok)
+    _abi.check(st, "vip_ln_gemm_bias_act_f16")
+    return out
+
+
 _MLP_H2_FUSED = os.environ.get("VIP_MLP_H2_FUSED", "1") != "0"
 
 
@@ -747,8 +791,8 @@ def mlp(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act="gelu", residual:
             _PROF.stop(tok)
         _abi.check(st, "vip_mlp_fused_f16")
         return out
-    if ln is not None:
-        x = layernorm(x, ln[0], ln[1], float(ln[2]))
+    if ln is not None:      # LayerNorm folded into fc1 where the shape allows (ln_dense), then fc2 (+ residual): two launches, else three
+        return dense(ln_dense(x, ln, fc1, act=act), fc2, residual=residual)
     return dense(dense(x, fc1, act=act), fc2, residual=residual)
 
 
@@ -1157,7 +1201,7 @@ def gcvit_attn_block(x, q_global, ln, qkv: ConvWeight, proj: ConvWeight, bias_ta
              and proj.cout == Cc and Hp % ws == 0 and Wp % ws == 0 and (ws != 14 or _GCVIT_BLOCK14)
              and _abi.lib().vip_gcvit_attn_block_supported(Cc, heads, ws))
     if not fused:
-        y = dense(layernorm(x, ln[0], ln[1], float(ln[2])), qkv)
+        y = ln_dense(x, ln, qkv)
         att = window_attention(y, q_global, bias_table, heads, ws, scale)
         return dense(att, proj, residual=x)
     _chk16(x, "gcvit_attn_block.x")

@@ -184,7 +184,7 @@ class ViT:
         t = ops.vit_tokens(pe.reshape(B, grid[0] * grid[1], cfg.embed_dim), self.cls, self._pos_by_grid[grid])
         scale = (cfg.embed_dim // cfg.nb_heads) ** -0.5
         for blk in self.blocks:                                          # ViTBlock.call (vit.py:214-227)
-            qkv = ops.dense(blk["n1"](t), blk["qkv"])
+            qkv = ops.ln_dense(t, (blk["n1"].g, blk["n1"].b, LN_EPS), blk["qkv"])      # norm1 folded into the qkv GEMM
             att = ops.mhsa(qkv, cfg.nb_heads, scale)
             t = ops.dense(att, blk["proj"], residual=t)
             t = ops.mlp(t, blk["fc1"], blk["fc2"], act="gelu", residual=t, ln=(blk["n2"].g, blk["n2"].b, LN_EPS))
