@@ -575,6 +575,38 @@ int vip_tta_augment_s32(const float* x, float* y, const int32_t* flags, int B, i
  * has no roofline measurement; SURVEY.md section 8(b) / 8(d) ask for these).
  * ------------------------------------------------------------------------------------------ */
 
+/* ------------------------------------------------------------------------------------------
+ * Evidence maps (Grad-CAM) for heads of the form GlobalAveragePooling -> [LayerNormalization] -> Dense -> activation (csrc/cam.hip).
+ * With v = mean_hw F, u = LN(v) | v, z = W u + b, p = act(z) the gradient Grad-CAM pools has a closed form, so the map comes out of
+ * the forward pass:  dz = d target / d z,  a = W^T dz,  [LayerNorm head, uh = (v - mean v) / sd:  a <- gamma a,
+ * a <- (a - mean a - uh mean(a uh)) / sd],  g = a / HW = mean_hw d target / d F,  cam[h,w] = max(0, sum_c F[h,w,c] g[c]).
+ * Replaces tape.gradient + reduce_mean + feats @ pooled_grads + maximum of models/gcvit/utils/gradcam.py:44-55 and
+ * keras_cv_attention_models/visualizing/visualizing.py:186-245 (use_v2=False), with the gradient mean taken PER IMAGE.
+ * vip_cam_f32 / _s32 / _h2: F in fp16 / fp32 / packed fp16-pair storage; the other arguments as vip_gap_ln_dense_s32 (gamma = beta =
+ *   NULL: no LayerNorm; W f32 [N][C]; bias f32 [N] or NULL; C <= 4096, N <= 64).  act: 0 linear, 1 element-wise sigmoid, 2 softmax
+ *   (vip_head_act_f32).  target: -1 = the score vip_prob_to_score_f32 forms (p[0] for N = 1, else 1 - p[0]), k >= 0 = p[k]
+ *   (`class_channel = preds[:, pred_index]`, gradcam.py:48).  Outputs, all f32: cam [B][HW] (after the max with 0, NOT normalised),
+ *   peak [B] = max_hw cam (0 for an all-zero map; NaN when a position is not finite - the caller's error), z [B][N] the logits.
+ * vip_cam_compose_f32: `members` (1 .. 16) low-resolution maps - host arrays of device pointers maps_h[m] -> [n][gh*gw] f32 and
+ *   peaks_h[m] -> [n] f32, grids grid_h_h / grid_w_h, weights weights_h - -> sum_m weight[m] * resize(map_m / peak_m) per image at
+ *   its own size (sizes_hw, slot layout [n][maxH][maxW] as vip_resize_bicubic_norm_f16; outside the image 0).  Bilinear, half-pixel
+ *   centres, edge clamp (tf.image.resize(..., "bilinear"), visualizing.py:305); a member whose peak is 0 contributes 0, not NaN.
+ *   out: f32, or with out_u8 = 1 uint8 round(255 * map).
+ * vip_cam_overlay_u8: out = clip(round(rgb + alpha * table[map]), 0, 255): the colour table [256][3] uint8 applied to the uint8 map and
+ *   blended over the decoded pixels (gradcam.py:57-65); rgb / out [n][maxH][maxW][3], map [n][maxH][maxW].
+ * ------------------------------------------------------------------------------------------ */
+int vip_cam_f32(const void* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* cam,
+                float* peak, float* z, int B, int HW, int C, int ldx, long img_stride, int N, int act, int target, void* stream);
+int vip_cam_s32(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* cam,
+                float* peak, float* z, int B, int HW, int C, int ldx, long img_stride, int N, int act, int target, void* stream);
+int vip_cam_h2(const void* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* cam,
+               float* peak, float* z, int B, int HW, int C, int ldx, long img_stride, int N, int act, int target, void* stream);
+int vip_cam_compose_f32(const float* const* maps_h, const int* grid_h_h, const int* grid_w_h, const float* const* peaks_h,
+                        const float* weights_h, int members, const int32_t* sizes_hw, int n, int maxH, int maxW, void* out,
+                        int out_u8, void* stream);
+int vip_cam_overlay_u8(const uint8_t* rgb_u8, const uint8_t* map_u8, const uint8_t* table_u8, float alpha, int n, int maxH,
+                       int maxW, uint8_t* out_u8, void* stream);
+
 /* Which kernel vip_conv2d_nhwc_f16 / _gated_ / _hilo_ would launch for this descriptor ("pw_gemm_kernel",
  * "pwk_direct_kernel", "pwk_gemm_kernel", "pwk_gemm_kernel(im2col)", "rows_gemm_kernel", "conv_igemm_kernel"):
  * the dispatcher itself in a dry run, nothing is launched.  Used to label profiler records (bench.py roofline). */

@@ -138,6 +138,12 @@ SIGNATURES = {
     "vip_gap_ln_dense_h2": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, C.c_long, _i, _vp]),
     "vip_window_attn_fwd_h2": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp]),
     "vip_mhsa_fwd_h2": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    # evidence maps (Grad-CAM): csrc/cam.hip
+    "vip_cam_f32": (_i, [_vp, _vp, _vp, _f] + [_vp] * 5 + [_i] * 4 + [C.c_long, _i, _i, _i, _vp]),
+    "vip_cam_s32": (_i, [_vp, _vp, _vp, _f] + [_vp] * 5 + [_i] * 4 + [C.c_long, _i, _i, _i, _vp]),
+    "vip_cam_h2": (_i, [_vp, _vp, _vp, _f] + [_vp] * 5 + [_i] * 4 + [C.c_long, _i, _i, _i, _vp]),
+    "vip_cam_compose_f32": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "vip_cam_overlay_u8": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     "vip_conv2d_kernel_name": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_workspace_bytes": (_sz, [_i, C.POINTER(C.c_int64), _i]),
     "vip_microbench_copy": (_i, [_vp, _vp, _sz, _vp]),

@@ -185,7 +185,8 @@ def tta_flags_pass(n_images: int, t: int, seed: int = 0) -> np.ndarray:
 def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, members: List[Tuple[object, object]],
                 batch_size: int = REF_BATCH, rank: int = 0, world: int = 1, dist=None,
                 scorer: Optional[Callable] = None, tta: int = 1, tta_seed: int = 0,
-                shard: str = "images", costs: Optional[Sequence[float]] = None) -> np.ndarray:
+                shard: str = "images", costs: Optional[Sequence[float]] = None,
+                batch_scorer: Optional[Callable] = None) -> np.ndarray:
     """Score images [0, n_images) with every member; returns ``[M, n_images]`` fp32 probabilities on every rank.
 
     ``jpegs_for(lo, hi)`` returns the JPEG / PNG byte strings of images lo..hi-1 (read lazily, per batch).
@@ -195,7 +196,11 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
     ``shard`` / ``costs``: the ShardPlan mode and, for ``hybrid``, the per-member cost (ms/image; identical on every rank).
     A rank only calls ``model.predict`` of the members its plan names, so under ``members`` / ``hybrid`` the others need not
     be resident (``members[i][1]`` may be None there).
-    ``scorer(raws, members[, flags]) -> [M, n]`` replaces the GPU path in the CPU (gloo) tests."""
+    ``scorer(raws, members[, flags]) -> [M, n]`` replaces the GPU path in the CPU (gloo) tests.
+    ``batch_scorer(staged, members, b0, b1, after_fork) -> [M, n]`` replaces ``_score_batch`` for images b0..b1-1 and keeps the staged
+    host decode and read-ahead (``main.py --heatmaps``: ``explain_batch`` plus the files it writes); not with ``tta`` > 1."""
+    if batch_scorer is not None and tta > 1:
+        raise ValueError("score_files: batch_scorer does not take TTA passes")
     plan = ShardPlan(shard, len(members), world, costs)
     flags_all = tta_flags(n_images, tta, tta_seed) if tta > 1 else None
     work = []                                   # (shard, member indices, b0, b1)
@@ -248,6 +253,8 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
             fl = None if flags_all is None else flags_all[:, b0:b1]
             if scorer is not None:
                 rows = scorer(staged, sub) if fl is None else scorer(staged, sub, fl)
+            elif batch_scorer is not None:
+                rows = batch_scorer(staged, sub, b0, b1, after_fork)
             else:
                 rows = _score_batch(staged, sub, fl, after_fork=after_fork)
             for j, m in enumerate(midx):
@@ -291,6 +298,13 @@ def member_inputs(batch, members) -> Dict:
 def _record_stream(t, stream):
     if isinstance(t, torch.Tensor) and t.is_cuda:
         t.record_stream(stream)
+    elif isinstance(t, (tuple, list)):             # a member call that returns several tensors (predict_with_cam)
+        for u in t:
+            _record_stream(u, stream)
+
+
+def _predict(model, x):
+    return model.predict(x)
 
 
 def _input_for(inputs, spec, model):
@@ -313,13 +327,13 @@ class MemberStreams:
         self._assign: Dict[Tuple[str, ...], List[List[int]]] = {}    # per member list (a ShardPlan may hand over sub-lists)
         self.cost_ms: Dict[str, float] = {}                              # last one-off timing per member (ms per batch)
 
-    def _calibrate(self, members, inputs):
+    def _calibrate(self, members, inputs, call=_predict):
         """one serial, timed pass; its predictions ARE the first batch's result (nothing is computed twice)"""
         cost, out = [], []
         for i, (spec, model) in enumerate(members):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            out.append(model.predict(_input_for(inputs, spec, model)))
+            out.append(call(model, _input_for(inputs, spec, model)))
             e1.record()
             e1.synchronize()
             cost.append(e0.elapsed_time(e1))
@@ -334,20 +348,21 @@ class MemberStreams:
         self._assign[tuple(spec.name for spec, _ in members)] = assign
         return out
 
-    def predict_all(self, members, inputs, after_fork=None, defer_join: bool = False):
-        """inputs: {input_hw: tensor} produced on the current stream.  Returns member.predict() per member.
+    def predict_all(self, members, inputs, after_fork=None, defer_join: bool = False, call=_predict):
+        """inputs: {input_hw: tensor} produced on the current stream.  Returns member.predict() per member - or, with ``call``, whatever
+        ``call(model, x)`` returns (a tensor or a tuple of tensors: ``explain_batch`` asks for the evidence map along with the prediction).
         ``after_fork()`` is called once the members are enqueued on their streams and BEFORE the current stream joins them: work it
         enqueues on the current stream (the next batch's H2D + IDCT) runs under the members instead of in front of the next step.
         ``defer_join``: return ``(predictions, join_events)`` without making the current stream wait - the caller joins later
         (``MemberStreams.join``), so the next batch's members can start on the streams that finish first."""
         if self.n <= 1 or len(members) <= 1:
-            out = [model.predict(_input_for(inputs, spec, model)) for spec, model in members]
+            out = [call(model, _input_for(inputs, spec, model)) for spec, model in members]
             if after_fork is not None:
                 after_fork()
             return (out, []) if defer_join else out
         assign = self._assign.get(tuple(spec.name for spec, _ in members))
         if assign is None:
-            out = self._calibrate(members, inputs)
+            out = self._calibrate(members, inputs, call)
             if after_fork is not None:
                 after_fork()
             return (out, []) if defer_join else out
@@ -369,7 +384,7 @@ class MemberStreams:
                     # block can be handed out again while the other stream still has work queued on it (a caller that drops its
                     # reference early - or a deferred join - would otherwise race with the block's next owner)
                     _record_stream(x, st)
-                    out[i] = model.predict(x)
+                    out[i] = call(model, x)
                     _record_stream(out[i], main)
             done = torch.cuda.Event()
             done.record(st)
@@ -449,3 +464,64 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
         s = one_pass(aug)
         acc = s if acc is None else acc + s
     return acc / float(len(flags))
+
+
+class Explanation:
+    """What ``explain_batch`` returns: ``scores`` ``[M, n]`` (device; exactly what ``_score_batch`` returns), per member ``maps[m]``
+    ``[n, gh, gw]`` fp32 (un-normalised, ``ops.cam``) and ``peaks[m]`` ``[n]`` - None for a member without a map, with the reason in
+    ``unsupported[name]`` - the composed full-size map ``map`` ``[n, maxH, maxW]`` (fp32 in [0, 1] or uint8; None when no member can
+    produce one), and the decoded ``batch`` it belongs to (``batch.sizes_host[i]`` = the image's own height and width)."""
+
+    def __init__(self, scores, names, maps, peaks, unsupported, full, batch):
+        self.scores, self.names, self.maps, self.peaks, self.unsupported, self.map, self.batch = scores, names, maps, peaks, unsupported, full, batch
+
+
+def cam_support(members) -> Dict[str, Optional[str]]:
+    """``{member name: None | why it has no evidence map}`` for ``members`` = [(spec, model)]"""
+    from . import cam
+    return {spec.name: cam.unsupported_reason(model) for spec, model in members}
+
+
+def explain_batch(staged, members, target="score", out: str = "u8", after_fork=None) -> Explanation:
+    """``_score_batch`` plus Grad-CAM evidence: every map-capable member runs ``predict_with_cam`` (ONE pass through its body: the
+    probabilities of ``predict``, bit for bit, and the low-resolution map), the others ``predict``; the members run on ``MemberStreams``
+    as they do for scoring.  The maps are normalised, resampled to each image's own size and averaged over the members that have one
+    in a single launch (``ops.cam_compose``; ``out`` = ``"u8"`` or ``"f32"``).  A fold ensemble contributes the mean of its folds' maps.
+    Raises ``VipError`` when a map is not finite."""
+    from . import ops, pipeline
+    if isinstance(staged, pipeline.DecodedBatch):
+        batch = staged
+    else:
+        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
+            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    global _MEMBER_STREAMS
+    if _MEMBER_STREAMS is None:
+        _MEMBER_STREAMS = MemberStreams(default_streams())
+    inputs = member_inputs(batch, members)
+    why = cam_support(members)
+
+    def call(model, x):
+        if getattr(model, "cam_supported", False):
+            return model.predict_with_cam(x, target)
+        return (model.predict(x), None, None)
+
+    res = _MEMBER_STREAMS.predict_all(members, inputs, after_fork=after_fork, call=call)
+    rows = torch.empty((len(res), res[0][0].shape[0]), dtype=torch.float32, device=res[0][0].device)
+    maps, peaks, parts, weights = [], [], [], []
+    n_cam = sum(1 for r in res if r[1] is not None)
+    for m, (p, cm, pk) in enumerate(res):
+        ops.binary_score(p, out=rows[m])                         # main.py:113-114
+        maps.append(cm)
+        peaks.append(pk)
+        if cm is not None:
+            folds = list(zip(cm, pk)) if isinstance(cm, (list, tuple)) else [(cm, pk)]
+            for c_, p_ in folds:
+                parts.append((c_, p_))
+                weights.append(1.0 / (n_cam * len(folds)))
+    full = None
+    if parts:
+        # one transfer for every member's peaks (a synchronising check: a non-finite map is an error, not an output)
+        ops.cam_check(torch.stack([p_ for _, p_ in parts]), "explain_batch: members "
+                      + ", ".join(spec.name for (spec, _), pk in zip(members, peaks) if pk is not None) + " (row, image)")
+        full = ops.cam_compose([c_ for c_, _ in parts], [p_ for _, p_ in parts], batch.sizes, batch.rgb.shape[1:3], weights, out=out)
+    return Explanation(rows, [spec.name for spec, _ in members], maps, peaks, {k: v for k, v in why.items() if v is not None}, full, batch)

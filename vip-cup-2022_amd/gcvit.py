@@ -10,6 +10,7 @@ from typing import Dict
 import torch
 
 from . import ops
+from .cam import CamMixin, HeadSpec
 from .pipeline import keras_predict
 from .synth import ParamGen
 
@@ -141,7 +142,7 @@ class _Block:
 
 
 @keras_predict
-class GCViT:
+class GCViT(CamMixin):
     def __init__(self, params: Dict[str, torch.Tensor], window_size, dim, depths, num_heads, mlp_ratio=3.0,
                  layer_scale=None, classes: int = 1, device="cuda", first_strides: int = 2, head_act: str = "default"):
         p, dev = params, device
@@ -203,6 +204,11 @@ class GCViT:
             if collect is not None:
                 collect.append(y)
         return self.norm(y)
+
+    def head_spec(self) -> HeadSpec:
+        """forward_head (models/gcvit.py:107-113): pool -> Dense on the map AFTER the final LayerNorm, which ``features`` returns - the
+        tensor gradcam.py:16 takes; no LayerNorm inside the head"""
+        return HeadSpec(self.head_w, self.head_b, None, getattr(self, "head_act", "default"))
 
     def logits(self, x):
         return ops.gap_dense_f32(self.features(x), self.head_w, self.head_b)

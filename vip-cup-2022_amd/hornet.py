@@ -8,6 +8,7 @@ from typing import Dict
 import torch
 
 from . import ops
+from .cam import CamMixin, HeadSpec
 from .pipeline import keras_predict
 from .synth import ParamGen
 
@@ -66,7 +67,7 @@ class _LN:
 
 
 @keras_predict
-class HorNet:
+class HorNet(CamMixin):
     def __init__(self, params: Dict[str, torch.Tensor], num_blocks, embed_dim, mlp_ratio=4, gn_split=(2, 3, 4, 5),
                  scale=0.3333333, classes: int = 1, first_strides: int = 2, device="cuda", classifier_activation: str = "default"):
         p, dev = params, device
@@ -135,6 +136,11 @@ class HorNet:
             if collect is not None:
                 collect.append(y)
         return y
+
+    def head_spec(self) -> HeadSpec:
+        """avg_pool -> pre_output_ln -> Dense (hornet.py:166-171): the LayerNorm sits between the pool and the Dense"""
+        n = self.head_ln
+        return HeadSpec(self.head_w, self.head_b, (n.g, n.b, LN_EPS), getattr(self, "head_act", "default"))
 
     def logits(self, x):
         n = self.head_ln                                                    # avg_pool -> pre_output_ln -> Dense  (:166-171), fp32

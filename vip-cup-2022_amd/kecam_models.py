@@ -20,6 +20,7 @@ from typing import Dict
 import torch
 
 from . import ops
+from .cam import CamMixin, HeadSpec
 from .pipeline import keras_predict
 from .synth import ParamGen, fold_bn
 
@@ -58,8 +59,13 @@ def _head(p, dev):
 
 
 @keras_predict
-class _Base:
+class _Base(CamMixin):
     classes = 1
+
+    def head_spec(self) -> HeadSpec:
+        """GlobalAveragePooling2D -> Dense (kecam common_layers.py:278-283): no LayerNorm, weights as ``logits`` feeds them to ``ops.gap_dense_f32``"""
+        return HeadSpec(self.head_w, self.head_b, None, getattr(self, "head_act", "default"))
+
 
     def logits(self, x):
         return ops.gap_dense_f32(self.features(x), self.head_w, self.head_b)

@@ -1,6 +1,7 @@
 """Drop-in CLI for the reference entry point (main.py:151-235):
 
     python3 vip-cup-2022_amd/main.py <input.csv> <output.csv> [--scores-out scores.csv] [--synthetic]
+                                     [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
     python -m torch.distributed.run --nproc-per-node N ... vip-cup-2022_amd/main.py in.csv out.csv
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
@@ -8,6 +9,10 @@ Same contract: the input CSV has a ``filename`` column with paths relative to th
 (main.py:143-145,225).  ``--scores-out`` additionally writes the continuous ensemble mean (the reference keeps
 it only in memory).  The ensemble manifest is ``ckpts/ckpts.json`` ([name, [H,W], idx],
 main.py:171-198); members whose graph is not built yet are reported and skipped only under ``--allow-missing``.
+``--heatmaps DIR`` additionally writes, per input file, the ensemble's Grad-CAM evidence map (``<name>.npy``: fp32 in [0, 1] at the
+image's own size; or with ``--heatmap-format png`` a jet overlay ``<name>.png``), with ``--heatmap-members`` every member's
+low-resolution map and peak in ``<name>.members.npz``, and ``heatmaps.json`` (per member: supported or why not).  The CSV outputs do
+not change with the flag.
 
 Checkpoints: ``<script dir>/ckpts/<name>/ckpt/*.h5`` (Keras weight / model files, as in the reference), else ``ckpt/saved_model.pb`` (a
 Keras SavedModel directory: its variables are read by ``tfbundle``), or ``*.npz`` (a flat dict of
@@ -28,6 +33,51 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+
+def _heatmap_writer(a, names, members, rank):
+    """the ``batch_scorer`` of ``--heatmaps``: ``explain_batch`` on every batch, the files of its images written as they come (under
+    ``--shard images`` a rank only ever sees its own images: nothing is exchanged), the scores handed on unchanged"""
+    from vipcup_amd import cam, ensemble, ops
+    os.makedirs(a.heatmaps, exist_ok=True)
+    why = ensemble.cam_support(members)
+    if rank == 0:
+        with open(os.path.join(a.heatmaps, "heatmaps.json"), "w") as f:
+            json.dump({"target": "score", "format": a.heatmap_format, "alpha": 0.4 if a.heatmap_format == "png" else None,
+                       "members": [{"name": spec.name, "cam_supported": why[spec.name] is None, "reason": why[spec.name]}
+                                   for spec, _ in members]}, f, indent=1)
+    if all(v is not None for v in why.values()):
+        raise SystemExit("vipcup_amd main: --heatmaps: no member of this ensemble can produce an evidence map: "
+                         + "; ".join(f"{k}: {v}" for k, v in why.items()))
+
+    def score(staged, sub, b0, b1, after_fork):
+        ex = ensemble.explain_batch(staged, sub, target="score", out="u8" if a.heatmap_format == "png" else "f32", after_fork=after_fork)
+        sizes = ex.batch.sizes_host
+        if a.heatmap_format == "png":
+            full = ops.cam_overlay(ex.batch.rgb, ex.map, cam.jet_table_device(ex.map.device), 0.4).cpu().numpy()
+        else:
+            full = ex.map.cpu().numpy()
+        low = None
+        if a.heatmap_members:
+            low = [(n, m, p) for n, m, p in zip(ex.names, ex.maps, ex.peaks) if m is not None]
+            low = [(n, [t.cpu().numpy() for t in (m if isinstance(m, (list, tuple)) else [m])],
+                    [t.cpu().numpy() for t in (p if isinstance(p, (list, tuple)) else [p])]) for n, m, p in low]
+        for i in range(b1 - b0):
+            h, w = sizes[i]
+            stem = os.path.join(a.heatmaps, cam.heatmap_stem(names[b0 + i]))
+            if a.heatmap_format == "png":
+                cam.write_png(stem + ".png", full[i, :h, :w])
+            else:
+                np.save(stem + ".npy", np.ascontiguousarray(full[i, :h, :w]))
+            if low is not None:
+                arrays = {}
+                for n, ms, ps in low:
+                    for k, (m, p) in enumerate(zip(ms, ps)):
+                        key = n if len(ms) == 1 else f"{n}/fold{k}"
+                        arrays[key + "/cam"], arrays[key + "/peak"] = m[i], p[i]
+                np.savez(stem + ".members.npz", **arrays)
+        return ex.scores
+    return score
 
 
 def main(argv=None):
@@ -56,7 +106,20 @@ def main(argv=None):
                          "per-channel input means; inputs only, no labels)")
     ap.add_argument("--no-bias-calibration", action="store_true",
                     help="fast mode: plain fp16 weights, no calibration pass at load time")
+    ap.add_argument("--heatmaps", default=None, metavar="DIR",
+                    help="write the ensemble's Grad-CAM evidence map of every input file into DIR (the mean over the members that have "
+                         "a spatial map, each normalised to its own peak; ViT members are listed as unsupported in DIR/heatmaps.json)")
+    ap.add_argument("--heatmap-format", default="npy", choices=["npy", "png"],
+                    help="npy: the fp32 map in [0, 1] at the image's size; png: the jet colour table blended over the image (alpha 0.4)")
+    ap.add_argument("--heatmap-members", action="store_true",
+                    help="also write every member's low-resolution map and peak: DIR/<name>.members.npz")
     a = ap.parse_args(argv)
+    if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
+        # the maps of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
+        raise SystemExit("vipcup_amd main: --heatmaps works with --shard images and --tta 1 only (got --shard "
+                         f"{a.shard} --tta {a.tta}): evidence maps under member sharding or TTA are not implemented")
+    if a.heatmaps is None and (a.heatmap_members or a.heatmap_format != "npy"):
+        raise SystemExit("vipcup_amd main: --heatmap-format / --heatmap-members need --heatmaps DIR")
 
     import pandas as pd
     import torch
@@ -143,6 +206,10 @@ def main(argv=None):
                 out.append(f.read())
         return out
 
+    batch_scorer = None
+    if a.heatmaps is not None:
+        batch_scorer = _heatmap_writer(a, names, members, rank)
+
     t0 = time.time()
     costs = None
     if a.shard == "hybrid" and world > 1:
@@ -150,7 +217,7 @@ def main(argv=None):
         if rank == 0:
             print("> HYBRID PLAN:", ensemble.ShardPlan("hybrid", len(members), world, costs).describe())
     per_model = ensemble.score_files(jpegs_for, len(paths), members, a.batch_size, rank, world, dist,
-                                     tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs)
+                                     tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
     uniq, score, decision = ensemble.aggregate(names, per_model)
     if rank == 0:
         pd.DataFrame({"filename": uniq, "logit": decision}).to_csv(a.output_csv, index=False)  # main.py:143-145

@@ -1118,6 +1118,99 @@ def ensemble_mean(scores: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def cam(features, w_nc: torch.Tensor, bias: Optional[torch.Tensor], ln=None, act="default", target="score"):
+    """Grad-CAM of a ``GAP -> [LayerNorm] -> Dense -> activation`` head from the feature map alone (csrc/cam.hip: the gradient has a
+    closed form, no backward pass).  ``features`` ``[B,H,W,C]`` in any activation storage; ``w_nc`` fp32 ``[N,C]``; ``ln`` =
+    ``(gamma, beta, eps)`` or None; ``act`` as ``head_prob``; ``target``: ``"score"`` (what ``binary_score`` makes of the probabilities)
+    or a class index.  Returns ``(cam [B,H,W]`` fp32, after the max with 0 and NOT normalised, ``peak [B]``, ``z [B,N])``.  The
+    normalised map is ``cam / peak``, all zero where ``peak == 0``; a NaN ``peak`` marks a non-finite map (``cam_check``)."""
+    if features.dim() != 4:
+        raise _abi.VipError(f"cam: expected a [B,H,W,C] feature map, got {tuple(features.shape)}")
+    B, H, W, Cc = features.shape
+    # images may sit at a pitch of their own (a batch slice of a wider buffer); inside an image the map is dense
+    pitch = features.stride(0) if B > 1 else H * W * Cc
+    if features.stride()[1:] != (W * Cc, Cc, 1) or pitch < H * W * Cc:
+        raise _abi.VipError(f"cam.features: expected dense [H,W,C] images at a pitch >= H*W*C, got strides {features.stride()}")
+    kind = _kind(features[:1], "cam.features")
+    N = w_nc.shape[0]
+    assert w_nc.dtype == torch.float32 and w_nc.shape == (N, Cc) and w_nc.is_contiguous()
+    assert bias is None or (bias.dtype == torch.float32 and bias.numel() == N)
+    if act == "default":
+        act = "sigmoid" if N == 1 else "softmax"
+    if act not in HEAD_ACTS:
+        raise ValueError(f"head activation {act!r}: expected one of {sorted(k for k in HEAD_ACTS if isinstance(k, str))}")
+    if target == "score":
+        tgt = -1
+    elif isinstance(target, int) and not isinstance(target, bool) and 0 <= target < N:
+        tgt = target
+    else:
+        raise ValueError(f"cam target {target!r}: expected 'score' or a class index below {N}")
+    g, b, eps = (None, None, 0.0) if ln is None else (ln[0], ln[1], float(ln[2]))
+    if ln is not None:
+        assert g.dtype == b.dtype == torch.float32 and g.shape == b.shape == (Cc,)
+    out = torch.empty((B, H, W), dtype=torch.float32, device=features.device)
+    peak = torch.empty((B,), dtype=torch.float32, device=features.device)
+    z = torch.empty((B, N), dtype=torch.float32, device=features.device)
+    fn = {"f16": "vip_cam_f32", "s32": "vip_cam_s32", "h2": "vip_cam_h2"}[kind]
+    st = getattr(_abi.lib(), fn)(_p(features), _p(g), _p(b), eps, _p(w_nc), _p(bias), _p(out), _p(peak), _p(z), B, H * W, Cc, Cc,
+                                 pitch, N, HEAD_ACTS[act], tgt, _stream())
+    _abi.check(st, fn)
+    return out, peak, z
+
+
+def cam_check(peak: torch.Tensor, what: str = "cam") -> torch.Tensor:
+    """Synchronising check of ``ops.cam``'s peaks: a non-finite peak is an error, not a map.  Returns the peaks on the host."""
+    host = peak.detach().float().cpu()
+    if not bool(torch.isfinite(host).all()):
+        raise _abi.VipError(f"{what}: the evidence map of image(s) {torch.nonzero(~torch.isfinite(host)).tolist()} is not finite")
+    return host
+
+
+CAM_MAX_MEMBERS = 16
+
+
+def cam_compose(maps, peaks, sizes: torch.Tensor, max_hw, weights=None, out: str = "f32") -> torch.Tensor:
+    """Members' low-resolution maps -> one full-size map per image: each ``maps[m]`` ``[n,gh,gw]`` fp32 (``ops.cam``) is normalised by
+    ``peaks[m]`` ``[n]``, resampled to the image's own size (bilinear, half-pixel centres, edge clamp) and the results are averaged
+    (``weights``: default 1 / members) - one pass, the full-size map is written once.  ``sizes`` int32 ``[n,2]`` (h, w) and ``max_hw`` =
+    the slot size, as ``DecodedBatch.sizes`` / ``.rgb.shape[1:3]``.  ``out``: ``"f32"`` -> fp32 ``[n,maxH,maxW]`` in [0, 1], ``"u8"`` ->
+    uint8 ``round(255 * map)``; zero outside an image."""
+    M = len(maps)
+    if not 1 <= M <= CAM_MAX_MEMBERS or len(peaks) != M:
+        raise _abi.VipError(f"cam_compose: {M} maps / {len(peaks)} peaks (1 .. {CAM_MAX_MEMBERS} members)")
+    if out not in ("f32", "u8"):
+        raise ValueError(f"cam_compose out={out!r}: expected 'f32' or 'u8'")
+    n = maps[0].shape[0]
+    maxH, maxW = int(max_hw[0]), int(max_hw[1])
+    assert sizes.dtype == torch.int32 and sizes.shape == (n, 2) and sizes.is_cuda and sizes.is_contiguous()
+    for m_, p_ in zip(maps, peaks):
+        _chk32(m_, "cam_compose.map")
+        _chk32(p_, "cam_compose.peak")
+        assert m_.dim() == 3 and m_.shape[0] == n and p_.shape == (n,), (m_.shape, p_.shape)
+    w = [1.0 / M] * M if weights is None else [float(v) for v in weights]
+    assert len(w) == M
+    res = torch.empty((n, maxH, maxW), dtype=torch.uint8 if out == "u8" else torch.float32, device=maps[0].device)
+    st = _abi.lib().vip_cam_compose_f32((C.c_void_p * M)(*[m_.data_ptr() for m_ in maps]), (C.c_int * M)(*[m_.shape[1] for m_ in maps]),
+                                        (C.c_int * M)(*[m_.shape[2] for m_ in maps]), (C.c_void_p * M)(*[p_.data_ptr() for p_ in peaks]),
+                                        (C.c_float * M)(*w), M, _p(sizes), n, maxH, maxW, _p(res), int(out == "u8"), _stream())
+    _abi.check(st, "vip_cam_compose_f32")
+    return res
+
+
+def cam_overlay(rgb: torch.Tensor, map_u8: torch.Tensor, table: torch.Tensor, alpha: float = 0.4) -> torch.Tensor:
+    """``clip(round(rgb + alpha * table[map]))``: the colour table (uint8 ``[256,3]``) applied to a uint8 map ``[n,maxH,maxW]``
+    (``cam_compose(..., out="u8")``) and blended over the decoded pixels ``rgb`` uint8 ``[n,maxH,maxW,3]`` (``DecodedBatch.rgb``)."""
+    for t, name in ((rgb, "rgb"), (map_u8, "map"), (table, "table")):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise _abi.VipError(f"cam_overlay.{name}: expected a contiguous CUDA uint8 tensor, got {t.dtype} {t.device}")
+    n, maxH, maxW, ch = rgb.shape
+    assert ch == 3 and map_u8.shape == (n, maxH, maxW) and table.shape == (256, 3), (rgb.shape, map_u8.shape, table.shape)
+    out = torch.empty_like(rgb)
+    st = _abi.lib().vip_cam_overlay_u8(_p(rgb), _p(map_u8), _p(table), float(alpha), n, maxH, maxW, _p(out), _stream())
+    _abi.check(st, "vip_cam_overlay_u8")
+    return out
+
+
 def scale_add_act(x, scale=None, residual=None, act=None, act2=None):
     """act(x * scale[b,c] + residual); with ``act2`` returns ``(y, act2(y))`` from one launch.
     ``scale`` is [B, C] fp16 or a split gate [B, 2, C] (planes summed in fp32)."""

@@ -11,6 +11,7 @@ from typing import Dict, List
 import torch
 
 from . import ops
+from .cam import CamMixin, HeadSpec
 from .pipeline import keras_predict
 from .synth import ParamGen, fold_bn
 
@@ -66,7 +67,7 @@ def synth_params(depth: int = 50, seed: int = 1006, classes: int = 1, se_ratio: 
 
 
 @keras_predict
-class ResNetRS:
+class ResNetRS(CamMixin):
     """Inference-only ResNet-RS.  ``params`` is a checkpoint dict (see synth_params)."""
 
     def __init__(self, params: Dict[str, torch.Tensor], depth: int = 50, bn_epsilon: float = 1e-5,
@@ -144,6 +145,10 @@ class ResNetRS:
             if collect is not None:
                 collect.append(y)
         return y
+
+    def head_spec(self) -> HeadSpec:
+        """GlobalAveragePooling2D -> Dense (resnet_rs_model.py:468-476): no LayerNorm, weights as ``logits`` feeds them to ``ops.gap_dense_f32``"""
+        return HeadSpec(self.head_w, self.head_b, None, getattr(self, "head_act", "default"))
 
     def logits(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 ``[B, classes]`` pre-activation outputs of the ``predictions`` Dense."""

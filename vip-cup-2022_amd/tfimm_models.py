@@ -10,7 +10,8 @@ from typing import Dict, Tuple
 
 import torch
 
-from . import ops
+from . import _abi, ops
+from .cam import VIT_REASON, CamMixin, HeadSpec
 from .pipeline import keras_predict
 from .synth import ParamGen
 
@@ -192,6 +193,16 @@ class ViT:
                 collect.append(t)
         return self.norm(t)
 
+    # Grad-CAM: ``head(norm(x)[:, 0])`` reads the class token only (vit.py:441-461)
+    cam_supported = False
+    cam_unsupported_reason = VIT_REASON
+
+    def cam(self, x, target="score"):
+        raise _abi.VipError(f"{self.cfg.name}: no evidence map - {VIT_REASON}")
+
+    def predict_with_cam(self, x, target="score"):
+        raise _abi.VipError(f"{self.cfg.name}: no evidence map - {VIT_REASON}")
+
     def logits(self, x):
         t = self.features(x)                                             # head(norm(x)[:, 0]) (vit.py:441-461)
         return ops.cls_dense_f32(t, self.head_w, self.head_b)
@@ -252,7 +263,7 @@ def convnext_synth_params(cfg: ConvNeXtConfig, seed: int) -> Dict[str, torch.Ten
 
 
 @keras_predict
-class ConvNeXt:
+class ConvNeXt(CamMixin):
     def __init__(self, params: Dict[str, torch.Tensor], cfg: ConvNeXtConfig, device="cuda"):
         p, dev = params, device
         self.cfg = cfg
@@ -296,6 +307,11 @@ class ConvNeXt:
             if collect is not None:
                 collect.append(y)
         return y
+
+    def head_spec(self) -> HeadSpec:
+        """pool -> head/norm -> head/fc (convnext.py:432-436): the LayerNorm sits between the pool and the Dense"""
+        n = self.head_norm
+        return HeadSpec(self.head_w, self.head_b, (n.g, n.b, LN_EPS), getattr(self, "head_act", "default"))
 
     def logits(self, x):
         f = self.features(x)                                                      # pool -> norm -> fc (:432-436)

@@ -222,6 +222,22 @@ def _fold_mean_cls():
         def predict(self, x):
             ps = [m.predict(x) for m in self.folds]
             return ps[0] if len(ps) == 1 else sum(ps) / float(len(ps))
+
+        @property
+        def cam_supported(self):
+            return all(getattr(m, "cam_supported", False) for m in self.folds)
+
+        @property
+        def cam_unsupported_reason(self):
+            return getattr(self.folds[0], "cam_unsupported_reason", "the member defines no head_spec()")
+
+        def predict_with_cam(self, x, target="score"):
+            """``(predict(x), cam, peak)`` with one pass per fold; several folds: ``cam`` / ``peak`` are per-fold lists (the member's
+            map is the mean of its folds' normalised maps - ``ensemble.explain_batch`` composes them with weight 1 / folds)"""
+            rs = [m.predict_with_cam(x, target) for m in self.folds]
+            if len(rs) == 1:
+                return rs[0]
+            return sum(r[0] for r in rs) / float(len(rs)), [r[1] for r in rs], [r[2] for r in rs]
     return FoldMean
 
 
