@@ -346,6 +346,35 @@ int vip_jpeg_entropy_decode_h(const uint8_t* const* jpeg_h, const size_t* len_h,
 int vip_jpeg_idct_rgb_u8(const int16_t* coef, const vip_jpeg_desc* desc, int n, int max_blocks,
                          uint8_t* planes_ws, uint8_t* rgb_u8, int maxH, int maxW, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG re-save (dataset/augment.py:110-113, JpegCompress -> tf.image.random_jpeg_quality: an encode -> decode round trip) without the
+ * entropy coder, which is lossless: RGB -> quantised DCT coefficients in the layout above, which vip_jpeg_idct_rgb_u8 then turns into
+ * the pixels the re-saved file would decode to.  The arithmetic is libjpeg's baseline compressor with its defaults (what
+ * tf.image.encode_jpeg and Pillow run), all of it in integers, so coefficients and pixels are bit-exact against libjpeg-turbo.
+ *
+ * vip_jpeg_quality_tables_h (host): jpeg_set_quality(quality, force_baseline) of jcparam.c - scale = 5000 / q below 50, 200 - 2 q from
+ *   50; entry = (base * scale + 50) / 100 clamped to 1..255 over the luminance / chrominance tables of ITU-T T.81 Annex K.
+ *   luma_h, chroma_h: uint16 [64], natural (row-major) order.  quality outside 1..100 -> VIP_ERR_BAD_ARG.
+ * vip_jpeg_encode_layout_h (host): the descriptor vip_jpeg_probe_h reads from a file written at this size, subsampling (420 or 444;
+ *   anything else -> VIP_ERR_BAD_ARG) and quality: ncomp = 3, rgb_coded = 0, sampling 2x2,1x1,1x1 or 1x1 three times, blocks_* padded
+ *   to whole MCUs, qt rows 0 / 1 / 2 = luma / chroma / chroma, coef_off relative to 0; *coef_elems_h = int16 coefficients the image
+ *   needs.  A side outside 1..65535 or more than VIP_MAX_JPEG_PIXELS (environment, default 64 Mi) pixels -> VIP_ERR_BAD_ARG.
+ * vip_jpeg_fdct_quant_u8 (device): rgb_u8 [n][maxH][maxW][3] (image i in the top-left height x width corner of its slot, the layout
+ *   vip_jpeg_idct_rgb_u8 writes) -> YCbCr (jccolor.c: 16 fractional bits) -> 4:2:0 chroma by h2v2_downsample (jcsample.c: four-sample
+ *   sum + bias 1, 2, 1, 2 along the row, >> 2) or none -> component planes in planes_ws (one byte per coefficient, same offsets) ->
+ *   level shift, ISLOW forward DCT (jfdctint.c), quantisation (jcdctmgr.c: divisor 8 x table entry, magnitude rounded to nearest) ->
+ *   coef (int16, natural order, block-major per component, at desc[i].coef_off).  Edges as libjpeg pads them: last column / row
+ *   replicated out to whole blocks (for 4:2:0 chroma the columns before the downsampling, the rows after it); the blocks that only
+ *   fill the last MCU column / row are jccoefct.c's dummy blocks (AC zero, DC of the block before them in the MCU).
+ *   desc: DEVICE copy of n vip_jpeg_encode_layout_h descriptors with coef_off made absolute; max_blocks = the largest per-image block
+ *   count (all components); planes_ws and coef hold the sum of the images' coefficient counts and are 16-byte aligned
+ *   (VIP_ERR_ALIGNMENT otherwise).  An image whose descriptor is all zero is skipped.  No allocation, no atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int vip_jpeg_quality_tables_h(int quality, uint16_t* luma_h, uint16_t* chroma_h);
+int vip_jpeg_encode_layout_h(int width, int height, int subsampling, int quality, vip_jpeg_desc* desc_h, size_t* coef_elems_h);
+int vip_jpeg_fdct_quant_u8(const uint8_t* rgb_u8, const vip_jpeg_desc* desc, int n, int max_blocks, uint8_t* planes_ws,
+                           int16_t* coef, int maxH, int maxW, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

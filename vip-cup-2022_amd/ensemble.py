@@ -466,6 +466,76 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     return acc / float(len(flags))
 
 
+def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None) -> torch.Tensor:
+    """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
+    bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
+    (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
+    ``_score_batch``; it is decoded once.  Returns ``[1 + Q, M, n]`` fp32 (device), rows 1.. in the order of ``qualities``."""
+    from . import ops, pipeline
+    if isinstance(staged, pipeline.DecodedBatch):
+        batch = staged
+    else:
+        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
+            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    rows = [_score_batch(batch, members, None, after_fork=after_fork)]
+    for q in qualities:
+        rows.append(_score_batch(pipeline.recompress(batch, int(q), subsampling), members))
+    if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
+        ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
+    return torch.stack(rows)
+
+
+def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
+                       dist=None) -> np.ndarray:
+    """The extra exchange step of a stress run under the ``images`` plan: ``kept`` = this rank's ``stress_batch`` rows ``[Q, M, n_batch]`` in
+    batch order (its image shard, ``shard_bounds(n_images, rank, world)``).  ONE ``all_gather_into_tensor`` of the ranks' rows, padded to the
+    longest shard; returns ``[Q, M, n_images]`` fp32 (numpy) on every rank."""
+    lo, hi = shard_bounds(n_images, rank, world)
+    dev = kept[0].device if kept else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    local = torch.cat(list(kept), dim=2).to(torch.float32) if kept else torch.zeros((n_q, n_members, 0), dtype=torch.float32, device=dev)
+    assert tuple(local.shape) == (n_q, n_members, hi - lo), (tuple(local.shape), (n_q, n_members, hi - lo))
+    if dist is None or world == 1:
+        return local.cpu().numpy()
+    width = max(shard_bounds(n_images, r, world)[1] - shard_bounds(n_images, r, world)[0] for r in range(world))
+    mine = torch.zeros((n_q, n_members, max(width, 1)), dtype=torch.float32, device=dev)
+    mine[:, :, :hi - lo] = local
+    allp = torch.empty((world * mine.numel(),), dtype=torch.float32, device=dev)
+    dist.all_gather_into_tensor(allp, mine.reshape(-1))
+    allp = allp.view(world, n_q, n_members, max(width, 1))
+    full = torch.zeros((n_q, n_members, n_images), dtype=torch.float32, device=dev)
+    for r in range(world):
+        rlo, rhi = shard_bounds(n_images, r, world)
+        full[:, :, rlo:rhi] = allp[r, :, :, :rhi - rlo]
+    return full.cpu().numpy()
+
+
+def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence[int], thr: float = THR):
+    """``scores`` ``[1 + Q, M, n]`` (``stress_batch`` rows over all images, in the order of ``names``) -> ``(table, summary)``; numpy only.
+    ``table``: per sorted unique filename (duplicates averaged first, decision = mean ``> thr``: the rule of ``aggregate``) ``filename``,
+    ``p`` / ``decision`` unperturbed, ``p_q`` / ``decision_q`` ``[F, Q]``, ``stable`` (every decision equals the unperturbed one) and
+    ``flips_at`` (the highest listed quality whose decision differs, None when stable).  ``summary``: per quality the number and rate of
+    files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files."""
+    scores = np.asarray(scores)
+    qs = [int(q) for q in qualities]
+    assert scores.ndim == 3 and scores.shape[0] == 1 + len(qs) and scores.shape[2] == len(names), (scores.shape, len(qs), len(names))
+    agg = [aggregate(names, s, thr) for s in scores]
+    uniq = agg[0][0]
+    p, dec = agg[0][1], agg[0][2]
+    F = len(uniq)
+    p_q = np.stack([a[1] for a in agg[1:]], axis=1) if qs else np.zeros((F, 0), np.float32)
+    dec_q = np.stack([a[2] for a in agg[1:]], axis=1) if qs else np.zeros((F, 0), np.float32)
+    differs = dec_q != dec[:, None]
+    stable = ~differs.any(axis=1)
+    flips_at = [max((q for q, d in zip(qs, row) if d), default=None) for row in differs]
+    table = {"filename": uniq, "p": p, "decision": dec, "p_q": p_q, "decision_q": dec_q, "stable": stable, "flips_at": flips_at}
+    summary = {"n_files": F, "threshold": float(thr), "qualities": qs, "n_stable": int(stable.sum()),
+               "flips": {str(q): int(differs[:, k].sum()) for k, q in enumerate(qs)},
+               "flip_rate": {str(q): (float(differs[:, k].mean()) if F else 0.0) for k, q in enumerate(qs)},
+               "mean_abs_dp": {str(q): (float(np.abs(p_q[:, k].astype(np.float64) - p.astype(np.float64)).mean()) if F else 0.0)
+                               for k, q in enumerate(qs)}}
+    return table, summary
+
+
 class Explanation:
     """What ``explain_batch`` returns: ``scores`` ``[M, n]`` (device; exactly what ``_score_batch`` returns), per member ``maps[m]``
     ``[n, gh, gw]`` fp32 (un-normalised, ``ops.cam``) and ``peaks[m]`` ``[n]`` - None for a member without a map, with the reason in

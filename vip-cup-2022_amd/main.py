@@ -2,6 +2,7 @@
 
     python3 vip-cup-2022_amd/main.py <input.csv> <output.csv> [--scores-out scores.csv] [--synthetic]
                                      [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
+                                     [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
     python -m torch.distributed.run --nproc-per-node N ... vip-cup-2022_amd/main.py in.csv out.csv
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
@@ -13,6 +14,11 @@ main.py:171-198); members whose graph is not built yet are reported and skipped 
 image's own size; or with ``--heatmap-format png`` a jet overlay ``<name>.png``), with ``--heatmap-members`` every member's
 low-resolution map and peak in ``<name>.members.npz``, and ``heatmaps.json`` (per member: supported or why not).  The CSV outputs do
 not change with the flag.
+``--stress-jpeg 90,70,50 --stress-out stress.csv`` additionally scores every image as it would come back from a JPEG save at each listed
+quality (dataset/augment.py:110-113 ``JpegCompress``; the decoded image is re-saved at its own size, before the members' resize, with
+libjpeg's default 4:2:0 chroma or ``--stress-subsampling 444``) and writes, per input file, ``filename, p, decision, p_q<Q>...,
+decision_q<Q>..., stable, flips_at`` (``flips_at``: the highest listed quality at which the decision differs from the unperturbed one) and
+``stress.json`` with the per-quality flip counts, flip rates, mean |p_q - p| and the settings.  The CSV outputs do not change with the flag.
 
 Checkpoints: ``<script dir>/ckpts/<name>/ckpt/*.h5`` (Keras weight / model files, as in the reference), else ``ckpt/saved_model.pb`` (a
 Keras SavedModel directory: its variables are read by ``tfbundle``), or ``*.npz`` (a flat dict of
@@ -80,6 +86,39 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
+def _stress_scorer(qualities, subsampling, kept):
+    """the ``batch_scorer`` of ``--stress-jpeg``: ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of
+    the re-saved batches ``[Q, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
+    from vipcup_amd import ensemble
+
+    def score(staged, sub, b0, b1, after_fork):
+        rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
+        kept.append(rows[1:])
+        return rows[0]
+    return score
+
+
+def _write_stress(a, names, members, per_model, stressed, qualities, mode):
+    """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
+    import pandas as pd
+    from vipcup_amd import ensemble
+    scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
+    table, summary = ensemble.stress_table(names, scores, qualities)
+    cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
+    for k, q in enumerate(qualities):
+        cols[f"p_q{q}"] = table["p_q"][:, k]
+    for k, q in enumerate(qualities):
+        cols[f"decision_q{q}"] = table["decision_q"][:, k]
+    cols["stable"] = table["stable"].astype(np.int64)
+    cols["flips_at"] = ["" if q is None else str(q) for q in table["flips_at"]]
+    pd.DataFrame(cols).to_csv(a.stress_out, index=False)
+    summary["settings"] = {"qualities": list(qualities), "subsampling": {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling],
+                           "threshold": ensemble.THR, "precision": mode, "batch_size": a.batch_size, "n_images": len(names),
+                           "members": [spec.name for spec, _ in members]}
+    with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
+        json.dump(summary, f, indent=1)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input_csv")
@@ -113,7 +152,34 @@ def main(argv=None):
                     help="npy: the fp32 map in [0, 1] at the image's size; png: the jet colour table blended over the image (alpha 0.4)")
     ap.add_argument("--heatmap-members", action="store_true",
                     help="also write every member's low-resolution map and peak: DIR/<name>.members.npz")
+    ap.add_argument("--stress-jpeg", default=None, metavar="Q[,Q...]",
+                    help="recompression stress test: also score every image re-saved as JPEG at each quality (1..100; duplicates are "
+                         "dropped, highest first) and report whether the decision survives; needs --stress-out")
+    ap.add_argument("--stress-out", default=None, metavar="FILE.csv",
+                    help="per input file: filename, p, decision, p_q<Q>..., decision_q<Q>..., stable, flips_at; FILE.json next to it "
+                         "holds the per-quality flip counts and rates, mean |p_q - p| and the settings")
+    ap.add_argument("--stress-subsampling", default="420", choices=["420", "444"],
+                    help="chroma sampling of the simulated re-save: 420 (libjpeg's default) or 444")
     a = ap.parse_args(argv)
+    qualities = None
+    if a.stress_jpeg is not None:
+        try:
+            qualities = sorted({int(t) for t in a.stress_jpeg.split(",")}, reverse=True)
+        except ValueError:
+            qualities = []
+        if not qualities or qualities[-1] < 1 or qualities[0] > 100:
+            raise SystemExit(f"vipcup_amd main: --stress-jpeg {a.stress_jpeg!r}: expected a comma-separated list of integer qualities in 1..100")
+        if a.stress_out is None:
+            raise SystemExit("vipcup_amd main: --stress-jpeg needs --stress-out FILE.csv")
+        if a.shard != "images" or a.tta > 1:
+            # the scores of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
+            raise SystemExit("vipcup_amd main: --stress-jpeg works with --shard images and --tta 1 only (got --shard "
+                             f"{a.shard} --tta {a.tta}): the recompression stress test under member sharding or TTA is not implemented")
+        if a.heatmaps is not None:
+            raise SystemExit("vipcup_amd main: --stress-jpeg and --heatmaps cannot be combined (both replace the batch scorer): "
+                             "run them one after the other")
+    elif a.stress_out is not None or a.stress_subsampling != "420":
+        raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]")
     if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
         # the maps of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
         raise SystemExit("vipcup_amd main: --heatmaps works with --shard images and --tta 1 only (got --shard "
@@ -209,6 +275,9 @@ def main(argv=None):
     batch_scorer = None
     if a.heatmaps is not None:
         batch_scorer = _heatmap_writer(a, names, members, rank)
+    stress_rows = []
+    if qualities is not None:
+        batch_scorer = _stress_scorer(qualities, {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows)
 
     t0 = time.time()
     costs = None
@@ -219,6 +288,9 @@ def main(argv=None):
     per_model = ensemble.score_files(jpegs_for, len(paths), members, a.batch_size, rank, world, dist,
                                      tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
     uniq, score, decision = ensemble.aggregate(names, per_model)
+    stressed = None
+    if qualities is not None:                   # the one extra collective of a stress run: every rank's [Q, M, n_local] rows
+        stressed = ensemble.gather_stress_rows(stress_rows, len(qualities), len(members), len(paths), rank, world, dist)
     if rank == 0:
         pd.DataFrame({"filename": uniq, "logit": decision}).to_csv(a.output_csv, index=False)  # main.py:143-145
         if a.scores_out:
@@ -226,6 +298,9 @@ def main(argv=None):
             for (spec, _), row in zip(members, per_model):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
+        if stressed is not None:
+            _write_stress(a, names, members, per_model, stressed, qualities, mode)
+            print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         dt = time.time() - t0
         print(f"> FINAL PREDICTION SAVED TO {a.output_csv}")
         print(f"> TIME TO INFER: {dt / 60:.2f} min ({len(paths) / dt:.1f} images/s on {world} GPU(s))")  # main.py:231-235

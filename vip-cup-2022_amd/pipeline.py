@@ -271,6 +271,65 @@ def decode_entropy(host_stage, device="cuda") -> DecodedBatch:
     return DecodedBatch(rgb, sizes, sizes_host)
 
 
+SUBSAMPLINGS = {"4:2:0": 420, "420": 420, 420: 420, "4:4:4": 444, "444": 444, 444: 444}
+
+
+def quality_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
+    """libjpeg's ``jpeg_set_quality(quality, force_baseline)`` tables: (luma, chroma), uint16 [64], natural order (host)."""
+    luma, chroma = np.zeros((64,), np.uint16), np.zeros((64,), np.uint16)
+    st = _abi.lib().vip_jpeg_quality_tables_h(int(quality), luma.ctypes.data_as(C.c_void_p), chroma.ctypes.data_as(C.c_void_p))
+    _abi.check(st, "vip_jpeg_quality_tables_h")
+    return luma, chroma
+
+
+def encode_layout(sizes_host: Sequence[Tuple[int, int]], quality: int, subsampling="4:2:0"):
+    """Host: the descriptors of a batch re-saved as JPEG at ``quality`` / ``subsampling`` - what ``entropy_decode`` would return for the
+    files - as ``(desc (ctypes array, coef_off absolute), total int16 coefficients, max_blocks)``.  ``sizes_host`` = [(h, w)]."""
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling {subsampling!r}: expected '4:2:0' or '4:4:4'")
+    lib = _abi.lib()
+    desc = (_abi.JpegDesc * len(sizes_host))()
+    need = C.c_size_t(0)
+    done: Dict[Tuple[int, int], Tuple[_abi.JpegDesc, int]] = {}     # a batch holds few distinct sizes
+    total = max_blocks = 0
+    for i, (h, w) in enumerate(sizes_host):
+        if (h, w) not in done:
+            tmp = _abi.JpegDesc()
+            st = lib.vip_jpeg_encode_layout_h(int(w), int(h), SUBSAMPLINGS[subsampling], int(quality), C.byref(tmp), C.byref(need))
+            _abi.check(st, "vip_jpeg_encode_layout_h")
+            done[(h, w)] = (tmp, int(need.value))
+        tmp, elems = done[(h, w)]
+        C.memmove(C.byref(desc[i]), C.byref(tmp), C.sizeof(_abi.JpegDesc))
+        for c in range(3):
+            desc[i].coef_off[c] += total
+        total += elems
+        max_blocks = max(max_blocks, elems // 64)
+    return desc, total, max_blocks
+
+
+def recompress(batch: DecodedBatch, quality: int, subsampling: str = "4:2:0") -> DecodedBatch:
+    """The batch as it would come back from a JPEG save at ``quality`` (1..100) and a load - dataset/augment.py:110-113 ``JpegCompress``
+    (``tf.image.random_jpeg_quality``) at a fixed quality, each image re-saved at its own size: forward colour conversion, chroma
+    downsampling, DCT and quantisation on the GPU (``vip_jpeg_fdct_quant_u8``), then the decoder's own ``vip_jpeg_idct_rgb_u8``.  The
+    pixels are those of libjpeg(-turbo) writing and reading the file, bit for bit (the entropy coder in between is lossless and is
+    skipped).  Returns a new batch of the same sizes; ``batch`` is not touched.  Runs on the current stream; only the descriptors
+    (a few hundred bytes per image) come from the host."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    desc, total, max_blocks = encode_layout(batch.sizes_host, quality, subsampling)
+    desc_d = torch.from_numpy(np.frombuffer(bytes(desc), dtype=np.uint8).copy()).to(device)
+    coef = torch.empty((total,), dtype=torch.int16, device=device)
+    planes = torch.empty((total,), dtype=torch.uint8, device=device)
+    rgb = torch.zeros_like(batch.rgb)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    lib = _abi.lib()
+    st = lib.vip_jpeg_fdct_quant_u8(_p(src), _p(desc_d), n, max_blocks, _p(planes), _p(coef), maxH, maxW, _stream())
+    _abi.check(st, "vip_jpeg_fdct_quant_u8")
+    st = lib.vip_jpeg_idct_rgb_u8(_p(coef), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW, _stream())
+    _abi.check(st, "vip_jpeg_idct_rgb_u8")
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
     """Deterministic form of dataset/augment.py ``apply_augment`` (:153-182): per-image flags instead of the
     reference's TF RNG draws (p=0.8 gate, hflip .5, vflip .5, gray .3) — the caller owns the randomness."""
