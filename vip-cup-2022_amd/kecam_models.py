@@ -14,7 +14,6 @@ Load-time folding (all exact in fp32, then cast to fp16 once):
   * ECA's Conv1D over channels as a banded [C,C] matrix for the GEMM kernel (common_layers.py:335-353).
 """
 import math
-import os
 from typing import Dict
 
 import torch
@@ -327,7 +326,7 @@ class EfficientNet(_Base):
                     y = ops.conv2d(y, blk["out"], stride=s, pad=pad, act=act, residual=inp if blk["shortcut"] else None)
             else:
                 pad = self._pad(y.shape[1:3], k, s)
-                if blk["se"] is not None and os.environ.get("VIP_MBCONV_FUSED", "0") != "1":
+                if blk["se"] is not None and not ops.mbconv_fused():
                     # depthwise conv that leaves the squeeze-excite pool's partial sums: the gate kernel does not read h again
                     e = ops.conv2d(y, blk["exp"], act=act) if blk["exp"] is not None else y
                     h, a = ops.dwconv2d_se(e, blk["dw"][0], blk["dw"][1], k, s, pad, act, blk["se"][0], blk["se"][1], act, "sigmoid")

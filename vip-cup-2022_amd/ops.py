@@ -4,6 +4,7 @@ PyTorch is used for device memory and streams only.  Activations are fp16, conti
 (``[B,H,W,C]``) or row-major ``[rows, C]``.  Every function launches on torch's current stream.
 """
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -11,6 +12,53 @@ from typing import Optional
 import torch
 
 from . import _abi
+
+
+# ---- knobs: every VIP_* variable this module reads -------------------------------------------------------------------------------
+def _env_flag(name: str, default: bool) -> bool:
+    """a default-on switch is off only at "0", a default-off switch is on only at "1" """
+    v = os.environ.get(name)
+    return default if v is None else (v != "0" if default else v == "1")
+
+
+def _env_int(name: str, default: int) -> int:
+    return int(os.environ.get(name, default))
+
+
+# read once, at import (tests and tools set the module attribute instead)
+PRECISION = os.environ.get("VIP_PRECISION", "fast")            # "fast" | "strict" | "f32": see "precision mode" below
+# STRICT GEMM arithmetic: "bf16x3" (default) = three-term bf16 splits, six bf16 MFMAs per block (vip_conv2d_nhwc_s32x); "f32" = the
+# f32-input MFMA (vip_conv2d_nhwc_s32), 2.7x lower matrix rate.  Same results to f32 round-off (tests/test_gpu_strict.py runs both).
+# "bf16x2" = two-term splits, three MFMAs per block (vip_conv2d_nhwc_s32x2): 2^-17 of each product dropped - NOT f32 quality, 64x finer
+# than fp16 storage; the member logits stay inside the 1e-3 tolerance with less margin (DESIGN.md section 4).
+STRICT_GEMM = os.environ.get("VIP_STRICT_GEMM", "bf16x3")
+_LN_GEMM = _env_flag("VIP_LN_GEMM", True)                      # ln_dense as one launch (vip_ln_gemm_bias_act_f16)
+_MLP_H2_FUSED = _env_flag("VIP_MLP_H2_FUSED", True)            # packed strict: mlp as one launch (vip_mlp_fused_h2)
+_SE_H2_FUSED = _env_flag("VIP_SE_H2_FUSED", True)              # packed strict: se_gate as one launch (vip_se_gate_h2)
+_H2_GATED = _env_flag("VIP_H2_GATED", True)                    # packed strict: the gate folded into the GEMM's activation operand
+_DW_H2_LDS = _env_int("VIP_DW_H2_LDS", 3)                      # smallest k the LDS-staged strict depthwise kernel takes (0: never)
+_DW_SE_FUSED = _env_flag("VIP_DW_SE_POOL", True)               # dwconv2d_se: the depthwise kernel leaves the pool's partial sums
+_GCVIT_BLOCK_FUSED = _env_flag("VIP_GCVIT_BLOCK_FUSED", True)  # gcvit_attn_block as one launch
+# the 14 x 14-window form of the fused block (C = 256, 8 heads: csrc/gcvit_block14.hip) is correct and NOT faster than the four launches
+# (116 us either way at B = 256: one 8-wave workgroup per CU, three barriers and a synchronous 51 KB weight stage per head) - opt-in
+_GCVIT_BLOCK14 = _env_flag("VIP_GCVIT_BLOCK14", False)
+
+
+# read at every call (tests and tools flip the variable between calls)
+def hilo_enabled() -> bool:
+    """two-term (w + w_lo) weights where ``hilo_eligible`` (VIP_HILO=0 switches them off)"""
+    return _env_flag("VIP_HILO", True)
+
+
+def mbconv_fused() -> bool:
+    """``mbconv_expand_dw`` as one launch where the C ABI takes the shape (VIP_MBCONV_FUSED=1; measured slower, see there)"""
+    return _env_flag("VIP_MBCONV_FUSED", False)
+
+
+def offset_calibration() -> bool:
+    """``zoo.calibrate``'s whole-model second pass (VIP_OFFSET_CALIBRATION=1): the K-doubled twins are built and kept for it"""
+    return _env_flag("VIP_OFFSET_CALIBRATION", False)
+
 
 ACT = {None: 0, "none": 0, "linear": 0, "relu": 1, "silu": 2, "swish": 2, "gelu": 3, "sigmoid": 4}
 
@@ -106,12 +154,43 @@ def h2_check(what: str = "strict forward pass", device=None):
                             "use --precision f32 (fp32 storage) for this model")
 
 
-def _strict_call(base: str, kind: str, *args, status: bool = True):
-    """``vip_<base>_s32(*args, stream)`` or ``vip_<base>_h2(*args, status, stream)``"""
-    fn = f"vip_{base}_{kind}"
-    extra = [_p(h2_status())] if (kind == "h2" and status) else []
-    st = getattr(_abi.lib(), fn)(*args, *extra, _stream())
-    _abi.check(st, fn)
+def _launch(name: str, *args, status: bool = False, prof=None):
+    """The one way onto the device: ``name(*args[, the h2 status word], current stream)``, its status checked under that name.
+    ``prof``: a callable -> ``(kernel, flops, bytes[, tag])``, evaluated (and the launch bracketed) only while a profiler is installed."""
+    fn = getattr(_abi.lib(), name)
+    if status:
+        args += (_p(h2_status()),)
+    tok = _PROF.start(*prof()) if (_PROF is not None and prof is not None) else None
+    st = fn(*args, _stream())
+    if tok is not None:
+        _PROF.stop(tok)
+    _abi.check(st, name)
+
+
+# Operators with ONE signature across storages: base name -> ({storage kind: entry-point suffix}, whether the packed entry point
+# takes the status word).  Where the fp16 signature differs (scale_add_act3, radix_combine2, gap_*_f32) only the strict two are listed.
+_ALL_KINDS = {"f16": "f16", "s32": "s32", "h2": "h2"}
+_STRICT_KINDS = {"s32": "s32", "h2": "h2"}
+_KIND_OPS = {
+    "layernorm": (_ALL_KINDS, True),
+    "pool2d_nhwc": (_ALL_KINDS, True),
+    "global_avgpool": (_ALL_KINDS, True),
+    "mul": (_ALL_KINDS, True),
+    "vit_tokens": (_ALL_KINDS, True),
+    "mhsa_fwd": (_ALL_KINDS, True),
+    "dwconv2d_nhwc": (_ALL_KINDS, True),
+    "window_attn_fwd": (_ALL_KINDS, True),
+    "cam": ({"f16": "f32", "s32": "s32", "h2": "h2"}, False),
+    "scale_add_act": (_STRICT_KINDS, True),
+    "radix_combine": (_STRICT_KINDS, True),
+    "gap_ln_dense": (_STRICT_KINDS, False),
+}
+
+
+def _launch_kind(base: str, kind: str, *args, prof=None):
+    """``vip_<base>_<suffix of kind>`` through ``_launch``"""
+    suffix, status = _KIND_OPS[base]
+    _launch(f"vip_{base}_{suffix[kind]}", *args, status=status and kind == "h2", prof=prof)
 
 
 def pack_h2(x: torch.Tensor) -> torch.Tensor:
@@ -119,8 +198,7 @@ def pack_h2(x: torch.Tensor) -> torch.Tensor:
     _chk32(x, "pack_h2.x")
     assert x.shape[-1] % 8 == 0, x.shape
     out = torch.empty(x.shape, dtype=PACKED, device=x.device)
-    st = _abi.lib().vip_pack_h2(_p(x), _p(out), x.numel(), _p(h2_status()), _stream())
-    _abi.check(st, "vip_pack_h2")
+    _launch("vip_pack_h2", _p(x), _p(out), x.numel(), status=True)
     return out
 
 
@@ -128,8 +206,7 @@ def unpack_h2(x: torch.Tensor) -> torch.Tensor:
     """packed strict tensor -> fp32 of the same logical shape (hi + lo)"""
     _chkp(x, "unpack_h2.x")
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    st = _abi.lib().vip_unpack_h2(_p(x), _p(out), x.numel(), _stream())
-    _abi.check(st, "vip_unpack_h2")
+    _launch("vip_unpack_h2", _p(x), _p(out), x.numel())
     return out
 
 
@@ -143,7 +220,6 @@ def unpack_h2(x: torch.Tensor) -> torch.Tensor:
 #           the reference arithmetic and as the fallback when an activation leaves the fp16 range (h2_check).
 # The mode is a property of the WEIGHTS a model was constructed with (``precision(mode)`` around the constructor) and of the
 # activation dtype it is fed: every operator below dispatches on ``x.dtype``.
-PRECISION = os.environ.get("VIP_PRECISION", "fast")
 PRECISIONS = ("fast", "strict", "f32")
 
 
@@ -243,8 +319,8 @@ class calibration:
     def __exit__(self, *exc):
         global _CALIB, _UNFUSED
         _CALIB, _UNFUSED = self._old
-        if os.environ.get("VIP_OFFSET_CALIBRATION", "0") != "1":
-            drop_exact_weights()            # nothing will read the twins: do not let a caller without zoo.calibrate() leak them
+        if not offset_calibration():
+            drop_exact_weights()           # nothing will read the twins: do not let a caller without zoo.calibrate() leak them
         return False
 
 
@@ -304,7 +380,7 @@ def _bias_correct(cw: "ConvWeight", x_eff: torch.Tensor):
     k = cw.kh * cw.kw * cw.cin_g
     cog = cw.cout // cw.groups
     taps = cw.kh * cw.kw
-    if os.environ.get("VIP_OFFSET_CALIBRATION", "0") == "1":       # the K-doubled twin is only read by zoo.calibrate's opt-in second pass
+    if offset_calibration():       # the K-doubled twin is only read by zoo.calibrate's opt-in second pass
         w2 = torch.cat([cw.w[:, :k].reshape(cw.cout, taps, cw.cin_g), cw.err[:, :k].to(torch.float16).reshape(cw.cout, taps, cw.cin_g)], 2)
         w2 = w2.reshape(cw.cout, 2 * k)
         if (2 * k) % 8:
@@ -365,7 +441,6 @@ def split_h2_weights(w_rows: torch.Tensor):
     mx = float(w.abs().max()) if w.numel() else 0.0
     scale = 1.0
     if mx > 0.0 and mx == mx and mx != float("inf"):
-        import math
         scale = 2.0 ** math.floor(math.log2(8191.0 / mx))
     ws = w * scale
     hi = ws.to(torch.float16)
@@ -374,20 +449,12 @@ def split_h2_weights(w_rows: torch.Tensor):
     return packed.contiguous(), float(scale)
 
 
-# STRICT GEMM arithmetic: "bf16x3" (default) = three-term bf16 splits, six bf16 MFMAs per block (vip_conv2d_nhwc_s32x); "f32" = the
-# f32-input MFMA (vip_conv2d_nhwc_s32), 2.7x lower matrix rate.  Same results to f32 round-off (tests/test_gpu_strict.py runs both).
-# "bf16x2" = two-term splits, three MFMAs per block (vip_conv2d_nhwc_s32x2): 2^-17 of each product dropped - NOT f32 quality, 64x finer
-# than fp16 storage; the member logits stay inside the 1e-3 tolerance with less margin.
-STRICT_GEMM = os.environ.get("VIP_STRICT_GEMM", "bf16x3")
-
-
 HILO_MAX_K = 256     # vip_conv2d_hilo_nhwc_f16: the streaming kernel's K limit
 
 
 def hilo_eligible(kh: int, kw: int, cin: int, groups: int = 1) -> bool:
     """Can a layer carry two-term weights (w + w_lo)?  1x1, ungrouped, K <= 256 (VIP_HILO=0 switches them off)."""
-    import os
-    return kh == 1 and kw == 1 and groups == 1 and cin <= HILO_MAX_K and os.environ.get("VIP_HILO", "1") != "0"
+    return kh == 1 and kw == 1 and groups == 1 and cin <= HILO_MAX_K and hilo_enabled()
 
 
 def make_conv_weight(kernel_hwio: torch.Tensor, bias: Optional[torch.Tensor], groups: int = 1,
@@ -469,6 +536,77 @@ def conv_kernel_name(d: "_abi.ConvDesc", has_residual: bool, has_gate: bool = Fa
     return buf.value.decode() if st == 0 else None
 
 
+def conv_kernel_name_h2(d: "_abi.ConvDesc", has_residual: bool) -> Optional[str]:
+    """the kernel vip_conv2d_nhwc_h2 launches for this descriptor (a dry run of the C dispatcher)"""
+    buf = C.create_string_buffer(64)
+    st = _abi.lib().vip_conv2d_kernel_name_h2(C.byref(d), int(has_residual), buf, 64)
+    return buf.value.decode() if st == 0 else None
+
+
+# ---- named terms of the fusion decisions below -------------------------------------------------------------------------------------
+SE_FUSED_MAX_WEIGHTS = 256 * 1024      # the one-launch gate kernels re-read both matrices per image: beyond this the batched GEMMs win
+
+
+def _pointwise(cw: ConvWeight) -> bool:
+    """1x1 and ungrouped: a plain GEMM over the channel axis"""
+    return cw.kh == cw.kw == 1 and cw.groups == 1
+
+
+def _se_chain_ok(fc1: ConvWeight, fc2: ConvWeight, C_: int) -> bool:
+    """fc1 -> fc2 is a squeeze-excite chain on ``C_`` channels that the one-launch gate kernels take"""
+    return (_pointwise(fc1) and _pointwise(fc2) and fc1.cin == C_ and fc2.cin == fc1.cout
+            and C_ * fc1.cout + fc1.cout * fc2.cout <= SE_FUSED_MAX_WEIGHTS)
+
+
+def _epilogue_ok(act, act_post, residual) -> bool:
+    """what the fused-prologue GEMMs (LayerNorm / gate in the activation load) carry: (activation) or (residual [+ ReLU])"""
+    if residual is None:
+        return act_post is None
+    return act is None and act_post in (None, "relu")
+
+
+def _dw_filter_ok(w_khwc: torch.Tensor, k: int, C_: int) -> bool:
+    return w_khwc.dtype == torch.float32 and w_khwc.is_contiguous() and w_khwc.shape == (k, k, C_)
+
+
+def _ln_args(ln):
+    """``ln = (gamma, beta, eps)`` or None -> the three arguments of a C entry point with an optional LayerNorm prologue"""
+    return (ln[0], ln[1], float(ln[2])) if ln is not None else (None, None, 0.0)
+
+
+def _out_hw(H: int, W: int, kh: int, kw: int, sh: int, sw: int, pad):
+    pt, pb, pl, pr = pad
+    return (H + pt + pb - kh) // sh + 1, (W + pl + pr - kw) // sw + 1
+
+
+# ---- convolution / dense ------------------------------------------------------------------------------------------------------------
+def _conv_front(kind: str, x, cw: ConvWeight, stride, pad, act, act_post, residual, out, cin_off, cout_off):
+    """What the three storages share: operand checks, output size, ``out`` allocated in the storage of ``x`` -> ``(out, ConvDesc)``"""
+    B, H, W, ldx = x.shape
+    sh, sw = (stride, stride) if isinstance(stride, int) else stride
+    Ho, Wo = _out_hw(H, W, cw.kh, cw.kw, sh, sw, pad)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cw.cout), dtype=x.dtype, device=x.device)
+    else:
+        _chk_kind(out, kind, "conv2d.out")
+        assert out.shape[:3] == (B, Ho, Wo), (out.shape, (B, Ho, Wo))
+    if residual is not None:
+        _chk_kind(residual, kind, "conv2d.residual")
+        assert residual.shape[:3] == (B, Ho, Wo) and residual.shape[3] >= cw.cout
+    return out, _abi.ConvDesc(B=B, H=H, W=W, Cin=cw.cin, Cout=cw.cout, kh=cw.kh, kw=cw.kw, sh=sh, sw=sw, pt=pad[0], pl=pad[2], Ho=Ho, Wo=Wo,
+                              groups=cw.groups, ldx=ldx, cin_off=cin_off, ldy=out.shape[3], cout_off=cout_off,
+                              ldr=0 if residual is None else residual.shape[3], res_off=0, ldw=cw.ldw, act_pre=_act(act),
+                              act_post=_act(act_post))
+
+
+def _conv_prof(kernel: str, d, cw: ConvWeight, residual, act_bytes: float, w_bytes: float, tag: str = ""):
+    """profiler entry of a convolution launch: algorithmic FLOPs, bytes at ``act_bytes`` per activation / ``w_bytes`` per weight element"""
+    M = d.B * d.Ho * d.Wo
+    return (kernel, 2.0 * M * cw.cout * (cw.kh * cw.kw * cw.alg_cin_g),
+            act_bytes * (d.B * d.H * d.W * cw.cin + M * cw.cout * (2 if residual is not None else 1)) + w_bytes * cw.w.numel(),
+            f"M={M} N={cw.cout} K={cw.kh * cw.kw * cw.cin_g} k{cw.kh} s{d.sh} g{cw.groups}{tag}")
+
+
 def conv2d(x: torch.Tensor, cw: ConvWeight, stride=1, pad=(0, 0, 0, 0), act=None, act_post=None,
            residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
            cin_off: int = 0, cout_off: int = 0, gate: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -481,10 +619,8 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, stride=1, pad=(0, 0, 0, 0), act=None
     kind = _kind(x, "conv2d.x")
     if kind != cw.kind:
         raise _abi.VipError(f"conv2d: {kind} activations with {cw.kind} weights - build the model and its input in the same precision")
-    if kind == "s32":
-        return _conv2d_s32(x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off, gate)
-    if kind == "h2":
-        return _conv2d_h2(x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off, gate)
+    if kind != "f16":
+        return _CONV_STRICT[kind](x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off, gate)
     if gate is not None and _UNFUSED:
         assert gate.shape == (x.shape[0], 2, cw.cin) and x.shape[3] == cw.cin and cin_off == 0
         x, gate = scale_add_act(x, gate, None, None), None
@@ -492,162 +628,95 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, stride=1, pad=(0, 0, 0, 0), act=None
         _bias_correct(cw, x[..., cin_off:cin_off + cw.cin])
     if _EXACT and cw.exact is not None:
         x, cw, cin_off = _exact_operands(x, cw, cin_off)
-    B, H, W, ldx = x.shape
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - cw.kh) // sh + 1
-    Wo = (W + pl + pr - cw.kw) // sw + 1
-    d = _abi.ConvDesc(B=B, H=H, W=W, Cin=cw.cin, Cout=cw.cout, kh=cw.kh, kw=cw.kw, sh=sh, sw=sw, pt=pt, pl=pl,
-                      Ho=Ho, Wo=Wo, groups=cw.groups, ldx=ldx, cin_off=cin_off, ldy=cw.cout if out is None else out.shape[3],
-                      cout_off=cout_off, ldr=0 if residual is None else residual.shape[3], res_off=0, ldw=cw.ldw,
-                      act_pre=_act(act), act_post=_act(act_post))
+    out, d = _conv_front("f16", x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off)
     if gate is not None:
         _chk16(gate, "conv2d.gate")
-        assert gate.shape == (B, 2, cw.cin) and ldx == cw.cin and cin_off == 0
+        assert gate.shape == (d.B, 2, cw.cin) and d.ldx == cw.cin and cin_off == 0
         if conv_kernel_name(d, residual is not None, has_gate=True) is None:
-            x = scale_add_act(x, gate, None, None)
-            gate = None
-    if out is None:
-        out = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float16, device=x.device)
-    else:
-        _chk16(out, "conv2d.out")
-        assert out.shape[:3] == (B, Ho, Wo), (out.shape, (B, Ho, Wo))
-    if residual is not None:
-        _chk16(residual, "conv2d.residual")
-        assert residual.shape[:3] == (B, Ho, Wo) and residual.shape[3] >= cw.cout
-    tok = None
-    if _PROF is not None:
-        M = B * Ho * Wo
-        kk = cw.kh * cw.kw * cw.alg_cin_g
-        name = conv_kernel_name(d, residual is not None, gate is not None, cw.w_lo is not None) or "unsupported"
-        tok = _PROF.start(name, 2.0 * M * cw.cout * kk,
-                          2.0 * (B * H * W * cw.cin + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()),
-                          f"M={M} N={cw.cout} K={cw.kh * cw.kw * cw.cin_g} k{cw.kh} s{sh} g{cw.groups}"
-                          f"{' gate' if gate is not None else ''}{' res' if residual is not None else ''} act={act}")
-    if cw.w_lo is not None:
-        if gate is not None:
+            x, gate = scale_add_act(x, gate, None, None), None
+    has_gate, has_lo = gate is not None, cw.w_lo is not None
+
+    def prof():
+        return _conv_prof(conv_kernel_name(d, residual is not None, has_gate, has_lo) or "unsupported", d, cw, residual, 2.0, 2.0,
+                          f"{' gate' if has_gate else ''}{' res' if residual is not None else ''} act={act}")
+    tail = (_p(cw.bias), _p(residual), _p(out), C.byref(d))
+    if has_lo:
+        if has_gate:
             raise _abi.VipError("conv2d: a two-term-weight layer cannot take a gate")
-        st = _abi.lib().vip_conv2d_hilo_nhwc_f16(_p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(residual), _p(out),
-                                                 C.byref(d), _stream())
-    elif gate is not None:
-        st = _abi.lib().vip_conv2d_gated_nhwc_f16(_p(x), _p(gate), _p(cw.w), _p(cw.bias), _p(residual), _p(out),
-                                                  C.byref(d), _stream())
+        _launch("vip_conv2d_hilo_nhwc_f16", _p(x), _p(cw.w), _p(cw.w_lo), *tail, prof=prof)
+    elif has_gate:
+        _launch("vip_conv2d_gated_nhwc_f16", _p(x), _p(gate), _p(cw.w), *tail, prof=prof)
     else:
-        st = _abi.lib().vip_conv2d_nhwc_f16(_p(x), _p(cw.w), _p(cw.bias), _p(residual), _p(out), C.byref(d), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_conv2d_nhwc_f16")
+        _launch("vip_conv2d_nhwc_f16", _p(x), _p(cw.w), *tail, prof=prof)
     return out
-
-
-def conv_kernel_name_h2(d: "_abi.ConvDesc", has_residual: bool) -> Optional[str]:
-    """the kernel vip_conv2d_nhwc_h2 launches for this descriptor (a dry run of the C dispatcher)"""
-    buf = C.create_string_buffer(64)
-    st = _abi.lib().vip_conv2d_kernel_name_h2(C.byref(d), int(has_residual), buf, 64)
-    return buf.value.decode() if st == 0 else None
 
 
 _H2_SPAN_MAX = 0xFFFFFFE0       # the C kernels address every tensor through 32-bit buffer offsets
 
 
-_H2_GATED = os.environ.get("VIP_H2_GATED", "1") != "0"
-
-
 def _conv2d_h2(x, cw: ConvWeight, stride, pad, act, act_post, residual, out, cin_off, cout_off, gate):
     """packed-STRICT conv2d: packed x / residual / out, vip_conv2d_nhwc_h2; a packed gate [B, Cin] is multiplied in first.  Tensors
     beyond the 4 GiB the kernels can address are processed in batch slices (images are independent)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    pt, pb, pl, pr = pad
     if gate is not None:
         assert gate.shape == (x.shape[0], cw.cin) and x.shape[3] == cw.cin and cin_off == 0, (gate.shape, x.shape, cw.cin)
         _chkp(gate, "conv2d.gate")
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
         # in the GEMM's activation operand (vip_conv2d_gated_nhwc_h2) where the C ABI carries it: 1x1 stride-1 ungrouped, no padding,
         # (activation) or (residual [+ReLU]) epilogue; otherwise a separate multiply pass first
-        fold = (_H2_GATED and not _UNFUSED and cw.kh == cw.kw == 1 and (sh, sw) == (1, 1) and cw.groups == 1 and pad == (0, 0, 0, 0)
-                and 4 * x.numel() < 0xFFFF0000 - 4 * cw.cin
-                and ((residual is None and act_post is None) or (residual is not None and act is None and act_post in (None, "relu"))))
+        fold = (_H2_GATED and not _UNFUSED and _pointwise(cw) and (sh, sw) == (1, 1) and pad == (0, 0, 0, 0)
+                and 4 * x.numel() < 0xFFFF0000 - 4 * cw.cin and _epilogue_ok(act, act_post, residual))
         if not fold:
-            x = scale_add_act(x, gate, None, None)
-            gate = None
-    B, H, W, ldx = x.shape
-    Ho = (H + pt + pb - cw.kh) // sh + 1
-    Wo = (W + pl + pr - cw.kw) // sw + 1
-    if out is None:
-        out = torch.empty((B, Ho, Wo, cw.cout), dtype=PACKED, device=x.device)
-    else:
-        _chkp(out, "conv2d.out")
-        assert out.shape[:3] == (B, Ho, Wo), (out.shape, (B, Ho, Wo))
-    if residual is not None:
-        _chkp(residual, "conv2d.residual")
-        assert residual.shape[:3] == (B, Ho, Wo) and residual.shape[3] >= cw.cout
-    per_img = 4 * max(H * W * ldx, Ho * Wo * out.shape[3], 0 if residual is None else Ho * Wo * residual.shape[3])
+            x, gate = scale_add_act(x, gate, None, None), None
+    out, d = _conv_front("h2", x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off)
+    B = d.B
+    per_img = 4 * max(d.H * d.W * d.ldx, d.Ho * d.Wo * d.ldy, d.Ho * d.Wo * d.ldr)
     bmax = max(1, (_H2_SPAN_MAX - 1) // per_img)
+
+    def prof():
+        return _conv_prof("h2:" + ("pwk_direct_kernel" if gate is not None else conv_kernel_name_h2(d, residual is not None) or "unsupported"),
+                          d, cw, residual, 4.0, 2.0)
     for b0 in range(0, B, bmax):
         b1 = min(B, b0 + bmax)
-        xs, os_, rs = x[b0:b1], out[b0:b1], None if residual is None else residual[b0:b1]
-        d = _abi.ConvDesc(B=b1 - b0, H=H, W=W, Cin=cw.cin, Cout=cw.cout, kh=cw.kh, kw=cw.kw, sh=sh, sw=sw, pt=pt, pl=pl, Ho=Ho, Wo=Wo,
-                          groups=cw.groups, ldx=ldx, cin_off=cin_off, ldy=out.shape[3], cout_off=cout_off,
-                          ldr=0 if residual is None else residual.shape[3], res_off=0, ldw=cw.ldw, act_pre=_act(act), act_post=_act(act_post))
-        tok = None
-        if _PROF is not None:
-            M = (b1 - b0) * Ho * Wo
-            kk = cw.kh * cw.kw * cw.alg_cin_g
-            tok = _PROF.start("h2:" + ("pwk_direct_kernel" if gate is not None else conv_kernel_name_h2(d, residual is not None) or "unsupported"),
-                              2.0 * M * cw.cout * kk,
-                              4.0 * ((b1 - b0) * H * W * cw.cin + M * cw.cout * (2 if residual is not None else 1)) + 2.0 * cw.w.numel(),
-                              f"M={M} N={cw.cout} K={cw.kh * cw.kw * cw.cin_g} k{cw.kh} s{sh} g{cw.groups}")
+        d.B = b1 - b0
+        rs = None if residual is None else residual[b0:b1]
+        tail = (_p(cw.w), _p(cw.bias), _p(rs), _p(out[b0:b1]), C.byref(d), 1.0 / cw.h2_scale)
         if gate is not None:
-            st = _abi.lib().vip_conv2d_gated_nhwc_h2(_p(xs), _p(gate[b0:b1]), _p(cw.w), _p(cw.bias), _p(rs), _p(os_), C.byref(d), 1.0 / cw.h2_scale,
-                                                     _p(h2_status()), _stream())
+            _launch("vip_conv2d_gated_nhwc_h2", _p(x[b0:b1]), _p(gate[b0:b1]), *tail, status=True, prof=prof)
         else:
-            st = _abi.lib().vip_conv2d_nhwc_h2(_p(xs), _p(cw.w), _p(cw.bias), _p(rs), _p(os_), C.byref(d), 1.0 / cw.h2_scale,
-                                               _p(h2_status()), _stream())
-        if tok is not None:
-            _PROF.stop(tok)
-        _abi.check(st, "vip_conv2d_gated_nhwc_h2" if gate is not None else "vip_conv2d_nhwc_h2")
+            _launch("vip_conv2d_nhwc_h2", _p(x[b0:b1]), *tail, status=True, prof=prof)
     return out
 
 
 def _conv2d_s32(x, cw: ConvWeight, stride, pad, act, act_post, residual, out, cin_off, cout_off, gate):
     """fp32-storage conv2d: fp32 x / weights / residual / out, vip_conv2d_nhwc_s32; a gate [B, Cin] fp32 is multiplied in first."""
-    if not cw.strict:
-        raise _abi.VipError("conv2d: fp32 activations with fp16 weights - build the model under ops.precision('f32')")
     if gate is not None:
         assert gate.shape == (x.shape[0], cw.cin) and x.shape[3] == cw.cin and cin_off == 0, (gate.shape, x.shape, cw.cin)
         x = scale_add_act(x, gate, None, None)
-    B, H, W, ldx = x.shape
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - cw.kh) // sh + 1
-    Wo = (W + pl + pr - cw.kw) // sw + 1
-    if out is None:
-        out = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float32, device=x.device)
+    out, d = _conv_front("s32", x, cw, stride, pad, act, act_post, residual, out, cin_off, cout_off)
+    split = STRICT_GEMM in ("bf16x3", "bf16x2") and cw.w_bf3 is not None     # bf16 planes of the weights; otherwise the f32-input MFMA
+
+    def prof():
+        return _conv_prof("sconv6_kernel" if split else "sconv_kernel", d, cw, residual, 4.0, 4.0)
+    tail = (_p(cw.bias), _p(residual), _p(out), C.byref(d))
+    if split:
+        _launch("vip_conv2d_nhwc_s32x2" if STRICT_GEMM == "bf16x2" else "vip_conv2d_nhwc_s32x", _p(x), _p(cw.w_bf3), cw.w_bf3.shape[2], *tail,
+                prof=prof)
     else:
-        _chk32(out, "conv2d.out")
-        assert out.shape[:3] == (B, Ho, Wo), (out.shape, (B, Ho, Wo))
-    if residual is not None:
-        _chk32(residual, "conv2d.residual")
-        assert residual.shape[:3] == (B, Ho, Wo) and residual.shape[3] >= cw.cout
-    d = _abi.ConvDesc(B=B, H=H, W=W, Cin=cw.cin, Cout=cw.cout, kh=cw.kh, kw=cw.kw, sh=sh, sw=sw, pt=pt, pl=pl, Ho=Ho, Wo=Wo,
-                      groups=cw.groups, ldx=ldx, cin_off=cin_off, ldy=out.shape[3], cout_off=cout_off,
-                      ldr=0 if residual is None else residual.shape[3], res_off=0, ldw=cw.ldw, act_pre=_act(act), act_post=_act(act_post))
-    tok = None
-    if _PROF is not None:
-        M = B * Ho * Wo
-        kk = cw.kh * cw.kw * cw.alg_cin_g
-        tok = _PROF.start("sconv6_kernel" if (STRICT_GEMM in ("bf16x3", "bf16x2") and cw.w_bf3 is not None) else "sconv_kernel", 2.0 * M * cw.cout * kk,
-                          4.0 * (B * H * W * cw.cin + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()),
-                          f"M={M} N={cw.cout} K={cw.kh * cw.kw * cw.cin_g} k{cw.kh} s{sh} g{cw.groups}")
-    if STRICT_GEMM == "bf16x2" and cw.w_bf3 is not None:
-        st = _abi.lib().vip_conv2d_nhwc_s32x2(_p(x), _p(cw.w_bf3), cw.w_bf3.shape[2], _p(cw.bias), _p(residual), _p(out), C.byref(d), _stream())
-    elif STRICT_GEMM == "bf16x3" and cw.w_bf3 is not None:
-        st = _abi.lib().vip_conv2d_nhwc_s32x(_p(x), _p(cw.w_bf3), cw.w_bf3.shape[2], _p(cw.bias), _p(residual), _p(out), C.byref(d), _stream())
-    else:
-        st = _abi.lib().vip_conv2d_nhwc_s32(_p(x), _p(cw.w), _p(cw.bias), _p(residual), _p(out), C.byref(d), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_conv2d_nhwc_s32[x]")
+        _launch("vip_conv2d_nhwc_s32", _p(x), _p(cw.w), *tail, prof=prof)
     return out
+
+
+_CONV_STRICT = {"s32": _conv2d_s32, "h2": _conv2d_h2}
+
+
+def _rows_out(x, cw: ConvWeight, residual, name: str):
+    """``x [..., K]`` as M rows -> ``(M, K, out [..., cout] fp16, ldr)`` with the fp16 ``residual`` checked against ``out``"""
+    K = x.shape[-1]
+    out = torch.empty((*x.shape[:-1], cw.cout), dtype=torch.float16, device=x.device)
+    if residual is not None:
+        _chk16(residual, name)
+        assert residual.shape == out.shape
+    return x.numel() // K, K, out, 0 if residual is None else cw.cout
 
 
 def dense(x: torch.Tensor, cw: ConvWeight, act=None, act_post=None, residual: Optional[torch.Tensor] = None):
@@ -658,52 +727,31 @@ def dense(x: torch.Tensor, cw: ConvWeight, act=None, act_post=None, residual: Op
             raise _abi.VipError(f"dense: {kind} activations with {cw.kind} weights - build the model and its input in the same precision")
         lead, K = x.shape[:-1], x.shape[-1]
         r4 = None if residual is None else residual.reshape(-1, 1, 1, cw.cout)
-        fn = _conv2d_s32 if kind == "s32" else _conv2d_h2
-        return fn(x.reshape(-1, 1, 1, K), cw, 1, (0, 0, 0, 0), act, act_post, r4, None, 0, 0, None).reshape(*lead, cw.cout)
+        return _CONV_STRICT[kind](x.reshape(-1, 1, 1, K), cw, 1, (0, 0, 0, 0), act, act_post, r4, None, 0, 0, None).reshape(*lead, cw.cout)
     if _CALIB and cw.err is not None:
         _bias_correct(cw, x)
     if _EXACT and cw.exact is not None:
         x, cw, _ = _exact_operands(x, cw)
-    lead = x.shape[:-1]
-    K = x.shape[-1]
-    M = x.numel() // K
-    out = torch.empty((*lead, cw.cout), dtype=torch.float16, device=x.device)
-    ldr = 0
-    if residual is not None:
-        _chk16(residual, "dense.residual")
-        assert residual.shape == out.shape
-        ldr = cw.cout
-    tok = None
-    if _PROF is not None:
+    M, K, out, ldr = _rows_out(x, cw, residual, "dense.residual")
+
+    def prof():
         d = _abi.ConvDesc(B=M, H=1, W=1, Cin=K, Cout=cw.cout, kh=1, kw=1, sh=1, sw=1, pt=0, pl=0, Ho=1, Wo=1, groups=1, ldx=K,
                           cin_off=0, ldy=cw.cout, cout_off=0, ldr=ldr, res_off=0, ldw=cw.ldw, act_pre=_act(act),
                           act_post=_act(act_post))
-        name = conv_kernel_name(d, residual is not None) or "unsupported"
-        tok = _PROF.start(name, 2.0 * M * cw.cout * K,
-                          2.0 * (M * K + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()),
-                          f"M={M} N={cw.cout} K={K} dense{' res' if residual is not None else ''} act={act}")
-    st = _abi.lib().vip_gemm_bias_act_f16(_p(x), _p(cw.w), _p(cw.bias), _p(residual), _p(out), M, cw.cout, K,
-                                          K, cw.ldw, cw.cout, ldr, _act(act), _act(act_post), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_gemm_bias_act_f16")
+        return (conv_kernel_name(d, residual is not None) or "unsupported", 2.0 * M * cw.cout * K,
+                2.0 * (M * K + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()),
+                f"M={M} N={cw.cout} K={K} dense{' res' if residual is not None else ''} act={act}")
+    _launch("vip_gemm_bias_act_f16", _p(x), _p(cw.w), _p(cw.bias), _p(residual), _p(out), M, cw.cout, K, K, cw.ldw, cw.cout, ldr,
+            _act(act), _act(act_post), prof=prof)
     return out
-
-
-_LN_GEMM = os.environ.get("VIP_LN_GEMM", "1") != "0"
 
 
 def ln_gemm_fused(x: torch.Tensor, cw: ConvWeight, act=None, act_post=None, residual: Optional[torch.Tensor] = None) -> bool:
     """whether ``ln_dense`` runs as ONE launch (``vip_ln_gemm_bias_act_f16``) for these operands"""
-    if (not _LN_GEMM or _UNFUSED or _CALIB or _EXACT or x.dtype != torch.float16 or not x.is_contiguous() or cw.kind != "f16"
-            or cw.groups != 1 or cw.kh != 1 or cw.kw != 1 or cw.cin != x.shape[-1] or 2 * x.numel() >= 0xFFFF0000 - 2 * x.shape[-1]):
-        return False
-    if residual is not None and (act is not None or act_post not in (None, "relu")):
-        return False
-    if residual is None and act_post is not None:
-        return False
     K = x.shape[-1]
-    return bool(_abi.lib().vip_ln_gemm_supported(x.numel() // K, K, cw.cout, _act(act)))
+    return bool(_LN_GEMM and not (_UNFUSED or _CALIB or _EXACT) and x.dtype == torch.float16 and x.is_contiguous() and cw.kind == "f16"
+                and _pointwise(cw) and cw.cin == K and 2 * x.numel() < 0xFFFF0000 - 2 * K and _epilogue_ok(act, act_post, residual)
+                and _abi.lib().vip_ln_gemm_supported(x.numel() // K, K, cw.cout, _act(act)))
 
 
 def ln_dense(x: torch.Tensor, ln, cw: ConvWeight, act=None, act_post=None, residual: Optional[torch.Tensor] = None):
@@ -711,30 +759,17 @@ def ln_dense(x: torch.Tensor, ln, cw: ConvWeight, act=None, act_post=None, resid
     (``vip_ln_gemm_supported``: the row is normalised in the registers of the GEMM, LN(x) never goes to memory), otherwise - and always
     on the strict storages and inside ``unfused()`` / ``calibration()`` / ``exact_weights()`` - LayerNorm then Dense, two launches.
     Same arithmetic either way: the normalised operand is rounded to fp16 where the separate launch stored it."""
+    g, b, eps = _ln_args(ln)
     if not ln_gemm_fused(x, cw, act, act_post, residual):
-        return dense(layernorm(x, ln[0], ln[1], float(ln[2])), cw, act=act, act_post=act_post, residual=residual)
-    lead, K = x.shape[:-1], x.shape[-1]
-    M = x.numel() // K
-    out = torch.empty((*lead, cw.cout), dtype=torch.float16, device=x.device)
-    ldr = 0
-    if residual is not None:
-        _chk16(residual, "ln_dense.residual")
-        assert residual.shape == out.shape and residual.is_contiguous()
-        ldr = cw.cout
-    tok = None
-    if _PROF is not None:       # bytes: x in, y out (+ residual), the weights - no LN(x) round trip
-        tok = _PROF.start("pwx_ln_kernel", 2.0 * M * cw.cout * K,
+        return dense(layernorm(x, g, b, eps), cw, act=act, act_post=act_post, residual=residual)
+    M, K, out, ldr = _rows_out(x, cw, residual, "ln_dense.residual")
+    # bytes: x in, y out (+ residual), the weights - no LN(x) round trip
+    _launch("vip_ln_gemm_bias_act_f16", _p(x), _p(g), _p(b), eps, _p(cw.w), _p(cw.bias), _p(residual), _p(out), M, cw.cout, K, K, cw.ldw,
+            cw.cout, ldr, _act(act), _act(act_post),
+            prof=lambda: ("pwx_ln_kernel", 2.0 * M * cw.cout * K,
                           2.0 * (M * K + M * cw.cout * (2 if residual is not None else 1) + cw.w.numel()) + 8.0 * K,
-                          f"M={M} N={cw.cout} K={K} ln+dense{' res' if residual is not None else ''} act={act}")
-    st = _abi.lib().vip_ln_gemm_bias_act_f16(_p(x), _p(ln[0]), _p(ln[1]), float(ln[2]), _p(cw.w), _p(cw.bias), _p(residual), _p(out),
-                                             M, cw.cout, K, K, cw.ldw, cw.cout, ldr, _act(act), _act(act_post), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_ln_gemm_bias_act_f16")
+                          f"M={M} N={cw.cout} K={K} ln+dense{' res' if residual is not None else ''} act={act}"))
     return out
-
-
-_MLP_H2_FUSED = os.environ.get("VIP_MLP_H2_FUSED", "1") != "0"
 
 
 def mlp(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act="gelu", residual: Optional[torch.Tensor] = None, ln=None):
@@ -742,61 +777,41 @@ def mlp(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act="gelu", residual:
     (LayerNorm in the prologue, hidden tensor in registers) when the C ABI supports the shape, otherwise LayerNorm +
     two Dense launches - same arithmetic either way."""
     kind = _kind(x, "mlp.x")
-    if kind != "f16":
-        C_ = x.shape[-1]
-        M = x.numel() // C_
-        if (kind == "h2" and _MLP_H2_FUSED and not _UNFUSED and fc1.kind == fc2.kind == "h2" and fc2.cout == C_ and fc1.cin == C_
-                and fc2.cin == fc1.cout and fc1.groups == fc2.groups == 1 and fc1.kh == fc1.kw == fc2.kh == fc2.kw == 1 and x.is_contiguous()
-                and 4 * x.numel() < _H2_SPAN_MAX and _abi.lib().vip_mlp_fused_supported_h2(M, C_, fc1.cout, _act(act))):
-            # one launch (vip_mlp_fused_h2): LayerNorm in the prologue, the hidden tensor in registers
-            out = torch.empty_like(x)
-            if residual is not None:
-                _chkp(residual, "mlp.residual")
-                assert residual.shape == out.shape and residual.is_contiguous()
-            g, b, eps = (ln[0], ln[1], float(ln[2])) if ln is not None else (None, None, 0.0)
-            tok = None
-            if _PROF is not None:
-                tok = _PROF.start("h2:mlp_h2_kernel", 4.0 * M * C_ * fc1.cout,
-                                  4.0 * M * C_ * (3 if residual is not None else 2) + 2.0 * (fc1.w.numel() + fc2.w.numel()),
-                                  f"M={M} C={C_} hidden={fc1.cout}")
-            st = _abi.lib().vip_mlp_fused_h2(_p(x), _p(g), _p(b), eps, _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias),
-                                             1.0 / fc2.h2_scale, _p(residual), _p(out), M, C_, fc1.cout, C_, fc1.ldw, fc2.ldw, C_,
-                                             C_ if residual is not None else 0, _act(act), _p(h2_status()), _stream())
-            if tok is not None:
-                _PROF.stop(tok)
-            _abi.check(st, "vip_mlp_fused_h2")
-            return out
-        # otherwise LayerNorm, Dense + activation, Dense (+ residual) as three launches
-        if ln is not None:
-            x = layernorm(x, ln[0], ln[1], float(ln[2]))
-        return dense(dense(x, fc1, act=act), fc2, residual=residual)
     C_ = x.shape[-1]
     M = x.numel() // C_
     hid = fc1.cout
-    if (not _UNFUSED and fc2.cout == C_ and fc1.groups == 1 and fc2.groups == 1 and x.is_contiguous()
-            and _abi.lib().vip_mlp_fused_supported(M, C_, hid, _act(act))):
-        out = torch.empty_like(x)
-        if residual is not None:
-            _chk16(residual, "mlp.residual")
-            assert residual.shape == out.shape
-        g, b, eps = (ln[0], ln[1], float(ln[2])) if ln is not None else (None, None, 0.0)
-        tok = None
-        if _PROF is not None:
-            tok = _PROF.start("mlp_fused_kernel" if C_ <= 96 else "mlp_stream_kernel", 4.0 * M * C_ * hid,
-                              2.0 * (M * C_ * (3 if residual is not None else 2) + fc1.w.numel() + fc2.w.numel()))
-        st = _abi.lib().vip_mlp_fused_f16(_p(x), _p(g), _p(b), eps, _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias),
-                                          _p(residual), _p(out), M, C_, hid, C_, fc1.ldw, fc2.ldw, C_,
-                                          C_ if residual is not None else 0, _act(act), _stream())
-        if tok is not None:
-            _PROF.stop(tok)
-        _abi.check(st, "vip_mlp_fused_f16")
-        return out
-    if ln is not None:      # LayerNorm folded into fc1 where the shape allows (ln_dense), then fc2 (+ residual): two launches, else three
-        return dense(ln_dense(x, ln, fc1, act=act), fc2, residual=residual)
-    return dense(dense(x, fc1, act=act), fc2, residual=residual)
-
-
-_SE_H2_FUSED = os.environ.get("VIP_SE_H2_FUSED", "1") != "0"
+    g, b, eps = _ln_args(ln)
+    ldr = C_ if residual is not None else 0
+    if kind == "f16":
+        fused = (not _UNFUSED and fc2.cout == C_ and fc1.groups == 1 and fc2.groups == 1 and x.is_contiguous()
+                 and _abi.lib().vip_mlp_fused_supported(M, C_, hid, _act(act)))
+    else:
+        fused = (kind == "h2" and _MLP_H2_FUSED and not _UNFUSED and fc1.kind == fc2.kind == "h2" and fc2.cout == C_ and fc1.cin == C_
+                 and fc2.cin == hid and _pointwise(fc1) and _pointwise(fc2) and x.is_contiguous() and 4 * x.numel() < _H2_SPAN_MAX
+                 and _abi.lib().vip_mlp_fused_supported_h2(M, C_, hid, _act(act)))
+    if not fused:
+        if ln is not None and kind == "f16":      # LayerNorm folded into fc1 where the shape allows (ln_dense): two launches, else three
+            return dense(ln_dense(x, ln, fc1, act=act), fc2, residual=residual)
+        if ln is not None:
+            x = layernorm(x, g, b, eps)
+        return dense(dense(x, fc1, act=act), fc2, residual=residual)
+    # one launch: LayerNorm in the prologue, the hidden tensor in registers
+    out = torch.empty_like(x)
+    if residual is not None:
+        _chk_kind(residual, kind, "mlp.residual")
+        assert residual.shape == out.shape
+    if kind == "h2":
+        _launch("vip_mlp_fused_h2", _p(x), _p(g), _p(b), eps, _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias),
+                1.0 / fc2.h2_scale, _p(residual), _p(out), M, C_, hid, C_, fc1.ldw, fc2.ldw, C_, ldr, _act(act), status=True,
+                prof=lambda: ("h2:mlp_h2_kernel", 4.0 * M * C_ * hid,
+                              4.0 * M * C_ * (3 if residual is not None else 2) + 2.0 * (fc1.w.numel() + fc2.w.numel()),
+                              f"M={M} C={C_} hidden={hid}"))
+    else:
+        _launch("vip_mlp_fused_f16", _p(x), _p(g), _p(b), eps, _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(residual), _p(out),
+                M, C_, hid, C_, fc1.ldw, fc2.ldw, C_, ldr, _act(act),
+                prof=lambda: ("mlp_fused_kernel" if C_ <= 96 else "mlp_stream_kernel", 4.0 * M * C_ * hid,
+                              2.0 * (M * C_ * (3 if residual is not None else 2) + fc1.w.numel() + fc2.w.numel())))
+    return out
 
 
 def se_gate(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act1, act2="sigmoid", split: bool = True) -> torch.Tensor:
@@ -810,27 +825,23 @@ def se_gate(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act1, act2="sigmo
     kind = _kind(x, "se_gate.x")
     if kind != "f16":    # STRICT: the gate is a plain [B, C] in the activation storage
         B, Cc = x.shape[0], x.shape[-1]
-        if (kind == "h2" and _SE_H2_FUSED and fc1.kind == fc2.kind == "h2" and fc1.groups == fc2.groups == 1 and fc1.kh == fc1.kw == fc2.kh == fc2.kw == 1
-                and fc1.cin == Cc and fc2.cin == fc1.cout and Cc * fc1.cout + fc1.cout * fc2.cout <= 256 * 1024 and x.dim() == 4):
+        if kind == "h2" and _SE_H2_FUSED and fc1.kind == fc2.kind == "h2" and _se_chain_ok(fc1, fc2, Cc) and x.dim() == 4:
             # one launch (vip_se_gate_h2: the fp16 path's one-workgroup-per-image kernel on the packed storage)
             out = torch.empty((B, fc2.cout), dtype=PACKED, device=x.device)
-            st = _abi.lib().vip_se_gate_h2(_p(x), _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias), 1.0 / fc2.h2_scale,
-                                           _p(out), B, x.shape[1] * x.shape[2], Cc, Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1),
-                                           _act(act2), _p(h2_status()), _stream())
-            _abi.check(st, "vip_se_gate_h2")
+            _launch("vip_se_gate_h2", _p(x), _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias), 1.0 / fc2.h2_scale,
+                    _p(out), B, x.shape[1] * x.shape[2], Cc, Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2), status=True)
             return out
         return dense(dense(global_avgpool(x), fc1, act=act1), fc2, act=act2)    # pool -> Dense -> Dense
     B, H, W, Cc = x.shape
-    assert fc1.groups == 1 and fc2.groups == 1 and fc1.kh == fc1.kw == fc2.kh == fc2.kw == 1
+    assert _pointwise(fc1) and _pointwise(fc2)
     assert fc1.cin == Cc and fc2.cin == fc1.cout, (fc1.cin, Cc, fc2.cin, fc1.cout)
-    if _UNFUSED or Cc * fc1.cout + fc1.cout * fc2.cout > 256 * 1024:
+    if _UNFUSED or not _se_chain_ok(fc1, fc2, Cc):
         # pooled and hidden vectors as hi/lo planes too (the one-launch kernel keeps them in fp32)
         g = dense_split(dense_split(global_avgpool(x, split=True), fc1, act=act1), fc2, act=act2)
         return g if split else g[:, 0].contiguous()
     out = torch.empty((B, 2, fc2.cout) if split else (B, fc2.cout), dtype=torch.float16, device=x.device)
-    st = _abi.lib().vip_se_gate_f16(_p(x), _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(out), B, H * W, Cc, Cc,
-                                    fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2), int(split), _stream())
-    _abi.check(st, "vip_se_gate_f16")
+    _launch("vip_se_gate_f16", _p(x), _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(out), B, H * W, Cc, Cc, fc1.cout, fc1.ldw,
+            fc2.cout, fc2.ldw, _act(act1), _act(act2), int(split))
     return out
 
 
@@ -849,17 +860,15 @@ def dense_split(x: torch.Tensor, cw: ConvWeight, act=None) -> torch.Tensor:
     out = torch.empty((M, 2, cw.cout), dtype=torch.float16, device=x.device)
     for m0 in range(0, M, 256):       # the C entry points take at most 256 rows (a batch of pooled vectors)
         m1 = min(M, m0 + 256)
+        head = (_p(x[m0:m1]), _p(cw.w), _p(cw.bias), _p(out[m0:m1]), m1 - m0, cw.cout, K)
         if split_in:
-            st = _abi.lib().vip_gemm_split2_f16(_p(x[m0:m1]), _p(cw.w), _p(cw.bias), _p(out[m0:m1]), m1 - m0, cw.cout, K,
-                                                cw.ldw, _act(act), _stream())
+            _launch("vip_gemm_split2_f16", *head, cw.ldw, _act(act))
         else:
-            st = _abi.lib().vip_gemm_split_f16(_p(x[m0:m1]), _p(cw.w), _p(cw.bias), _p(out[m0:m1]), m1 - m0, cw.cout, K, K,
-                                               cw.ldw, _act(act), _stream())
-        _abi.check(st, "vip_gemm_split2_f16" if split_in else "vip_gemm_split_f16")
+            _launch("vip_gemm_split_f16", *head, K, cw.ldw, _act(act))
     return out
 
 
-_DW_H2_LDS = int(os.environ.get("VIP_DW_H2_LDS", "3"))      # smallest k the LDS-staged strict kernel takes (0: never)
+# ---- depthwise convolution ----------------------------------------------------------------------------------------------------------
 _DW_QUAD = {}      # filter storage -> (filter, its quad-major copy); the filter is kept alive so that the address cannot be reused
 
 
@@ -869,8 +878,7 @@ def _dw_quad_major(w_khwc: torch.Tensor, k: int) -> torch.Tensor:
     hit = _DW_QUAD.get(key)
     if hit is None:
         wq = torch.empty_like(w_khwc)
-        st = _abi.lib().vip_dw_filter_quad_major(_p(w_khwc), _p(wq), k, w_khwc.shape[-1], _stream())
-        _abi.check(st, "vip_dw_filter_quad_major")
+        _launch("vip_dw_filter_quad_major", _p(w_khwc), _p(wq), k, w_khwc.shape[-1])
         hit = _DW_QUAD[key] = (w_khwc, wq)
     return hit[1]
 
@@ -878,30 +886,20 @@ def _dw_quad_major(w_khwc: torch.Tensor, k: int) -> torch.Tensor:
 def dwconv2d(x, w_khwc: torch.Tensor, bias: Optional[torch.Tensor], k: int, stride=1, pad=(0, 0, 0, 0), act=None):
     """Depthwise conv; ``w_khwc`` fp32 ``[k,k,C]``, bias fp32 ``[C]``."""
     kind = _kind(x, "dwconv2d.x")
-    if w_khwc.dtype != torch.float32 or not w_khwc.is_contiguous() or w_khwc.shape != (k, k, x.shape[-1]):
-        raise ValueError("dwconv2d: the filter must be a contiguous fp32 [k,k,C] tensor")
     B, H, W, Cc = x.shape
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
+    if not _dw_filter_ok(w_khwc, k, Cc):
+        raise ValueError("dwconv2d: the filter must be a contiguous fp32 [k,k,C] tensor")
+    pt, _, pl, _ = pad
+    Ho, Wo = _out_hw(H, W, k, k, stride, stride, pad)
     out = torch.empty((B, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    if kind != "f16":
-        if (kind == "h2" and _DW_H2_LDS and stride == 1 and k >= _DW_H2_LDS
-                and _abi.lib().vip_dwconv2d_s1_supported_h2(B, H, W, Cc, k, Ho, Wo)):
-            # the LDS-staged kernel (dwconv_lds_h2.hip) on the quad-major copy of the filter
-            st = _abi.lib().vip_dwconv2d_s1_h2(_p(x), _p(_dw_quad_major(w_khwc, k)), _p(bias), _p(out), B, H, W, Cc, k, pt, pl, Ho, Wo, _act(act),
-                                               _p(h2_status()), _stream())
-            _abi.check(st, "vip_dwconv2d_s1_h2")
-            return out
-        _strict_call("dwconv2d_nhwc", kind, _p(x), _p(w_khwc), _p(bias), _p(out), B, H, W, Cc, k, stride, pt, pl, Ho, Wo, _act(act))
-        return out
-    st = _abi.lib().vip_dwconv2d_nhwc_f16(_p(x), _p(w_khwc), _p(bias), _p(out), B, H, W, Cc, k, stride, pt, pl,
-                                          Ho, Wo, _act(act), _stream())
-    _abi.check(st, "vip_dwconv2d_nhwc_f16")
+    if (kind == "h2" and _DW_H2_LDS and stride == 1 and k >= _DW_H2_LDS
+            and _abi.lib().vip_dwconv2d_s1_supported_h2(B, H, W, Cc, k, Ho, Wo)):
+        # the LDS-staged kernel (dwconv_lds_h2.hip) on the quad-major copy of the filter
+        _launch("vip_dwconv2d_s1_h2", _p(x), _p(_dw_quad_major(w_khwc, k)), _p(bias), _p(out), B, H, W, Cc, k, pt, pl, Ho, Wo, _act(act),
+                status=True)
+    else:
+        _launch_kind("dwconv2d_nhwc", kind, _p(x), _p(w_khwc), _p(bias), _p(out), B, H, W, Cc, k, stride, pt, pl, Ho, Wo, _act(act))
     return out
-
-
-_DW_SE_FUSED = os.environ.get("VIP_DW_SE_POOL", "1") != "0"
 
 
 def dwconv2d_se(x, w_khwc: torch.Tensor, bias: Optional[torch.Tensor], k: int, stride, pad, act, fc1: ConvWeight, fc2: ConvWeight,
@@ -913,46 +911,33 @@ def dwconv2d_se(x, w_khwc: torch.Tensor, bias: Optional[torch.Tensor], k: int, s
     outputs and the gate kernel finishes the mean from those instead of reading ``h`` again (``vip_dwconv2d_pool_nhwc_f16`` +
     ``vip_se_gate_pooled_f16``; ``VIP_DW_SE_POOL=0``: always the two plain calls)."""
     B, H, W, Cc = x.shape
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
-    if (x.dtype == PACKED and _DW_SE_FUSED and _SE_H2_FUSED and not _UNFUSED and stride == 1 and _DW_H2_LDS and k >= _DW_H2_LDS
-            and fc1.kind == fc2.kind == "h2" and fc1.groups == fc2.groups == 1 and fc1.kh == fc1.kw == fc2.kh == fc2.kw == 1
-            and fc1.cin == Cc and fc2.cin == fc1.cout and Cc * fc1.cout + fc1.cout * fc2.cout <= 256 * 1024
-            and w_khwc.dtype == torch.float32 and w_khwc.is_contiguous() and w_khwc.shape == (k, k, Cc)):
-        # packed strict storage: the LDS-staged depthwise kernel leaves the pool's partial sums, the gate kernel finishes from them
-        parts = _abi.lib().vip_dwconv2d_s1_pool_parts_h2(B, H, W, Cc, k, Ho, Wo)
-        if parts > 0:
-            _chkp(x, "dwconv2d_se.x")
-            h = torch.empty((B, Ho, Wo, Cc), dtype=PACKED, device=x.device)
-            partials = torch.empty((B, parts, Cc), dtype=torch.float32, device=x.device)
-            st = _abi.lib().vip_dwconv2d_s1_pool_h2(_p(x), _p(_dw_quad_major(w_khwc, k)), _p(bias), _p(h), _p(partials), parts, B, H, W, Cc, k,
-                                                    pt, pl, Ho, Wo, _act(act), _p(h2_status()), _stream())
-            _abi.check(st, "vip_dwconv2d_s1_pool_h2")
-            gate = torch.empty((B, fc2.cout), dtype=PACKED, device=x.device)
-            st = _abi.lib().vip_se_gate_pooled_h2(_p(partials), parts, _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias),
-                                                  1.0 / fc2.h2_scale, _p(gate), B, Ho * Wo, Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1),
-                                                  _act(act2), _p(h2_status()), _stream())
-            _abi.check(st, "vip_se_gate_pooled_h2")
-            return h, gate
-    fused = (_DW_SE_FUSED and not _UNFUSED and not _CALIB and not _EXACT and x.dtype == torch.float16 and stride == 1
-             and fc1.cin == Cc and Cc * fc1.cout + fc1.cout * fc2.cout <= 256 * 1024
-             and w_khwc.dtype == torch.float32 and w_khwc.is_contiguous() and w_khwc.shape == (k, k, Cc))
-    parts = _abi.lib().vip_dwconv2d_pool_parts(B, H, W, Cc, k, stride, Ho, Wo) if fused else 0
+    pt, _, pl, _ = pad
+    Ho, Wo = _out_hw(H, W, k, k, stride, stride, pad)
+    # both storages: the depthwise kernel leaves the pool's partial sums and the one-launch gate kernel finishes from them
+    pooled = _DW_SE_FUSED and not _UNFUSED and stride == 1 and _se_chain_ok(fc1, fc2, Cc) and _dw_filter_ok(w_khwc, k, Cc)
+    parts = 0
+    if pooled and x.dtype == PACKED and _SE_H2_FUSED and _DW_H2_LDS and k >= _DW_H2_LDS and fc1.kind == fc2.kind == "h2":
+        parts = _abi.lib().vip_dwconv2d_s1_pool_parts_h2(B, H, W, Cc, k, Ho, Wo)      # the LDS-staged depthwise kernel
+    elif pooled and x.dtype == torch.float16 and not _CALIB and not _EXACT:
+        parts = _abi.lib().vip_dwconv2d_pool_parts(B, H, W, Cc, k, stride, Ho, Wo)
     if parts <= 0:
         h = dwconv2d(x, w_khwc, bias, k, stride, pad, act=act)
         return h, se_gate(h, fc1, fc2, act1, act2, split=split)
-    _chk16(x, "dwconv2d_se.x")
-    assert fc1.groups == 1 and fc2.groups == 1 and fc1.kh == fc1.kw == fc2.kh == fc2.kw == 1 and fc2.cin == fc1.cout
-    h = torch.empty((B, Ho, Wo, Cc), dtype=torch.float16, device=x.device)
+    kind = _kind(x, "dwconv2d_se.x")
+    h = torch.empty((B, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
     partials = torch.empty((B, parts, Cc), dtype=torch.float32, device=x.device)
-    st = _abi.lib().vip_dwconv2d_pool_nhwc_f16(_p(x), _p(w_khwc), _p(bias), _p(h), _p(partials), parts, B, H, W, Cc, k, stride, pt, pl,
-                                               Ho, Wo, _act(act), _stream())
-    _abi.check(st, "vip_dwconv2d_pool_nhwc_f16")
-    gate = torch.empty((B, 2, fc2.cout) if split else (B, fc2.cout), dtype=torch.float16, device=x.device)
-    st = _abi.lib().vip_se_gate_pooled_f16(_p(partials), parts, _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(gate), B, Ho * Wo,
-                                           Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2), int(split), _stream())
-    _abi.check(st, "vip_se_gate_pooled_f16")
+    if kind == "h2":
+        _launch("vip_dwconv2d_s1_pool_h2", _p(x), _p(_dw_quad_major(w_khwc, k)), _p(bias), _p(h), _p(partials), parts, B, H, W, Cc, k,
+                pt, pl, Ho, Wo, _act(act), status=True)
+        gate = torch.empty((B, fc2.cout), dtype=PACKED, device=x.device)
+        _launch("vip_se_gate_pooled_h2", _p(partials), parts, _p(fc1.w), _p(fc1.bias), 1.0 / fc1.h2_scale, _p(fc2.w), _p(fc2.bias),
+                1.0 / fc2.h2_scale, _p(gate), B, Ho * Wo, Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2), status=True)
+    else:
+        _launch("vip_dwconv2d_pool_nhwc_f16", _p(x), _p(w_khwc), _p(bias), _p(h), _p(partials), parts, B, H, W, Cc, k, stride, pt, pl,
+                Ho, Wo, _act(act))
+        gate = torch.empty((B, 2, fc2.cout) if split else (B, fc2.cout), dtype=torch.float16, device=x.device)
+        _launch("vip_se_gate_pooled_f16", _p(partials), parts, _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(gate), B, Ho * Wo,
+                Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2), int(split))
     return h, gate
 
 
@@ -964,37 +949,26 @@ def mbconv_expand_dw(x, cw: ConvWeight, w_khwc: torch.Tensor, dw_bias: Optional[
     the two HBM-bound kernels hide their swish evaluations (exp + rcp each) behind memory, the fused one is VALU-bound on them plus
     the halo recompute.  Calibration / exact-weight passes always run the two launches."""
     B, H, W, ldx = x.shape
-    ok = (not _UNFUSED and x.dtype == torch.float16 and os.environ.get("VIP_MBCONV_FUSED", "0") == "1" and cw.kh == cw.kw == 1 and cw.groups == 1 and ldx == cw.cin
+    ok = (not _UNFUSED and x.dtype == torch.float16 and mbconv_fused() and _pointwise(cw) and ldx == cw.cin
           and w_khwc.shape == (k, k, cw.cout) and _abi.lib().vip_mbconv_expand_dw_supported(cw.cin, cw.cout, k, stride))
     if not ok:
         return dwconv2d(conv2d(x, cw, act=act), w_khwc, dw_bias, k, stride, pad, act=act)
     _chk16(x, "mbconv_expand_dw.x")
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
+    Ho, Wo = _out_hw(H, W, k, k, stride, stride, pad)
     out = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float16, device=x.device)
-    tok = None
-    if _PROF is not None:
-        tok = _PROF.start("mbconv_expand_dw_kernel", 2.0 * B * (H * W * cw.cin + Ho * Wo * k * k) * cw.cout,
-                          2.0 * (x.numel() + out.numel() + cw.w.numel()), f"{H}x{W} Cin={cw.cin} Ce={cw.cout} k{k} s{stride}")
-    st = _abi.lib().vip_mbconv_expand_dw_f16(_p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(w_khwc), _p(dw_bias), _p(out), B, H, W,
-                                             cw.cin, cw.cout, cw.ldw, k, stride, pt, pl, Ho, Wo, _act(act), _act(act), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_mbconv_expand_dw_f16")
+    _launch("vip_mbconv_expand_dw_f16", _p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(w_khwc), _p(dw_bias), _p(out), B, H, W,
+            cw.cin, cw.cout, cw.ldw, k, stride, pad[0], pad[2], Ho, Wo, _act(act), _act(act),
+            prof=lambda: ("mbconv_expand_dw_kernel", 2.0 * B * (H * W * cw.cin + Ho * Wo * k * k) * cw.cout,
+                          2.0 * (x.numel() + out.numel() + cw.w.numel()), f"{H}x{W} Cin={cw.cin} Ce={cw.cout} k{k} s{stride}"))
     return out
 
 
+# ---- elementwise, pooling, heads ----------------------------------------------------------------------------------------------------
 def layernorm(x, gamma: torch.Tensor, beta: torch.Tensor, eps: float):
     kind = _kind(x, "layernorm.x")
     Cc = x.shape[-1]
-    rows = x.numel() // Cc
     out = torch.empty_like(x)
-    if kind != "f16":
-        _strict_call("layernorm", kind, _p(x), _p(gamma), _p(beta), _p(out), rows, Cc, float(eps))
-        return out
-    st = _abi.lib().vip_layernorm_f16(_p(x), _p(gamma), _p(beta), _p(out), rows, Cc, float(eps), _stream())
-    _abi.check(st, "vip_layernorm_f16")
+    _launch_kind("layernorm", kind, _p(x), _p(gamma), _p(beta), _p(out), x.numel() // Cc, Cc, float(eps))
     return out
 
 
@@ -1006,19 +980,12 @@ def pool2d(x, k: int, stride: int, pad=(0, 0, 0, 0), mode=POOL_MAX_ZEROPAD, out_
     stride 1 and zero-pad max pooling the op is a zero-padded copy (GCViT FitWindow) or a crop (level.py:61)."""
     kind = _kind(x, "pool2d.x")
     B, H, W, Cc = x.shape
-    pt, pb, pl, pr = pad
-    Ho = (H + pt + pb - k) // stride + 1
-    Wo = (W + pl + pr - k) // stride + 1
+    Ho, Wo = _out_hw(H, W, k, k, stride, stride, pad)
     if out_hw is not None:
         assert out_hw[0] <= Ho and out_hw[1] <= Wo
         Ho, Wo = out_hw
     out = torch.empty((B, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    if kind != "f16":
-        _strict_call("pool2d_nhwc", kind, _p(x), _p(out), B, H, W, Cc, Cc, Cc, k, stride, pt, pl, Ho, Wo, mode)
-        return out
-    st = _abi.lib().vip_pool2d_nhwc_f16(_p(x), _p(out), B, H, W, Cc, Cc, Cc, k, stride, pt, pl, Ho, Wo, mode,
-                                        _stream())
-    _abi.check(st, "vip_pool2d_nhwc_f16")
+    _launch_kind("pool2d_nhwc", kind, _p(x), _p(out), B, H, W, Cc, Cc, Cc, k, stride, pad[0], pad[2], Ho, Wo, mode)
     return out
 
 
@@ -1027,14 +994,12 @@ def global_avgpool(x, split: bool = False):
     B, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * Cc)
     kind = _kind(x, "global_avgpool.x")
-    if kind != "f16":     # STRICT: [B, C] in the activation storage whatever ``split`` says
+    if split and kind == "f16":     # the STRICT storages: [B, C] whatever ``split`` says
+        out = torch.empty((B, 2, Cc), dtype=torch.float16, device=x.device)
+        _launch("vip_global_avgpool_split_f16", _p(x), _p(out), B, HW, Cc, Cc)
+    else:
         out = torch.empty((B, Cc), dtype=x.dtype, device=x.device)
-        _strict_call("global_avgpool", kind, _p(x), _p(out), B, HW, Cc, Cc)
-        return out
-    out = torch.empty((B, 2, Cc) if split else (B, Cc), dtype=torch.float16, device=x.device)
-    fn = "vip_global_avgpool_split_f16" if split else "vip_global_avgpool_f16"
-    st = getattr(_abi.lib(), fn)(_p(x), _p(out), B, HW, Cc, Cc, _stream())
-    _abi.check(st, fn)
+        _launch_kind("global_avgpool", kind, _p(x), _p(out), B, HW, Cc, Cc)
     return out
 
 
@@ -1048,10 +1013,9 @@ def gap_dense_f32(x, w_nc: torch.Tensor, bias: Optional[torch.Tensor]):
     assert w_nc.dtype == torch.float32 and w_nc.shape == (N, Cc) and w_nc.is_contiguous()
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
     if kind != "f16":
-        _strict_call("gap_ln_dense", kind, _p(x), None, None, 0.0, _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, HW * Cc, N, status=False)
-        return out
-    st = _abi.lib().vip_gap_dense_f32(_p(x), _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, N, _stream())
-    _abi.check(st, "vip_gap_dense_f32")
+        _launch_kind("gap_ln_dense", kind, _p(x), None, None, 0.0, _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, HW * Cc, N)
+    else:
+        _launch("vip_gap_dense_f32", _p(x), _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, N)
     return out
 
 
@@ -1065,13 +1029,11 @@ def gap_ln_dense_f32(x, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w_n
     assert w_nc.dtype == torch.float32 and w_nc.shape == (N, Cc) and w_nc.is_contiguous()
     assert gamma.dtype == beta.dtype == torch.float32 and gamma.shape == beta.shape == (Cc,)
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    head = (_p(x), _p(gamma), _p(beta), float(eps), _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc)
     if kind != "f16":
-        _strict_call("gap_ln_dense", kind, _p(x), _p(gamma), _p(beta), float(eps), _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, HW * Cc, N,
-                     status=False)
-        return out
-    st = _abi.lib().vip_gap_ln_dense_f32(_p(x), _p(gamma), _p(beta), float(eps), _p(w_nc), _p(bias), _p(out), B, HW, Cc, Cc, N,
-                                         _stream())
-    _abi.check(st, "vip_gap_ln_dense_f32")
+        _launch_kind("gap_ln_dense", kind, *head, HW * Cc, N)
+    else:
+        _launch("vip_gap_ln_dense_f32", *head, N)
     return out
 
 
@@ -1086,13 +1048,11 @@ def head_prob(z: torch.Tensor, act="default") -> torch.Tensor:
     out = torch.empty_like(z)
     n = z.shape[1]
     if act == "default" or (act == "sigmoid" and n == 1) or (act == "softmax" and n > 1):
-        st = _abi.lib().vip_head_prob_f32(_p(z), _p(out), None, z.shape[0], n, _stream())
-        _abi.check(st, "vip_head_prob_f32")
+        _launch("vip_head_prob_f32", _p(z), _p(out), None, z.shape[0], n)
         return out
     if act not in HEAD_ACTS:
         raise ValueError(f"head activation {act!r}: expected one of {sorted(k for k in HEAD_ACTS if isinstance(k, str))}")
-    st = _abi.lib().vip_head_act_f32(_p(z), _p(out), z.shape[0], n, HEAD_ACTS[act], _stream())
-    _abi.check(st, "vip_head_act_f32")
+    _launch("vip_head_act_f32", _p(z), _p(out), z.shape[0], n, HEAD_ACTS[act])
     return out
 
 
@@ -1104,8 +1064,7 @@ def binary_score(p: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
         out = torch.empty((n,), dtype=torch.float32, device=p.device)
     assert out.dtype == torch.float32 and out.shape == (n,) and out.is_contiguous()
     pf = p if (p.dtype == torch.float32 and p.is_contiguous()) else p.float().contiguous()
-    st = _abi.lib().vip_prob_to_score_f32(_p(pf), _p(out), n, Cc, _stream())
-    _abi.check(st, "vip_prob_to_score_f32")
+    _launch("vip_prob_to_score_f32", _p(pf), _p(out), n, Cc)
     return out
 
 
@@ -1113,8 +1072,7 @@ def ensemble_mean(scores: torch.Tensor) -> torch.Tensor:
     """fp32 ``[M, n]`` member scores -> ``[n]`` ensemble mean (main.py:142-143)."""
     assert scores.dtype == torch.float32 and scores.is_cuda and scores.dim() == 2 and scores.stride(1) == 1
     out = torch.empty((scores.shape[1],), dtype=torch.float32, device=scores.device)
-    st = _abi.lib().vip_ensemble_mean_f32(_p(scores), _p(out), scores.shape[0], scores.shape[1], scores.stride(0), _stream())
-    _abi.check(st, "vip_ensemble_mean_f32")
+    _launch("vip_ensemble_mean_f32", _p(scores), _p(out), scores.shape[0], scores.shape[1], scores.stride(0))
     return out
 
 
@@ -1145,16 +1103,14 @@ def cam(features, w_nc: torch.Tensor, bias: Optional[torch.Tensor], ln=None, act
         tgt = target
     else:
         raise ValueError(f"cam target {target!r}: expected 'score' or a class index below {N}")
-    g, b, eps = (None, None, 0.0) if ln is None else (ln[0], ln[1], float(ln[2]))
+    g, b, eps = _ln_args(ln)
     if ln is not None:
         assert g.dtype == b.dtype == torch.float32 and g.shape == b.shape == (Cc,)
     out = torch.empty((B, H, W), dtype=torch.float32, device=features.device)
     peak = torch.empty((B,), dtype=torch.float32, device=features.device)
     z = torch.empty((B, N), dtype=torch.float32, device=features.device)
-    fn = {"f16": "vip_cam_f32", "s32": "vip_cam_s32", "h2": "vip_cam_h2"}[kind]
-    st = getattr(_abi.lib(), fn)(_p(features), _p(g), _p(b), eps, _p(w_nc), _p(bias), _p(out), _p(peak), _p(z), B, H * W, Cc, Cc,
-                                 pitch, N, HEAD_ACTS[act], tgt, _stream())
-    _abi.check(st, fn)
+    _launch_kind("cam", kind, _p(features), _p(g), _p(b), eps, _p(w_nc), _p(bias), _p(out), _p(peak), _p(z), B, H * W, Cc, Cc, pitch, N,
+                 HEAD_ACTS[act], tgt)
     return out, peak, z
 
 
@@ -1190,10 +1146,9 @@ def cam_compose(maps, peaks, sizes: torch.Tensor, max_hw, weights=None, out: str
     w = [1.0 / M] * M if weights is None else [float(v) for v in weights]
     assert len(w) == M
     res = torch.empty((n, maxH, maxW), dtype=torch.uint8 if out == "u8" else torch.float32, device=maps[0].device)
-    st = _abi.lib().vip_cam_compose_f32((C.c_void_p * M)(*[m_.data_ptr() for m_ in maps]), (C.c_int * M)(*[m_.shape[1] for m_ in maps]),
-                                        (C.c_int * M)(*[m_.shape[2] for m_ in maps]), (C.c_void_p * M)(*[p_.data_ptr() for p_ in peaks]),
-                                        (C.c_float * M)(*w), M, _p(sizes), n, maxH, maxW, _p(res), int(out == "u8"), _stream())
-    _abi.check(st, "vip_cam_compose_f32")
+    _launch("vip_cam_compose_f32", (C.c_void_p * M)(*[m_.data_ptr() for m_ in maps]), (C.c_int * M)(*[m_.shape[1] for m_ in maps]),
+            (C.c_int * M)(*[m_.shape[2] for m_ in maps]), (C.c_void_p * M)(*[p_.data_ptr() for p_ in peaks]),
+            (C.c_float * M)(*w), M, _p(sizes), n, maxH, maxW, _p(res), int(out == "u8"))
     return res
 
 
@@ -1206,41 +1161,29 @@ def cam_overlay(rgb: torch.Tensor, map_u8: torch.Tensor, table: torch.Tensor, al
     n, maxH, maxW, ch = rgb.shape
     assert ch == 3 and map_u8.shape == (n, maxH, maxW) and table.shape == (256, 3), (rgb.shape, map_u8.shape, table.shape)
     out = torch.empty_like(rgb)
-    st = _abi.lib().vip_cam_overlay_u8(_p(rgb), _p(map_u8), _p(table), float(alpha), n, maxH, maxW, _p(out), _stream())
-    _abi.check(st, "vip_cam_overlay_u8")
+    _launch("vip_cam_overlay_u8", _p(rgb), _p(map_u8), _p(table), float(alpha), n, maxH, maxW, _p(out))
     return out
 
 
 def scale_add_act(x, scale=None, residual=None, act=None, act2=None):
     """act(x * scale[b,c] + residual); with ``act2`` returns ``(y, act2(y))`` from one launch.
-    ``scale`` is [B, C] fp16 or a split gate [B, 2, C] (planes summed in fp32)."""
+    ``scale`` is [B, C] in the storage of ``x``, or on the fp16 storage a split gate [B, 2, C] (planes summed in fp32)."""
     B, Cc = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * Cc)
     kind = _kind(x, "scale_add_act.x")
-    if kind != "f16":      # STRICT: scale is a plain [B, C] in the activation storage
-        if scale is not None:
-            _chk_kind(scale, kind, "scale_add_act.scale")
-            assert scale.shape == (B, Cc), scale.shape
-        if residual is not None:
-            _chk_kind(residual, kind, "scale_add_act.residual")
-            assert residual.shape == x.shape
-        out = torch.empty_like(x)
-        out2 = torch.empty_like(x) if act2 is not None else None
-        _strict_call("scale_add_act", kind, _p(x), _p(scale), _p(residual), _p(out), _p(out2), B, HW, Cc, _act(act), _act(act2))
-        return out if act2 is None else (out, out2)
-    planes = 1
     if scale is not None:
-        _chk16(scale, "scale_add_act.scale")
-        assert scale.shape in ((B, Cc), (B, 2, Cc)), scale.shape
-        planes = 2 if scale.dim() == 3 else 1
+        _chk_kind(scale, kind, "scale_add_act.scale")
+        assert scale.shape == (B, Cc) or (kind == "f16" and scale.shape == (B, 2, Cc)), scale.shape
     if residual is not None:
-        _chk16(residual, "scale_add_act.residual")
+        _chk_kind(residual, kind, "scale_add_act.residual")
         assert residual.shape == x.shape
     out = torch.empty_like(x)
     out2 = torch.empty_like(x) if act2 is not None else None
-    st = _abi.lib().vip_scale_add_act3_f16(_p(x), _p(scale), planes, _p(residual), _p(out), _p(out2), B, HW, Cc,
-                                           _act(act), _act(act2), _stream())
-    _abi.check(st, "vip_scale_add_act3_f16")
+    tail = (_p(residual), _p(out), _p(out2), B, HW, Cc, _act(act), _act(act2))
+    if kind == "f16":       # this entry point alone takes the number of scale planes
+        _launch("vip_scale_add_act3_f16", _p(x), _p(scale), 2 if (scale is not None and scale.dim() == 3) else 1, *tail)
+    else:
+        _launch_kind("scale_add_act", kind, _p(x), _p(scale), *tail)
     return out if act2 is None else (out, out2)
 
 
@@ -1255,29 +1198,17 @@ def window_attention(qkv, q_global, bias_table, heads: int, ws: int, scale: floa
         assert q_global.numel() == B * ws * ws * Cc
     assert bias_table.dtype == torch.float32 and bias_table.shape == ((2 * ws - 1) ** 2, heads)
     out = torch.empty((B, Hp, Wp, Cc), dtype=qkv.dtype, device=qkv.device)
-    if kind != "f16":
-        _strict_call("window_attn_fwd", kind, _p(qkv), _p(q_global), _p(bias_table), _p(out), B, Hp, Wp, Cc, heads, ws, nq, float(scale))
-        return out
-    tok = None
-    if _PROF is not None:
+
+    def prof():
         # algorithmic work of the attention core: 4*N^2*hd FLOPs and 4*N*hd fp16 elements
         # (q, k, v read + out written) per (window, head)
         nwh = B * (Hp // ws) * (Wp // ws) * heads
         N = ws * ws
-        tok = _PROF.start("window_attn_kernel", nwh * 4.0 * N * N * 32, nwh * 4.0 * N * 32 * 2,
-                          f"attn core ws{ws} C={Cc} heads={heads} map={Hp}x{Wp} global={int(q_global is not None)}")
-    st = _abi.lib().vip_window_attn_fwd_f16(_p(qkv), _p(q_global), _p(bias_table), _p(out), B, Hp, Wp, Cc, heads,
-                                            ws, nq, float(scale), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_window_attn_fwd_f16")
+        return ("window_attn_kernel", nwh * 4.0 * N * N * 32, nwh * 4.0 * N * 32 * 2,
+                f"attn core ws{ws} C={Cc} heads={heads} map={Hp}x{Wp} global={int(q_global is not None)}")
+    _launch_kind("window_attn_fwd", kind, _p(qkv), _p(q_global), _p(bias_table), _p(out), B, Hp, Wp, Cc, heads, ws, nq, float(scale),
+                 prof=prof if kind == "f16" else None)     # the roofline counts the fp16 core only
     return out
-
-
-_GCVIT_BLOCK_FUSED = os.environ.get("VIP_GCVIT_BLOCK_FUSED", "1") != "0"
-# the 14 x 14-window form of the fused block (C = 256, 8 heads: csrc/gcvit_block14.hip) is correct and NOT faster than the four launches
-# (116 us either way at B = 256: one 8-wave workgroup per CU, three barriers and a synchronous 51 KB weight stage per head) - opt-in
-_GCVIT_BLOCK14 = os.environ.get("VIP_GCVIT_BLOCK14", "0") == "1"
 
 
 def gcvit_attn_block(x, q_global, ln, qkv: ConvWeight, proj: ConvWeight, bias_table, heads: int, ws: int, scale: float):
@@ -1288,10 +1219,10 @@ def gcvit_attn_block(x, q_global, ln, qkv: ConvWeight, proj: ConvWeight, bias_ta
     (``VIP_GCVIT_BLOCK_FUSED=0``: always; calibration / exact-weight passes too, they hook the Dense layers)."""
     B, Hp, Wp, Cc = x.shape
     nq = 2 if q_global is not None else 3
-    fused = (_GCVIT_BLOCK_FUSED and not _UNFUSED and not _CALIB and not _EXACT and x.dtype == torch.float16 and x.is_contiguous()
-             and qkv.w_lo is None and proj.w_lo is None and qkv.groups == 1 and proj.groups == 1
-             and qkv.kh == qkv.kw == proj.kh == proj.kw == 1 and qkv.cin == Cc and qkv.cout == nq * Cc and proj.cin == Cc
-             and proj.cout == Cc and Hp % ws == 0 and Wp % ws == 0 and (ws != 14 or _GCVIT_BLOCK14)
+    fused = (_GCVIT_BLOCK_FUSED and not (_UNFUSED or _CALIB or _EXACT) and x.dtype == torch.float16 and x.is_contiguous()
+             and qkv.w_lo is None and proj.w_lo is None and _pointwise(qkv) and _pointwise(proj)
+             and qkv.cin == Cc and qkv.cout == nq * Cc and proj.cin == Cc and proj.cout == Cc
+             and Hp % ws == 0 and Wp % ws == 0 and (ws != 14 or _GCVIT_BLOCK14)
              and _abi.lib().vip_gcvit_attn_block_supported(Cc, heads, ws))
     if not fused:
         y = ln_dense(x, ln, qkv)
@@ -1303,19 +1234,16 @@ def gcvit_attn_block(x, q_global, ln, qkv: ConvWeight, proj: ConvWeight, bias_ta
         assert q_global.numel() == B * ws * ws * Cc
     assert bias_table.dtype == torch.float32 and bias_table.shape == ((2 * ws - 1) ** 2, heads) and bias_table.is_contiguous()
     out = torch.empty_like(x)
-    tok = None
-    if _PROF is not None:
+
+    def prof():
         # the fused form of SURVEY.md section 8(d): per window 2 N C^2 (1 + nq) + 4 N^2 C FLOPs (= 8 N C^2 + 4 N^2 C with q, k, v) and
         # 4 N C bytes (x in, y out, fp16)
         nwin, N = B * (Hp // ws) * (Wp // ws), ws * ws
-        tok = _PROF.start("gcvit_attn_block_kernel", nwin * (2.0 * N * Cc * Cc * (1 + nq) + 4.0 * N * N * Cc), nwin * 4.0 * N * Cc,
-                          f"attn block ws{ws} C={Cc} heads={heads} map={Hp}x{Wp} global={int(q_global is not None)}")
-    st = _abi.lib().vip_gcvit_attn_block_f16(_p(x), _p(q_global), _p(ln[0]), _p(ln[1]), float(ln[2]), _p(qkv.w), qkv.ldw, _p(qkv.bias),
-                                             _p(proj.w), proj.ldw, _p(proj.bias), _p(bias_table), _p(out), B, Hp, Wp, Cc, heads, ws,
-                                             float(scale), _stream())
-    if tok is not None:
-        _PROF.stop(tok)
-    _abi.check(st, "vip_gcvit_attn_block_f16")
+        return ("gcvit_attn_block_kernel", nwin * (2.0 * N * Cc * Cc * (1 + nq) + 4.0 * N * N * Cc), nwin * 4.0 * N * Cc,
+                f"attn block ws{ws} C={Cc} heads={heads} map={Hp}x{Wp} global={int(q_global is not None)}")
+    g, b, eps = _ln_args(ln)
+    _launch("vip_gcvit_attn_block_f16", _p(x), _p(q_global), _p(g), _p(b), eps, _p(qkv.w), qkv.ldw, _p(qkv.bias), _p(proj.w), proj.ldw,
+            _p(proj.bias), _p(bias_table), _p(out), B, Hp, Wp, Cc, heads, ws, float(scale), prof=prof)
     return out
 
 
@@ -1325,11 +1253,7 @@ def mhsa(qkv, heads: int, scale: float):
     B, N, D3 = qkv.shape
     D = D3 // 3
     out = torch.empty((B, N, D), dtype=qkv.dtype, device=qkv.device)
-    if kind != "f16":
-        _strict_call("mhsa_fwd", kind, _p(qkv), _p(out), B, N, D, heads, float(scale))
-        return out
-    st = _abi.lib().vip_mhsa_fwd_f16(_p(qkv), _p(out), B, N, D, heads, float(scale), _stream())
-    _abi.check(st, "vip_mhsa_fwd_f16")
+    _launch_kind("mhsa_fwd", kind, _p(qkv), _p(out), B, N, D, heads, float(scale))
     return out
 
 
@@ -1352,11 +1276,7 @@ def vit_tokens(patches, cls_token, pos_embed):
     assert cls_token.numel() == D and pos_embed.numel() == (NP + 1) * D
     assert cls_token.dtype == pos_embed.dtype == patches.dtype, "vit_tokens: cls / pos must be stored in the activation dtype"
     out = torch.empty((B, NP + 1, D), dtype=patches.dtype, device=patches.device)
-    if kind != "f16":
-        _strict_call("vit_tokens", kind, _p(patches), _p(cls_token), _p(pos_embed), _p(out), B, NP, D)
-        return out
-    st = _abi.lib().vip_vit_tokens_f16(_p(patches), _p(cls_token), _p(pos_embed), _p(out), B, NP, D, _stream())
-    _abi.check(st, "vip_vit_tokens_f16")
+    _launch_kind("vit_tokens", kind, _p(patches), _p(cls_token), _p(pos_embed), _p(out), B, NP, D)
     return out
 
 
@@ -1368,10 +1288,9 @@ def cls_dense_f32(tokens, w_nc: torch.Tensor, bias: Optional[torch.Tensor]):
     assert w_nc.dtype == torch.float32 and w_nc.shape == (n_out, D) and w_nc.is_contiguous()
     out = torch.empty((B, n_out), dtype=torch.float32, device=tokens.device)
     if kind != "f16":
-        _strict_call("gap_ln_dense", kind, _p(tokens), None, None, 0.0, _p(w_nc), _p(bias), _p(out), B, 1, D, D, N * D, n_out, status=False)
-        return out
-    st = _abi.lib().vip_gap_dense_f32(_p(tokens), _p(w_nc), _p(bias), _p(out), B, 1, D, N * D, n_out, _stream())
-    _abi.check(st, "vip_gap_dense_f32")
+        _launch_kind("gap_ln_dense", kind, _p(tokens), None, None, 0.0, _p(w_nc), _p(bias), _p(out), B, 1, D, D, N * D, n_out)
+    else:
+        _launch("vip_gap_dense_f32", _p(tokens), _p(w_nc), _p(bias), _p(out), B, 1, D, N * D, n_out)
     return out
 
 
@@ -1383,31 +1302,23 @@ def mul(a: torch.Tensor, b: torch.Tensor, c: int, a_off: int = 0, b_off: int = 0
     assert a.shape[:-1] == b.shape[:-1]
     rows = a.numel() // a.shape[-1]
     out = torch.empty((*a.shape[:-1], c), dtype=a.dtype, device=a.device)
-    if kind != "f16":
-        _strict_call("mul", kind, _p(a), _p(b), _p(out), rows, c, a.shape[-1], a_off, b.shape[-1], b_off, c, 0)
-        return out
-    st = _abi.lib().vip_mul_f16(_p(a), _p(b), _p(out), rows, c, a.shape[-1], a_off, b.shape[-1], b_off, c, 0, _stream())
-    _abi.check(st, "vip_mul_f16")
+    _launch_kind("mul", kind, _p(a), _p(b), _p(out), rows, c, a.shape[-1], a_off, b.shape[-1], b_off, c, 0)
     return out
 
 
 def radix_combine(x, scale, radix: int = 2):
-    """ResNeSt split-attention combine: x ``[B,H,W,radix*C]``, scale ``[B,radix*C]`` or split ``[B,2,radix*C]``
+    """ResNeSt split-attention combine: x ``[B,H,W,radix*C]``, scale ``[B,radix*C]`` or on the fp16 storage split ``[B,2,radix*C]``
     -> ``[B,H,W,C]``."""
     B, H, W, RC = x.shape
     Cc = RC // radix
     kind = _kind(x, "radix_combine.x")
-    if kind != "f16":
-        _chk_kind(scale, kind, "radix_combine.scale")
-        assert scale.shape == (B, RC), scale.shape
-        out = torch.empty((B, H, W, Cc), dtype=x.dtype, device=x.device)
-        _strict_call("radix_combine", kind, _p(x), _p(scale), _p(out), B, H * W, Cc, radix)
-        return out
-    _chk16(scale, "radix_combine.scale")
-    assert scale.shape in ((B, RC), (B, 2, RC)), scale.shape
-    out = torch.empty((B, H, W, Cc), dtype=torch.float16, device=x.device)
-    st = _abi.lib().vip_radix_combine2_f16(_p(x), _p(scale), scale.dim() - 1, _p(out), B, H * W, Cc, radix, _stream())
-    _abi.check(st, "vip_radix_combine_f16")
+    _chk_kind(scale, kind, "radix_combine.scale")
+    assert scale.shape == (B, RC) or (kind == "f16" and scale.shape == (B, 2, RC)), scale.shape
+    out = torch.empty((B, H, W, Cc), dtype=x.dtype, device=x.device)
+    if kind == "f16":       # this entry point alone takes the number of scale planes
+        _launch("vip_radix_combine2_f16", _p(x), _p(scale), scale.dim() - 1, _p(out), B, H * W, Cc, radix)
+    else:
+        _launch_kind("radix_combine", kind, _p(x), _p(scale), _p(out), B, H * W, Cc, radix)
     return out
 
 

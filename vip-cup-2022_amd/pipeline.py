@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .ops import _p, _stream
+from .ops import _launch, _p
 
 _TABLE_DEV: Dict[int, torch.Tensor] = {}
 
@@ -81,9 +81,7 @@ class DecodedBatch:
             return ops.pack_h2(self.resized(out_h, out_w, c_out, torch.float32))
         out = torch.empty((n, out_h, out_w, c_out), dtype=dtype, device=self.rgb.device)
         fn = {torch.float16: "vip_resize_bicubic_norm_f16", torch.float32: "vip_resize_bicubic_norm_s32"}[dtype]
-        st = getattr(_abi.lib(), fn)(_p(self.rgb), _p(self.sizes), _p(bicubic_table(self.rgb.device)), n,
-                                     maxH, maxW, _p(out), out_h, out_w, c_out, _stream())
-        _abi.check(st, fn)
+        _launch(fn, _p(self.rgb), _p(self.sizes), _p(bicubic_table(self.rgb.device)), n, maxH, maxW, _p(out), out_h, out_w, c_out)
         return out
 
 
@@ -166,8 +164,7 @@ def _png_into(stage: PngStage, slots: Sequence[int], n: int, rgb: torch.Tensor, 
         stream_d = stage.stream.to(device, non_blocking=True)
     else:
         stream_d = torch.from_numpy(stage.stream).to(device)
-    st = _abi.lib().vip_png_unfilter_rgb_u8(_p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW, _stream())
-    _abi.check(st, "vip_png_unfilter_rgb_u8")
+    _launch("vip_png_unfilter_rgb_u8", _p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW)
 
 
 def decode_png_stage(staged: PngStage, device="cuda") -> DecodedBatch:
@@ -264,9 +261,7 @@ def decode_entropy(host_stage, device="cuda") -> DecodedBatch:
     desc_d = torch.from_numpy(desc_bytes.copy()).to(device)
     planes = torch.empty((coef_d.numel(),), dtype=torch.uint8, device=device)
     rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    st = _abi.lib().vip_jpeg_idct_rgb_u8(_p(coef_d), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW,
-                                         _stream())
-    _abi.check(st, "vip_jpeg_idct_rgb_u8")
+    _launch("vip_jpeg_idct_rgb_u8", _p(coef_d), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW)
     sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
     return DecodedBatch(rgb, sizes, sizes_host)
 
@@ -322,11 +317,8 @@ def recompress(batch: DecodedBatch, quality: int, subsampling: str = "4:2:0") ->
     planes = torch.empty((total,), dtype=torch.uint8, device=device)
     rgb = torch.zeros_like(batch.rgb)
     src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    lib = _abi.lib()
-    st = lib.vip_jpeg_fdct_quant_u8(_p(src), _p(desc_d), n, max_blocks, _p(planes), _p(coef), maxH, maxW, _stream())
-    _abi.check(st, "vip_jpeg_fdct_quant_u8")
-    st = lib.vip_jpeg_idct_rgb_u8(_p(coef), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW, _stream())
-    _abi.check(st, "vip_jpeg_idct_rgb_u8")
+    _launch("vip_jpeg_fdct_quant_u8", _p(src), _p(desc_d), n, max_blocks, _p(planes), _p(coef), maxH, maxW)
+    _launch("vip_jpeg_idct_rgb_u8", _p(coef), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW)
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
 
 
@@ -342,8 +334,7 @@ def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
         return ops.pack_h2(apply_augment(ops.unpack_h2(x), hflip, vflip, gray))
     out = torch.empty_like(x)
     fn = "vip_tta_augment_s32" if x.dtype == torch.float32 else "vip_tta_augment_f16"
-    st = getattr(_abi.lib(), fn)(_p(x), _p(out), _p(flags), B, H, W, Cc, _stream())
-    _abi.check(st, fn)
+    _launch(fn, _p(x), _p(out), _p(flags), B, H, W, Cc)
     return out
 
 

@@ -183,7 +183,7 @@ def calibrate(model, x):
     from . import ops
     with ops.calibration():
         model.logits(x)
-    if os.environ.get("VIP_OFFSET_CALIBRATION", "0") == "1":
+    if ops.offset_calibration():
         with ops.unfused():
             z16 = model.logits(x).float()
         with ops.exact_weights():
