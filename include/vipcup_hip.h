@@ -375,6 +375,43 @@ int vip_jpeg_encode_layout_h(int width, int height, int subsampling, int quality
 int vip_jpeg_fdct_quant_u8(const uint8_t* rgb_u8, const vip_jpeg_desc* desc, int n, int max_blocks, uint8_t* planes_ws,
                            int16_t* coef, int maxH, int maxW, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Antialiased resampling of decoded u8 RGB to a new size: what an image editor or an upload does before it re-saves (the first half of
+ * the challenge's "resized and then JPEG-compressed").  NOT the network-input resize below, which stays TensorFlow's non-antialiased
+ * bicubic.  The operation is Pillow's 8-bit Image.resize, bit for bit: integer tables from the host, integer passes on the device.
+ *
+ * vip_resample_coeffs_h (host, double precision): the tables of ONE axis for in_size -> out_size samples and a filter
+ *   (VIP_RESAMPLE_BILINEAR support 1, _BICUBIC Keys a = -0.5 support 2, _LANCZOS support 3).  scale = in / out, fscale = max(scale, 1),
+ *   support = filter support * fscale, *ksize_h = 2 ceil(support) + 1.  Per output index x: center = (x + 0.5) scale,
+ *   xmin = max(int(center - support + 0.5), 0), count = min(int(center + support + 0.5), in) - xmin,
+ *   w_j = f((j + xmin - center + 0.5) * (1 / fscale)); the weights are summed left to right and divided by the sum when it is not 0;
+ *   k = int(w * 2^22 +- 0.5), the sign of the 0.5 that of w; unused slots 0.
+ *   bounds_h int32 [out][2] = (xmin, count), k_h int32 [out][ksize]; bounds_cap / k_cap = the buffers' sizes in int32.  With both
+ *   buffers NULL only *ksize_h is written (a size query).  Sizes outside 1..2^20, an unknown filter, one buffer NULL or a buffer too
+ *   short -> VIP_ERR_BAD_ARG with a message, before anything is written.
+ * vip_resample_rgb_u8 (device, caller's stream, one launch per batch): src_u8 [n][maxH][maxW][3] with image i in the top-left
+ *   src_sizes_hw[i] = (h, w) corner of its slot -> dst_u8 [n][maxHo][maxWo][3], image i at dst_sizes_hw[i] = (h', w').  Per channel:
+ *   horizontal pass to u8 = clamp((2^21 + sum px * k) >> 22, 0, 255) with a 32-bit accumulator and an arithmetic shift, then the same
+ *   formula vertically over the ROUNDED u8 rows; a pass whose sizes are equal is skipped.  Only the h' x w' pixels of an image are
+ *   written: the rest of dst_u8 keeps what the caller put there.
+ *   image_tab int32 [n][8]: first tile of the image (prefix sum over the batch), tiles per tile row, then horizontal and vertical
+ *   (bounds offset, coefficient offset, ksize) into `tables`, the concatenated vip_resample_coeffs_h outputs (device copies; the
+ *   offsets of a skipped pass are unused).  A tile is rows x bytes of vip_resample_tile_shape over the interleaved output row:
+ *   tiles per row = ceil(3 w' / bytes), tile rows = ceil(h' / rows); total_tiles = their sum over the batch.
+ *   A workgroup resamples the input rows its tile's vertical window needs horizontally into LDS and runs the vertical pass from there;
+ *   a window taller than window_rows is worked through in groups of output rows inside the same launch, with the same arithmetic.
+ *   max_window = the largest tap count of one output row over the batch (min(vertical ksize, h)); beyond window_rows (a shrink
+ *   past ~25x) the call is refused with VIP_ERR_UNSUPPORTED - there is no two-launch fallback.  No allocation, no atomics:
+ *   bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+enum { VIP_RESAMPLE_BILINEAR = 0, VIP_RESAMPLE_BICUBIC = 1, VIP_RESAMPLE_LANCZOS = 2 };
+int vip_resample_coeffs_h(int in_size, int out_size, int filter, int32_t* bounds_h, size_t bounds_cap, int32_t* k_h, size_t k_cap,
+                          int* ksize_h);
+int vip_resample_tile_shape(int* rows_h, int* bytes_h, int* window_rows_h);
+int vip_resample_rgb_u8(const uint8_t* src_u8, const int32_t* src_sizes_hw, int maxH, int maxW, uint8_t* dst_u8,
+                        const int32_t* dst_sizes_hw, int maxHo, int maxWo, const int32_t* image_tab, const int32_t* tables, int n,
+                        int total_tiles, int max_window, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

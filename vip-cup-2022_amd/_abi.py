@@ -91,6 +91,9 @@ SIGNATURES = {
     "vip_jpeg_quality_tables_h": (_i, [_i, _vp, _vp]),
     "vip_jpeg_encode_layout_h": (_i, [_i, _i, _i, _i, _vp, _vp]),
     "vip_jpeg_fdct_quant_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "vip_resample_coeffs_h": (_i, [_i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "vip_resample_tile_shape": (_i, [_vp, _vp, _vp]),
+    "vip_resample_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
     "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),

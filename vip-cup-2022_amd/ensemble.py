@@ -466,23 +466,46 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     return acc / float(len(flags))
 
 
-def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None) -> torch.Tensor:
+def stress_labels(qualities: Sequence[int], scales: Sequence[int] = ()) -> List[str]:
+    """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
+    ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved)."""
+    labels = [f"q{int(q)}" for q in qualities]
+    for pc in scales:
+        labels.append(f"r{int(pc)}")
+        labels += [f"r{int(pc)}_q{int(q)}" for q in qualities]
+    return labels
+
+
+def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
+                 resize_filter: str = "bicubic"):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
-    ``_score_batch``; it is decoded once.  Returns ``[1 + Q, M, n]`` fp32 (device), rows 1.. in the order of ``qualities``."""
+    ``_score_batch``; it is decoded once.  Returns ``[1 + Q, M, n]`` fp32 (device), rows 1.. in the order of ``qualities``.
+    With ``scales`` (percents, sorted largest first here) the batch is also rescaled to each percent of its size with ``resize_filter``
+    (``pipeline.rescale``) and scored unsaved and re-saved at every quality - rescale first, ``recompress`` second, the order in which
+    the challenge's test images were made.  Then the result is ``(rows [1 + V, M, n], labels)`` with ``labels`` =
+    ``stress_labels(qualities, scales)``, the names of rows 1.. ."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
     else:
         batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
             isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    scales = sorted((int(pc) for pc in scales), reverse=True)
     rows = [_score_batch(batch, members, None, after_fork=after_fork)]
     for q in qualities:
         rows.append(_score_batch(pipeline.recompress(batch, int(q), subsampling), members))
+    for pc in scales:
+        small = pipeline.rescale(batch, pc, resize_filter)
+        rows.append(_score_batch(small, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(small, int(q), subsampling), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    return torch.stack(rows)
+    if not scales:
+        return torch.stack(rows)
+    return torch.stack(rows), stress_labels(qualities, scales)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -509,30 +532,42 @@ def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n
     return full.cpu().numpy()
 
 
-def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence[int], thr: float = THR):
+def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, thr: float = THR):
     """``scores`` ``[1 + Q, M, n]`` (``stress_batch`` rows over all images, in the order of ``names``) -> ``(table, summary)``; numpy only.
     ``table``: per sorted unique filename (duplicates averaged first, decision = mean ``> thr``: the rule of ``aggregate``) ``filename``,
     ``p`` / ``decision`` unperturbed, ``p_q`` / ``decision_q`` ``[F, Q]``, ``stable`` (every decision equals the unperturbed one) and
     ``flips_at`` (the highest listed quality whose decision differs, None when stable).  ``summary``: per quality the number and rate of
-    files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files."""
+    files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
+    ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``).  With ``q`` labels alone the
+    result is the one above.  With rescaled variants ``p_q`` / ``decision_q`` are ``[F, V]`` over all variants, ``stable`` is taken
+    over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only), ``table`` gains ``labels`` and
+    ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants`` (the labels in order) and keys
+    its per-variant counts by label; ``summary["qualities"]`` lists the qualities of the 100 % rows."""
     scores = np.asarray(scores)
-    qs = [int(q) for q in qualities]
-    assert scores.ndim == 3 and scores.shape[0] == 1 + len(qs) and scores.shape[2] == len(names), (scores.shape, len(qs), len(names))
+    labels = [v if isinstance(v, str) else f"q{int(v)}" for v in qualities]
+    plain = [int(v[1:]) if v[:1] == "q" and v[1:].isdigit() else None for v in labels]
+    mixed = any(q is None for q in plain)
+    assert scores.ndim == 3 and scores.shape[0] == 1 + len(labels) and scores.shape[2] == len(names), (scores.shape, len(labels), len(names))
     agg = [aggregate(names, s, thr) for s in scores]
     uniq = agg[0][0]
     p, dec = agg[0][1], agg[0][2]
     F = len(uniq)
-    p_q = np.stack([a[1] for a in agg[1:]], axis=1) if qs else np.zeros((F, 0), np.float32)
-    dec_q = np.stack([a[2] for a in agg[1:]], axis=1) if qs else np.zeros((F, 0), np.float32)
+    p_q = np.stack([a[1] for a in agg[1:]], axis=1) if labels else np.zeros((F, 0), np.float32)
+    dec_q = np.stack([a[2] for a in agg[1:]], axis=1) if labels else np.zeros((F, 0), np.float32)
     differs = dec_q != dec[:, None]
     stable = ~differs.any(axis=1)
-    flips_at = [max((q for q, d in zip(qs, row) if d), default=None) for row in differs]
+    flips_at = [max((q for q, d in zip(plain, row) if d and q is not None), default=None) for row in differs]
     table = {"filename": uniq, "p": p, "decision": dec, "p_q": p_q, "decision_q": dec_q, "stable": stable, "flips_at": flips_at}
-    summary = {"n_files": F, "threshold": float(thr), "qualities": qs, "n_stable": int(stable.sum()),
-               "flips": {str(q): int(differs[:, k].sum()) for k, q in enumerate(qs)},
-               "flip_rate": {str(q): (float(differs[:, k].mean()) if F else 0.0) for k, q in enumerate(qs)},
-               "mean_abs_dp": {str(q): (float(np.abs(p_q[:, k].astype(np.float64) - p.astype(np.float64)).mean()) if F else 0.0)
-                               for k, q in enumerate(qs)}}
+    keys = labels if mixed else [str(q) for q in plain]
+    summary = {"n_files": F, "threshold": float(thr), "qualities": [q for q in plain if q is not None], "n_stable": int(stable.sum()),
+               "flips": {key: int(differs[:, k].sum()) for k, key in enumerate(keys)},
+               "flip_rate": {key: (float(differs[:, k].mean()) if F else 0.0) for k, key in enumerate(keys)},
+               "mean_abs_dp": {key: (float(np.abs(p_q[:, k].astype(np.float64) - p.astype(np.float64)).mean()) if F else 0.0)
+                               for k, key in enumerate(keys)}}
+    if mixed:
+        table["labels"] = labels
+        table["flips"] = [";".join(v for v, d in zip(labels, row) if d) for row in differs]
+        summary["variants"] = labels
     return table, summary
 
 

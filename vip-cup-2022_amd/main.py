@@ -3,6 +3,7 @@
     python3 vip-cup-2022_amd/main.py <input.csv> <output.csv> [--scores-out scores.csv] [--synthetic]
                                      [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
                                      [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
+                                     [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
     python -m torch.distributed.run --nproc-per-node N ... vip-cup-2022_amd/main.py in.csv out.csv
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
@@ -19,6 +20,12 @@ quality (dataset/augment.py:110-113 ``JpegCompress``; the decoded image is re-sa
 libjpeg's default 4:2:0 chroma or ``--stress-subsampling 444``) and writes, per input file, ``filename, p, decision, p_q<Q>...,
 decision_q<Q>..., stable, flips_at`` (``flips_at``: the highest listed quality at which the decision differs from the unperturbed one) and
 ``stress.json`` with the per-quality flip counts, flip rates, mean |p_q - p| and the settings.  The CSV outputs do not change with the flag.
+``--stress-resize 150,50 --stress-out stress.csv`` rescales every decoded image to each listed percent of its own size first (an antialiased
+bicubic by default, ``--stress-resize-filter``; integer arithmetic and a uint8 result, what an image editor or an upload does) and scores
+it unsaved (``r<P>``) and, with ``--stress-jpeg``, re-saved at every quality (``r<P>_q<Q>``): resized, then compressed, the way the
+challenge's test images were made.  The table is then ``filename, p, decision, p_<label>..., decision_<label>..., stable, flips_at, flips``
+over the labels ``q<Q>..., r<P>, r<P>_q<Q>...`` (``stable`` over all variants, ``flips_at`` over the 100 % rows as before, ``flips`` the
+``;``-joined labels whose decision differs) and ``stress.json`` lists the labels under ``variants`` and keys its counts by label.
 
 Checkpoints: ``<script dir>/ckpts/<name>/ckpt/*.h5`` (Keras weight / model files, as in the reference), else ``ckpt/saved_model.pb`` (a
 Keras SavedModel directory: its variables are read by ``tfbundle``), or ``*.npz`` (a flat dict of
@@ -86,35 +93,46 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
-def _stress_scorer(qualities, subsampling, kept):
-    """the ``batch_scorer`` of ``--stress-jpeg``: ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of
-    the re-saved batches ``[Q, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
+def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic"):
+    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize``: ``stress_batch`` on every batch; the unperturbed row is handed on
+    unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra
+    collective"""
     from vipcup_amd import ensemble
 
     def score(staged, sub, b0, b1, after_fork):
-        rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
+        if scales:
+            rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
+                                            resize_filter=resize_filter)
+        else:
+            rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
         return rows[0]
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode):
+def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=()):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    table, summary = ensemble.stress_table(names, scores, qualities)
+    labels = ensemble.stress_labels(qualities, scales)
+    table, summary = ensemble.stress_table(names, scores, labels if scales else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
-    for k, q in enumerate(qualities):
-        cols[f"p_q{q}"] = table["p_q"][:, k]
-    for k, q in enumerate(qualities):
-        cols[f"decision_q{q}"] = table["decision_q"][:, k]
+    for k, v in enumerate(labels):
+        cols[f"p_{v}"] = table["p_q"][:, k]
+    for k, v in enumerate(labels):
+        cols[f"decision_{v}"] = table["decision_q"][:, k]
     cols["stable"] = table["stable"].astype(np.int64)
     cols["flips_at"] = ["" if q is None else str(q) for q in table["flips_at"]]
+    if scales:
+        cols["flips"] = table["flips"]
     pd.DataFrame(cols).to_csv(a.stress_out, index=False)
     summary["settings"] = {"qualities": list(qualities), "subsampling": {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling],
                            "threshold": ensemble.THR, "precision": mode, "batch_size": a.batch_size, "n_images": len(names),
                            "members": [spec.name for spec, _ in members]}
+    if scales:
+        summary["settings"]["scales"] = list(scales)
+        summary["settings"]["resize_filter"] = a.stress_resize_filter
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
 
@@ -160,7 +178,36 @@ def main(argv=None):
                          "holds the per-quality flip counts and rates, mean |p_q - p| and the settings")
     ap.add_argument("--stress-subsampling", default="420", choices=["420", "444"],
                     help="chroma sampling of the simulated re-save: 420 (libjpeg's default) or 444")
+    ap.add_argument("--stress-resize", default=None, metavar="P[,P...]",
+                    help="resize stress test: also score every image rescaled to each percent of its own size (integers in 10..400; "
+                         "duplicates and 100 are dropped, largest first), unsaved and - with --stress-jpeg - re-saved at every quality; "
+                         "needs --stress-out, whose table becomes filename, p, decision, p_<label>..., decision_<label>..., stable, "
+                         "flips_at, flips over the labels q<Q>, r<P>, r<P>_q<Q>")
+    ap.add_argument("--stress-resize-filter", default="bicubic", choices=["bilinear", "bicubic", "lanczos"],
+                    help="the antialiased filter of the simulated resize (what an image editor's resize offers)")
     a = ap.parse_args(argv)
+    scales = None
+    if a.stress_resize is not None:
+        try:
+            given = [int(t) for t in a.stress_resize.split(",")]
+        except ValueError:
+            given = []
+        if not given or min(given) < 10 or max(given) > 400:
+            raise SystemExit(f"vipcup_amd main: --stress-resize {a.stress_resize!r}: expected a comma-separated list of integer percents in 10..400")
+        scales = sorted({pc for pc in given if pc != 100}, reverse=True)
+        if not scales:
+            raise SystemExit(f"vipcup_amd main: --stress-resize {a.stress_resize!r}: nothing left after dropping 100 (the unperturbed row)")
+        if a.stress_out is None:
+            raise SystemExit("vipcup_amd main: --stress-resize needs --stress-out FILE.csv")
+        if a.shard != "images" or a.tta > 1:
+            # as for --stress-jpeg: the scores of one image would be spread over ranks or over augmented copies
+            raise SystemExit("vipcup_amd main: --stress-resize works with --shard images and --tta 1 only (got --shard "
+                             f"{a.shard} --tta {a.tta}): the resize stress test under member sharding or TTA is not implemented")
+        if a.heatmaps is not None:
+            raise SystemExit("vipcup_amd main: --stress-resize and --heatmaps cannot be combined (both replace the batch scorer): "
+                             "run them one after the other")
+    elif a.stress_resize_filter != "bicubic":
+        raise SystemExit("vipcup_amd main: --stress-resize-filter needs --stress-resize P[,P...]")
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -178,8 +225,9 @@ def main(argv=None):
         if a.heatmaps is not None:
             raise SystemExit("vipcup_amd main: --stress-jpeg and --heatmaps cannot be combined (both replace the batch scorer): "
                              "run them one after the other")
-    elif a.stress_out is not None or a.stress_subsampling != "420":
-        raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]")
+    elif (a.stress_out is not None and scales is None) or a.stress_subsampling != "420":
+        raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]"
+                         + (" (--stress-out alone also goes with --stress-resize P[,P...])" if a.stress_out is not None else ""))
     if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
         # the maps of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
         raise SystemExit("vipcup_amd main: --heatmaps works with --shard images and --tta 1 only (got --shard "
@@ -276,8 +324,9 @@ def main(argv=None):
     if a.heatmaps is not None:
         batch_scorer = _heatmap_writer(a, names, members, rank)
     stress_rows = []
-    if qualities is not None:
-        batch_scorer = _stress_scorer(qualities, {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows)
+    if qualities is not None or scales is not None:
+        batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
+                                      scales or (), a.stress_resize_filter)
 
     t0 = time.time()
     costs = None
@@ -289,8 +338,9 @@ def main(argv=None):
                                      tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
-    if qualities is not None:                   # the one extra collective of a stress run: every rank's [Q, M, n_local] rows
-        stressed = ensemble.gather_stress_rows(stress_rows, len(qualities), len(members), len(paths), rank, world, dist)
+    if qualities is not None or scales is not None:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or ()))
+        stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     if rank == 0:
         pd.DataFrame({"filename": uniq, "logit": decision}).to_csv(a.output_csv, index=False)  # main.py:143-145
         if a.scores_out:
@@ -299,7 +349,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities, mode)
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or ())
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         dt = time.time() - t0
         print(f"> FINAL PREDICTION SAVED TO {a.output_csv}")

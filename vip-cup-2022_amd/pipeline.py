@@ -322,6 +322,112 @@ def recompress(batch: DecodedBatch, quality: int, subsampling: str = "4:2:0") ->
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
 
 
+RESAMPLE_FILTERS = {"bilinear": 0, "bicubic": 1, "lanczos": 2}      # VIP_RESAMPLE_* (include/vipcup_hip.h)
+_RESAMPLE_TABLES: Dict[Tuple[int, int, str], Tuple[np.ndarray, np.ndarray, int]] = {}
+_RESAMPLE_TILE: List[int] = []
+
+
+def resample_coeffs(in_size: int, out_size: int, filter: str = "bicubic") -> Tuple[np.ndarray, np.ndarray, int]:
+    """Host: the integer tables of one axis of an antialiased 8-bit resize, ``(bounds int32 [out, 2] = (first tap, taps), k int32
+    [out, ksize], ksize)`` (``vip_resample_coeffs_h``), cached per ``(in, out, filter)`` - a batch holds few sizes."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"filter {filter!r}: expected one of {', '.join(RESAMPLE_FILTERS)}")
+    key = (int(in_size), int(out_size), filter)
+    if key not in _RESAMPLE_TABLES:
+        lib = _abi.lib()
+        ksize = C.c_int(0)
+        st = lib.vip_resample_coeffs_h(key[0], key[1], RESAMPLE_FILTERS[filter], None, 0, None, 0, C.byref(ksize))
+        _abi.check(st, "vip_resample_coeffs_h")
+        bounds = np.zeros((key[1], 2), np.int32)
+        k = np.zeros((key[1], ksize.value), np.int32)
+        st = lib.vip_resample_coeffs_h(key[0], key[1], RESAMPLE_FILTERS[filter], bounds.ctypes.data_as(C.c_void_p), bounds.size,
+                                       k.ctypes.data_as(C.c_void_p), k.size, C.byref(ksize))
+        _abi.check(st, "vip_resample_coeffs_h")
+        if len(_RESAMPLE_TABLES) >= 256:                  # sizes keep coming (a folder of arbitrary images): start over
+            _RESAMPLE_TABLES.clear()
+        _RESAMPLE_TABLES[key] = (bounds, k, int(ksize.value))
+    return _RESAMPLE_TABLES[key]
+
+
+def scaled_size(h: int, w: int, percent: int) -> Tuple[int, int]:
+    """the size ``rescale`` gives an ``h x w`` image: each side times percent / 100, rounded half up, at least 1"""
+    return max(1, int(h * percent / 100 + 0.5)), max(1, int(w * percent / 100 + 0.5))
+
+
+def rescale(batch: DecodedBatch, percent: int, filter: str = "bicubic") -> DecodedBatch:
+    """The batch as an image editor or an upload would resize it: every image to ``percent`` % of its own size (``scaled_size``) with
+    an antialiased ``filter`` (bilinear, bicubic or lanczos: the support widens with the shrink factor), integer arithmetic and a uint8
+    result - Pillow's ``Image.resize``, bit for bit (``vip_resample_rgb_u8``, one launch).  This is the first half of the challenge's
+    "resized and then JPEG-compressed"; ``recompress`` is the second.  Not the network-input resize (``DecodedBatch.resized``).
+    Returns a new batch at the new sizes, pixels outside an image 0; ``batch`` is not touched.  Runs on the current stream; only the
+    coefficient tables and their offsets (a few KiB per distinct size) come from the host.  ``percent`` = 100 returns the pixels unchanged."""
+    if isinstance(percent, bool) or not isinstance(percent, (int, np.integer)) or not 10 <= int(percent) <= 400:
+        raise ValueError(f"percent {percent!r}: expected an integer in 10..400")
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"filter {filter!r}: expected one of {', '.join(RESAMPLE_FILTERS)}")
+    percent = int(percent)
+    new_sizes = [scaled_size(h, w, percent) for h, w in batch.sizes_host]
+    for i, (h, w) in enumerate(new_sizes):
+        if h * w > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"image {i}: {w}x{h} after a {percent} % resize exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+    maxHo, maxWo = max(h for h, _ in new_sizes), max(w for _, w in new_sizes)
+    rgb = torch.zeros((len(batch), maxHo, maxWo, 3), dtype=torch.uint8, device=batch.rgb.device)
+    return _resample_into(batch, new_sizes, filter, rgb)
+
+
+def resample_plan(sizes_host: Sequence[Tuple[int, int]], new_sizes: Sequence[Tuple[int, int]], filter: str):
+    """Host: what ``vip_resample_rgb_u8`` needs besides the pixels - ``(image_tab int32 [n, 8], tables int32, total tiles, widest
+    vertical window)`` for images of ``sizes_host`` = [(h, w)] going to ``new_sizes``; the tables of a size pair appear once."""
+    if not _RESAMPLE_TILE:
+        shape = (C.c_int * 3)()
+        st = _abi.lib().vip_resample_tile_shape(C.byref(shape, 0), C.byref(shape, 4), C.byref(shape, 8))
+        _abi.check(st, "vip_resample_tile_shape")
+        _RESAMPLE_TILE.extend(int(v) for v in shape)
+    tile_rows, tile_bytes, _ = _RESAMPLE_TILE
+    parts: List[np.ndarray] = []
+    placed: Dict[Tuple[int, int], Tuple[int, int, int]] = {}        # (in, out) -> (bounds offset, coefficient offset, ksize)
+    used = 0
+
+    def place(n_in, n_out):
+        nonlocal used
+        if n_in == n_out:
+            return 0, 0, 0                                           # skipped pass: the kernel does not read its tables
+        if (n_in, n_out) not in placed:
+            bounds, k, ksize = resample_coeffs(n_in, n_out, filter)
+            placed[(n_in, n_out)] = (used, used + bounds.size, ksize)
+            parts.extend((bounds.reshape(-1), k.reshape(-1)))
+            used += bounds.size + k.size
+        return placed[(n_in, n_out)]
+
+    tab = np.zeros((len(sizes_host), 8), np.int32)
+    tiles, max_window = 0, 1
+    for i, ((h, w), (ho, wo)) in enumerate(zip(sizes_host, new_sizes)):
+        tiles_x = -(-wo * 3 // tile_bytes)
+        tab[i] = (tiles, tiles_x) + place(w, wo) + place(h, ho)
+        tiles += tiles_x * -(-ho // tile_rows)
+        max_window = max(max_window, min(int(tab[i, 7]), h))
+    tables = np.concatenate(parts) if parts else np.zeros((1,), np.int32)
+    return tab, tables, tiles, max_window
+
+
+def _resample_into(batch: DecodedBatch, new_sizes: List[Tuple[int, int]], filter: str, rgb: torch.Tensor) -> DecodedBatch:
+    """``rescale``'s launch: image i of ``batch`` resampled to ``new_sizes[i]`` = (h, w) into its slot of ``rgb`` [n, maxHo, maxWo, 3]
+    (contiguous uint8 on the batch's device; only the pixels of the images are written)."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    maxHo, maxWo = int(rgb.shape[1]), int(rgb.shape[2])
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3
+    assert all(1 <= h <= maxHo and 1 <= w <= maxWo for h, w in new_sizes)
+    tab, tables, tiles, max_window = resample_plan(batch.sizes_host, new_sizes, filter)
+    tab_d = torch.from_numpy(tab).to(device)
+    tables_d = torch.from_numpy(tables).to(device)
+    sizes = torch.tensor(new_sizes, dtype=torch.int32, device=device)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    _launch("vip_resample_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), _p(sizes), maxHo, maxWo, _p(tab_d), _p(tables_d), n,
+            tiles, max_window)
+    return DecodedBatch(rgb, sizes, list(new_sizes))
+
+
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
     """Deterministic form of dataset/augment.py ``apply_augment`` (:153-182): per-image flags instead of the
     reference's TF RNG draws (p=0.8 gate, hflip .5, vflip .5, gray .3) — the caller owns the randomness."""
