@@ -460,6 +460,18 @@ int vip_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* sizes_hw, 
                                 int n, int maxH, int maxW, void* out, int outH, int outW, int c_out,
                                 void* stream);
 
+/* Native-resolution tiles (main.py --tiles-out): tile t of tile_tab int32 [n_tiles][4] = (image, y0, x0, 0) is the tile x tile
+ * pixels at (y0, x0) of that image's slot in rgb_u8 [n][maxH][maxW][3], scored as an image of its own.  out [n_tiles][outH][outW]
+ * [c_out] holds exactly what vip_resize_bicubic_norm_f16 / _s32 gives for the same pixels held as a stand-alone tile x tile image -
+ * dataset/dataset.py:31-38 applied to the crop: p / 255 when out == tile, else the legacy bicubic with the same table and order
+ * of operations, its taps clamped at the TILE's edge (no neighbouring pixel of the large image and no slot padding is read).
+ * One launch per call, n_tiles <= 65535, out 16-byte aligned; a row of tile_tab that does not lie inside a slot yields a zero
+ * tile.  _f16: fp16 output; _s32: the unrounded fp32 values (STRICT path). */
+int vip_tile_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles, int maxH,
+                                     int maxW, int tile, void* out, int outH, int outW, int c_out, void* stream);
+int vip_tile_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles, int maxH,
+                                     int maxW, int tile, float* out, int outH, int outW, int c_out, void* stream);
+
 /* TTA ops (dataset/augment.py:115-120,142-146) on f16 NHWC batches: flags int32 [B]: bit0 horizontal flip,
  * bit1 vertical flip, bit2 RGB->gray->RGB (0.2989, 0.5870, 0.1140). */
 int vip_tta_augment_f16(const void* x, void* y, const int32_t* flags, int B, int H, int W, int C,
@@ -500,6 +512,11 @@ int vip_head_prob_f32(const float* logits, float* prob, float* score, int B, int
 int vip_head_act_f32(const float* logits, float* prob, int B, int N, int act, void* stream);
 int vip_prob_to_score_f32(const float* prob, float* score, int B, int N, void* stream);
 int vip_ensemble_mean_f32(const float* scores, float* mean, int M, int n, long ld, void* stream);
+/* Tile report: scores f32 [rows][T] (rows = members + 1, the last row the per-tile ensemble mean), seg int32 [n + 1] with the
+ * tiles of image i at columns seg[i] .. seg[i+1]-1 -> out f32 [3][rows][n] = per row and image the mean of its tile scores (fp32,
+ * summed sequentially in tile order: independent of the launch shape), their max, and the fraction of tiles > thr.  An image
+ * without tiles gets NaN in all three. */
+int vip_tile_aggregate_f32(const float* scores, const int32_t* seg, int n, int rows, int T, float thr, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * STRICT precision path, packed storage (entry points ending in _h2) - the default of `--precision strict` since round 4.

@@ -276,6 +276,84 @@ __global__ __launch_bounds__(256) void resize_norm_kernel(const uint8_t* __restr
     store(res);
 }
 
+// ---- native-resolution tiles: tile t = the tile x tile pixels at (y0, x0) of image tab[t].image, taken as an image of its own.
+// The arithmetic is resize_norm_kernel's with h = w = tile, expression for expression (same taps, horizontal pass first, the
+// same __fmul_rn / __fadd_rn chains, __fdiv_rn by 255): a tile's values are bit for bit those of the stand-alone crop.  The
+// taps clamp at the tile's edge (bicubic_taps(.., tile, ..)), so no pixel outside the tile is ever read - neither a
+// neighbour in the large image nor the padding of the slot.
+// One thread = one output pixel, one vector store per pixel (16 B for 8 fp16 channels); grid.z = tile.  The source bytes
+// (3 per output pixel on the identity branch, 48 on the bicubic one, shared between neighbours through L1 / L2) are read
+// as bytes, as resize_norm_kernel reads them (measured in DESIGN.md section 3; profiles/tiles_gather_ab.log).
+template <typename T>
+__device__ __forceinline__ void store_pixel(T* __restrict__ o, const float (&res)[3], int c_out) {
+    if (sizeof(T) == 2 && c_out == 8) {              // one 16-byte store per pixel
+        U4H8 v;
+        v.u = make_uint4(0, 0, 0, 0);
+        v.e[0] = (f16)res[0]; v.e[1] = (f16)res[1]; v.e[2] = (f16)res[2];
+        *reinterpret_cast<uint4*>(o) = v.u;
+    } else if (sizeof(T) == 2 && c_out == 4) {
+        U4H8 v;
+        v.u = make_uint4(0, 0, 0, 0);
+        v.e[0] = (f16)res[0]; v.e[1] = (f16)res[1]; v.e[2] = (f16)res[2];
+        *reinterpret_cast<uint2*>(o) = make_uint2(v.u.x, v.u.y);
+    } else if (sizeof(T) == 4 && (c_out == 8 || c_out == 4)) {
+        float4* o4 = reinterpret_cast<float4*>(o);
+        o4[0] = make_float4(res[0], res[1], res[2], 0.f);
+        if (c_out == 8) o4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        for (int c = 0; c < c_out; ++c) o[c] = (T)(c < 3 ? res[c] : 0.f);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void tile_resize_norm_kernel(const uint8_t* __restrict__ rgb, const int* __restrict__ tab,
+                                                               const float* __restrict__ table, T* __restrict__ out,
+                                                               int maxH, int maxW, int tile, int outH, int outW, int c_out) {
+    const int t = blockIdx.z;
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (ox >= outW || oy >= outH) return;
+    const int n = tab[4 * t], y0 = tab[4 * t + 1], x0 = tab[4 * t + 2];
+    T* o = out + (((long)t * outH + oy) * outW + ox) * c_out;
+    if (n < 0 || y0 < 0 || x0 < 0 || y0 > maxH - tile || x0 > maxW - tile) {
+        // a table row that does not lie inside a slot (not one of pipeline.tile_plan's): nothing is read, the tile is 0
+        const float zero[3] = {0.f, 0.f, 0.f};
+        store_pixel(o, zero, c_out);
+        return;
+    }
+    const long pitch = (long)maxW * 3;
+    const uint8_t* img = rgb + (((long)n * maxH + y0) * maxW + x0) * 3;       // the tile's first pixel, any byte alignment
+    if (tile == outH && tile == outW) {
+        // the identity branch of resize_norm_kernel: taps (0, 1, 0, 0) in both axes
+        const uint8_t* p = img + (long)oy * pitch + (long)ox * 3;
+        const float res[3] = {__fdiv_rn((float)p[0], 255.f), __fdiv_rn((float)p[1], 255.f), __fdiv_rn((float)p[2], 255.f)};
+        store_pixel(o, res, c_out);
+        return;
+    }
+    const Taps ty = bicubic_taps(oy, tile, __fdiv_rn((float)tile, (float)outH), table);
+    const Taps tx = bicubic_taps(ox, tile, __fdiv_rn((float)tile, (float)outW), table);
+    float res[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float rowv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint8_t* p = img + (long)ty.idx[r] * pitch + c;
+            float v = __fmul_rn((float)p[tx.idx[0] * 3], tx.w[0]);
+            v = __fadd_rn(v, __fmul_rn((float)p[tx.idx[1] * 3], tx.w[1]));
+            v = __fadd_rn(v, __fmul_rn((float)p[tx.idx[2] * 3], tx.w[2]));
+            v = __fadd_rn(v, __fmul_rn((float)p[tx.idx[3] * 3], tx.w[3]));
+            rowv[r] = v;
+        }
+        float v = __fmul_rn(rowv[0], ty.w[0]);
+        v = __fadd_rn(v, __fmul_rn(rowv[1], ty.w[1]));
+        v = __fadd_rn(v, __fmul_rn(rowv[2], ty.w[2]));
+        v = __fadd_rn(v, __fmul_rn(rowv[3], ty.w[3]));
+        res[c] = __fdiv_rn(v, 255.f);
+    }
+    store_pixel(o, res, c_out);
+}
+
 // TTA: flags bit0 hflip, bit1 vflip, bit2 gray (tf.image.rgb_to_grayscale weights 0.2989/0.5870/0.1140)
 template <typename T>
 __global__ __launch_bounds__(256) void tta_kernel(const T* __restrict__ x, T* __restrict__ y,
@@ -347,6 +425,34 @@ extern "C" int vip_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t*
     hipLaunchKernelGGL(resize_norm_kernel<float>, dim3((outW + 63) / 64, (outH + 3) / 4, n), dim3(256), 0, (hipStream_t)stream,
                        rgb_u8, sizes_hw, table, out, maxH, maxW, outH, outW, c_out);
     return vip_launch_status("vip_resize_bicubic_norm_s32");
+}
+
+template <typename T>
+static int tile_resize_launch(const char* name, const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles,
+                              int maxH, int maxW, int tile, T* out, int outH, int outW, int c_out, void* stream) {
+    VIP_REQUIRE(rgb_u8 && tile_tab && table && out, VIP_ERR_BAD_ARG, "%s: null pointer", name);
+    VIP_REQUIRE(n_tiles > 0 && n_tiles <= 65535 && maxH > 0 && maxW > 0 && outH > 0 && outW > 0 && c_out >= 3, VIP_ERR_BAD_ARG,
+                "%s: bad size", name);
+    VIP_REQUIRE(tile > 0 && tile <= maxH && tile <= maxW, VIP_ERR_BAD_ARG, "%s: tile %d does not fit a %d x %d slot", name, tile,
+                maxH, maxW);
+    VIP_REQUIRE(((uintptr_t)out & 15) == 0, VIP_ERR_ALIGNMENT, "%s: out is not 16-byte aligned", name);
+    hipLaunchKernelGGL(tile_resize_norm_kernel<T>, dim3((outW + 63) / 64, (outH + 3) / 4, n_tiles), dim3(256), 0, (hipStream_t)stream,
+                       rgb_u8, tile_tab, table, out, maxH, maxW, tile, outH, outW, c_out);
+    return vip_launch_status(name);
+}
+
+extern "C" int vip_tile_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles,
+                                                int maxH, int maxW, int tile, void* out, int outH, int outW, int c_out,
+                                                void* stream) {
+    return tile_resize_launch<f16>("vip_tile_resize_bicubic_norm_f16", rgb_u8, tile_tab, table, n_tiles, maxH, maxW, tile, (f16*)out,
+                                   outH, outW, c_out, stream);
+}
+
+extern "C" int vip_tile_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles,
+                                                int maxH, int maxW, int tile, float* out, int outH, int outW, int c_out,
+                                                void* stream) {
+    return tile_resize_launch<float>("vip_tile_resize_bicubic_norm_s32", rgb_u8, tile_tab, table, n_tiles, maxH, maxW, tile, out,
+                                     outH, outW, c_out, stream);
 }
 
 extern "C" int vip_tta_augment_f16(const void* x, void* y, const int32_t* flags, int B, int H, int W, int C,

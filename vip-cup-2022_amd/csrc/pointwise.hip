@@ -649,6 +649,38 @@ __global__ __launch_bounds__(256) void ensemble_mean_kernel(const float* __restr
     for (int m = 0; m < M; ++m) acc += s[(long)m * ld + i];
     out[i] = acc / (float)M;
 }
+
+// per (row r of scores, image i): mean, max and fraction above thr of the tile scores scores[r][seg[i] .. seg[i+1]).  One thread
+// per (row, image) walks its tiles in order with a sequential fp32 sum, so the result is a function of the values alone - the
+// launch shape (256 images per workgroup, grid.y = row) only decides who computes it.  An image without tiles gets NaN three times.
+__global__ __launch_bounds__(256) void tile_aggregate_kernel(const float* __restrict__ scores, const int* __restrict__ seg,
+                                                             float* __restrict__ out, int n, int rows, int T, float thr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int r = blockIdx.y;
+    if (i >= n) return;
+    int lo = seg[i], hi = seg[i + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > T ? T : hi;                                   // a broken table reads nothing outside the row
+    float mean = __builtin_nanf(""), mx = mean, frac = mean;
+    if (hi > lo) {
+        const float* s = scores + (long)r * T;
+        float acc = 0.f;
+        int above = 0;
+        mx = s[lo];
+        for (int t = lo; t < hi; ++t) {
+            const float v = s[t];
+            acc = __fadd_rn(acc, v);
+            mx = fmaxf(mx, v);
+            above += v > thr ? 1 : 0;
+        }
+        mean = __fdiv_rn(acc, (float)(hi - lo));
+        frac = __fdiv_rn((float)above, (float)(hi - lo));
+    }
+    const long plane = (long)rows * n;
+    out[(long)r * n + i] = mean;
+    out[plane + (long)r * n + i] = mx;
+    out[2 * plane + (long)r * n + i] = frac;
+}
 }  // namespace
 
 extern "C" int vip_head_prob_f32(const float* logits, float* prob, float* score, int B, int N, void* stream) {
@@ -700,4 +732,13 @@ extern "C" int vip_ensemble_mean_f32(const float* scores, float* mean, int M, in
     VIP_REQUIRE(M > 0 && n > 0 && ld >= n, VIP_ERR_BAD_ARG, "vip_ensemble_mean_f32: bad dimension");
     hipLaunchKernelGGL(ensemble_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, scores, mean, M, n, ld);
     return vip_launch_status("vip_ensemble_mean_f32");
+}
+
+extern "C" int vip_tile_aggregate_f32(const float* scores, const int32_t* seg, int n, int rows, int T, float thr, float* out,
+                                      void* stream) {
+    VIP_REQUIRE(scores && seg && out, VIP_ERR_BAD_ARG, "vip_tile_aggregate_f32: null pointer");
+    VIP_REQUIRE(n > 0 && rows > 0 && rows <= 65535 && T > 0, VIP_ERR_BAD_ARG, "vip_tile_aggregate_f32: bad dimension");
+    hipLaunchKernelGGL(tile_aggregate_kernel, dim3((n + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, scores, seg, out, n,
+                       rows, T, thr);
+    return vip_launch_status("vip_tile_aggregate_f32");
 }

@@ -571,6 +571,89 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     return table, summary
 
 
+def tile_batch(staged, members, tile: int = 200, stride: Optional[int] = None, max_tiles: int = 256, chunk: int = 128,
+               after_fork=None):
+    """One batch scored the plain way and as native-resolution tiles.  ``staged`` as for ``_score_batch``; it is decoded once.  Row 0 is
+    ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so bit for bit what a plain run returns.  Then every
+    image at least ``tile`` pixels high and wide is cut into ``tile x tile`` crops (``pipeline.tile_plan``) and each crop is scored as an
+    image of its own: at most ``chunk`` tiles at a time, in plan order, one gather launch per distinct ``input_key``
+    (``DecodedBatch.tiles``: identity for a member whose resolution is ``tile``, the training pipeline's bicubic for the others), then
+    ``MemberStreams.predict_all`` and ``ops.binary_score`` exactly as a plain pass makes them.
+    Returns ``(plain [M, n], tiles [M + 1, T], agg [3, M + 1, n], plan)`` (device tensors, fp32): ``tiles[m]`` = member m's score of
+    every tile, ``tiles[M]`` their ensemble mean (``ops.ensemble_mean``); ``agg`` = per row and image the mean / max / fraction ``> THR``
+    of its tiles (``ops.tile_aggregate``), NaN for an image without tiles."""
+    from . import ops, pipeline
+    chunk = pipeline._int_arg("chunk", chunk, 1, 65535)
+    if isinstance(staged, pipeline.DecodedBatch):
+        batch = staged
+    else:
+        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
+            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    plan = pipeline.tile_plan(batch.sizes_host, tile, stride, max_tiles)
+    plain = _score_batch(batch, members, None, after_fork=after_fork)
+    device = batch.rgb.device
+    M, T = len(members), int(plan.tab.shape[0])
+    tiles = torch.empty((M + 1, T), dtype=torch.float32, device=device)
+    seg_d = torch.from_numpy(plan.seg).to(device)
+    if T:
+        tab_d = torch.from_numpy(plan.tab).to(device)
+        for lo in range(0, T, chunk):
+            hi = min(lo + chunk, T)
+            inputs: Dict = {}
+            for spec, model in members:
+                k = input_key(spec, model)
+                if k not in inputs:
+                    inputs[k] = batch.tiles(tab_d, lo, hi, plan.tile, spec.input_hw, dtype=k[1])
+            preds = _MEMBER_STREAMS.predict_all(members, inputs)
+            for m, p in enumerate(preds):
+                ops.binary_score(p, out=tiles[m, lo:hi])             # main.py:113-114
+        ops.ensemble_mean(tiles[:M], out=tiles[M])
+    if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
+        ops.h2_check("tile_batch")                                   # no activation of a tile left the packed storage's range
+    return plain, tiles, ops.tile_aggregate(tiles, seg_d, THR), plan
+
+
+def tile_table(names: Sequence[str], plain: np.ndarray, agg: np.ndarray, plan, thr: float = THR, tile_agg: str = "mean"):
+    """The per-file report of a tile run; numpy only.  ``plain`` ``[M, n]`` and ``agg`` ``[3, M + 1, n]`` (``tile_batch``'s, over all images in
+    the order of ``names``), ``plan`` = ``pipeline.tile_plan`` of the same images (its ``sizes``, ``grids`` and ``thinned`` are read).
+    Returns ``(table, summary)``: ``table`` per sorted unique filename (duplicates averaged first, the rule of ``aggregate``) ``filename,
+    width, height, tiles, grid`` (``"<ny>x<nx>"``, ``"0x0"`` when not tiled), ``p`` / ``decision`` of the plain run, ``p_tiles_mean,
+    p_tiles_max, frac_tiles`` of the ensemble row (NaN when not tiled), ``decision_tiles`` (the ``tile_agg`` column ``> thr``; the plain
+    decision when not tiled) and ``agrees``; ``summary``: the counts of tiled and untiled files, the files that disagree and the
+    files whose grid ``max_tiles`` thinned."""
+    if tile_agg not in ("mean", "max"):
+        raise ValueError(f"tile_agg {tile_agg!r}: expected 'mean' or 'max'")
+    plain, agg = np.asarray(plain), np.asarray(agg)
+    n = len(names)
+    assert plain.ndim == 2 and plain.shape[1] == n and agg.shape == (3, plain.shape[0] + 1, n) and len(plan.sizes) == n, \
+        (plain.shape, agg.shape, n, len(plan.sizes))
+    uniq, p, dec = aggregate(names, plain, thr)
+    _, inv = np.unique(np.asarray(names), return_inverse=True)
+    first = np.full(len(uniq), -1, np.int64)
+    for i in range(n - 1, -1, -1):
+        first[inv[i]] = i                                            # size and grid of a file: those of its first row
+    cnts = np.bincount(inv, minlength=len(uniq)).astype(np.float64)
+    cols = []
+    for k in range(3):                                               # duplicates: the mean of their rows (NaN stays NaN)
+        sums = np.zeros(len(uniq), np.float64)
+        np.add.at(sums, inv, agg[k, -1].astype(np.float64))
+        cols.append((sums / cnts).astype(np.float32))
+    p_mean, p_max, frac = cols
+    grids = [plan.grids[i] for i in first]
+    tiled = np.array([g[0] * g[1] > 0 for g in grids], dtype=bool)
+    pick = p_mean if tile_agg == "mean" else p_max
+    dec_tiles = np.where(tiled, (np.nan_to_num(pick, nan=0.0) > thr).astype(np.float32), dec).astype(np.float32)
+    agrees = dec_tiles == dec
+    table = {"filename": uniq, "width": [plan.sizes[i][1] for i in first], "height": [plan.sizes[i][0] for i in first],
+             "tiles": [g[0] * g[1] for g in grids], "grid": [f"{g[0]}x{g[1]}" for g in grids], "p": p, "decision": dec,
+             "p_tiles_mean": p_mean, "p_tiles_max": p_max, "frac_tiles": frac, "decision_tiles": dec_tiles, "agrees": agrees}
+    summary = {"n_files": len(uniq), "threshold": float(thr), "tile_agg": tile_agg, "n_tiled": int(tiled.sum()),
+               "n_untiled": int((~tiled).sum()), "n_disagree": int((~agrees).sum()),
+               "disagreements": [u for u, a in zip(uniq, agrees) if not a],
+               "thinned": [u for u, i in zip(uniq, first) if plan.thinned[i]]}
+    return table, summary
+
+
 class Explanation:
     """What ``explain_batch`` returns: ``scores`` ``[M, n]`` (device; exactly what ``_score_batch`` returns), per member ``maps[m]``
     ``[n, gh, gw]`` fp32 (un-normalised, ``ops.cam``) and ``peaks[m]`` ``[n]`` - None for a member without a map, with the reason in

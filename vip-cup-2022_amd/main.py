@@ -4,6 +4,7 @@
                                      [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
                                      [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
                                      [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
+                                     [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
     python -m torch.distributed.run --nproc-per-node N ... vip-cup-2022_amd/main.py in.csv out.csv
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
@@ -26,6 +27,16 @@ it unsaved (``r<P>``) and, with ``--stress-jpeg``, re-saved at every quality (``
 challenge's test images were made.  The table is then ``filename, p, decision, p_<label>..., decision_<label>..., stable, flips_at, flips``
 over the labels ``q<Q>..., r<P>, r<P>_q<Q>...`` (``stable`` over all variants, ``flips_at`` over the 100 % rows as before, ``flips`` the
 ``;``-joined labels whose decision differs) and ``stress.json`` lists the labels under ``variants`` and keys its counts by label.
+``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
+it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
+last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
+crop goes through the members as a 200 x 200 file would (dataset/dataset.py:31-38 on the crop).  ``tiles.csv`` holds, per input file,
+``filename, width, height, tiles, grid`` (``<rows>x<columns>``; ``0x0`` for a file that is smaller than a tile, or exactly one tile),
+``p, decision`` (the plain run), ``p_tiles_mean, p_tiles_max, frac_tiles`` (the ensemble's tile scores: mean, max, fraction above the
+threshold), ``decision_tiles`` (``--tile-agg`` of them ``> 0.487``; the plain decision for an untiled file) and ``agrees``; ``tiles.json`` the
+settings, the counts of tiled and untiled files, the files that disagree and the files whose grid ``--tile-max`` thinned; and, with
+one rank, ``tiles.tiles.csv`` every tile: ``filename, ty, tx, y0, x0, p`` and one column per member.  The CSV outputs do not change with
+the flag.
 
 Checkpoints: ``<script dir>/ckpts/<name>/ckpt/*.h5`` (Keras weight / model files, as in the reference), else ``ckpt/saved_model.pb`` (a
 Keras SavedModel directory: its variables are read by ``tfbundle``), or ``*.npz`` (a flat dict of
@@ -137,6 +148,52 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         json.dump(summary, f, indent=1)
 
 
+def _tile_scorer(a, kept, kept_tiles):
+    """the ``batch_scorer`` of ``--tiles-out``: ``tile_batch`` on every batch; the plain rows are handed on unchanged, the per-image
+    aggregates ``[3, M + 1, n]`` plus two rows holding every image's height and width stay on this rank (``kept``, in batch order) until
+    the run's one extra collective, and so do the per-tile scores ``[M + 1, T]`` (``kept_tiles``), which are only written with one rank"""
+    import torch
+    from vipcup_amd import ensemble
+
+    def score(staged, sub, b0, b1, after_fork):
+        plain, tiles, agg, plan = ensemble.tile_batch(staged, sub, a.tile_size, a.tile_stride, a.tile_max, after_fork=after_fork)
+        hw = torch.tensor(plan.sizes, dtype=torch.float32, device=agg.device).t()          # [2, n]: exact in fp32 (sides < 2^24)
+        kept.append(torch.cat([agg, hw[:, None, :].expand(2, agg.shape[1], agg.shape[2])], dim=0))
+        kept_tiles.append(tiles)
+        return plain
+    return score
+
+
+def _write_tiles(a, names, members, per_model, rows, tiles, mode, world):
+    """``--tiles-out``: the per-file table as CSV, the summary and settings as JSON next to it and, with one rank, the long form"""
+    import pandas as pd
+    from vipcup_amd import ensemble, pipeline
+    sizes = [(int(h), int(w)) for h, w in zip(rows[3, 0], rows[4, 0])]
+    plan = pipeline.tile_plan(sizes, a.tile_size, a.tile_stride, a.tile_max)         # a function of the sizes alone: every rank's plans again
+    table, summary = ensemble.tile_table(names, per_model, rows[:3], plan, ensemble.THR, a.tile_agg)
+    table["agrees"] = table["agrees"].astype(np.int64)
+    pd.DataFrame(table).to_csv(a.tiles_out, index=False)
+    stem = os.path.splitext(a.tiles_out)[0]
+    long_form = stem + ".tiles.csv" if world == 1 else None
+    summary["settings"] = {"tile": plan.tile, "stride": plan.stride, "max_tiles": plan.max_tiles, "tile_agg": a.tile_agg,
+                           "threshold": ensemble.THR, "precision": mode, "batch_size": a.batch_size, "n_images": len(names),
+                           "members": [spec.name for spec, _ in members]}
+    summary["tiles_file"] = None if long_form is None else os.path.basename(long_form)
+    if long_form is None:
+        summary["tiles_file_skipped"] = f"the per-tile scores stay on the rank that computed them: written with one rank only (got {world})"
+    with open(stem + ".json", "w") as f:
+        json.dump(summary, f, indent=1)
+    if long_form is not None:
+        tab = plan.tab
+        assert tiles.shape == (len(members) + 1, tab.shape[0]), (tiles.shape, tab.shape)
+        nx = np.array([max(plan.grids[i][1], 1) for i in tab[:, 0]], dtype=np.int64)
+        k = np.arange(tab.shape[0]) - plan.seg[tab[:, 0]]
+        cols = {"filename": [names[i] for i in tab[:, 0]], "ty": k // nx, "tx": k % nx, "y0": tab[:, 1], "x0": tab[:, 2], "p": tiles[-1]}
+        for (spec, _), row in zip(members, tiles):
+            cols[spec.name] = row
+        pd.DataFrame(cols).to_csv(long_form, index=False)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input_csv")
@@ -185,7 +242,35 @@ def main(argv=None):
                          "flips_at, flips over the labels q<Q>, r<P>, r<P>_q<Q>")
     ap.add_argument("--stress-resize-filter", default="bicubic", choices=["bilinear", "bicubic", "lanczos"],
                     help="the antialiased filter of the simulated resize (what an image editor's resize offers)")
+    ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
+                    help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
+                         "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
+                         "p_tiles_mean, p_tiles_max, frac_tiles, decision_tiles, agrees; FILE.json next to it holds the settings and "
+                         "counts, FILE.tiles.csv (one rank only) every tile's scores")
+    ap.add_argument("--tile-size", type=int, default=200, help="side of a tile in pixels, 16..1024 (200: the challenge's own image size)")
+    ap.add_argument("--tile-stride", type=int, default=None, metavar="S",
+                    help="largest distance between neighbouring tiles, 1..tile size (default: the tile size, no more overlap than needed)")
+    ap.add_argument("--tile-max", type=int, default=256,
+                    help="most tiles per image, 1..4096; a larger grid is thinned to an evenly spaced sample (listed in FILE.json)")
+    ap.add_argument("--tile-agg", default="mean", choices=["mean", "max"],
+                    help="decision_tiles = this statistic of the ensemble's tile scores > 0.487")
     a = ap.parse_args(argv)
+    if a.tiles_out is not None:
+        if a.shard != "images" or a.tta > 1:
+            # as for the stress runs: the scores of one image would be spread over ranks or over augmented copies
+            raise SystemExit("vipcup_amd main: --tiles-out works with --shard images and --tta 1 only (got --shard "
+                             f"{a.shard} --tta {a.tta}): tile scoring under member sharding or TTA is not implemented")
+        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None:
+            raise SystemExit("vipcup_amd main: --tiles-out cannot be combined with --heatmaps or --stress-* (each replaces the batch scorer): "
+                             "run them one after the other")
+        if not 16 <= a.tile_size <= 1024:
+            raise SystemExit(f"vipcup_amd main: --tile-size {a.tile_size}: expected an integer in 16..1024")
+        if a.tile_stride is not None and not 1 <= a.tile_stride <= a.tile_size:
+            raise SystemExit(f"vipcup_amd main: --tile-stride {a.tile_stride}: expected an integer in 1..{a.tile_size} (the tile size)")
+        if not 1 <= a.tile_max <= 4096:
+            raise SystemExit(f"vipcup_amd main: --tile-max {a.tile_max}: expected an integer in 1..4096")
+    elif a.tile_size != 200 or a.tile_stride is not None or a.tile_max != 256 or a.tile_agg != "mean":
+        raise SystemExit("vipcup_amd main: --tile-size / --tile-stride / --tile-max / --tile-agg need --tiles-out FILE.csv")
     scales = None
     if a.stress_resize is not None:
         try:
@@ -327,6 +412,9 @@ def main(argv=None):
     if qualities is not None or scales is not None:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
                                       scales or (), a.stress_resize_filter)
+    tile_rows, tile_scores = [], []
+    if a.tiles_out is not None:
+        batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
 
     t0 = time.time()
     costs = None
@@ -341,6 +429,9 @@ def main(argv=None):
     if qualities is not None or scales is not None:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
         n_rows = len(ensemble.stress_labels(qualities or [], scales or ()))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
+    tiled = None
+    if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
+        tiled = ensemble.gather_stress_rows(tile_rows, 5, len(members) + 1, len(paths), rank, world, dist)
     if rank == 0:
         pd.DataFrame({"filename": uniq, "logit": decision}).to_csv(a.output_csv, index=False)  # main.py:143-145
         if a.scores_out:
@@ -351,6 +442,12 @@ def main(argv=None):
         if stressed is not None:
             _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or ())
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
+        if tiled is not None:
+            per_tile = None
+            if world == 1:
+                per_tile = torch.cat(tile_scores, dim=1).cpu().numpy() if tile_scores else np.zeros((len(members) + 1, 0), np.float32)
+            _write_tiles(a, names, members, per_model, tiled, per_tile, mode, world)
+            print(f"> TILE REPORT SAVED TO {a.tiles_out}")
         dt = time.time() - t0
         print(f"> FINAL PREDICTION SAVED TO {a.output_csv}")
         print(f"> TIME TO INFER: {dt / 60:.2f} min ({len(paths) / dt:.1f} images/s on {world} GPU(s))")  # main.py:231-235

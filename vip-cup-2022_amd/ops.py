@@ -1068,11 +1068,28 @@ def binary_score(p: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     return out
 
 
-def ensemble_mean(scores: torch.Tensor) -> torch.Tensor:
-    """fp32 ``[M, n]`` member scores -> ``[n]`` ensemble mean (main.py:142-143)."""
+def ensemble_mean(scores: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 ``[M, n]`` member scores -> ``[n]`` ensemble mean (main.py:142-143); ``out``: a contiguous fp32 ``[n]`` row to write it to."""
     assert scores.dtype == torch.float32 and scores.is_cuda and scores.dim() == 2 and scores.stride(1) == 1
-    out = torch.empty((scores.shape[1],), dtype=torch.float32, device=scores.device)
+    if out is None:
+        out = torch.empty((scores.shape[1],), dtype=torch.float32, device=scores.device)
+    assert out.dtype == torch.float32 and out.shape == (scores.shape[1],) and out.is_contiguous() and out.device == scores.device
     _launch("vip_ensemble_mean_f32", _p(scores), _p(out), scores.shape[0], scores.shape[1], scores.stride(0))
+    return out
+
+
+def tile_aggregate(scores: torch.Tensor, seg: torch.Tensor, thr: float) -> torch.Tensor:
+    """fp32 ``[R, T]`` tile scores and ``seg`` int32 ``[n + 1]`` (image i owns columns ``seg[i]:seg[i + 1]``) -> fp32 ``[3, R, n]``: per row
+    and image the mean of its tile scores (a sequential fp32 sum in tile order), their max and the fraction ``> thr``; NaN for an
+    image without tiles (``vip_tile_aggregate_f32``)."""
+    assert scores.dtype == torch.float32 and scores.is_cuda and scores.dim() == 2 and scores.is_contiguous()
+    assert seg.dtype == torch.int32 and seg.dim() == 1 and seg.is_contiguous() and seg.device == scores.device and seg.numel() >= 2
+    R, T = scores.shape
+    n = seg.numel() - 1
+    if T == 0:                                           # no image of the batch is tiled: nothing to read
+        return torch.full((3, R, n), float("nan"), dtype=torch.float32, device=scores.device)
+    out = torch.empty((3, R, n), dtype=torch.float32, device=scores.device)
+    _launch("vip_tile_aggregate_f32", _p(scores), _p(seg), n, R, T, C.c_float(float(thr)), _p(out))
     return out
 
 

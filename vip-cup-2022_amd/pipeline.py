@@ -84,6 +84,102 @@ class DecodedBatch:
         _launch(fn, _p(self.rgb), _p(self.sizes), _p(bicubic_table(self.rgb.device)), n, maxH, maxW, _p(out), out_h, out_w, c_out)
         return out
 
+    def tiles(self, tab_d: torch.Tensor, lo: int, hi: int, tile: int, out_hw: int, c_out: int = 8,
+              dtype: torch.dtype = torch.float16) -> torch.Tensor:
+        """Tiles ``tab_d[lo:hi]`` of this batch (``tab_d``: the device copy of ``tile_plan``'s ``tab``, int32 ``[T, 4]``) as network
+        inputs ``[hi - lo, out_hw, out_hw, c_out]``: every ``tile x tile`` crop treated as an image of its own and sent through
+        dataset/dataset.py:31-38 - exactly the values ``DecodedBatch(crop).resized(out_hw, out_hw, c_out, dtype)`` gives, the bicubic
+        taps clamped at the tile's edge.  One launch (``vip_tile_resize_bicubic_norm_*``), no intermediate uint8 batch."""
+        n, maxH, maxW, _ = self.rgb.shape
+        from . import ops
+        if dtype == ops.PACKED:
+            return ops.pack_h2(self.tiles(tab_d, lo, hi, tile, out_hw, c_out, torch.float32))
+        if tab_d.dtype != torch.int32 or tab_d.dim() != 2 or tab_d.shape[1] != 4 or not tab_d.is_contiguous() or \
+                tab_d.device != self.rgb.device:
+            raise ValueError(f"tiles: tab_d must be a contiguous int32 [T, 4] tensor on {self.rgb.device}, got {tab_d.dtype} "
+                             f"{tuple(tab_d.shape)} on {tab_d.device}")
+        if not 0 <= lo < hi <= tab_d.shape[0]:
+            raise ValueError(f"tiles: rows {lo}:{hi} of a table of {tab_d.shape[0]}")
+        if not 1 <= int(tile) <= min(maxH, maxW):
+            raise ValueError(f"tiles: tile {tile} does not fit the batch's {maxH} x {maxW} slots")
+        src = self.rgb if self.rgb.is_contiguous() else self.rgb.contiguous()
+        out = torch.empty((hi - lo, out_hw, out_hw, c_out), dtype=dtype, device=self.rgb.device)
+        fn = {torch.float16: "vip_tile_resize_bicubic_norm_f16", torch.float32: "vip_tile_resize_bicubic_norm_s32"}[dtype]
+        _launch(fn, _p(src), _p(tab_d[lo:hi]), _p(bicubic_table(self.rgb.device)), hi - lo, maxH, maxW, int(tile), _p(out), out_hw, out_hw,
+                c_out)
+        return out
+
+
+def _int_arg(name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name} {v!r}: expected an integer in {lo}..{hi}")
+    return int(v)
+
+
+def _tile_args(tile, stride, max_tiles) -> Tuple[int, int, int]:
+    tile = _int_arg("tile", tile, 16, 1024)
+    stride = tile if stride is None else _int_arg("stride", stride, 1, tile)
+    return tile, stride, _int_arg("max_tiles", max_tiles, 1, 4096)
+
+
+def _tile_positions(length: int, tile: int, n: int) -> List[int]:
+    """``n`` tile origins along an axis of ``length`` >= ``tile``: the first at 0, the last at ``length - tile``, the others spaced evenly
+    between them (rounded to the nearest pixel, halves up) - so whatever overlap or gap there is, is spread over the whole axis"""
+    if n <= 1:
+        return [0]
+    return [(2 * k * (length - tile) + (n - 1)) // (2 * (n - 1)) for k in range(n)]
+
+
+def tile_grid(h: int, w: int, tile: int = 200, stride: Optional[int] = None, max_tiles: int = 256) -> Tuple[List[int], List[int]]:
+    """Where the ``tile x tile`` crops of an ``h x w`` image start: ``(ys, xs)``, the grid is their product.  Per axis of length L
+    ``ceil((L - tile) / stride) + 1`` tiles (``stride`` defaults to ``tile``), placed by ``_tile_positions``: the image is covered edge to
+    edge and neighbours never lie further apart than ``stride``.  While the grid holds more than ``max_tiles`` the larger count (rows on a
+    tie) drops by one and that axis is laid out again: the grid is then an evenly spaced sample of the image with gaps.  An image
+    smaller than a tile in either direction has no tiles: ``([], [])``.  Pure host arithmetic."""
+    tile, stride, max_tiles = _tile_args(tile, stride, max_tiles)
+    h, w = int(h), int(w)
+    if h < tile or w < tile:
+        return [], []
+    ny, nx = -(-(h - tile) // stride) + 1, -(-(w - tile) // stride) + 1
+    while ny * nx > max_tiles:
+        if ny >= nx:
+            ny -= 1
+        else:
+            nx -= 1
+    return _tile_positions(h, tile, ny), _tile_positions(w, tile, nx)
+
+
+class TilePlan:
+    """What ``tile_plan`` returns; unpacks as ``tab, seg = tile_plan(...)``.  ``tab`` int32 ``[T, 4]`` = (image, y0, x0, 0) in image
+    order, then row-major; ``seg`` int32 ``[n + 1]``: the tiles of image i are ``tab[seg[i]:seg[i + 1]]``.  Per image also ``sizes`` (h, w),
+    ``grids`` (ny, nx) - (0, 0) for an image that is not tiled - and ``thinned`` (``max_tiles`` removed rows or columns: the grid has
+    gaps, or less overlap than ``stride`` asks for); and the settings ``tile``, ``stride``, ``max_tiles``."""
+
+    def __init__(self, tab, seg, sizes, grids, thinned, tile, stride, max_tiles):
+        self.tab, self.seg, self.sizes, self.grids, self.thinned = tab, seg, sizes, grids, thinned
+        self.tile, self.stride, self.max_tiles = tile, stride, max_tiles
+
+    def __iter__(self):
+        return iter((self.tab, self.seg))
+
+
+def tile_plan(sizes_host: Sequence[Tuple[int, int]], tile: int = 200, stride: Optional[int] = None, max_tiles: int = 256) -> TilePlan:
+    """The tiles of a batch of images of ``sizes_host`` = [(h, w)]: ``tile_grid`` per image, ``max_tiles`` per image.  An image that IS one
+    tile (``tile x tile`` exactly: the challenge's own 200 x 200 files) is left out like one that is too small - its only tile would be
+    the plain input again.  A pure function of its arguments: every rank derives the same plan from the same sizes."""
+    tile, stride, max_tiles = _tile_args(tile, stride, max_tiles)
+    rows: List[Tuple[int, int, int, int]] = []
+    seg, grids, thinned = [0], [], []
+    for i, (h, w) in enumerate(sizes_host):
+        ys, xs = ([], []) if (int(h), int(w)) == (tile, tile) else tile_grid(h, w, tile, stride, max_tiles)
+        rows += [(i, y, x, 0) for y in ys for x in xs]
+        seg.append(len(rows))
+        grids.append((len(ys), len(xs)))
+        thinned.append(bool(ys) and len(ys) * len(xs) < (-(-(int(h) - tile) // stride) + 1) * (-(-(int(w) - tile) // stride) + 1))
+    tab = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+    return TilePlan(tab, np.asarray(seg, dtype=np.int32), [(int(h), int(w)) for h, w in sizes_host], grids, thinned, tile, stride,
+                    max_tiles)
+
 
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
