@@ -472,6 +472,24 @@ int vip_tile_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* tile_
 int vip_tile_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t* tile_tab, const float* table, int n_tiles, int maxH,
                                      int maxW, int tile, float* out, int outH, int outW, int c_out, void* stream);
 
+/* Occlusion variants (main.py --occlusion): variant v of occ_tab int32 [V][8] = (image, y0, x0, y1, x1, 0, 0, 0) is that image with
+ * the pixels y0 <= y < y1, x0 <= x < x1 replaced by fill_u8[image] (uint8 [n][4] = r, g, b, 0; 4-byte aligned), sent through
+ * dataset/dataset.py:31-38.  out [V][outH][outW][c_out] holds exactly what vip_resize_bicubic_norm_f16 / _s32 gives for an occluded
+ * uint8 copy of the image: the same taps on the image's own size, the same order of operations, the identity branch when
+ * h == outH && w == outW.  The replacement is applied per tap as the byte is read: one launch per call, V <= 65535, no intermediate
+ * uint8 batch, out 16-byte aligned.  n = the number of images in rgb_u8 / sizes_hw / fill_u8: a row whose image index is not in
+ * 0 .. n-1 or whose rectangle does not lie inside its image (0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w) yields a zero output and
+ * reads nothing.  _f16: fp16 output; _s32: the unrounded fp32 values (STRICT path; packed storage = vip_pack_h2 of them).
+ * vip_image_mean_u8: fill_u8[i] = the mean colour of image i over its own h x w pixels (the slot's padding is never read), per
+ * channel (sum + h w / 2) / (h w) in 64-bit integers - exact, halves up; byte 3 is 0. */
+int vip_image_mean_u8(const uint8_t* rgb_u8, const int32_t* sizes_hw, int n, int maxH, int maxW, uint8_t* fill_u8, void* stream);
+int vip_occlude_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* sizes_hw, const uint8_t* fill_u8, const int32_t* occ_tab,
+                                        const float* table, int n, int V, int maxH, int maxW, void* out, int outH, int outW, int c_out,
+                                        void* stream);
+int vip_occlude_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t* sizes_hw, const uint8_t* fill_u8, const int32_t* occ_tab,
+                                        const float* table, int n, int V, int maxH, int maxW, float* out, int outH, int outW, int c_out,
+                                        void* stream);
+
 /* TTA ops (dataset/augment.py:115-120,142-146) on f16 NHWC batches: flags int32 [B]: bit0 horizontal flip,
  * bit1 vertical flip, bit2 RGB->gray->RGB (0.2989, 0.5870, 0.1140). */
 int vip_tta_augment_f16(const void* x, void* y, const int32_t* flags, int B, int H, int W, int C,
@@ -517,6 +535,22 @@ int vip_ensemble_mean_f32(const float* scores, float* mean, int M, int n, long l
  * summed sequentially in tile order: independent of the launch shape), their max, and the fraction of tiles > thr.  An image
  * without tiles gets NaN in all three. */
 int vip_tile_aggregate_f32(const float* scores, const int32_t* seg, int n, int rows, int T, float thr, float* out, void* stream);
+/* Occlusion report: scores f32 [rows][V] (rows = members + 1, the last row the per-variant ensemble mean), plain f32 [rows][n] the
+ * scores of the images as they are, seg int32 [n + 1] with the variants of image i at columns seg[i] .. seg[i+1]-1: the
+ * (G - K + 1)^2 windows of K x K cells on its G x G grid, row-major (2 <= G <= 32, 1 <= K <= G).  delta = plain - score.
+ * cells f32 [rows][n][G][G]: per cell the mean of delta over the windows that cover it (fp32, summed sequentially in variant order,
+ * one division: independent of the launch shape).  stats f32 [rows][n][4] = (max delta, min delta, index of the first variant with
+ * the max delta, number of variants whose (score > thr) differs from (plain > thr)).  An image without variants (seg[i] ==
+ * seg[i+1]) gets NaN in all of them.  seg is device memory, so a count that is neither 0 nor (G - K + 1)^2 cannot be refused here:
+ * such an image reads nothing and gets NaN too; the caller checks its host copy of seg (ops.occlusion_cells raises). */
+int vip_occlusion_cells_f32(const float* scores, const float* plain, const int32_t* seg, int n, int rows, int V, int G, int K, float thr,
+                            float* cells, float* stats, void* stream);
+/* Full-size map of one row: cells_row f32 [n][G][G], sizes_hw int32 [n][2] -> out [n][maxH][maxW]: pixel (y, x) of image i takes
+ * the value of the cell whose range [(g L) / G, ((g + 1) L) / G) holds it on each axis - the occluder's own edges; 0 outside the
+ * image.  out_u8 = 0: f32, the values as they are.  out_u8 = 1: uint8 round(255 (0.5 + 0.5 v / peak)), peak = max |cell| of the
+ * image; 128 (= no effect) everywhere in an image whose peak is 0 or whose cells are NaN - a map vip_cam_overlay_u8 blends. */
+int vip_occlusion_map(const float* cells_row, const int32_t* sizes_hw, int n, int maxH, int maxW, int G, void* out, int out_u8,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * STRICT precision path, packed storage (entry points ending in _h2) - the default of `--precision strict` since round 4.

@@ -102,6 +102,11 @@ SIGNATURES = {
     "vip_tile_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tile_resize_bicubic_norm_s32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tile_aggregate_f32": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "vip_image_mean_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "vip_occlude_resize_bicubic_norm_f16": (_i, [_vp] * 5 + [_i] * 4 + [_vp, _i, _i, _i, _vp]),
+    "vip_occlude_resize_bicubic_norm_s32": (_i, [_vp] * 5 + [_i] * 4 + [_vp, _i, _i, _i, _vp]),
+    "vip_occlusion_cells_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "vip_occlusion_map": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "vip_tta_augment_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "vip_vit_tokens_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     # STRICT precision path (fp32 storage, fp32 arithmetic): csrc/strict_conv.hip, csrc/strict_ops.hip

@@ -354,6 +354,117 @@ __global__ __launch_bounds__(256) void tile_resize_norm_kernel(const uint8_t* __
     store_pixel(o, res, c_out);
 }
 
+// ---- occlusion variants (main.py --occlusion): variant v = image tab[v].image with the pixels y0 <= y < y1, x0 <= x < x1 replaced
+// by that image's fill colour, sent through resize_norm_kernel's arithmetic expression for expression (same taps on the image's own
+// size, horizontal pass first, the same __fmul_rn / __fadd_rn chains, __fdiv_rn by 255, the identity branch when the sizes are equal):
+// the values are bit for bit those of resize_norm_kernel on an occluded uint8 copy.  The replacement happens per tap, at the moment
+// the byte is read - there is no such copy.  One thread = one output pixel, one vector store per pixel; grid.z = variant.  The
+// source bytes are read as bytes, as the tile kernel above reads them (same access pattern, measured there).
+struct OccRect {
+    int y0, x0, y1, x1;
+    uint32_t fill;                                  // r | g << 8 | b << 16
+};
+__device__ __forceinline__ float occ_px(const uint8_t* __restrict__ img, long pitch, int y, int x, int c, const OccRect& r) {
+    if (y >= r.y0 && y < r.y1 && x >= r.x0 && x < r.x1) return (float)((r.fill >> (8 * c)) & 255u);
+    return (float)img[(long)y * pitch + (long)x * 3 + c];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void occlude_resize_norm_kernel(const uint8_t* __restrict__ rgb, const int* __restrict__ sizes,
+                                                                  const uint32_t* __restrict__ fill, const int* __restrict__ tab,
+                                                                  const float* __restrict__ table, T* __restrict__ out, int n_images,
+                                                                  int maxH, int maxW, int outH, int outW, int c_out) {
+    const int v = blockIdx.z;
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (ox >= outW || oy >= outH) return;
+    const int n = tab[8 * v];
+    OccRect r;
+    r.y0 = tab[8 * v + 1]; r.x0 = tab[8 * v + 2]; r.y1 = tab[8 * v + 3]; r.x1 = tab[8 * v + 4];
+    T* o = out + (((long)v * outH + oy) * outW + ox) * c_out;
+    int h = 0, w = 0;
+    if (n >= 0 && n < n_images) {
+        h = sizes[2 * n];
+        w = sizes[2 * n + 1];
+    }
+    if (h < 1 || w < 1 || h > maxH || w > maxW || r.y0 < 0 || r.x0 < 0 || r.y0 > r.y1 || r.x0 > r.x1 || r.y1 > h || r.x1 > w) {
+        // a table row whose image or rectangle does not lie inside its image (not one of pipeline.occlusion_plan's): nothing is
+        // read, the variant is 0
+        const float zero[3] = {0.f, 0.f, 0.f};
+        store_pixel(o, zero, c_out);
+        return;
+    }
+    r.fill = fill[n];
+    const long pitch = (long)maxW * 3;
+    const uint8_t* img = rgb + (long)n * maxH * pitch;
+    if (h == outH && w == outW) {
+        // the identity branch of resize_norm_kernel: taps (0, 1, 0, 0) in both axes
+        const float res[3] = {__fdiv_rn(occ_px(img, pitch, oy, ox, 0, r), 255.f), __fdiv_rn(occ_px(img, pitch, oy, ox, 1, r), 255.f),
+                              __fdiv_rn(occ_px(img, pitch, oy, ox, 2, r), 255.f)};
+        store_pixel(o, res, c_out);
+        return;
+    }
+    const Taps ty = bicubic_taps(oy, h, __fdiv_rn((float)h, (float)outH), table);
+    const Taps tx = bicubic_taps(ox, w, __fdiv_rn((float)w, (float)outW), table);
+    float res[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float rowv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = ty.idx[k];
+            float a = __fmul_rn(occ_px(img, pitch, y, tx.idx[0], c, r), tx.w[0]);
+            a = __fadd_rn(a, __fmul_rn(occ_px(img, pitch, y, tx.idx[1], c, r), tx.w[1]));
+            a = __fadd_rn(a, __fmul_rn(occ_px(img, pitch, y, tx.idx[2], c, r), tx.w[2]));
+            a = __fadd_rn(a, __fmul_rn(occ_px(img, pitch, y, tx.idx[3], c, r), tx.w[3]));
+            rowv[k] = a;
+        }
+        float a = __fmul_rn(rowv[0], ty.w[0]);
+        a = __fadd_rn(a, __fmul_rn(rowv[1], ty.w[1]));
+        a = __fadd_rn(a, __fmul_rn(rowv[2], ty.w[2]));
+        a = __fadd_rn(a, __fmul_rn(rowv[3], ty.w[3]));
+        res[c] = __fdiv_rn(a, 255.f);
+    }
+    store_pixel(o, res, c_out);
+}
+
+// the mean colour of every image over its own h x w pixels (the slot's padding is never read): one workgroup per image, 64-bit
+// integer sums (64 Mi pixels x 255 does not fit in 32 bits), reduced through LDS; (sum + h w / 2) / (h w) in integers
+__global__ __launch_bounds__(256) void image_mean_kernel(const uint8_t* __restrict__ rgb, const int* __restrict__ sizes,
+                                                         uint32_t* __restrict__ fill, int maxH, int maxW) {
+    __shared__ unsigned long long part[3][256];
+    const int n = blockIdx.x;
+    int h = sizes[2 * n], w = sizes[2 * n + 1];
+    h = h < 0 ? 0 : (h > maxH ? maxH : h);
+    w = w < 0 ? 0 : (w > maxW ? maxW : w);
+    const uint8_t* img = rgb + (long)n * maxH * maxW * 3;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
+    for (int y = threadIdx.x >> 6; y < h; y += 4) {
+        const uint8_t* row = img + (long)y * maxW * 3;
+        for (int x = threadIdx.x & 63; x < w; x += 64) {
+            s0 += row[x * 3];
+            s1 += row[x * 3 + 1];
+            s2 += row[x * 3 + 2];
+        }
+    }
+    part[0][threadIdx.x] = s0;
+    part[1][threadIdx.x] = s1;
+    part[2][threadIdx.x] = s2;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step)
+            for (int c = 0; c < 3; ++c) part[c][threadIdx.x] += part[c][threadIdx.x + step];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const unsigned long long hw = (unsigned long long)h * (unsigned long long)w;
+        uint32_t v = 0;
+        if (hw)
+            for (int c = 0; c < 3; ++c) v |= (uint32_t)((part[c][0] + hw / 2) / hw) << (8 * c);
+        fill[n] = v;
+    }
+}
+
 // TTA: flags bit0 hflip, bit1 vflip, bit2 gray (tf.image.rgb_to_grayscale weights 0.2989/0.5870/0.1140)
 template <typename T>
 __global__ __launch_bounds__(256) void tta_kernel(const T* __restrict__ x, T* __restrict__ y,
@@ -453,6 +564,43 @@ extern "C" int vip_tile_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int
                                                 void* stream) {
     return tile_resize_launch<float>("vip_tile_resize_bicubic_norm_s32", rgb_u8, tile_tab, table, n_tiles, maxH, maxW, tile, out,
                                      outH, outW, c_out, stream);
+}
+
+extern "C" int vip_image_mean_u8(const uint8_t* rgb_u8, const int32_t* sizes_hw, int n, int maxH, int maxW, uint8_t* fill_u8,
+                                 void* stream) {
+    VIP_REQUIRE(rgb_u8 && sizes_hw && fill_u8, VIP_ERR_BAD_ARG, "vip_image_mean_u8: null pointer");
+    VIP_REQUIRE(n > 0 && maxH > 0 && maxW > 0, VIP_ERR_BAD_ARG, "vip_image_mean_u8: bad size");
+    VIP_REQUIRE(((uintptr_t)fill_u8 & 3) == 0, VIP_ERR_ALIGNMENT, "vip_image_mean_u8: fill_u8 is not 4-byte aligned");
+    hipLaunchKernelGGL(image_mean_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, rgb_u8, sizes_hw, (uint32_t*)fill_u8, maxH, maxW);
+    return vip_launch_status("vip_image_mean_u8");
+}
+
+template <typename T>
+static int occlude_resize_launch(const char* name, const uint8_t* rgb_u8, const int32_t* sizes_hw, const uint8_t* fill_u8,
+                                 const int32_t* occ_tab, const float* table, int n, int V, int maxH, int maxW, T* out, int outH, int outW,
+                                 int c_out, void* stream) {
+    VIP_REQUIRE(rgb_u8 && sizes_hw && fill_u8 && occ_tab && table && out, VIP_ERR_BAD_ARG, "%s: null pointer", name);
+    VIP_REQUIRE(n > 0 && V > 0 && V <= 65535 && maxH > 0 && maxW > 0 && outH > 0 && outW > 0 && c_out >= 3, VIP_ERR_BAD_ARG,
+                "%s: bad size", name);
+    VIP_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)fill_u8 & 3) == 0, VIP_ERR_ALIGNMENT,
+                "%s: out is not 16-byte aligned or fill_u8 not 4-byte aligned", name);
+    hipLaunchKernelGGL(occlude_resize_norm_kernel<T>, dim3((outW + 63) / 64, (outH + 3) / 4, V), dim3(256), 0, (hipStream_t)stream,
+                       rgb_u8, sizes_hw, (const uint32_t*)fill_u8, occ_tab, table, out, n, maxH, maxW, outH, outW, c_out);
+    return vip_launch_status(name);
+}
+
+extern "C" int vip_occlude_resize_bicubic_norm_f16(const uint8_t* rgb_u8, const int32_t* sizes_hw, const uint8_t* fill_u8,
+                                                   const int32_t* occ_tab, const float* table, int n, int V, int maxH, int maxW,
+                                                   void* out, int outH, int outW, int c_out, void* stream) {
+    return occlude_resize_launch<f16>("vip_occlude_resize_bicubic_norm_f16", rgb_u8, sizes_hw, fill_u8, occ_tab, table, n, V, maxH, maxW,
+                                      (f16*)out, outH, outW, c_out, stream);
+}
+
+extern "C" int vip_occlude_resize_bicubic_norm_s32(const uint8_t* rgb_u8, const int32_t* sizes_hw, const uint8_t* fill_u8,
+                                                   const int32_t* occ_tab, const float* table, int n, int V, int maxH, int maxW,
+                                                   float* out, int outH, int outW, int c_out, void* stream) {
+    return occlude_resize_launch<float>("vip_occlude_resize_bicubic_norm_s32", rgb_u8, sizes_hw, fill_u8, occ_tab, table, n, V, maxH,
+                                        maxW, out, outH, outW, c_out, stream);
 }
 
 extern "C" int vip_tta_augment_f16(const void* x, void* y, const int32_t* flags, int B, int H, int W, int C,

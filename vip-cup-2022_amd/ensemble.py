@@ -654,6 +654,101 @@ def tile_table(names: Sequence[str], plain: np.ndarray, agg: np.ndarray, plan, t
     return table, summary
 
 
+OCCLUSION_FILLS = ("mean", "gray")
+
+
+def occlusion_batch(staged, members, grid: int = 8, window: int = 2, fill: str = "mean", chunk: int = 128, after_fork=None):
+    """One batch scored the plain way and with every window of an occlusion grid hidden.  ``staged`` as for ``_score_batch``; it is decoded
+    once.  Row 0 is ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so bit for bit what a plain run returns.
+    Then every image at least ``grid`` pixels high and wide is scored once per window of ``pipeline.occlusion_plan`` with the window's
+    pixels replaced by ``fill`` - ``"mean"``: the image's own mean colour (``DecodedBatch.mean_colour``), ``"gray"``: (128, 128, 128) - at
+    most ``chunk`` variants at a time, in plan order, one gather launch per distinct ``input_key`` (``DecodedBatch.occluded``: the member's
+    ordinary input path on the occluded pixels), then ``MemberStreams.predict_all`` and ``ops.binary_score`` exactly as a plain pass makes
+    them.  No gradients and no knowledge of a member's head: every member has a map, ViTs included.
+    Returns ``(plain [M, n], variants [M + 1, V], cells [M + 1, n, G, G], stats [M + 1, n, 4], plan)`` (device tensors, fp32):
+    ``variants[m]`` = member m's score of every variant, ``variants[M]`` their ensemble mean (``ops.ensemble_mean``); ``cells`` and ``stats``
+    (``ops.occlusion_cells`` at ``THR``) are taken on delta = plain - variant per row, row M against the ensemble mean of ``plain``:
+    positive where hiding the region lowers the synthetic score.  NaN for an image without variants."""
+    from . import ops, pipeline
+    chunk = pipeline._int_arg("chunk", chunk, 1, 65535)
+    if fill not in OCCLUSION_FILLS:
+        raise ValueError(f"fill {fill!r}: expected one of {', '.join(OCCLUSION_FILLS)}")
+    if isinstance(staged, pipeline.DecodedBatch):
+        batch = staged
+    else:
+        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
+            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    plan = pipeline.occlusion_plan(batch.sizes_host, grid, window)
+    plain = _score_batch(batch, members, None, after_fork=after_fork)
+    device = batch.rgb.device
+    M, n, V = len(members), len(batch), int(plan.tab.shape[0])
+    variants = torch.empty((M + 1, V), dtype=torch.float32, device=device)
+    if V:
+        tab_d = torch.from_numpy(plan.tab).to(device)
+        if fill == "mean":
+            fill_d = batch.mean_colour()
+        else:
+            fill_d = torch.tensor([[128, 128, 128, 0]] * n, dtype=torch.uint8, device=device)
+        for lo in range(0, V, chunk):
+            hi = min(lo + chunk, V)
+            inputs: Dict = {}
+            for spec, model in members:
+                k = input_key(spec, model)
+                if k not in inputs:
+                    inputs[k] = batch.occluded(tab_d, lo, hi, fill_d, spec.input_hw, spec.input_hw, dtype=k[1])
+            preds = _MEMBER_STREAMS.predict_all(members, inputs)
+            for m, p in enumerate(preds):
+                ops.binary_score(p, out=variants[m, lo:hi])          # main.py:113-114
+        ops.ensemble_mean(variants[:M], out=variants[M])
+    if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
+        ops.h2_check("occlusion_batch")                              # no activation of a variant left the packed storage's range
+    rows = torch.empty((M + 1, n), dtype=torch.float32, device=device)
+    rows[:M] = plain
+    ops.ensemble_mean(plain, out=rows[M])
+    cells, stats = ops.occlusion_cells(variants, rows, plan.seg, plan.grid, plan.window, THR)
+    return plain, variants, cells, stats, plan
+
+
+def occlusion_table(names: Sequence[str], plain: np.ndarray, stats: np.ndarray, plan, thr: float = THR):
+    """The per-file report of an occlusion run; numpy only.  ``plain`` ``[M, n]`` and ``stats`` ``[M + 1, n, 4]`` (``occlusion_batch``'s, over all
+    images in the order of ``names``; the ensemble row is read), ``plan`` = ``pipeline.occlusion_plan`` of the same images (its ``sizes``,
+    ``seg``, ``grid`` and ``window`` are read).  Returns ``(table, summary)``: ``table`` per sorted unique filename (duplicates averaged first,
+    the rule of ``aggregate``; size, variant count and ``cell_max`` are those of a file's first row) ``filename, width, height, variants``
+    (0 for a skipped file), ``p`` / ``decision`` of the plain run, ``delta_max, delta_min`` (the largest and smallest delta-p of the ensemble
+    over the file's variants), ``cell_max`` (``"gy,gx"``: the first cell of the window with the largest delta; empty when skipped) and
+    ``flips`` (variants whose decision differs from the plain one) - NaN for a skipped file; ``summary``: the counts, the skipped files
+    and the files with ``flips > 0``."""
+    plain, stats = np.asarray(plain), np.asarray(stats)
+    n = len(names)
+    assert plain.ndim == 2 and plain.shape[1] == n and stats.shape == (plain.shape[0] + 1, n, 4) and len(plan.sizes) == n, \
+        (plain.shape, stats.shape, n, len(plan.sizes))
+    uniq, p, dec = aggregate(names, plain, thr)
+    _, inv = np.unique(np.asarray(names), return_inverse=True)
+    first = np.full(len(uniq), -1, np.int64)
+    for i in range(n - 1, -1, -1):
+        first[inv[i]] = i
+    cnts = np.bincount(inv, minlength=len(uniq)).astype(np.float64)
+    cols = []
+    for k in (0, 1, 3):                                              # duplicates: the mean of their rows (NaN stays NaN)
+        sums = np.zeros(len(uniq), np.float64)
+        np.add.at(sums, inv, stats[-1, :, k].astype(np.float64))
+        cols.append((sums / cnts).astype(np.float32))
+    d_max, d_min, flips = cols
+    per_axis = plan.grid - plan.window + 1
+    variants = [int(plan.seg[i + 1] - plan.seg[i]) for i in first]
+    cell_max = []
+    for i, v in zip(first, variants):
+        at = stats[-1, i, 2]
+        cell_max.append("" if v == 0 or np.isnan(at) else f"{int(at) // per_axis},{int(at) % per_axis}")
+    table = {"filename": uniq, "width": [plan.sizes[i][1] for i in first], "height": [plan.sizes[i][0] for i in first],
+             "variants": variants, "p": p, "decision": dec, "delta_max": d_max, "delta_min": d_min, "cell_max": cell_max, "flips": flips}
+    skipped = [u for u, v in zip(uniq, variants) if v == 0]
+    summary = {"n_files": len(uniq), "threshold": float(thr), "grid": plan.grid, "window": plan.window,
+               "variants_per_image": per_axis * per_axis, "n_explained": len(uniq) - len(skipped), "n_skipped": len(skipped),
+               "skipped": skipped, "flipped": [u for u, f in zip(uniq, flips) if f > 0]}
+    return table, summary
+
+
 class Explanation:
     """What ``explain_batch`` returns: ``scores`` ``[M, n]`` (device; exactly what ``_score_batch`` returns), per member ``maps[m]``
     ``[n, gh, gw]`` fp32 (un-normalised, ``ops.cam``) and ``peaks[m]`` ``[n]`` - None for a member without a map, with the reason in

@@ -5,6 +5,8 @@
                                      [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
                                      [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
+                                     [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
+                                                      [--occlusion-format npy|png] [--occlusion-members]]
     python -m torch.distributed.run --nproc-per-node N ... vip-cup-2022_amd/main.py in.csv out.csv
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
@@ -37,6 +39,19 @@ threshold), ``decision_tiles`` (``--tile-agg`` of them ``> 0.487``; the plain de
 settings, the counts of tiled and untiled files, the files that disagree and the files whose grid ``--tile-max`` thinned; and, with
 one rank, ``tiles.tiles.csv`` every tile: ``filename, ty, tx, y0, x0, p`` and one column per member.  The CSV outputs do not change with
 the flag.
+``--occlusion DIR`` additionally asks which part of each image the verdict depends on: the image is divided into ``--occlusion-grid`` (8) x
+8 cells (cell g of an axis of length L = pixels ``(g L) // G .. ((g + 1) L) // G - 1``) and scored again with every window of
+``--occlusion-window`` (2) x 2 cells hidden behind the image's own mean colour (``--occlusion-fill gray``: 128, 128, 128) - 49 variants at
+the defaults, each through the members' ordinary input path.  Per input file ``DIR/<name>.npy`` holds the ensemble's map at the image's
+own size, fp32, in units of delta-p: every pixel carries the mean of ``p - p_variant`` over the windows that cover its cell, positive
+where hiding the region lowers the synthetic score (``--occlusion-format png``: ``<name>.png`` instead, the map scaled to the image's
+largest ``|value|`` around 128 = no effect, through the jet table, blended over the image, alpha 0.4); with ``--occlusion-members``
+``<name>.members.npz`` every member's (and the ensemble's) ``[G, G]`` cells, plain score and per-variant scores, plus the variants'
+pixel rectangles.  It needs no gradients, so the ViT members have maps too.  ``DIR/occlusion.csv`` holds, per input file, ``filename,
+width, height, variants, p, decision, delta_max, delta_min, cell_max`` (``gy,gx``: the first cell of the window with the largest delta-p)
+and ``flips`` (variants whose decision differs); ``DIR/occlusion.json`` the settings, the counts, the skipped files (lower or narrower
+than the grid: no variants, empty columns) and the files with ``flips > 0``.  A run costs 1 plain run plus ``(G - K + 1)^2`` member
+passes per image.  The CSV outputs do not change with the flag.
 
 Checkpoints: ``<script dir>/ckpts/<name>/ckpt/*.h5`` (Keras weight / model files, as in the reference), else ``ckpt/saved_model.pb`` (a
 Keras SavedModel directory: its variables are read by ``tfbundle``), or ``*.npz`` (a flat dict of
@@ -194,6 +209,65 @@ def _write_tiles(a, names, members, per_model, rows, tiles, mode, world):
         pd.DataFrame(cols).to_csv(long_form, index=False)
 
 
+def _occlusion_scorer(a, names, members, kept):
+    """the ``batch_scorer`` of ``--occlusion``: ``occlusion_batch`` on every batch, the files of its images written as they come (under
+    ``--shard images`` a rank only ever sees its own images); the plain rows are handed on unchanged, the per-image statistics
+    ``[4, M + 1, n]`` plus two rows holding every image's height and width stay on this rank (``kept``, in batch order) until the run's one
+    extra collective"""
+    import torch
+    from vipcup_amd import cam, ensemble, ops, pipeline
+    os.makedirs(a.occlusion, exist_ok=True)
+    png = a.occlusion_format == "png"
+
+    def score(staged, sub, b0, b1, after_fork):
+        batch = staged if isinstance(staged, pipeline.DecodedBatch) else pipeline.decode_staged(staged)     # the read-ahead may have decoded it
+        # chunks of the run's own batch size: a member pass over variants then has the shape of a plain pass
+        plain, variants, cells, stats, plan = ensemble.occlusion_batch(batch, sub, a.occlusion_grid, a.occlusion_window, a.occlusion_fill,
+                                                                       chunk=min(max(a.batch_size, 1), 65535), after_fork=after_fork)
+        full = ops.occlusion_map(cells[-1], batch.sizes, batch.rgb.shape[1:3], out="u8" if png else "f32")
+        if png:
+            rgb = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+            full = ops.cam_overlay(rgb, full, cam.jet_table_device(full.device), 0.4)
+        full = full.cpu().numpy()
+        hw = torch.tensor(plan.sizes, dtype=torch.float32, device=stats.device).t()        # [2, n]: exact in fp32 (sides < 2^24)
+        kept.append(torch.cat([stats.permute(2, 0, 1), hw[:, None, :].expand(2, stats.shape[0], stats.shape[1])], dim=0))
+        if a.occlusion_members:
+            cells_h, variants_h = cells.cpu().numpy(), variants.cpu().numpy()
+            plain_h = (plain.cpu().numpy(), ops.ensemble_mean(plain).cpu().numpy())
+        for i in range(b1 - b0):
+            h, w = plan.sizes[i]
+            stem = os.path.join(a.occlusion, cam.heatmap_stem(names[b0 + i]))
+            if png:
+                cam.write_png(stem + ".png", full[i, :h, :w])
+            else:
+                np.save(stem + ".npy", np.ascontiguousarray(full[i, :h, :w]))
+            if a.occlusion_members:
+                lo, hi = int(plan.seg[i]), int(plan.seg[i + 1])
+                arrays = {"rects": plan.tab[lo:hi, 1:5]}
+                for m, key in enumerate([spec.name for spec, _ in sub] + ["ensemble"]):
+                    arrays[key + "/cells"], arrays[key + "/variants"] = cells_h[m, i], variants_h[m, lo:hi]
+                    arrays[key + "/p"] = plain_h[0][m, i] if m < len(sub) else plain_h[1][i]
+                np.savez(stem + ".members.npz", **arrays)
+        return plain
+    return score
+
+
+def _write_occlusion(a, names, members, per_model, rows, mode):
+    """``--occlusion``: the per-file table ``DIR/occlusion.csv`` and the summary and settings ``DIR/occlusion.json``"""
+    import pandas as pd
+    from vipcup_amd import ensemble, pipeline
+    sizes = [(int(h), int(w)) for h, w in zip(rows[4, 0], rows[5, 0])]
+    plan = pipeline.occlusion_plan(sizes, a.occlusion_grid, a.occlusion_window)     # a function of the sizes alone: every rank's plans again
+    table, summary = ensemble.occlusion_table(names, per_model, np.ascontiguousarray(rows[:4].transpose(1, 2, 0)), plan, ensemble.THR)
+    pd.DataFrame(table).to_csv(os.path.join(a.occlusion, "occlusion.csv"), index=False)
+    summary["settings"] = {"grid": plan.grid, "window": plan.window, "fill": a.occlusion_fill, "format": a.occlusion_format,
+                           "alpha": 0.4 if a.occlusion_format == "png" else None, "members_files": bool(a.occlusion_members),
+                           "threshold": ensemble.THR, "precision": mode, "batch_size": a.batch_size, "n_images": len(names),
+                           "members": [spec.name for spec, _ in members]}
+    with open(os.path.join(a.occlusion, "occlusion.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input_csv")
@@ -254,7 +328,37 @@ def main(argv=None):
                     help="most tiles per image, 1..4096; a larger grid is thinned to an evenly spaced sample (listed in FILE.json)")
     ap.add_argument("--tile-agg", default="mean", choices=["mean", "max"],
                     help="decision_tiles = this statistic of the ensemble's tile scores > 0.487")
+    ap.add_argument("--occlusion", default=None, metavar="DIR",
+                    help="occlusion sensitivity: also score every image with each window of a grid hidden and write into DIR, per input "
+                         "file, the ensemble's full-size map of delta-p (what hiding the region takes off the synthetic score), plus "
+                         "DIR/occlusion.csv and DIR/occlusion.json; needs no gradients, so ViT members are covered; costs "
+                         "(grid - window + 1)^2 extra member passes per image, 49 at the defaults")
+    ap.add_argument("--occlusion-grid", type=int, default=8, help="cells per axis, 2..32; an image lower or narrower than this is skipped")
+    ap.add_argument("--occlusion-window", type=int, default=2, help="side of the hidden window in cells, 1..grid")
+    ap.add_argument("--occlusion-fill", default="mean", choices=["mean", "gray"],
+                    help="what hides a window: the image's own mean colour, or (128, 128, 128)")
+    ap.add_argument("--occlusion-format", default="npy", choices=["npy", "png"],
+                    help="npy: the fp32 delta-p map at the image's size; png: the map scaled to its largest |value| around 128 = no "
+                         "effect, through the jet colour table, blended over the image (alpha 0.4)")
+    ap.add_argument("--occlusion-members", action="store_true",
+                    help="also write every member's [grid, grid] cells and per-variant scores: DIR/<name>.members.npz")
     a = ap.parse_args(argv)
+    if a.occlusion is not None:
+        if a.shard != "images" or a.tta > 1:
+            # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
+            raise SystemExit("vipcup_amd main: --occlusion works with --shard images and --tta 1 only (got --shard "
+                             f"{a.shard} --tta {a.tta}): occlusion maps under member sharding or TTA are not implemented")
+        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
+                a.tiles_out is not None:
+            raise SystemExit("vipcup_amd main: --occlusion cannot be combined with --heatmaps, --stress-* or --tiles-out (each replaces the "
+                             "batch scorer): run them one after the other")
+        if not 2 <= a.occlusion_grid <= 32:
+            raise SystemExit(f"vipcup_amd main: --occlusion-grid {a.occlusion_grid}: expected an integer in 2..32")
+        if not 1 <= a.occlusion_window <= a.occlusion_grid:
+            raise SystemExit(f"vipcup_amd main: --occlusion-window {a.occlusion_window}: expected an integer in 1..{a.occlusion_grid} (the grid)")
+    elif a.occlusion_grid != 8 or a.occlusion_window != 2 or a.occlusion_fill != "mean" or a.occlusion_format != "npy" or a.occlusion_members:
+        raise SystemExit("vipcup_amd main: --occlusion-grid / --occlusion-window / --occlusion-fill / --occlusion-format / --occlusion-members "
+                         "need --occlusion DIR")
     if a.tiles_out is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the stress runs: the scores of one image would be spread over ranks or over augmented copies
@@ -415,6 +519,9 @@ def main(argv=None):
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
+    occlusion_rows = []
+    if a.occlusion is not None:
+        batch_scorer = _occlusion_scorer(a, names, members, occlusion_rows)
 
     t0 = time.time()
     costs = None
@@ -432,6 +539,9 @@ def main(argv=None):
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
         tiled = ensemble.gather_stress_rows(tile_rows, 5, len(members) + 1, len(paths), rank, world, dist)
+    occluded = None
+    if a.occlusion is not None:                         # the one extra collective of an occlusion run: every rank's [4 + 2, M + 1, n_local] rows
+        occluded = ensemble.gather_stress_rows(occlusion_rows, 6, len(members) + 1, len(paths), rank, world, dist)
     if rank == 0:
         pd.DataFrame({"filename": uniq, "logit": decision}).to_csv(a.output_csv, index=False)  # main.py:143-145
         if a.scores_out:
@@ -448,6 +558,9 @@ def main(argv=None):
                 per_tile = torch.cat(tile_scores, dim=1).cpu().numpy() if tile_scores else np.zeros((len(members) + 1, 0), np.float32)
             _write_tiles(a, names, members, per_model, tiled, per_tile, mode, world)
             print(f"> TILE REPORT SAVED TO {a.tiles_out}")
+        if occluded is not None:
+            _write_occlusion(a, names, members, per_model, occluded, mode)
+            print(f"> OCCLUSION MAPS AND REPORT SAVED TO {a.occlusion}")
         dt = time.time() - t0
         print(f"> FINAL PREDICTION SAVED TO {a.output_csv}")
         print(f"> TIME TO INFER: {dt / 60:.2f} min ({len(paths) / dt:.1f} images/s on {world} GPU(s))")  # main.py:231-235

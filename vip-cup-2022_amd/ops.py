@@ -9,6 +9,7 @@ import os
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _abi
@@ -1091,6 +1092,57 @@ def tile_aggregate(scores: torch.Tensor, seg: torch.Tensor, thr: float) -> torch
     out = torch.empty((3, R, n), dtype=torch.float32, device=scores.device)
     _launch("vip_tile_aggregate_f32", _p(scores), _p(seg), n, R, T, C.c_float(float(thr)), _p(out))
     return out
+
+
+def occlusion_cells(scores: torch.Tensor, plain: torch.Tensor, seg, grid: int, window: int, thr: float):
+    """fp32 ``[R, V]`` variant scores, ``[R, n]`` plain scores and ``seg`` int32 ``[n + 1]`` - the HOST array of ``pipeline.occlusion_plan``
+    (image i owns columns ``seg[i]:seg[i + 1]``: none, or its ``(grid - window + 1)^2`` windows row-major; anything else raises
+    ``ValueError``) -> ``(cells [R, n, grid, grid], stats [R, n, 4])``: per cell the mean of ``plain - score`` over the windows covering it
+    (a sequential fp32 sum in variant order), and per image (max delta, min delta, index of the variant with the max, variants whose
+    side of ``thr`` differs from the plain score's); NaN for an image without variants (``vip_occlusion_cells_f32``)."""
+    seg = np.ascontiguousarray(np.asarray(seg))
+    if seg.dtype != np.int32 or seg.ndim != 1 or seg.size < 2:
+        raise ValueError(f"occlusion_cells: seg must be a host int32 [n + 1] array, got {seg.dtype} {seg.shape}")
+    G, K = int(grid), int(window)
+    if not (2 <= G <= 32 and 1 <= K <= G):
+        raise ValueError(f"occlusion_cells: grid {grid!r} / window {window!r}: expected 2 <= grid <= 32 and 1 <= window <= grid")
+    n, per = seg.size - 1, (G - K + 1) ** 2
+    counts = np.diff(seg.astype(np.int64))
+    if seg[0] != 0 or not np.isin(counts, (0, per)).all():
+        raise ValueError(f"occlusion_cells: every image has 0 or {per} variants at grid {G}, window {K}; seg gives {counts.tolist()} "
+                         f"from {int(seg[0])}")
+    if scores.dim() != 2 or int(seg[-1]) != scores.shape[1]:
+        raise ValueError(f"occlusion_cells: seg ends at {int(seg[-1])}, the scores are {tuple(scores.shape)}")
+    assert scores.dtype == torch.float32 and scores.is_cuda and scores.is_contiguous()
+    R, V = scores.shape
+    assert plain.dtype == torch.float32 and plain.shape == (R, n) and plain.is_contiguous() and plain.device == scores.device
+    if V == 0:                                           # no image of the batch has variants: nothing to read
+        nan = float("nan")
+        return (torch.full((R, n, G, G), nan, dtype=torch.float32, device=scores.device),
+                torch.full((R, n, 4), nan, dtype=torch.float32, device=scores.device))
+    cells = torch.empty((R, n, G, G), dtype=torch.float32, device=scores.device)
+    stats = torch.empty((R, n, 4), dtype=torch.float32, device=scores.device)
+    seg_d = torch.from_numpy(seg).to(scores.device)
+    _launch("vip_occlusion_cells_f32", _p(scores), _p(plain), _p(seg_d), n, R, V, G, K, C.c_float(float(thr)), _p(cells), _p(stats))
+    return cells, stats
+
+
+def occlusion_map(cells_row: torch.Tensor, sizes: torch.Tensor, max_hw, out: str = "f32") -> torch.Tensor:
+    """One row of ``occlusion_cells``' cells, fp32 ``[n, G, G]``, as full-size maps ``[n, maxH, maxW]``: every pixel of an image takes its
+    cell's value (cell g of an axis of length L = pixels ``(g L) // G .. ((g + 1) L) // G - 1``, the occluder's own edges), 0 outside the
+    image.  ``sizes`` int32 ``[n, 2]`` (h, w) and ``max_hw`` = the slot size, as ``DecodedBatch.sizes`` / ``.rgb.shape[1:3]``.  ``out``:
+    ``"f32"`` the values as they are; ``"u8"`` uint8 ``round(255 * (0.5 + 0.5 * v / peak))`` with ``peak`` = the image's largest ``|cell|``,
+    128 (no effect) everywhere when that is 0 or the cells are NaN - what ``cam_overlay`` blends (``vip_occlusion_map``)."""
+    if out not in ("f32", "u8"):
+        raise ValueError(f"occlusion_map out={out!r}: expected 'f32' or 'u8'")
+    _chk32(cells_row, "occlusion_map.cells_row")
+    assert cells_row.dim() == 3 and cells_row.shape[1] == cells_row.shape[2], cells_row.shape
+    n, G = int(cells_row.shape[0]), int(cells_row.shape[1])
+    maxH, maxW = int(max_hw[0]), int(max_hw[1])
+    assert sizes.dtype == torch.int32 and sizes.shape == (n, 2) and sizes.is_cuda and sizes.is_contiguous()
+    res = torch.empty((n, maxH, maxW), dtype=torch.uint8 if out == "u8" else torch.float32, device=cells_row.device)
+    _launch("vip_occlusion_map", _p(cells_row), _p(sizes), n, maxH, maxW, G, _p(res), int(out == "u8"))
+    return res
 
 
 def cam(features, w_nc: torch.Tensor, bias: Optional[torch.Tensor], ln=None, act="default", target="score"):

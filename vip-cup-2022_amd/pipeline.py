@@ -109,6 +109,44 @@ class DecodedBatch:
                 c_out)
         return out
 
+    def mean_colour(self) -> torch.Tensor:
+        """uint8 ``[n, 4]`` on the device: (r, g, b, 0), each image's mean colour over its own ``h x w`` pixels, per channel
+        ``(sum + h * w // 2) // (h * w)`` in 64-bit integers (``vip_image_mean_u8``; the padding of the slots is not read)"""
+        n, maxH, maxW, _ = self.rgb.shape
+        src = self.rgb if self.rgb.is_contiguous() else self.rgb.contiguous()
+        out = torch.empty((n, 4), dtype=torch.uint8, device=self.rgb.device)
+        _launch("vip_image_mean_u8", _p(src), _p(self.sizes), n, maxH, maxW, _p(out))
+        return out
+
+    def occluded(self, tab_d: torch.Tensor, lo: int, hi: int, fill_d: torch.Tensor, out_h: int, out_w: int, c_out: int = 8,
+                 dtype: torch.dtype = torch.float16) -> torch.Tensor:
+        """Variants ``tab_d[lo:hi]`` of this batch (``tab_d``: the device copy of ``occlusion_plan``'s ``tab``, int32 ``[V, 8]`` = (image, y0,
+        x0, y1, x1, 0, 0, 0)) as network inputs ``[hi - lo, out_h, out_w, c_out]``: the image with the pixels of the rectangle replaced by
+        its row of ``fill_d`` (uint8 ``[n, 4]``, e.g. ``mean_colour()``) and sent through dataset/dataset.py:31-38 - exactly the values
+        ``resized(out_h, out_w, c_out, dtype)`` gives for an occluded copy of the pixels.  One launch
+        (``vip_occlude_resize_bicubic_norm_*``): the replacement happens as the resize reads each tap, no uint8 copy is made."""
+        n, maxH, maxW, _ = self.rgb.shape
+        from . import ops
+        if dtype == ops.PACKED:
+            return ops.pack_h2(self.occluded(tab_d, lo, hi, fill_d, out_h, out_w, c_out, torch.float32))
+        if dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"occluded: dtype {dtype}: expected torch.float16, torch.float32 or the packed strict storage")
+        if tab_d.dtype != torch.int32 or tab_d.dim() != 2 or tab_d.shape[1] != 8 or not tab_d.is_contiguous() or \
+                tab_d.device != self.rgb.device:
+            raise ValueError(f"occluded: tab_d must be a contiguous int32 [V, 8] tensor on {self.rgb.device}, got {tab_d.dtype} "
+                             f"{tuple(tab_d.shape)} on {tab_d.device}")
+        if not 0 <= lo < hi <= tab_d.shape[0]:
+            raise ValueError(f"occluded: rows {lo}:{hi} of a table of {tab_d.shape[0]}")
+        if fill_d.dtype != torch.uint8 or tuple(fill_d.shape) != (n, 4) or not fill_d.is_contiguous() or fill_d.device != self.rgb.device:
+            raise ValueError(f"occluded: fill_d must be a contiguous uint8 [{n}, 4] tensor on {self.rgb.device}, got {fill_d.dtype} "
+                             f"{tuple(fill_d.shape)} on {fill_d.device}")
+        src = self.rgb if self.rgb.is_contiguous() else self.rgb.contiguous()
+        out = torch.empty((hi - lo, out_h, out_w, c_out), dtype=dtype, device=self.rgb.device)
+        fn = {torch.float16: "vip_occlude_resize_bicubic_norm_f16", torch.float32: "vip_occlude_resize_bicubic_norm_s32"}[dtype]
+        _launch(fn, _p(src), _p(self.sizes), _p(fill_d), _p(tab_d[lo:hi]), _p(bicubic_table(self.rgb.device)), n, hi - lo, maxH, maxW,
+                _p(out), int(out_h), int(out_w), c_out)
+        return out
+
 
 def _int_arg(name: str, v, lo: int, hi: int) -> int:
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
@@ -179,6 +217,47 @@ def tile_plan(sizes_host: Sequence[Tuple[int, int]], tile: int = 200, stride: Op
     tab = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
     return TilePlan(tab, np.asarray(seg, dtype=np.int32), [(int(h), int(w)) for h, w in sizes_host], grids, thinned, tile, stride,
                     max_tiles)
+
+
+class OcclusionPlan:
+    """What ``occlusion_plan`` returns; unpacks as ``tab, seg = occlusion_plan(...)``.  ``tab`` int32 ``[V, 8]`` = (image, y0, x0, y1, x1, 0,
+    0, 0): the pixel rectangle each variant hides, in image order, then window row-major ``(wy, wx)``; ``seg`` int32 ``[n + 1]``: the
+    variants of image i are ``tab[seg[i]:seg[i + 1]]``.  Per image also ``sizes`` (h, w); ``skipped``: the indices of the images without
+    variants (lower or narrower than ``grid`` pixels); and the settings ``grid`` and ``window``."""
+
+    def __init__(self, tab, seg, sizes, skipped, grid, window):
+        self.tab, self.seg, self.sizes, self.skipped, self.grid, self.window = tab, seg, sizes, skipped, grid, window
+
+    def __iter__(self):
+        return iter((self.tab, self.seg))
+
+
+def occlusion_bounds(length: int, grid: int) -> List[int]:
+    """the ``grid + 1`` cell edges along an axis of ``length`` pixels: cell g covers ``[b[g], b[g + 1])``, ``b[g] = (g * length) // grid``"""
+    return [(g * int(length)) // int(grid) for g in range(int(grid) + 1)]
+
+
+def occlusion_plan(sizes_host: Sequence[Tuple[int, int]], grid: int = 8, window: int = 2) -> OcclusionPlan:
+    """The occlusion variants of a batch of images of ``sizes_host`` = [(h, w)]: every image is divided into ``grid x grid`` cells
+    (``occlusion_bounds`` per axis) and a window of ``window x window`` cells is placed at every cell offset ``0 .. grid - window`` in both
+    axes - ``(grid - window + 1)^2`` variants per image, each hiding the pixels of its window.  An image with ``h < grid`` or
+    ``w < grid`` (a cell would be empty) has no variants and is listed in ``skipped``.  Integer arithmetic only, a pure function of its
+    arguments: every rank derives the same plan from the same sizes."""
+    grid = _int_arg("grid", grid, 2, 32)
+    window = _int_arg("window", window, 1, grid)
+    rows: List[Tuple[int, ...]] = []
+    seg, skipped = [0], []
+    for i, (h, w) in enumerate(sizes_host):
+        h, w = int(h), int(w)
+        if h < grid or w < grid:
+            skipped.append(i)
+        else:
+            by, bx = occlusion_bounds(h, grid), occlusion_bounds(w, grid)
+            rows += [(i, by[wy], bx[wx], by[wy + window], bx[wx + window], 0, 0, 0)
+                     for wy in range(grid - window + 1) for wx in range(grid - window + 1)]
+        seg.append(len(rows))
+    tab = np.asarray(rows, dtype=np.int32).reshape(-1, 8)
+    return OcclusionPlan(tab, np.asarray(seg, dtype=np.int32), [(int(h), int(w)) for h, w in sizes_host], skipped, grid, window)
 
 
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
