@@ -412,6 +412,43 @@ int vip_resample_rgb_u8(const uint8_t* src_u8, const int32_t* src_sizes_hw, int 
                         const int32_t* dst_sizes_hw, int maxHo, int maxWo, const int32_t* image_tab, const int32_t* tables, int n,
                         int total_tiles, int max_window, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Smoothing of decoded u8 RGB at the image's own size: a Gaussian blur and a K x K median, the two filters of dataset/augment.py:131-140
+ * (`Blur`: tfa.image.gaussian_filter2d / median_filter2d) as stress perturbations.  Each image of the batch is filtered on its own and
+ * each channel separately; the output has the size of the input.
+ *
+ * Edges are REFLECT without repeating the edge sample (tfa's default, scipy's mode='mirror').  Sample i of an axis of n samples:
+ *   n == 1: 0;  otherwise p = 2 (n - 1), i = i mod p (non-negative), i = p - i if i >= n.
+ *   The formula reflects repeatedly, so a side shorter than the radius needs no special case.
+ *
+ * vip_blur_weights_h (host, double precision, no FP contraction): the 2 radius + 1 integer weights of one axis, w_h[j + radius] for
+ *   j = -radius..radius.  g[j] = exp(-j^2 / (2 sigma^2)), summed left to right and divided by the sum; w[j] = floor(g[j] * 65536 + 0.5);
+ *   then the centre takes the rounding, w[0] += 65536 - sum(w): the weights are non-negative and sum to exactly 65536.
+ *   cap = the buffer's size in int32.  sigma outside 0.3..5.0, radius outside 1..15 or a buffer shorter than 2 radius + 1
+ *   -> VIP_ERR_BAD_ARG with a message, before anything is written.
+ * vip_blur_gauss_rgb_u8 (device, caller's stream, one launch per batch): src_u8 [n][maxH][maxW][3] with image i in the top-left
+ *   sizes_hw[i] = (h, w) corner of its slot -> dst_u8 [n][dstMaxH][dstMaxW][3], image i in the same corner of its slot (a pitch of its
+ *   own, at least the image's size).  weights_d: a device copy of vip_blur_weights_h's output for `radius` (1..15).  Per channel, in
+ *   UNSIGNED 32-bit integers:
+ *     horizontal pass   t   = (sum_j w[j] * px[mirror(x + j)] + 128) >> 8              8.8 fixed point, <= 65280, held as u16
+ *     vertical pass     out = min((sum_j w[j] * t[mirror(y + j)] + 2^23) >> 24, 255)   the sum is <= 65536 * 65280 + 2^23 < 2^32
+ *   The intermediate is rounded once to 1 / 256 level and a weight is off by at most 2^-17: the result is within 0.75 level of the
+ *   exact convolution and at most one level from its rounded value.  Only the h x w pixels of an image are written: the rest of dst_u8
+ *   keeps what the caller put there.  An image larger than a source or destination slot is skipped.  src_u8 and dst_u8 overlapping
+ *   -> VIP_ERR_BAD_ARG (the filter cannot run in place).
+ *   A workgroup owns 16 rows x 256 bytes of the interleaved output row; it stages the tile and its halo once into LDS as u8, mirroring
+ *   on the pixel index, runs the horizontal pass into a u16 LDS plane and the vertical pass from there (40 KiB of LDS at any radius).
+ *   The grid is (tiles of a maxH x maxW image) x n; a tile outside its image returns at once.  No allocation, no atomics: bit-reproducible.
+ * vip_median_rgb_u8: the same conventions; per channel the element of rank k * k / 2 (0-based) of the mirrored k x k window, exact.
+ *   k = 3: sorted columns, then med3(max of the minima, median of the medians, min of the maxima); k = 5: a 99-exchange selection
+ *   network; both on packed 16-bit min / max, no data-dependent control flow.  k not 3 or 5 -> VIP_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------------------------ */
+int vip_blur_weights_h(double sigma, int radius, int32_t* w_h, size_t cap);
+int vip_blur_gauss_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                          const int32_t* weights_d, int radius, int n, void* stream);
+int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW, int k,
+                      int n, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

@@ -35,9 +35,9 @@ def _sources():
 # MFMA-heavy co-runners (tools/repro/); nothing in them is VALU-bound, and tools/isa_lint.py (a CPU test) keeps every
 # shipped kernel free of that form.
 # -ffp-contract=off: resample_host.cpp builds coefficient tables that are compared with Pillow's bit for bit; a fused multiply-add in the
-# filter polynomials would move a coefficient by one unit.
+# filter polynomials would move a coefficient by one unit.  blur_host.cpp: the same for the Gaussian weights and their restatement.
 EXTRA_FLAGS = {"se_gate.hip": ["-fno-slp-vectorize"], "jpeg_pipeline.hip": ["-fno-slp-vectorize"],
-               "resample_host.cpp": ["-ffp-contract=off"]}
+               "resample_host.cpp": ["-ffp-contract=off"], "blur_host.cpp": ["-ffp-contract=off"]}
 
 # sources that #include another SOURCE file (one kernel family, two arithmetic modes)
 INCLUDES_SOURCE = {"conv_h2.hip": ["conv_igemm.hip"]}

@@ -466,18 +466,26 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     return acc / float(len(flags))
 
 
-def stress_labels(qualities: Sequence[int], scales: Sequence[int] = ()) -> List[str]:
+def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = ()) -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
-    ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved)."""
+    ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
+    ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
+    of ``medians`` (ascending) ``m<K>`` and ``m<K>_q<Q>``."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
         labels += [f"r{int(pc)}_q{int(q)}" for q in qualities]
+    for tt in sorted(int(round(float(s) * 10)) for s in blurs):
+        labels.append(f"b{tt:02d}")
+        labels += [f"b{tt:02d}_q{int(q)}" for q in qualities]
+    for k in sorted(int(k) for k in medians):
+        labels.append(f"m{k}")
+        labels += [f"m{k}_q{int(q)}" for q in qualities]
     return labels
 
 
 def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
-                 resize_filter: str = "bicubic"):
+                 resize_filter: str = "bicubic", blurs: Sequence[float] = (), medians: Sequence[int] = (), blur_radius: Optional[int] = None):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -485,7 +493,12 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     With ``scales`` (percents, sorted largest first here) the batch is also rescaled to each percent of its size with ``resize_filter``
     (``pipeline.rescale``) and scored unsaved and re-saved at every quality - rescale first, ``recompress`` second, the order in which
     the challenge's test images were made.  Then the result is ``(rows [1 + V, M, n], labels)`` with ``labels`` =
-    ``stress_labels(qualities, scales)``, the names of rows 1.. ."""
+    ``stress_labels(qualities, scales)``, the names of rows 1.. .
+    With ``blurs`` (sigmas, sorted ascending here; ``blur_radius`` None = three sigma) and ``medians`` (windows, ascending) the decoded
+    batch AT FULL SIZE is also smoothed (``pipeline.blur`` / ``pipeline.median``; dataset/augment.py:131-140) and scored unsaved and
+    re-saved at every quality; smoothing is not composed with ``scales``, so the grid stays linear in the number of variants.  The
+    result is ``(rows, labels)`` whenever ``scales``, ``blurs`` or ``medians`` is non-empty, ``labels`` = ``stress_labels(qualities,
+    scales, blurs, medians)``."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
@@ -493,6 +506,8 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
             isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
     scales = sorted((int(pc) for pc in scales), reverse=True)
+    blurs = sorted(int(round(float(sg) * 10)) / 10 for sg in blurs)
+    medians = sorted(int(k) for k in medians)
     rows = [_score_batch(batch, members, None, after_fork=after_fork)]
     for q in qualities:
         rows.append(_score_batch(pipeline.recompress(batch, int(q), subsampling), members))
@@ -501,11 +516,16 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(small, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(small, int(q), subsampling), members))
+    for kind, arg in [("blur", sg) for sg in blurs] + [("median", k) for k in medians]:          # one smoothed batch alive at a time
+        smooth = pipeline.blur(batch, arg, blur_radius) if kind == "blur" else pipeline.median(batch, arg)
+        rows.append(_score_batch(smooth, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(smooth, int(q), subsampling), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales:
+    if not scales and not blurs and not medians:
         return torch.stack(rows)
-    return torch.stack(rows), stress_labels(qualities, scales)
+    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -538,11 +558,11 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     ``p`` / ``decision`` unperturbed, ``p_q`` / ``decision_q`` ``[F, Q]``, ``stable`` (every decision equals the unperturbed one) and
     ``flips_at`` (the highest listed quality whose decision differs, None when stable).  ``summary``: per quality the number and rate of
     files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
-    ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``).  With ``q`` labels alone the
-    result is the one above.  With rescaled variants ``p_q`` / ``decision_q`` are ``[F, V]`` over all variants, ``stable`` is taken
-    over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only), ``table`` gains ``labels`` and
-    ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants`` (the labels in order) and keys
-    its per-variant counts by label; ``summary["qualities"]`` lists the qualities of the 100 % rows."""
+    ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``).
+    With ``q`` labels alone the result is the one above.  With rescaled or smoothed variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
+    all variants, ``stable`` is taken over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only),
+    ``table`` gains ``labels`` and ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants``
+    (the labels in order) and keys its per-variant counts by label; ``summary["qualities"]`` lists the qualities of the 100 % rows."""
     scores = np.asarray(scores)
     labels = [v if isinstance(v, str) else f"q{int(v)}" for v in qualities]
     plain = [int(v[1:]) if v[:1] == "q" and v[1:].isdigit() else None for v in labels]

@@ -4,6 +4,8 @@
                                      [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
                                      [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
                                      [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
+                                     [--stress-blur S[,S...] --stress-out FILE.csv [--stress-blur-radius R]]
+                                     [--stress-median K[,K...] --stress-out FILE.csv]
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
                                                       [--occlusion-format npy|png] [--occlusion-members]]
@@ -29,6 +31,12 @@ it unsaved (``r<P>``) and, with ``--stress-jpeg``, re-saved at every quality (``
 challenge's test images were made.  The table is then ``filename, p, decision, p_<label>..., decision_<label>..., stable, flips_at, flips``
 over the labels ``q<Q>..., r<P>, r<P>_q<Q>...`` (``stable`` over all variants, ``flips_at`` over the 100 % rows as before, ``flips`` the
 ``;``-joined labels whose decision differs) and ``stress.json`` lists the labels under ``variants`` and keys its counts by label.
+``--stress-blur 0.5,1,2.5 --stress-out stress.csv`` smooths every decoded image at its own size with a Gaussian of each listed sigma (pixels,
+0.3..5.0 in steps of 0.1; cut off at three sigma, or at ``--stress-blur-radius``) and ``--stress-median 3,5`` with a 3 x 3 / 5 x 5 median -
+the two filters of dataset/augment.py:131-140 ``Blur``, edges mirrored as there - and scores it unsaved (``b<TT>``, ``TT`` = ten times
+sigma as two digits; ``m<K>``) and, with ``--stress-jpeg``, re-saved at every quality (``b<TT>_q<Q>``, ``m<K>_q<Q>``).  The rows follow
+those of ``--stress-resize`` in the same table layout; smoothing is not combined with resizing.  ``stress.json`` then lists
+``blur_sigmas``, ``blur_radius`` (null: three sigma) and ``medians`` under ``settings``.
 ``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
 it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
 last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
@@ -62,6 +70,7 @@ unless ``--synthetic`` asks for the seeded synthetic checkpoints.
 import argparse
 import json
 import os
+import re
 import sys
 import time
 from glob import glob
@@ -119,16 +128,16 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
-def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic"):
-    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize``: ``stress_batch`` on every batch; the unperturbed row is handed on
-    unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra
-    collective"""
+def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None):
+    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median``: ``stress_batch`` on
+    every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
+    in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales:
+        if scales or blurs or medians:
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
-                                            resize_filter=resize_filter)
+                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius)
         else:
             rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
@@ -136,13 +145,14 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=()):
+def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales)
-    table, summary = ensemble.stress_table(names, scores, labels if scales else qualities)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or ())
+    mixed = bool(scales or blurs or medians)
+    table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
         cols[f"p_{v}"] = table["p_q"][:, k]
@@ -150,7 +160,7 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         cols[f"decision_{v}"] = table["decision_q"][:, k]
     cols["stable"] = table["stable"].astype(np.int64)
     cols["flips_at"] = ["" if q is None else str(q) for q in table["flips_at"]]
-    if scales:
+    if mixed:
         cols["flips"] = table["flips"]
     pd.DataFrame(cols).to_csv(a.stress_out, index=False)
     summary["settings"] = {"qualities": list(qualities), "subsampling": {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling],
@@ -159,6 +169,10 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
     if scales:
         summary["settings"]["scales"] = list(scales)
         summary["settings"]["resize_filter"] = a.stress_resize_filter
+    if blurs is not None or medians is not None:
+        summary["settings"]["blur_sigmas"] = list(blurs or ())
+        summary["settings"]["blur_radius"] = a.stress_blur_radius
+        summary["settings"]["medians"] = list(medians or ())
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
 
@@ -316,6 +330,18 @@ def main(argv=None):
                          "flips_at, flips over the labels q<Q>, r<P>, r<P>_q<Q>")
     ap.add_argument("--stress-resize-filter", default="bicubic", choices=["bilinear", "bicubic", "lanczos"],
                     help="the antialiased filter of the simulated resize (what an image editor's resize offers)")
+    ap.add_argument("--stress-blur", default=None, metavar="S[,S...]",
+                    help="blur stress test: also score every image under a Gaussian blur of each sigma (pixels; decimals in 0.3..5.0 with at "
+                         "most one fractional digit; duplicates are dropped, smallest first), unsaved and - with --stress-jpeg - re-saved at "
+                         "every quality; needs --stress-out, whose table gains the labels b<TT>, b<TT>_q<Q> (TT = ten times sigma, two "
+                         "digits) in the layout of --stress-resize")
+    ap.add_argument("--stress-blur-radius", type=int, default=None, metavar="R",
+                    help="cut the Gaussian off R pixels from its centre (1..15; default ceil(3 sigma)); --stress-blur 1 "
+                         "--stress-blur-radius 1 is exactly the reference's gaussian_filter2d(filter_shape=3) (dataset/augment.py:131-140)")
+    ap.add_argument("--stress-median", default=None, metavar="K[,K...]",
+                    help="median stress test: also score every image under a K x K median filter (K = 3 or 5; 3 is the reference's "
+                         "median_filter2d), unsaved and - with --stress-jpeg - re-saved at every quality; needs --stress-out, whose table "
+                         "gains the labels m<K>, m<K>_q<Q>")
     ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
                     help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
                          "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
@@ -349,7 +375,7 @@ def main(argv=None):
             raise SystemExit("vipcup_amd main: --occlusion works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): occlusion maps under member sharding or TTA are not implemented")
         if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
-                a.tiles_out is not None:
+                a.tiles_out is not None or a.stress_blur is not None or a.stress_median is not None:
             raise SystemExit("vipcup_amd main: --occlusion cannot be combined with --heatmaps, --stress-* or --tiles-out (each replaces the "
                              "batch scorer): run them one after the other")
         if not 2 <= a.occlusion_grid <= 32:
@@ -364,7 +390,8 @@ def main(argv=None):
             # as for the stress runs: the scores of one image would be spread over ranks or over augmented copies
             raise SystemExit("vipcup_amd main: --tiles-out works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): tile scoring under member sharding or TTA is not implemented")
-        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None:
+        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
+                a.stress_blur is not None or a.stress_median is not None:
             raise SystemExit("vipcup_amd main: --tiles-out cannot be combined with --heatmaps or --stress-* (each replaces the batch scorer): "
                              "run them one after the other")
         if not 16 <= a.tile_size <= 1024:
@@ -397,6 +424,39 @@ def main(argv=None):
                              "run them one after the other")
     elif a.stress_resize_filter != "bicubic":
         raise SystemExit("vipcup_amd main: --stress-resize-filter needs --stress-resize P[,P...]")
+    sigmas = medians = None                             # sigmas in tenths of a pixel
+    if a.stress_blur is not None:
+        tokens = a.stress_blur.split(",")
+        if not all(re.fullmatch(r"\d{1,2}(\.\d)?", t) for t in tokens):
+            tokens = []
+        sigmas = sorted({int(t.replace(".", "")) if "." in t else 10 * int(t) for t in tokens})
+        if not sigmas or sigmas[0] < 3 or sigmas[-1] > 50:
+            raise SystemExit(f"vipcup_amd main: --stress-blur {a.stress_blur!r}: expected a comma-separated list of sigmas in 0.3..5.0 with at "
+                             "most one fractional digit")
+        if a.stress_blur_radius is not None and not 1 <= a.stress_blur_radius <= 15:
+            raise SystemExit(f"vipcup_amd main: --stress-blur-radius {a.stress_blur_radius}: expected an integer in 1..15")
+    elif a.stress_blur_radius is not None:
+        raise SystemExit("vipcup_amd main: --stress-blur-radius needs --stress-blur S[,S...]")
+    if a.stress_median is not None:
+        try:
+            medians = sorted({int(t) for t in a.stress_median.split(",")})
+        except ValueError:
+            medians = []
+        if not medians or any(k not in (3, 5) for k in medians):
+            raise SystemExit(f"vipcup_amd main: --stress-median {a.stress_median!r}: expected a comma-separated list of windows, each 3 or 5")
+    for flag, given in (("--stress-blur", sigmas), ("--stress-median", medians)):
+        if given is None:
+            continue
+        if a.stress_out is None:
+            raise SystemExit(f"vipcup_amd main: {flag} needs --stress-out FILE.csv")
+        if a.shard != "images" or a.tta > 1:
+            # as for --stress-jpeg: the scores of one image would be spread over ranks or over augmented copies
+            raise SystemExit(f"vipcup_amd main: {flag} works with --shard images and --tta 1 only (got --shard "
+                             f"{a.shard} --tta {a.tta}): the smoothing stress tests under member sharding or TTA are not implemented")
+        if a.heatmaps is not None:
+            raise SystemExit(f"vipcup_amd main: {flag} and --heatmaps cannot be combined (both replace the batch scorer): "
+                             "run them one after the other")
+    smoothed = sigmas is not None or medians is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -414,7 +474,7 @@ def main(argv=None):
         if a.heatmaps is not None:
             raise SystemExit("vipcup_amd main: --stress-jpeg and --heatmaps cannot be combined (both replace the batch scorer): "
                              "run them one after the other")
-    elif (a.stress_out is not None and scales is None) or a.stress_subsampling != "420":
+    elif (a.stress_out is not None and scales is None and not smoothed) or a.stress_subsampling != "420":
         raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]"
                          + (" (--stress-out alone also goes with --stress-resize P[,P...])" if a.stress_out is not None else ""))
     if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
@@ -513,9 +573,10 @@ def main(argv=None):
     if a.heatmaps is not None:
         batch_scorer = _heatmap_writer(a, names, members, rank)
     stress_rows = []
-    if qualities is not None or scales is not None:
+    blurs = None if sigmas is None else [t / 10 for t in sigmas]
+    if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
-                                      scales or (), a.stress_resize_filter)
+                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -533,8 +594,8 @@ def main(argv=None):
                                      tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
-    if qualities is not None or scales is not None:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or ()))
+    if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or ()))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -550,7 +611,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or ())
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

@@ -603,6 +603,76 @@ def _resample_into(batch: DecodedBatch, new_sizes: List[Tuple[int, int]], filter
     return DecodedBatch(rgb, sizes, list(new_sizes))
 
 
+_BLUR_WEIGHTS: Dict[Tuple[int, int], np.ndarray] = {}
+_BLUR_WEIGHTS_DEV: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+
+def _blur_args(sigma, radius) -> Tuple[int, int]:
+    """``(round(sigma * 10), radius)`` of a valid ``blur`` call: sigma a multiple of 0.1 in 0.3..5.0, radius None or an integer in 1..15"""
+    ok = not isinstance(sigma, bool) and isinstance(sigma, (int, float, np.integer, np.floating)) and np.isfinite(sigma)
+    tenths = int(round(float(sigma) * 10)) if ok else 0
+    if not ok or not 3 <= tenths <= 50 or abs(float(sigma) * 10 - tenths) > 1e-6:
+        raise ValueError(f"sigma {sigma!r}: expected a multiple of 0.1 in 0.3..5.0")
+    return tenths, (blur_radius(tenths / 10) if radius is None else _int_arg("radius", radius, 1, 15))
+
+
+def blur_radius(sigma: float) -> int:
+    """the default radius of ``blur``: three sigma, ``max(1, ceil(3 * sigma))``"""
+    return max(1, int(np.ceil(3 * float(sigma))))
+
+
+def blur_weights(sigma: float, radius: Optional[int] = None) -> np.ndarray:
+    """Host: the ``2 * radius + 1`` integer weights of one axis of ``blur`` (``vip_blur_weights_h``: a sampled Gaussian normalised in
+    double precision, 16 fractional bits, non-negative, summing to exactly 65536), int32, read-only, cached per ``(sigma, radius)``."""
+    key = _blur_args(sigma, radius)
+    if key not in _BLUR_WEIGHTS:
+        w = np.zeros((2 * key[1] + 1,), np.int32)
+        _abi.check(_abi.lib().vip_blur_weights_h(key[0] / 10, key[1], w.ctypes.data_as(C.c_void_p), w.size), "vip_blur_weights_h")
+        w.setflags(write=False)
+        _BLUR_WEIGHTS[key] = w
+    return _BLUR_WEIGHTS[key]
+
+
+def blur(batch: DecodedBatch, sigma: float, radius: Optional[int] = None) -> DecodedBatch:
+    """The batch under a Gaussian blur of ``sigma`` pixels (a multiple of 0.1 in 0.3..5.0) cut off at ``radius`` (1..15; default
+    ``blur_radius(sigma)``) - dataset/augment.py:131-140 ``Blur``'s ``gaussian_filter2d``, which is ``blur(batch, 1.0, 1)``.  Every image
+    is filtered at its own size, each channel separately, edges mirrored without repeating the edge sample (tfa's REFLECT); integer
+    arithmetic with 16-bit weights and an 8.8 intermediate, at most one level from the rounded exact convolution
+    (``vip_blur_gauss_rgb_u8``, one launch).  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched.
+    Runs on the current stream; only the weights (at most 31 integers, cached on the device) come from the host."""
+    key = _blur_args(sigma, radius)
+    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "gauss", key)
+
+
+def median(batch: DecodedBatch, k: int) -> DecodedBatch:
+    """The batch under a ``k x k`` median filter (``k`` 3 or 5) - dataset/augment.py:131-140 ``Blur``'s ``median_filter2d``, which is
+    ``median(batch, 3)``.  Every image at its own size, each channel separately, edges mirrored without repeating the edge sample; exact
+    (``vip_median_rgb_u8``, one launch).  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) not in (3, 5):
+        raise ValueError(f"k {k!r}: expected 3 or 5")
+    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "median", int(k))
+
+
+def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> DecodedBatch:
+    """``blur``'s (``kind`` "gauss", ``arg`` = (round(sigma * 10), radius)) and ``median``'s (``kind`` "median", ``arg`` = k) launch:
+    image i of ``batch`` filtered into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8 on the batch's device, slots at least as large
+    as the images; only the pixels of the images are written)."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    if kind == "gauss":
+        dkey = (device.index or 0,) + tuple(arg)
+        if dkey not in _BLUR_WEIGHTS_DEV:
+            _BLUR_WEIGHTS_DEV[dkey] = torch.from_numpy(blur_weights(arg[0] / 10, arg[1]).copy()).to(device)
+        _launch("vip_blur_gauss_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+                _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), n)
+    else:
+        _launch("vip_median_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), int(arg), n)
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
     """Deterministic form of dataset/augment.py ``apply_augment`` (:153-182): per-image flags instead of the
     reference's TF RNG draws (p=0.8 gate, hflip .5, vflip .5, gray .3) — the caller owns the randomness."""
