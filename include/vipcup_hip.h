@@ -449,6 +449,37 @@ int vip_blur_gauss_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int ma
 int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW, int k,
                       int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Geometry of decoded u8 RGB: an inverse affine warp with bilinear taps in integer arithmetic, the one kernel under the flip, crop and
+ * rotate stress perturbations (dataset/augment.py:115-120 `RandomFlip`, :68-107 `ShiftScaleShearRotate` through tfa.image.rotate /
+ * transform).  Each image of the batch has its own transform and its own output size.
+ *
+ * vip_warp_affine_rgb_u8 (device, caller's stream, one launch per batch): src_u8 [n][maxH][maxW][3] with image i in the top-left
+ *   sizes_hw[i] = (h, w) corner of its slot -> dst_u8 [n][dstMaxH][dstMaxW][3], image i in the top-left dst_sizes_hw[i] = (h', w')
+ *   corner of its slot.  xform_d: int64 [n][6] on the device, (A, B, TX, C, D, TY) per image: A..D the coefficients of the INVERSE map
+ *   (output -> source) in Q24, TX, TY its offsets in Q25, in pixel-edge coordinates (pixel x covers [x, x + 1)).  For output pixel
+ *   (x, y), with u = 2 x + 1 and v = 2 y + 1, in int64 throughout:
+ *     SX = A u + B v + TX - 2^24,  SY = C u + D v + TY - 2^24       the source sample-centre coordinate in Q25
+ *     ix = SX >> 25 (arithmetic shift),  wx = (SX >> 15) & 1023      and the same for y
+ *     per channel  top = p[iy][ix] (1024 - wx) + p[iy][ix + 1] wx,  bot likewise on row iy + 1
+ *                  out = (top (1024 - wy) + bot wy + 2^19) >> 20
+ *   Taps by `fill`: VIP_WARP_FILL_BLACK - a tap outside the source image is 0 (tfa's `constant`, the reference's CFG.fill_mode);
+ *   VIP_WARP_FILL_MIRROR - reflect without repeating the edge sample (the formula of the smoothing filters above; every tap of a
+ *   1-pixel axis is index 0).  With A = D = +-2^24, B = C = 0 and whole-pixel offsets both weights are 0: flips and crops are exact
+ *   copies.  Otherwise the result is within 0.5 (rounding) + 2 * 255 / 1024 (the truncated 10-bit weights) + about 0.02 (coefficient
+ *   rounding at sides up to 200) < 1.02 levels of the exact bilinear value; 16-bit coefficients with 8-bit weights were off by 2.
+ *   Only the h' x w' pixels of an image are written: the rest of dst_u8 keeps what the caller put there.  An image whose source or
+ *   output size is not positive or exceeds its slot is skipped.  Null pointer, n or a slot side not positive, fill not 0 or 1, src_u8
+ *   and dst_u8 overlapping -> VIP_ERR_BAD_ARG; sizes not 4-byte or xform_d not 8-byte aligned -> VIP_ERR_ALIGNMENT; all before any work.
+ *   A workgroup owns 64 pixels x 16 rows of the output - a compact tile, so that the source footprint of a rotated tile stays in the
+ *   CU's cache - with one wave per output row; results pass through an LDS image of the tile and leave as whole dwords.  The grid is
+ *   (tiles of a dstMaxH x dstMaxW image) x n; a tile outside its image returns at once.  No allocation, no atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+#define VIP_WARP_FILL_BLACK 0
+#define VIP_WARP_FILL_MIRROR 1
+int vip_warp_affine_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, const int32_t* dst_sizes_hw,
+                           int dstMaxH, int dstMaxW, const int64_t* xform_d, int fill, int n, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

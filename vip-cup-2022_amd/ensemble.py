@@ -466,11 +466,20 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     return acc / float(len(flags))
 
 
-def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = ()) -> List[str]:
+def _rot_tenths(rotations) -> List[int]:
+    return sorted(int(round(float(d) * 10)) for d in rotations)
+
+
+def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = (),
+                  flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
+                  rotate_fill: str = "crop") -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
     ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
     ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
-    of ``medians`` (ascending) ``m<K>`` and ``m<K>_q<Q>``."""
+    of ``medians`` (ascending) ``m<K>`` and ``m<K>_q<Q>``, then the geometry: ``fliph`` / ``flipv`` for the axes of ``flips`` (h first), ``crop<PP>``
+    for each percent of ``crops`` (descending), ``rot<TTT>`` / ``rotm<TTT>`` for each angle of ``rotations`` (ascending by signed angle; ``m``
+    marks a negative angle, ``TTT`` = ten times |degrees| as three digits: 7.5 -> ``rot075``, -12.3 -> ``rotm123``), each followed by its
+    ``_q<Q>`` labels (``crop_origin`` and ``rotate_fill`` are ``stress_batch``'s and do not change a label)."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
@@ -481,11 +490,18 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
     for k in sorted(int(k) for k in medians):
         labels.append(f"m{k}")
         labels += [f"m{k}_q{int(q)}" for q in qualities]
+    geometry = [f"flip{ax}" for ax in sorted(str(ax) for ax in flips)] + [f"crop{pc:02d}" for pc in sorted((int(pc) for pc in crops), reverse=True)] \
+        + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
+    for v in geometry:
+        labels.append(v)
+        labels += [f"{v}_q{int(q)}" for q in qualities]
     return labels
 
 
 def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
-                 resize_filter: str = "bicubic", blurs: Sequence[float] = (), medians: Sequence[int] = (), blur_radius: Optional[int] = None):
+                 resize_filter: str = "bicubic", blurs: Sequence[float] = (), medians: Sequence[int] = (), blur_radius: Optional[int] = None,
+                 flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
+                 rotate_fill: str = "crop"):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -498,7 +514,12 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     batch AT FULL SIZE is also smoothed (``pipeline.blur`` / ``pipeline.median``; dataset/augment.py:131-140) and scored unsaved and
     re-saved at every quality; smoothing is not composed with ``scales``, so the grid stays linear in the number of variants.  The
     result is ``(rows, labels)`` whenever ``scales``, ``blurs`` or ``medians`` is non-empty, ``labels`` = ``stress_labels(qualities,
-    scales, blurs, medians)``."""
+    scales, blurs, medians)``.
+    With ``flips`` (axes "h" / "v"), ``crops`` (percents, largest first here; ``crop_origin`` "centre" or "topleft") and ``rotations``
+    (degrees, ascending here; ``rotate_fill`` "crop", "mirror" or "black") the decoded batch is also mirrored, cropped and rotated
+    (``pipeline.flip`` / ``crop`` / ``rotate``; dataset/augment.py:68-120) and scored unsaved and re-saved at every quality, one warped
+    batch alive at a time; geometry is not composed with resizing or smoothing.  The result is ``(rows, labels)`` whenever any of the
+    lists but ``qualities`` is non-empty, ``labels`` = ``stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)``."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
@@ -508,6 +529,9 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     scales = sorted((int(pc) for pc in scales), reverse=True)
     blurs = sorted(int(round(float(sg) * 10)) / 10 for sg in blurs)
     medians = sorted(int(k) for k in medians)
+    flips = sorted(str(ax) for ax in flips)
+    crops = sorted((int(pc) for pc in crops), reverse=True)
+    rotations = [tt / 10 for tt in _rot_tenths(rotations)]
     rows = [_score_batch(batch, members, None, after_fork=after_fork)]
     for q in qualities:
         rows.append(_score_batch(pipeline.recompress(batch, int(q), subsampling), members))
@@ -521,11 +545,17 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(smooth, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(smooth, int(q), subsampling), members))
+    for kind, arg in [("flip", ax) for ax in flips] + [("crop", pc) for pc in crops] + [("rotate", dg) for dg in rotations]:
+        warped = pipeline.flip(batch, arg) if kind == "flip" else pipeline.crop(batch, arg, crop_origin) if kind == "crop" else \
+            pipeline.rotate(batch, arg, rotate_fill)             # one warped batch alive at a time
+        rows.append(_score_batch(warped, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(warped, int(q), subsampling), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales and not blurs and not medians:
+    if not scales and not blurs and not medians and not flips and not crops and not rotations:
         return torch.stack(rows)
-    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians)
+    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -558,8 +588,9 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     ``p`` / ``decision`` unperturbed, ``p_q`` / ``decision_q`` ``[F, Q]``, ``stable`` (every decision equals the unperturbed one) and
     ``flips_at`` (the highest listed quality whose decision differs, None when stable).  ``summary``: per quality the number and rate of
     files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
-    ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``).
-    With ``q`` labels alone the result is the one above.  With rescaled or smoothed variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
+    ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``,
+    ``flip<A>...``, ``crop<PP>...``, ``rot<TTT>...``).
+    With ``q`` labels alone the result is the one above.  With rescaled, smoothed or warped variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
     all variants, ``stable`` is taken over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only),
     ``table`` gains ``labels`` and ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants``
     (the labels in order) and keys its per-variant counts by label; ``summary["qualities"]`` lists the qualities of the 100 % rows."""

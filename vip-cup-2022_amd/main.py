@@ -6,6 +6,9 @@
                                      [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
                                      [--stress-blur S[,S...] --stress-out FILE.csv [--stress-blur-radius R]]
                                      [--stress-median K[,K...] --stress-out FILE.csv]
+                                     [--stress-flip h[,v] --stress-out FILE.csv]
+                                     [--stress-crop P[,P...] --stress-out FILE.csv [--stress-crop-origin centre|topleft]]
+                                     [--stress-rotate D[,D...] --stress-out FILE.csv [--stress-rotate-fill crop|mirror|black]]
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
                                                       [--occlusion-format npy|png] [--occlusion-members]]
@@ -37,6 +40,16 @@ the two filters of dataset/augment.py:131-140 ``Blur``, edges mirrored as there 
 sigma as two digits; ``m<K>``) and, with ``--stress-jpeg``, re-saved at every quality (``b<TT>_q<Q>``, ``m<K>_q<Q>``).  The rows follow
 those of ``--stress-resize`` in the same table layout; smoothing is not combined with resizing.  ``stress.json`` then lists
 ``blur_sigmas``, ``blur_radius`` (null: three sigma) and ``medians`` under ``settings``.
+``--stress-flip h,v``, ``--stress-crop 90,80`` and ``--stress-rotate -3,7.5`` (all with ``--stress-out stress.csv``) are the geometric
+perturbations, dataset/augment.py:68-120 on the decoded image at its own size: mirrored left-right / top-bottom (``fliph``, ``flipv``),
+cropped to each listed percent of its sides (50..99; ``crop<PP>``, largest first; from the middle, or with ``--stress-crop-origin
+topleft`` from the corner, which keeps a JPEG source's 8 x 8 grid) and rotated counter-clockwise by each listed angle (degrees, non-zero,
+-45..45 in steps of 0.1; ``rot<TTT>`` / ``rotm<TTT>`` for a negative angle, ``TTT`` = ten times the angle as three digits, ascending;
+bilinear, then cut down to the largest upright rectangle inside the rotated image, or with ``--stress-rotate-fill mirror|black`` kept at
+its size with the corners mirrored / black).  Each is scored unsaved and, with ``--stress-jpeg``, re-saved at every quality
+(``<label>_q<Q>``); the rows follow those of ``--stress-median``.  Geometry is not combined with resizing or smoothing.  ``stress.json``
+then lists ``flips``, ``crops``, ``crop_origin``, ``rotations`` and ``rotate_fill`` under ``settings``.  (A list that starts with a
+negative angle is written ``--stress-rotate=-3,7.5``.)
 ``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
 it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
 last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
@@ -128,16 +141,17 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
-def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None):
-    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median``: ``stress_batch`` on
-    every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
+def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None):
+    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
+    ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
     in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians:
+        if scales or blurs or medians or geometry:
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
-                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius)
+                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius,
+                                            **(geometry or {}))
         else:
             rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
@@ -145,13 +159,13 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None):
+def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or ())
-    mixed = bool(scales or blurs or medians)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}))
+    mixed = bool(scales or blurs or medians or geometry)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -173,6 +187,8 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         summary["settings"]["blur_sigmas"] = list(blurs or ())
         summary["settings"]["blur_radius"] = a.stress_blur_radius
         summary["settings"]["medians"] = list(medians or ())
+    if geometry:
+        summary["settings"].update(geometry)
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
 
@@ -342,6 +358,27 @@ def main(argv=None):
                     help="median stress test: also score every image under a K x K median filter (K = 3 or 5; 3 is the reference's "
                          "median_filter2d), unsaved and - with --stress-jpeg - re-saved at every quality; needs --stress-out, whose table "
                          "gains the labels m<K>, m<K>_q<Q>")
+    ap.add_argument("--stress-flip", default=None, metavar="h[,v]",
+                    help="flip stress test: also score every image mirrored left-right (h) and / or top-bottom (v), unsaved and - with "
+                         "--stress-jpeg - re-saved at every quality; needs --stress-out, whose table gains the labels fliph, flipv and "
+                         "their _q<Q> in the layout of --stress-resize (dataset/augment.py:115-120)")
+    ap.add_argument("--stress-crop", default=None, metavar="P[,P...]",
+                    help="crop stress test: also score every image cropped to each listed percent of its sides (integers in 50..99; "
+                         "duplicates are dropped, largest first), unsaved and - with --stress-jpeg - re-saved at every quality; needs "
+                         "--stress-out, whose table gains the labels crop<PP>, crop<PP>_q<Q>")
+    ap.add_argument("--stress-crop-origin", default="centre", choices=["centre", "topleft"],
+                    help="where the crop is taken: the middle of the image (off a JPEG source's 8 x 8 grid unless the offset happens to "
+                         "be a multiple of 8), or its top-left corner (on the grid)")
+    ap.add_argument("--stress-rotate", default=None, metavar="D[,D...]",
+                    help="rotation stress test: also score every image rotated counter-clockwise by each listed angle (degrees; non-zero "
+                         "decimals in -45..45 with at most one fractional digit; duplicates are dropped, ascending), bilinear, unsaved and "
+                         "- with --stress-jpeg - re-saved at every quality; needs --stress-out, whose table gains the labels rot<TTT> / "
+                         "rotm<TTT> (negative) and their _q<Q>, TTT = ten times the angle, three digits (dataset/augment.py:68-107); write a "
+                         "list that starts with a negative angle as --stress-rotate=-3,7.5")
+    ap.add_argument("--stress-rotate-fill", default="crop", choices=["crop", "mirror", "black"],
+                    help="what a rotated image's corners become: crop - the image is cut down to the largest upright rectangle inside the "
+                         "rotated one (an editor's 'straighten'); mirror / black - the size is kept and the corners are mirrored / black "
+                         "(black is the reference's constant fill)")
     ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
                     help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
                          "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
@@ -375,7 +412,8 @@ def main(argv=None):
             raise SystemExit("vipcup_amd main: --occlusion works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): occlusion maps under member sharding or TTA are not implemented")
         if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
-                a.tiles_out is not None or a.stress_blur is not None or a.stress_median is not None:
+                a.tiles_out is not None or a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or \
+                a.stress_crop is not None or a.stress_rotate is not None:
             raise SystemExit("vipcup_amd main: --occlusion cannot be combined with --heatmaps, --stress-* or --tiles-out (each replaces the "
                              "batch scorer): run them one after the other")
         if not 2 <= a.occlusion_grid <= 32:
@@ -391,7 +429,8 @@ def main(argv=None):
             raise SystemExit("vipcup_amd main: --tiles-out works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): tile scoring under member sharding or TTA is not implemented")
         if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
-                a.stress_blur is not None or a.stress_median is not None:
+                a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or a.stress_crop is not None or \
+                a.stress_rotate is not None:
             raise SystemExit("vipcup_amd main: --tiles-out cannot be combined with --heatmaps or --stress-* (each replaces the batch scorer): "
                              "run them one after the other")
         if not 16 <= a.tile_size <= 1024:
@@ -444,7 +483,34 @@ def main(argv=None):
             medians = []
         if not medians or any(k not in (3, 5) for k in medians):
             raise SystemExit(f"vipcup_amd main: --stress-median {a.stress_median!r}: expected a comma-separated list of windows, each 3 or 5")
-    for flag, given in (("--stress-blur", sigmas), ("--stress-median", medians)):
+    flips = crops = angles = None                       # angles in tenths of a degree
+    if a.stress_flip is not None:
+        flips = sorted(set(a.stress_flip.split(",")))
+        if not set(flips) <= {"h", "v"}:
+            raise SystemExit(f"vipcup_amd main: --stress-flip {a.stress_flip!r}: expected h, v or h,v")
+    if a.stress_crop is not None:
+        try:
+            crops = sorted({int(t) for t in a.stress_crop.split(",")}, reverse=True)
+        except ValueError:
+            crops = []
+        if not crops or crops[-1] < 50 or crops[0] > 99:
+            raise SystemExit(f"vipcup_amd main: --stress-crop {a.stress_crop!r}: expected a comma-separated list of integer percents in 50..99")
+    elif a.stress_crop_origin != "centre":
+        raise SystemExit("vipcup_amd main: --stress-crop-origin needs --stress-crop P[,P...]")
+    if a.stress_rotate is not None:
+        tokens = a.stress_rotate.split(",")
+        if not all(re.fullmatch(r"-?\d{1,2}(\.\d)?", t) for t in tokens):
+            tokens = []
+        angles = sorted({(-1 if t[0] == "-" else 1) * (int(t.lstrip("-").replace(".", "")) if "." in t else 10 * int(t.lstrip("-")))
+                         for t in tokens})
+        if not angles or angles[0] < -450 or angles[-1] > 450 or 0 in angles:
+            raise SystemExit(f"vipcup_amd main: --stress-rotate {a.stress_rotate!r}: expected a comma-separated list of non-zero angles in "
+                             "-45..45 with at most one fractional digit")
+    elif a.stress_rotate_fill != "crop":
+        raise SystemExit("vipcup_amd main: --stress-rotate-fill needs --stress-rotate D[,D...]")
+    for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
+                              ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
+                              ("--stress-rotate", angles, "geometric")):
         if given is None:
             continue
         if a.stress_out is None:
@@ -452,11 +518,15 @@ def main(argv=None):
         if a.shard != "images" or a.tta > 1:
             # as for --stress-jpeg: the scores of one image would be spread over ranks or over augmented copies
             raise SystemExit(f"vipcup_amd main: {flag} works with --shard images and --tta 1 only (got --shard "
-                             f"{a.shard} --tta {a.tta}): the smoothing stress tests under member sharding or TTA are not implemented")
+                             f"{a.shard} --tta {a.tta}): the {what} stress tests under member sharding or TTA are not implemented")
         if a.heatmaps is not None:
             raise SystemExit(f"vipcup_amd main: {flag} and --heatmaps cannot be combined (both replace the batch scorer): "
                              "run them one after the other")
-    smoothed = sigmas is not None or medians is not None
+    geometry = None
+    if flips is not None or crops is not None or angles is not None:
+        geometry = {"flips": flips or [], "crops": crops or [], "crop_origin": a.stress_crop_origin,
+                    "rotations": [t / 10 for t in angles or []], "rotate_fill": a.stress_rotate_fill}
+    smoothed = sigmas is not None or medians is not None or geometry is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -576,7 +646,7 @@ def main(argv=None):
     blurs = None if sigmas is None else [t / 10 for t in sigmas]
     if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
-                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius)
+                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -595,7 +665,7 @@ def main(argv=None):
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
     if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or ()))
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {})))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -611,7 +681,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians)
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

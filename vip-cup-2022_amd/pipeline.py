@@ -7,6 +7,7 @@ host (C++ threads inside libvipcup_hip.so) and turned into RGB once on the GPU; 
 re-decodes the files for every model.
 """
 import ctypes as C
+import math
 import os
 import re
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -671,6 +672,125 @@ def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> Deco
     else:
         _launch("vip_median_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), int(arg), n)
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
+WARP_FILLS = {"black": 0, "mirror": 1}                 # VIP_WARP_FILL_* (include/vipcup_hip.h)
+
+
+def warp_matrix(a: float, b: float, tx: float, c: float, d: float, ty: float) -> List[int]:
+    """The inverse map ``(X, Y) -> (a X + b Y + tx, c X + d Y + ty)`` (output point to source point, pixel-edge coordinates: pixel x
+    covers [x, x + 1)) as the six integers of ``warp``: coefficients ``floor(v * 2^24 + 0.5)``, offsets ``floor(v * 2^25 + 0.5)``."""
+    vals = [float(v) for v in (a, b, tx, c, d, ty)]
+    if not all(math.isfinite(v) and abs(v) < 2.0 ** 31 for v in vals):
+        raise ValueError(f"warp_matrix {vals!r}: expected six finite numbers below 2^31")
+    return [math.floor(v * (2.0 ** 25 if k % 3 == 2 else 2.0 ** 24) + 0.5) for k, v in enumerate(vals)]
+
+
+def _fill_arg(fill, allowed) -> str:
+    if not isinstance(fill, str) or fill not in allowed:
+        raise ValueError(f"fill {fill!r}: expected one of {', '.join(allowed)}")
+    return fill
+
+
+def warp(batch: DecodedBatch, xforms, out_sizes: Sequence[Tuple[int, int]], fill: str = "black") -> DecodedBatch:
+    """The general geometric transform: image i of the batch under the inverse affine map ``xforms[i]`` (int64 ``[n, 6]``, one
+    ``warp_matrix`` per image) into an image of ``out_sizes[i]`` = (h, w), bilinear taps in integer arithmetic
+    (``vip_warp_affine_rgb_u8``, one launch; the arithmetic is stated in include/vipcup_hip.h).  ``fill``: ``"black"`` - a tap outside
+    the image is 0 (tfa's ``constant``, the reference's ``CFG.fill_mode``) - or ``"mirror"`` (reflect without repeating the edge sample).
+    Returns a new batch at ``out_sizes``, pixels outside an image 0; ``batch`` is not touched.  Runs on the current stream; only the
+    transforms and sizes (56 bytes per image) come from the host."""
+    _fill_arg(fill, WARP_FILLS)
+    xf = np.asarray(xforms)
+    if xf.dtype != np.int64 or xf.ndim != 2 or xf.shape[1] != 6:
+        raise ValueError(f"xforms: expected an int64 [n, 6] array, got {xf.dtype} {tuple(xf.shape)}")
+    sizes = []
+    for i, s in enumerate(out_sizes):
+        if len(s) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in s):
+            raise ValueError(f"out_sizes[{i}] {s!r}: expected (height, width), positive integers")
+        sizes.append((int(s[0]), int(s[1])))
+    if len(sizes) != xf.shape[0] or len(sizes) != len(batch):
+        raise ValueError(f"warp: {len(batch)} images, {xf.shape[0]} transforms, {len(sizes)} output sizes")
+    for i, (h, w) in enumerate(sizes):
+        if h * w > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"image {i}: {w}x{h} after the warp exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+    rgb = torch.zeros((len(batch), max(h for h, _ in sizes), max(w for _, w in sizes), 3), dtype=torch.uint8, device=batch.rgb.device)
+    return _warp_into(batch, np.ascontiguousarray(xf), sizes, WARP_FILLS[fill], rgb)
+
+
+def _warp_into(batch: DecodedBatch, xf: np.ndarray, out_sizes: List[Tuple[int, int]], fill: int, rgb: torch.Tensor) -> DecodedBatch:
+    """``warp``'s launch: image i of ``batch`` warped to ``out_sizes[i]`` = (h, w) into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8
+    on the batch's device, slots at least as large as the output sizes; only the pixels of the images are written)."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in out_sizes)
+    sizes = torch.tensor(out_sizes, dtype=torch.int32, device=device)
+    xf_d = torch.from_numpy(xf).to(device)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    _launch("vip_warp_affine_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), _p(sizes), int(rgb.shape[1]), int(rgb.shape[2]),
+            _p(xf_d), int(fill), n)
+    return DecodedBatch(rgb, sizes, list(out_sizes))
+
+
+def flip(batch: DecodedBatch, axis: str) -> DecodedBatch:
+    """The batch mirrored left-right (``axis`` "h") or top-bottom ("v") - dataset/augment.py:115-120 ``RandomFlip`` on the decoded
+    pixels at their own size; an exact copy (``warp`` with whole-pixel coordinates).  Returns a new batch; ``batch`` is not touched."""
+    if not isinstance(axis, str) or axis not in ("h", "v"):
+        raise ValueError(f"axis {axis!r}: expected 'h' or 'v'")
+    xf = [warp_matrix(-1, 0, w, 0, 1, 0) if axis == "h" else warp_matrix(1, 0, 0, 0, -1, h) for h, w in batch.sizes_host]
+    return warp(batch, np.array(xf, np.int64).reshape(-1, 6), list(batch.sizes_host), "black")
+
+
+def crop(batch: DecodedBatch, percent: int, origin: str = "centre") -> DecodedBatch:
+    """The batch cropped to ``percent`` % (an integer in 50..99) of each side (``scaled_size``), taken from the middle - at
+    ``((h - h') // 2, (w - w') // 2)`` - or with ``origin="topleft"`` at (0, 0), which keeps the pixels on the 8 x 8 grid of a JPEG
+    source.  An exact copy.  Returns a new batch at the new sizes; ``batch`` is not touched."""
+    percent = _int_arg("percent", percent, 50, 99)
+    if not isinstance(origin, str) or origin not in ("centre", "topleft"):
+        raise ValueError(f"origin {origin!r}: expected 'centre' or 'topleft'")
+    sizes = [scaled_size(h, w, percent) for h, w in batch.sizes_host]
+    xf = [warp_matrix(1, 0, (w - ww) // 2 if origin == "centre" else 0, 0, 1, (h - hh) // 2 if origin == "centre" else 0)
+          for (h, w), (hh, ww) in zip(batch.sizes_host, sizes)]
+    return warp(batch, np.array(xf, np.int64).reshape(-1, 6), sizes, "black")
+
+
+def _rotate_args(degrees, fill) -> Tuple[int, str]:
+    """``(round(degrees * 10), fill)`` of a valid ``rotate`` call"""
+    ok = not isinstance(degrees, bool) and isinstance(degrees, (int, float, np.integer, np.floating)) and np.isfinite(degrees)
+    tenths = int(round(float(degrees) * 10)) if ok else 0
+    if not ok or tenths == 0 or not -450 <= tenths <= 450 or abs(float(degrees) * 10 - tenths) > 1e-6:
+        raise ValueError(f"degrees {degrees!r}: expected a non-zero multiple of 0.1 in -45..45")
+    return tenths, _fill_arg(fill, ("crop", "mirror", "black"))
+
+
+def rotated_rect(h: int, w: int, degrees: float) -> Tuple[int, int]:
+    """``(h', w')``: the largest axis-aligned rectangle, centred, that lies inside an ``h x w`` image rotated by ``degrees`` - what is
+    left after an editor's "straighten"; each side floored, at least 1."""
+    t = math.radians(float(degrees))
+    s, c = abs(math.sin(t)), abs(math.cos(t))
+    long_side, short_side = max(h, w), min(h, w)
+    if short_side <= 2.0 * s * c * long_side or s == c:   # half-constrained: two corners touch the long sides
+        x = 0.5 * short_side
+        wr, hr = (x / s, x / c) if w >= h else (x / c, x / s)
+    else:
+        wr, hr = (w * c - h * s) / (c * c - s * s), (h * c - w * s) / (c * c - s * s)
+    return max(1, int(math.floor(hr))), max(1, int(math.floor(wr)))
+
+
+def rotate(batch: DecodedBatch, degrees: float, fill: str = "crop") -> DecodedBatch:
+    """The batch rotated counter-clockwise by ``degrees`` (a non-zero multiple of 0.1 in -45..45; Pillow's direction) about each
+    image's centre, bilinear - dataset/augment.py:68-107 ``ShiftScaleShearRotate``'s ``tfa.image.rotate`` on the decoded pixels at
+    their own size.  ``fill``: ``"crop"`` (what an editor's "straighten" does) outputs the largest axis-aligned rectangle inside the
+    rotated image (``rotated_rect``), so no tap leaves the image (taps are mirrored, which only matters for 1-pixel axes); ``"black"``
+    (the reference's constant fill) and ``"mirror"`` keep the size.  At most 1 level from Pillow's ``Image.rotate(BILINEAR)``.
+    Returns a new batch; ``batch`` is not touched."""
+    tenths, fill = _rotate_args(degrees, fill)
+    t = math.radians(tenths / 10)
+    a, b, c, d = math.cos(t), -math.sin(t), math.sin(t), math.cos(t)
+    sizes = [rotated_rect(h, w, tenths / 10) if fill == "crop" else (h, w) for h, w in batch.sizes_host]
+    xf = [warp_matrix(a, b, w / 2 - a * ww / 2 - b * hh / 2, c, d, h / 2 - c * ww / 2 - d * hh / 2)   # output centre -> source centre
+          for (h, w), (hh, ww) in zip(batch.sizes_host, sizes)]
+    return warp(batch, np.array(xf, np.int64).reshape(-1, 6), sizes, "black" if fill == "black" else "mirror")
 
 
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
