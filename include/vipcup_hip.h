@@ -480,6 +480,37 @@ int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, 
 int vip_warp_affine_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, const int32_t* dst_sizes_hw,
                            int dstMaxH, int dstMaxW, const int64_t* xform_d, int fill, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Colour of decoded u8 RGB: a 3 x 3 matrix, a per-image mean term, an offset and a look-up table in integer arithmetic, the one kernel
+ * under the gray, BGR, hue, saturation, contrast, brightness and gamma stress perturbations (dataset/augment.py:142-146 `RandomGray`,
+ * :148-151 `RandomBGR`, :122-129 `RandomJitter`).  Every image keeps its size.
+ *
+ * vip_colour_rgb_u8 (device, caller's stream, one launch per batch): src_u8 [n][maxH][maxW][3] with image i in the top-left
+ *   sizes_hw[i] = (h, w) corner of its slot -> dst_u8 [n][dstMaxH][dstMaxW][3], image i in the same corner of its slot (a pitch of its
+ *   own).  coef_h: int32 [15] on the HOST, M[3][3] (row c = output channel c), K[3], O[3], all Q16; they are copied into the kernel's
+ *   arguments, so a variant costs no host-to-device copy and no synchronisation.  mean_u8: uint8 [n][4] on the device, (r, g, b, 0)
+ *   per image as vip_image_mean_u8 writes it, or NULL when every K is 0.  lut_d: uint8 [256] on the device, or NULL.  Per pixel
+ *   (R, G, B) of image i and output channel c, in signed 32-bit integers:
+ *     s_c   = M[c][0] R + M[c][1] G + M[c][2] B + K[c] mean_u8[i][c] + O[c] + 32768
+ *     v_c   = clamp(s_c >> 16, 0, 255)          arithmetic shift: floor, also for a negative sum
+ *     out_c = lut_d ? lut_d[v_c] : v_c
+ *   Admitted: |M[c][k]| <= 2^18 and |K[c]| <= 2^18 (4.0 in Q16), |O[c]| <= 2^25 (512 levels).  With samples and means of at most 255
+ *   |s_c| <= 3 * 255 * 2^18 + 255 * 2^18 + 2^25 + 2^15 = (1020 + 128) * 2^18 + 2^15 = 300 974 080 < 2^31: no sum leaves 32 bits.
+ *   Only the h x w pixels of an image are written: the rest of dst_u8 keeps what the caller put there, and nothing but the images'
+ *   pixels is read.  An image whose size is not positive or exceeds the source or the destination slot is skipped.  Null src_u8,
+ *   sizes_hw, dst_u8 or coef_h, n or a slot side not positive, src_u8 and dst_u8 overlapping, a coefficient outside the bounds above,
+ *   mean_u8 == NULL while some K[c] != 0 -> VIP_ERR_BAD_ARG; sizes_hw or mean_u8 not 4-byte aligned -> VIP_ERR_ALIGNMENT; all before
+ *   any work.
+ *   A workgroup owns 128 pixels x 8 rows.  A slot row starts at (i maxH + y) maxW 3 bytes, dword-aligned only by accident, and the two
+ *   pitches differ, so a tile row is fetched as the aligned dwords of the source that cover it into an LDS image that keeps the row's
+ *   phase, a lane converts one pixel from there into a second LDS image at the destination row's phase, and that image leaves as the
+ *   aligned dwords of the destination; the head and the tail of a row, where a dword also holds a neighbour's bytes, move byte by
+ *   byte.  lut_d is copied into LDS once per workgroup.  The grid is (tiles of the smaller slot) x n; a tile outside its image
+ *   returns at once.  No allocation, no atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+int vip_colour_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                      const int32_t* coef_h, const uint8_t* mean_u8, const uint8_t* lut_d, int n, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

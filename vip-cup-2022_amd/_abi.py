@@ -98,6 +98,7 @@ SIGNATURES = {
     "vip_blur_gauss_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     "vip_median_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "vip_warp_affine_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "vip_colour_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),

@@ -470,16 +470,33 @@ def _rot_tenths(rotations) -> List[int]:
     return sorted(int(round(float(d) * 10)) for d in rotations)
 
 
+def _colour_variants(gray=False, bgr=False, hues=(), saturations=(), contrasts=(), brightnesses=(), gammas=()) -> List[Tuple[str, str, object]]:
+    """``(label, pipeline function, argument)`` of every colour variant, in row order"""
+    out = [("gray", "gray", None)] if gray else []
+    out += [("bgr", "bgr", None)] if bgr else []
+    out += [(f"hue{'m' if d < 0 else ''}{abs(d):03d}", "hue", d) for d in sorted(int(d) for d in hues)]
+    out += [(f"sat{pc:03d}", "saturation", pc) for pc in sorted(int(pc) for pc in saturations)]
+    out += [(f"con{pc:03d}", "contrast", pc) for pc in sorted(int(pc) for pc in contrasts)]
+    out += [(f"bri{'m' if pc < 0 else ''}{abs(pc):02d}", "brightness", pc) for pc in sorted(int(pc) for pc in brightnesses)]
+    out += [(f"gam{hh:03d}", "gamma", hh / 100) for hh in sorted(int(round(float(g) * 100)) for g in gammas)]
+    return out
+
+
 def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = (),
                   flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
-                  rotate_fill: str = "crop") -> List[str]:
+                  rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
+                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = ()) -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
     ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
     ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
     of ``medians`` (ascending) ``m<K>`` and ``m<K>_q<Q>``, then the geometry: ``fliph`` / ``flipv`` for the axes of ``flips`` (h first), ``crop<PP>``
     for each percent of ``crops`` (descending), ``rot<TTT>`` / ``rotm<TTT>`` for each angle of ``rotations`` (ascending by signed angle; ``m``
     marks a negative angle, ``TTT`` = ten times |degrees| as three digits: 7.5 -> ``rot075``, -12.3 -> ``rotm123``), each followed by its
-    ``_q<Q>`` labels (``crop_origin`` and ``rotate_fill`` are ``stress_batch``'s and do not change a label)."""
+    ``_q<Q>`` labels (``crop_origin`` and ``rotate_fill`` are ``stress_batch``'s and do not change a label), then the colour: ``gray``,
+    ``bgr``, ``hue<DDD>`` / ``huem<DDD>`` for each angle of ``hues`` (ascending by signed angle; ``m`` marks a negative one, three digits),
+    ``sat<PPP>`` and ``con<PPP>`` for each percent of ``saturations`` / ``contrasts`` (ascending, three digits), ``bri<PP>`` / ``brim<PP>``
+    for each percent of ``brightnesses`` (ascending by signed value, two digits), ``gam<PPP>`` for each of ``gammas`` (ascending, ``PPP``
+    = 100 times gamma: 0.8 -> ``gam080``), each followed by its ``_q<Q>`` labels."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
@@ -492,7 +509,7 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
         labels += [f"m{k}_q{int(q)}" for q in qualities]
     geometry = [f"flip{ax}" for ax in sorted(str(ax) for ax in flips)] + [f"crop{pc:02d}" for pc in sorted((int(pc) for pc in crops), reverse=True)] \
         + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
-    for v in geometry:
+    for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)]:
         labels.append(v)
         labels += [f"{v}_q{int(q)}" for q in qualities]
     return labels
@@ -501,7 +518,8 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
 def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
                  resize_filter: str = "bicubic", blurs: Sequence[float] = (), medians: Sequence[int] = (), blur_radius: Optional[int] = None,
                  flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
-                 rotate_fill: str = "crop"):
+                 rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
+                 contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = ()):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -519,7 +537,12 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     (degrees, ascending here; ``rotate_fill`` "crop", "mirror" or "black") the decoded batch is also mirrored, cropped and rotated
     (``pipeline.flip`` / ``crop`` / ``rotate``; dataset/augment.py:68-120) and scored unsaved and re-saved at every quality, one warped
     batch alive at a time; geometry is not composed with resizing or smoothing.  The result is ``(rows, labels)`` whenever any of the
-    lists but ``qualities`` is non-empty, ``labels`` = ``stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)``."""
+    lists but ``qualities`` is non-empty, ``labels`` = ``stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)``.
+    With ``gray``, ``bgr``, ``hues`` (integer degrees), ``saturations`` / ``contrasts`` (percents), ``brightnesses`` (percents of full
+    scale) and ``gammas`` (each list ascending here) the decoded batch is also recoloured (``pipeline.gray`` / ``bgr`` / ``hue`` /
+    ``saturation`` / ``contrast`` / ``brightness`` / ``gamma``; dataset/augment.py:122-129, :142-151) and scored unsaved and re-saved at
+    every quality, one coloured batch alive at a time and the batch's mean colour computed at most once; colour is not composed with
+    resizing, smoothing or geometry.  Then too the result is ``(rows, labels)``, ``labels`` = ``stress_labels`` of the same keywords."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
@@ -551,11 +574,20 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(warped, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(warped, int(q), subsampling), members))
+    colours = _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)
+    mean = batch.mean_colour() if any(kind == "contrast" for _, kind, _ in colours) else None     # once per batch
+    for _, kind, arg in colours:
+        fn = getattr(pipeline, kind)
+        coloured = fn(batch) if arg is None else fn(batch, arg, mean) if kind == "contrast" else fn(batch, arg)   # one alive at a time
+        rows.append(_score_batch(coloured, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(coloured, int(q), subsampling), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales and not blurs and not medians and not flips and not crops and not rotations:
+    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours:
         return torch.stack(rows)
-    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)
+    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations, gray=gray, bgr=bgr, hues=hues,
+                                            saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -589,7 +621,8 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     ``flips_at`` (the highest listed quality whose decision differs, None when stable).  ``summary``: per quality the number and rate of
     files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
     ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``,
-    ``flip<A>...``, ``crop<PP>...``, ``rot<TTT>...``).
+    ``flip<A>...``, ``crop<PP>...``, ``rot<TTT>...``, ``gray...``, ``bgr...``, ``hue<DDD>...``, ``sat<PPP>...``, ``con<PPP>...``,
+    ``bri<PP>...``, ``gam<PPP>...``).
     With ``q`` labels alone the result is the one above.  With rescaled, smoothed or warped variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
     all variants, ``stable`` is taken over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only),
     ``table`` gains ``labels`` and ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants``

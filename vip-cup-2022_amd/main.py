@@ -9,6 +9,8 @@
                                      [--stress-flip h[,v] --stress-out FILE.csv]
                                      [--stress-crop P[,P...] --stress-out FILE.csv [--stress-crop-origin centre|topleft]]
                                      [--stress-rotate D[,D...] --stress-out FILE.csv [--stress-rotate-fill crop|mirror|black]]
+                                     [--stress-gray] [--stress-bgr] [--stress-hue D[,D...]] [--stress-saturation P[,P...]]
+                                     [--stress-contrast P[,P...]] [--stress-brightness P[,P...]] [--stress-gamma G[,G...]]   (--stress-out FILE.csv)
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
                                                       [--occlusion-format npy|png] [--occlusion-members]]
@@ -50,6 +52,18 @@ its size with the corners mirrored / black).  Each is scored unsaved and, with `
 (``<label>_q<Q>``); the rows follow those of ``--stress-median``.  Geometry is not combined with resizing or smoothing.  ``stress.json``
 then lists ``flips``, ``crops``, ``crop_origin``, ``rotations`` and ``rotate_fill`` under ``settings``.  (A list that starts with a
 negative angle is written ``--stress-rotate=-3,7.5``.)
+``--stress-gray``, ``--stress-bgr``, ``--stress-hue -30,30``, ``--stress-saturation 0,50,150``, ``--stress-contrast 50,150``,
+``--stress-brightness -10,10`` and ``--stress-gamma 0.8,1.25`` (all with ``--stress-out stress.csv``) are the colour perturbations,
+dataset/augment.py:122-129 and :142-151 on the decoded image at its own size, per pixel and in integers: ``v = clamp((M (R, G, B) + K
+mean + O + 32768) >> 16, 0, 255)`` with Q16 coefficients, then a 256-entry table.  ``gray``: Pillow's luma (19595 R + 38470 G + 7471 B)
+in three channels; ``bgr``: red and blue exchanged; ``hue<DDD>`` / ``huem<DDD>``: the chroma rotated by a non-zero integer angle in
+-180..180 degrees, as a rotation in the NTSC YIQ plane; ``sat<PPP>``: PPP % saturation (0..200, not 100), as a blend with the luma image -
+both are the LINEAR forms, not ``tf.image``'s HSV round trip; ``con<PPP>``: PPP % contrast (0..200, not 100) about the image's own mean
+colour, ``(x - mean) f + mean``; ``bri<PP>`` / ``brim<PP>``: PP % of full scale added (non-zero, -50..50); ``gam<PPP>``: ``255 (x / 255)
+** g`` with PPP = 100 g, g in 0.50..2.00 with at most two decimals, not 1.  Each is scored unsaved and, with ``--stress-jpeg``, re-saved
+at every quality (``<label>_q<Q>``); the rows follow those of ``--stress-rotate`` in this order, each list ascending.  Colour is not
+combined with resizing, smoothing or geometry.  ``stress.json`` then lists ``gray``, ``bgr``, ``hues``, ``saturations``, ``contrasts``,
+``brightnesses`` and ``gammas`` under ``settings``.  (A list that starts with a negative value is written ``--stress-hue=-30,30``.)
 ``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
 it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
 last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
@@ -141,17 +155,19 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
-def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None):
+def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None,
+                   colour=None):
     """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
-    ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
+    ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None) and the colour flags (``colour``:
+    likewise): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
     in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians or geometry:
+        if scales or blurs or medians or geometry or colour:
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
                                             resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius,
-                                            **(geometry or {}))
+                                            **(geometry or {}), **(colour or {}))
         else:
             rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
@@ -159,13 +175,13 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None):
+def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}))
-    mixed = bool(scales or blurs or medians or geometry)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}), **(colour or {}))
+    mixed = bool(scales or blurs or medians or geometry or colour)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -189,6 +205,8 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         summary["settings"]["medians"] = list(medians or ())
     if geometry:
         summary["settings"].update(geometry)
+    if colour:
+        summary["settings"].update(colour)
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
 
@@ -298,6 +316,17 @@ def _write_occlusion(a, names, members, per_model, rows, mode):
         json.dump(summary, f, indent=1)
 
 
+def _int_list(flag, text, lo, hi, banned, what):
+    """``--stress-hue`` and its kin: a comma-separated list of integers in lo..hi other than ``banned``, ascending, duplicates dropped"""
+    tokens = text.split(",")
+    if not all(re.fullmatch(r"-?\d{1,3}", t) for t in tokens):
+        tokens = []
+    given = sorted({int(t) for t in tokens})
+    if not given or given[0] < lo or given[-1] > hi or banned in given:
+        raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of {what}")
+    return given
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input_csv")
@@ -379,6 +408,34 @@ def main(argv=None):
                     help="what a rotated image's corners become: crop - the image is cut down to the largest upright rectangle inside the "
                          "rotated one (an editor's 'straighten'); mirror / black - the size is kept and the corners are mirrored / black "
                          "(black is the reference's constant fill)")
+    ap.add_argument("--stress-gray", action="store_true",
+                    help="colour stress test: also score every image as a gray image (Pillow's luma in three channels; "
+                         "dataset/augment.py:142-146), unsaved and - with --stress-jpeg - re-saved at every quality; needs --stress-out, whose "
+                         "table gains the labels gray, gray_q<Q> in the layout of --stress-resize")
+    ap.add_argument("--stress-bgr", action="store_true",
+                    help="colour stress test: also score every image with red and blue exchanged (dataset/augment.py:148-151); labels bgr, "
+                         "bgr_q<Q>; needs --stress-out")
+    ap.add_argument("--stress-hue", default=None, metavar="D[,D...]",
+                    help="colour stress test: also score every image with its chroma rotated by each listed angle (non-zero integer degrees "
+                         "in -180..180; duplicates are dropped, ascending) - a rotation in the YIQ plane, the linear form of a hue shift, not "
+                         "tf.image's HSV round trip; labels hue<DDD> / huem<DDD> (negative) and their _q<Q>; needs --stress-out; write a "
+                         "list that starts with a negative angle as --stress-hue=-30,30")
+    ap.add_argument("--stress-saturation", default=None, metavar="P[,P...]",
+                    help="colour stress test: also score every image at each listed percent of its saturation (integers in 0..200 other than "
+                         "100; ascending) - a blend with the luma image, the linear form; 0 is --stress-gray; labels sat<PPP>, "
+                         "sat<PPP>_q<Q>; needs --stress-out")
+    ap.add_argument("--stress-contrast", default=None, metavar="P[,P...]",
+                    help="colour stress test: also score every image at each listed percent of its contrast about its own mean colour "
+                         "(integers in 0..200 other than 100; ascending; tf.image.adjust_contrast); labels con<PPP>, con<PPP>_q<Q>; needs "
+                         "--stress-out")
+    ap.add_argument("--stress-brightness", default=None, metavar="P[,P...]",
+                    help="colour stress test: also score every image with each listed percent of full scale added (non-zero integers in "
+                         "-50..50; ascending; tf.image.adjust_brightness); labels bri<PP> / brim<PP> (negative) and their _q<Q>; needs "
+                         "--stress-out; write a list that starts with a negative value as --stress-brightness=-10,10")
+    ap.add_argument("--stress-gamma", default=None, metavar="G[,G...]",
+                    help="colour stress test: also score every image under 255 (x / 255) ** G for each listed G (decimals in 0.50..2.00 with "
+                         "at most two fractional digits, other than 1; ascending; below 1 brightens; tf.image.adjust_gamma); labels "
+                         "gam<PPP>, gam<PPP>_q<Q> with PPP = 100 G; needs --stress-out")
     ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
                     help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
                          "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
@@ -406,6 +463,10 @@ def main(argv=None):
     ap.add_argument("--occlusion-members", action="store_true",
                     help="also write every member's [grid, grid] cells and per-variant scores: DIR/<name>.members.npz")
     a = ap.parse_args(argv)
+    colour_flags = (("--stress-gray", a.stress_gray or None), ("--stress-bgr", a.stress_bgr or None), ("--stress-hue", a.stress_hue),
+                    ("--stress-saturation", a.stress_saturation), ("--stress-contrast", a.stress_contrast),
+                    ("--stress-brightness", a.stress_brightness), ("--stress-gamma", a.stress_gamma))
+    any_colour = any(v is not None for _, v in colour_flags)
     if a.occlusion is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
@@ -413,7 +474,7 @@ def main(argv=None):
                              f"{a.shard} --tta {a.tta}): occlusion maps under member sharding or TTA are not implemented")
         if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
                 a.tiles_out is not None or a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or \
-                a.stress_crop is not None or a.stress_rotate is not None:
+                a.stress_crop is not None or a.stress_rotate is not None or any_colour:
             raise SystemExit("vipcup_amd main: --occlusion cannot be combined with --heatmaps, --stress-* or --tiles-out (each replaces the "
                              "batch scorer): run them one after the other")
         if not 2 <= a.occlusion_grid <= 32:
@@ -430,7 +491,7 @@ def main(argv=None):
                              f"{a.shard} --tta {a.tta}): tile scoring under member sharding or TTA is not implemented")
         if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
                 a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or a.stress_crop is not None or \
-                a.stress_rotate is not None:
+                a.stress_rotate is not None or any_colour:
             raise SystemExit("vipcup_amd main: --tiles-out cannot be combined with --heatmaps or --stress-* (each replaces the batch scorer): "
                              "run them one after the other")
         if not 16 <= a.tile_size <= 1024:
@@ -508,9 +569,26 @@ def main(argv=None):
                              "-45..45 with at most one fractional digit")
     elif a.stress_rotate_fill != "crop":
         raise SystemExit("vipcup_amd main: --stress-rotate-fill needs --stress-rotate D[,D...]")
+    hues = sats = cons = bris = gammas = None           # gammas in hundredths
+    if a.stress_hue is not None:
+        hues = _int_list("--stress-hue", a.stress_hue, -180, 180, 0, "non-zero integer degrees in -180..180")
+    if a.stress_saturation is not None:
+        sats = _int_list("--stress-saturation", a.stress_saturation, 0, 200, 100, "integer percents in 0..200 other than 100")
+    if a.stress_contrast is not None:
+        cons = _int_list("--stress-contrast", a.stress_contrast, 0, 200, 100, "integer percents in 0..200 other than 100")
+    if a.stress_brightness is not None:
+        bris = _int_list("--stress-brightness", a.stress_brightness, -50, 50, 0, "non-zero integer percents in -50..50")
+    if a.stress_gamma is not None:
+        tokens = a.stress_gamma.split(",")
+        if not all(re.fullmatch(r"\d(\.\d{1,2})?", t) for t in tokens):
+            tokens = []
+        gammas = sorted({int(t[0]) * 100 + int((t[2:] + "0")[:2] if "." in t else 0) for t in tokens})
+        if not gammas or gammas[0] < 50 or gammas[-1] > 200 or 100 in gammas:
+            raise SystemExit(f"vipcup_amd main: --stress-gamma {a.stress_gamma!r}: expected a comma-separated list of decimals in 0.50..2.00 "
+                             "with at most two fractional digits, other than 1")
     for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
                               ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
-                              ("--stress-rotate", angles, "geometric")):
+                              ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags):
         if given is None:
             continue
         if a.stress_out is None:
@@ -526,7 +604,11 @@ def main(argv=None):
     if flips is not None or crops is not None or angles is not None:
         geometry = {"flips": flips or [], "crops": crops or [], "crop_origin": a.stress_crop_origin,
                     "rotations": [t / 10 for t in angles or []], "rotate_fill": a.stress_rotate_fill}
-    smoothed = sigmas is not None or medians is not None or geometry is not None
+    colour = None
+    if any_colour:
+        colour = {"gray": bool(a.stress_gray), "bgr": bool(a.stress_bgr), "hues": hues or [], "saturations": sats or [],
+                  "contrasts": cons or [], "brightnesses": bris or [], "gammas": [hh / 100 for hh in gammas or []]}
+    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -646,7 +728,7 @@ def main(argv=None):
     blurs = None if sigmas is None else [t / 10 for t in sigmas]
     if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
-                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry)
+                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -665,7 +747,7 @@ def main(argv=None):
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
     if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {})))
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {}), **(colour or {})))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -681,7 +763,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry)
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

@@ -793,6 +793,204 @@ def rotate(batch: DecodedBatch, degrees: float, fill: str = "crop") -> DecodedBa
     return warp(batch, np.array(xf, np.int64).reshape(-1, 6), sizes, "black" if fill == "black" else "mirror")
 
 
+GRAY_Q16 = (19595, 38470, 7471)                        # Pillow's convert("L"): (R 19595 + G 38470 + B 7471 + 32768) >> 16
+YIQ = ((0.299, 0.587, 0.114), (0.596, -0.274, -0.322), (0.211, -0.523, 0.312))     # NTSC: RGB -> (Y, I, Q)
+COLOUR_M_MAX, COLOUR_O_MAX = 1 << 18, 1 << 25          # the bounds of vip_colour_rgb_u8 (include/vipcup_hip.h)
+_LUT_DEV: Dict[Tuple[int, bytes], torch.Tensor] = {}    # (device, table bytes) -> the table on that device, the last _LUT_DEV_MAX used
+_LUT_DEV_MAX = 32
+
+
+def _q16(x) -> np.ndarray:
+    """``floor(x * 65536 + 0.5)`` in float64, as int64"""
+    return np.floor(np.asarray(x, np.float64) * 65536.0 + 0.5).astype(np.int64)
+
+
+def _ints(name: str, v, shape, bound: int) -> np.ndarray:
+    """``v`` as an int64 array of ``shape`` whose entries are integers of magnitude at most ``bound``; None: zeros"""
+    if v is None:
+        return np.zeros(shape, np.int64)
+    try:
+        arr = np.asarray(v)
+    except ValueError:
+        arr = np.zeros((0,))
+    if arr.shape != shape or arr.dtype.kind not in "iu":
+        raise ValueError(f"{name} {v!r}: expected {' x '.join(str(s) for s in shape)} integers")
+    arr = arr.astype(np.int64)
+    if (np.abs(arr) > bound).any():
+        raise ValueError(f"{name}: {int(arr.flat[int(np.abs(arr).argmax())])} is outside -{bound}..{bound}")
+    return arr
+
+
+def _colour_coef(M, K, O, lut) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """the 15 int32 of ``vip_colour_rgb_u8`` (M row by row, K, O) and the table as 256 uint8 or None, validated"""
+    if M is None:
+        raise ValueError("M None: expected 3 x 3 integers")
+    coef = np.concatenate([_ints("M", M, (3, 3), COLOUR_M_MAX).ravel(), _ints("K", K, (3,), COLOUR_M_MAX),
+                           _ints("O", O, (3,), COLOUR_O_MAX)]).astype(np.int32)
+    if lut is not None:
+        lut = _ints("lut", lut, (256,), 255)
+        if (lut < 0).any():
+            raise ValueError(f"lut: {int(lut.min())} is outside 0..255")
+        lut = lut.astype(np.uint8)
+    return coef, lut
+
+
+def colour(batch: DecodedBatch, M, K=None, O=None, lut=None, mean: Optional[torch.Tensor] = None) -> DecodedBatch:
+    """The general colour transform: every pixel (R, G, B) of image i becomes, per output channel c and in 32-bit integers,
+    ``v = clamp((M[c][0] R + M[c][1] G + M[c][2] B + K[c] mean_i[c] + O[c] + 32768) >> 16, 0, 255)`` and then ``lut[v]`` when a table is
+    given (``vip_colour_rgb_u8``, one launch; include/vipcup_hip.h).  ``M`` 3 x 3 and ``K`` Q16 integers of magnitude at most 2^18,
+    ``O`` Q16 integers of magnitude at most 2^25, ``lut`` 256 integers in 0..255; ``mean_i`` is the image's own rounded mean colour,
+    ``batch.mean_colour()`` - computed here only when some ``K`` is not 0 and ``mean`` (that tensor, from an earlier call) is not given.
+    Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched.  Runs on the current stream; the
+    coefficients travel as kernel arguments, a table is copied to the device once and cached (the 32 tables used last)."""
+    coef, lut = _colour_coef(M, K, O, lut)
+    return _colour_into(batch, coef, lut, mean, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+
+
+def _colour_into(batch: DecodedBatch, coef: np.ndarray, lut: Optional[np.ndarray], mean: Optional[torch.Tensor],
+                 rgb: torch.Tensor) -> DecodedBatch:
+    """``colour``'s launch: image i of ``batch`` into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8 on the batch's device, slots at
+    least as large as the images; only the pixels of the images are written)."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    assert coef.dtype == np.int32 and coef.shape == (15,) and coef.flags.c_contiguous
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
+    if coef[9:12].any():
+        if mean is None:
+            mean = batch.mean_colour()
+        assert mean.dtype == torch.uint8 and tuple(mean.shape) == (n, 4) and mean.is_contiguous() and mean.device == device
+    else:
+        mean = None
+    lut_d = None
+    if lut is not None:
+        key = (torch.cuda.current_device() if device.index is None else device.index, lut.tobytes())
+        lut_d = _LUT_DEV.pop(key, None)
+        if lut_d is None:
+            lut_d = torch.from_numpy(lut.copy()).to(device)
+        _LUT_DEV[key] = lut_d                           # most recently used last
+        while len(_LUT_DEV) > _LUT_DEV_MAX:
+            del _LUT_DEV[next(iter(_LUT_DEV))]
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    _launch("vip_colour_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+            coef.ctypes.data_as(C.c_void_p), _p(mean), _p(lut_d), n)
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
+def _identity_q16() -> np.ndarray:
+    return np.eye(3, dtype=np.int64) << 16
+
+
+def colour_gray():
+    """``(M, K, O, lut)`` of ``gray``: every output channel Pillow's ``convert("L")`` luma, ``(19595 R + 38470 G + 7471 B + 32768) >> 16``"""
+    return np.array([GRAY_Q16] * 3, np.int64), None, None, None
+
+
+def colour_bgr():
+    """``(M, K, O, lut)`` of ``bgr``: the channels reversed, an exact copy"""
+    return _identity_q16()[::-1].copy(), None, None, None
+
+
+def colour_hue(degrees: int):
+    """``(M, K, O, lut)`` of ``hue``: ``M = q(inv(T) R(theta) T)``, ``T`` the NTSC YIQ matrix, ``R`` the rotation of the (I, Q) plane by
+    ``degrees`` (a non-zero integer in -180..180), ``q(x) = floor(x * 65536 + 0.5)`` - the LINEAR form of a hue shift"""
+    d = _int_arg("degrees", degrees, -180, 180)
+    if d == 0:
+        raise ValueError(f"degrees {degrees!r}: expected a non-zero integer in -180..180")
+    T = np.array(YIQ, np.float64)
+    t = np.deg2rad(np.float64(d))
+    R = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(t), -np.sin(t)], [0.0, np.sin(t), np.cos(t)]], np.float64)
+    return _q16(np.linalg.inv(T) @ R @ T), None, None, None
+
+
+def _percent_not_100(name: str, percent) -> float:
+    p = _int_arg(name, percent, 0, 200)
+    if p == 100:
+        raise ValueError(f"{name} {percent!r}: expected an integer in 0..200 other than 100")
+    return p / 100.0
+
+
+def colour_saturation(percent: int):
+    """``(M, K, O, lut)`` of ``saturation``: ``M = q(f I + (1 - f) [w; w; w])`` with ``f = percent / 100`` (an integer in 0..200, not
+    100) and ``w`` the luma weights (19595, 38470, 7471) / 65536 - a blend with the gray image, the LINEAR form; 0 is ``colour_gray``"""
+    f = _percent_not_100("percent", percent)
+    w = np.array(GRAY_Q16, np.float64) / 65536.0
+    return _q16(f * np.eye(3) + (1.0 - f) * np.tile(w, (3, 1))), None, None, None
+
+
+def colour_contrast(percent: int):
+    """``(M, K, O, lut)`` of ``contrast``: ``M = q(f I)``, ``K = q(1 - f)`` on every channel, ``f = percent / 100`` (an integer in
+    0..200, not 100): ``(x - mean_c) f + mean_c`` with the image's own per-channel mean, ``tf.image.adjust_contrast``"""
+    f = _percent_not_100("percent", percent)
+    return _q16(f * np.eye(3)), _q16([1.0 - f] * 3), None, None
+
+
+def colour_brightness(percent: int):
+    """``(M, K, O, lut)`` of ``brightness``: the identity and ``O = q(percent / 100 * 255)`` (a non-zero integer in -50..50): a delta in
+    units of full scale, ``tf.image.adjust_brightness``"""
+    p = _int_arg("percent", percent, -50, 50)
+    if p == 0:
+        raise ValueError(f"percent {percent!r}: expected a non-zero integer in -50..50")
+    return _identity_q16(), None, _q16([p / 100.0 * 255.0] * 3), None
+
+
+def _gamma_hundredths(g) -> int:
+    ok = not isinstance(g, bool) and isinstance(g, (int, float, np.integer, np.floating)) and np.isfinite(g)
+    hundredths = int(round(float(g) * 100)) if ok else 0
+    if not ok or not 50 <= hundredths <= 200 or hundredths == 100 or abs(float(g) * 100 - hundredths) > 1e-6:
+        raise ValueError(f"gamma {g!r}: expected a decimal in 0.50..2.00 with at most two fractional digits, other than 1")
+    return hundredths
+
+
+def colour_gamma(g: float):
+    """``(M, K, O, lut)`` of ``gamma``: the identity and ``lut[v] = floor(255 (v / 255) ** g + 0.5)`` (``g`` in 0.50..2.00 with two
+    decimals, not 1; below 1 brightens), ``tf.image.adjust_gamma``"""
+    g = _gamma_hundredths(g) / 100.0
+    lut = np.floor(255.0 * (np.arange(256, dtype=np.float64) / 255.0) ** g + 0.5).astype(np.int64)
+    return _identity_q16(), None, None, lut
+
+
+def gray(batch: DecodedBatch) -> DecodedBatch:
+    """The batch as gray images in three equal channels - dataset/augment.py:142-146 ``RandomGray`` on the decoded pixels at their own
+    size, with Pillow's integer luma.  (``apply_augment``'s ``gray`` flag works on resized float inputs; this output can go into
+    ``recompress``.)  Returns a new batch; ``batch`` is not touched."""
+    return colour(batch, *colour_gray())
+
+
+def bgr(batch: DecodedBatch) -> DecodedBatch:
+    """The batch with red and blue exchanged - dataset/augment.py:148-151 ``RandomBGR``; an exact copy.  Returns a new batch."""
+    return colour(batch, *colour_bgr())
+
+
+def hue(batch: DecodedBatch, degrees: int) -> DecodedBatch:
+    """The batch with its chroma rotated by ``degrees`` (``colour_hue``: a rotation in the YIQ plane, not ``tf.image``'s HSV round
+    trip; gray pixels stay as they are) - dataset/augment.py:122-129 ``RandomJitter``.  Returns a new batch."""
+    return colour(batch, *colour_hue(degrees))
+
+
+def saturation(batch: DecodedBatch, percent: int) -> DecodedBatch:
+    """The batch at ``percent`` % of its saturation (``colour_saturation``: a blend with the luma image, not ``tf.image``'s HSV round
+    trip; 0 is ``gray``, above 100 clips) - dataset/augment.py:122-129.  Returns a new batch."""
+    return colour(batch, *colour_saturation(percent))
+
+
+def contrast(batch: DecodedBatch, percent: int, mean: Optional[torch.Tensor] = None) -> DecodedBatch:
+    """The batch at ``percent`` % of its contrast about each image's own mean colour (``colour_contrast``; the mean is
+    ``batch.mean_colour()``, or ``mean`` when the caller has it already) - dataset/augment.py:122-129.  Returns a new batch."""
+    return colour(batch, *colour_contrast(percent), mean=mean)
+
+
+def brightness(batch: DecodedBatch, percent: int) -> DecodedBatch:
+    """The batch with ``percent`` % of full scale added to every sample (``colour_brightness``) - dataset/augment.py:122-129.  Returns
+    a new batch."""
+    return colour(batch, *colour_brightness(percent))
+
+
+def gamma(batch: DecodedBatch, g: float) -> DecodedBatch:
+    """The batch under ``out = 255 (in / 255) ** g`` through a 256-entry table (``colour_gamma``).  Returns a new batch."""
+    return colour(batch, *colour_gamma(g))
+
+
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
     """Deterministic form of dataset/augment.py ``apply_augment`` (:153-182): per-image flags instead of the
     reference's TF RNG draws (p=0.8 gate, hflip .5, vflip .5, gray .3) — the caller owns the randomness."""
