@@ -511,6 +511,54 @@ int vip_warp_affine_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int m
 int vip_colour_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
                       const int32_t* coef_h, const uint8_t* mean_u8, const uint8_t* lut_d, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Noise on decoded u8 RGB: additive Gaussian (per channel, or one sample on all three channels), multiplicative speckle and
+ * salt-and-pepper impulses, in integer arithmetic from a counter-based generator - the one kernel under the noise stress perturbations.
+ * dataset/augment.py has no noise augmentation; this goes beyond the reference.  Every image keeps its size.
+ *
+ * vip_noise_rgb_u8 (device, caller's stream, one launch per batch): src_u8 [n][maxH][maxW][3] with image i in the top-left
+ *   sizes_hw[i] = (h, w) corner of its slot -> dst_u8 [n][dstMaxH][dstMaxW][3], image i in the same corner of its slot (a pitch of its
+ *   own); the two must not overlap.  mode 0 gaussian, 1 mono, 2 speckle, 3 impulse; amount: the integer a (modes 0..2) or thr (mode 3)
+ *   below; seed: one word for the run; keys_u32: uint32 [n] on the device, one word per image (the tools use zlib's crc32 of the file's
+ *   basename); table_i32: int32 [4097] on the device, the table T below (NULL is admitted in mode 3, which reads none).
+ *   Random words.  Philox4x32-10: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants 0x9E3779B9 and 0xBB67AE85, ten rounds, the key
+ *   bumped between rounds.  Pixel (x, y) of image i, IN THE IMAGE'S OWN COORDINATES, has the counter (x, y, 0, 0) and the key
+ *   (seed, keys_u32[i]); the four output words are w0..w3.  The field depends on seed, key and pixel position only - not on mode,
+ *   amount, batch index, slot pitch or batch size: two amounts see the same field at two gains, and an image keeps its noise wherever
+ *   it sits in whatever batch.
+ *   Standard normal, Q12.  T[i] = round(4096 Phi^-1(i / 4096)) for 0 < i < 4096, T[0] = -16384, T[4096] = 16384, built by the caller in
+ *   float64 (odd-symmetric, increasing, largest step 2101), and
+ *     z(w) = T[w >> 20] + (((T[(w >> 20) + 1] - T[w >> 20]) * ((w >> 5) & 0x7FFF) + 16384) >> 15)
+ *   the inverse CDF, linear inside each of the 4096 bins and cut at +-4 (std of the law 1.000034, kurtosis 2.9998); the product is
+ *   below 2101 * 32767 + 16384 < 2^27.
+ *   Modes.  Signed 32-bit integers, arithmetic shifts (floor, also for a negative sum), X the input sample:
+ *     0 gaussian  out_c = clamp(X_c + ((a z(w_c) + 2^19) >> 20), 0, 255), c = 0, 1, 2
+ *                 a = round(256 sigma), sigma 0.5..50.0 levels in steps of 0.1: 128 <= a <= 12800; |a z| <= 12800 * 16384 < 2^28
+ *     1 mono      mode 0 with z(w0) on all three channels (luminance noise); a as in mode 0
+ *     2 speckle   out_c = clamp(X_c + ((X_c a z(w_c) + 2^19) >> 20), 0, 255)
+ *                 a = round(256 P / 100), P = 1..50 percent: 3 <= a <= 128; |X a z| <= 255 * 128 * 16384 < 2^29
+ *     3 impulse   if w3 < thr (unsigned) all three channels become (w2 & 1) ? 255 : 0, otherwise the pixel is copied
+ *                 thr = round(P / 100 * 2^32), P = 0.1..50.0 percent in steps of 0.1: 4294967 <= thr <= 2^31
+ *   No sum leaves 32 bits.
+ *   Only the h x w pixels of an image are written: the rest of dst_u8 keeps what the caller put there, and nothing but the images'
+ *   pixels is read.  An image whose size is not positive or exceeds the source or the destination slot is skipped.  Null src_u8,
+ *   sizes_hw, dst_u8 or keys_u32, null table_i32 in modes 0..2, n or a slot side not positive, src_u8 and dst_u8 overlapping, a mode
+ *   outside 0..3, an amount outside its mode's range -> VIP_ERR_BAD_ARG; sizes_hw, keys_u32 or table_i32 not 4-byte aligned ->
+ *   VIP_ERR_ALIGNMENT; all before any work: a refused call launches nothing.
+ *   A workgroup owns 128 pixels x 8 rows and moves them as vip_colour_rgb_u8 does: aligned dwords of the source into an LDS image that
+ *   keeps each row's byte phase, one pixel per lane into a second LDS image at the destination row's phase, aligned dwords out; heads
+ *   and tails of rows byte by byte.  T is either gathered from global memory through the vector L1, one tile per workgroup, or copied
+ *   into LDS by a workgroup that then loops over 8 consecutive tiles; vip_noise_rgb_u8 uses the gathers, which measured faster
+ *   (README.md).  Mode 3 reads no table and copies none.  No allocation, no atomics: bit-reproducible.
+ * vip_noise_rgb_u8_placed: the same with the table's placement chosen by the caller (0: global gathers, 1: the LDS copy; anything
+ *   else -> VIP_ERR_BAD_ARG), for the benchmark (tools/bench_noise.py) and the tests; both placements write the same bytes.
+ * ------------------------------------------------------------------------------------------ */
+int vip_noise_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                     int mode, int64_t amount, uint32_t seed, const uint32_t* keys_u32, const int32_t* table_i32, int n, void* stream);
+int vip_noise_rgb_u8_placed(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                            int mode, int64_t amount, uint32_t seed, const uint32_t* keys_u32, const int32_t* table_i32, int placement,
+                            int n, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

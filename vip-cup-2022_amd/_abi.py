@@ -99,6 +99,8 @@ SIGNATURES = {
     "vip_median_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "vip_warp_affine_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "vip_colour_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "vip_noise_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_int64, C.c_uint32, _vp, _vp, _i, _vp]),
+    "vip_noise_rgb_u8_placed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_int64, C.c_uint32, _vp, _vp, _i, _i, _vp]),
     "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),

@@ -482,10 +482,22 @@ def _colour_variants(gray=False, bgr=False, hues=(), saturations=(), contrasts=(
     return out
 
 
+def _noise_variants(noises=(), mono_noises=(), speckles=(), impulses=()) -> List[Tuple[str, str, object]]:
+    """``(label, kind of pipeline.noise, amount)`` of every noise variant, in row order"""
+    tenths = lambda vs: sorted(int(round(float(v) * 10)) for v in vs)   # noqa: E731
+    out = [(f"n{tt:03d}", "gaussian", tt / 10) for tt in tenths(noises)]
+    out += [(f"nm{tt:03d}", "mono", tt / 10) for tt in tenths(mono_noises)]
+    out += [(f"spk{pc:02d}", "speckle", pc) for pc in sorted(int(pc) for pc in speckles)]
+    out += [(f"imp{tt:03d}", "impulse", tt / 10) for tt in tenths(impulses)]
+    return out
+
+
 def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = (),
                   flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
                   rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
-                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = ()) -> List[str]:
+                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
+                  mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
+                  noise_keys=None) -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
     ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
     ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
@@ -496,7 +508,11 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
     ``bgr``, ``hue<DDD>`` / ``huem<DDD>`` for each angle of ``hues`` (ascending by signed angle; ``m`` marks a negative one, three digits),
     ``sat<PPP>`` and ``con<PPP>`` for each percent of ``saturations`` / ``contrasts`` (ascending, three digits), ``bri<PP>`` / ``brim<PP>``
     for each percent of ``brightnesses`` (ascending by signed value, two digits), ``gam<PPP>`` for each of ``gammas`` (ascending, ``PPP``
-    = 100 times gamma: 0.8 -> ``gam080``), each followed by its ``_q<Q>`` labels."""
+    = 100 times gamma: 0.8 -> ``gam080``), each followed by its ``_q<Q>`` labels, then the noise: ``n<TTT>`` for each sigma of ``noises``
+    and ``nm<TTT>`` for each of ``mono_noises`` (ascending, ``TTT`` = ten times sigma as three digits: 3 -> ``n030``), ``spk<PP>`` for each
+    percent of ``speckles`` (ascending, two digits), ``imp<TTT>`` for each percent of ``impulses`` (ascending, ten times the percent: 1 ->
+    ``imp010``), each followed by its ``_q<Q>`` labels (``noise_seed`` and ``noise_keys`` are ``stress_batch``'s and do not change a
+    label)."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
@@ -509,7 +525,8 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
         labels += [f"m{k}_q{int(q)}" for q in qualities]
     geometry = [f"flip{ax}" for ax in sorted(str(ax) for ax in flips)] + [f"crop{pc:02d}" for pc in sorted((int(pc) for pc in crops), reverse=True)] \
         + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
-    for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)]:
+    for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)] \
+            + [v[0] for v in _noise_variants(noises, mono_noises, speckles, impulses)]:
         labels.append(v)
         labels += [f"{v}_q{int(q)}" for q in qualities]
     return labels
@@ -519,7 +536,9 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
                  resize_filter: str = "bicubic", blurs: Sequence[float] = (), medians: Sequence[int] = (), blur_radius: Optional[int] = None,
                  flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
                  rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
-                 contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = ()):
+                 contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
+                 mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
+                 noise_keys=None):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -542,7 +561,13 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     scale) and ``gammas`` (each list ascending here) the decoded batch is also recoloured (``pipeline.gray`` / ``bgr`` / ``hue`` /
     ``saturation`` / ``contrast`` / ``brightness`` / ``gamma``; dataset/augment.py:122-129, :142-151) and scored unsaved and re-saved at
     every quality, one coloured batch alive at a time and the batch's mean colour computed at most once; colour is not composed with
-    resizing, smoothing or geometry.  Then too the result is ``(rows, labels)``, ``labels`` = ``stress_labels`` of the same keywords."""
+    resizing, smoothing or geometry.  Then too the result is ``(rows, labels)``, ``labels`` = ``stress_labels`` of the same keywords.
+    With ``noises`` / ``mono_noises`` (sigmas in levels), ``speckles`` and ``impulses`` (percents; each list ascending here) the decoded
+    batch also gets Gaussian noise per channel, Gaussian luminance noise, speckle and salt-and-pepper impulses (``pipeline.noise``) and is
+    scored unsaved and re-saved at every quality, one noisy batch alive at a time; noise is not composed with the other families.
+    ``noise_seed`` and ``noise_keys`` (one integer per image, None: 0..n-1; ``pipeline.noise_keys`` of the file names makes a file's noise
+    independent of its batch) select the random field, which all noise variants of a batch share.  Then too the result is ``(rows,
+    labels)``."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
@@ -582,12 +607,20 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(coloured, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(coloured, int(q), subsampling), members))
+    noisy = _noise_variants(noises, mono_noises, speckles, impulses)
+    keys_d = pipeline.noise_keys_device(batch, noise_keys) if noisy else None                      # once per batch
+    for _, kind, arg in noisy:
+        grainy = pipeline.noise(batch, kind, arg, noise_seed, keys_d)                              # one alive at a time
+        rows.append(_score_batch(grainy, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(grainy, int(q), subsampling), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours:
+    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours and not noisy:
         return torch.stack(rows)
     return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations, gray=gray, bgr=bgr, hues=hues,
-                                            saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas)
+                                            saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas,
+                                            noises=noises, mono_noises=mono_noises, speckles=speckles, impulses=impulses)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -622,7 +655,7 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
     ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``,
     ``flip<A>...``, ``crop<PP>...``, ``rot<TTT>...``, ``gray...``, ``bgr...``, ``hue<DDD>...``, ``sat<PPP>...``, ``con<PPP>...``,
-    ``bri<PP>...``, ``gam<PPP>...``).
+    ``bri<PP>...``, ``gam<PPP>...``, ``n<TTT>...``, ``nm<TTT>...``, ``spk<PP>...``, ``imp<TTT>...``).
     With ``q`` labels alone the result is the one above.  With rescaled, smoothed or warped variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
     all variants, ``stable`` is taken over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only),
     ``table`` gains ``labels`` and ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants``

@@ -11,6 +11,8 @@
                                      [--stress-rotate D[,D...] --stress-out FILE.csv [--stress-rotate-fill crop|mirror|black]]
                                      [--stress-gray] [--stress-bgr] [--stress-hue D[,D...]] [--stress-saturation P[,P...]]
                                      [--stress-contrast P[,P...]] [--stress-brightness P[,P...]] [--stress-gamma G[,G...]]   (--stress-out FILE.csv)
+                                     [--stress-noise S[,S...]] [--stress-noise-mono S[,S...]] [--stress-speckle P[,P...]]
+                                     [--stress-impulse P[,P...]] [--stress-noise-seed N]                                     (--stress-out FILE.csv)
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
                                                       [--occlusion-format npy|png] [--occlusion-members]]
@@ -64,6 +66,17 @@ colour, ``(x - mean) f + mean``; ``bri<PP>`` / ``brim<PP>``: PP % of full scale 
 at every quality (``<label>_q<Q>``); the rows follow those of ``--stress-rotate`` in this order, each list ascending.  Colour is not
 combined with resizing, smoothing or geometry.  ``stress.json`` then lists ``gray``, ``bgr``, ``hues``, ``saturations``, ``contrasts``,
 ``brightnesses`` and ``gammas`` under ``settings``.  (A list that starts with a negative value is written ``--stress-hue=-30,30``.)
+``--stress-noise 1,3,10``, ``--stress-noise-mono 3``, ``--stress-speckle 5,20`` and ``--stress-impulse 0.5,2`` (all with ``--stress-out
+stress.csv``) are the noise perturbations - the reference has none - on the decoded image at its own size, per pixel and in integers:
+``n<TTT>``: Gaussian noise of sigma = TTT / 10 levels (0.5..50.0 in steps of 0.1) on every channel independently, ``clamp(X + ((a z +
+2^19) >> 20), 0, 255)`` with ``a = round(256 sigma)`` and z a Q12 standard normal; ``nm<TTT>``: one such sample on all three channels
+(luminance noise); ``spk<PP>``: speckle, every sample times ``1 + PP / 100 z`` (integer percents 1..50); ``imp<TTT>``: TTT / 10 percent
+of the pixels (0.1..50.0 in steps of 0.1) black or white.  The random words are Philox4x32-10 of the pixel's position under the key
+(``--stress-noise-seed`` N, default 0; crc32 of the file's basename): a file gets the same noise at any place in the CSV, at any batch
+size, on any rank, in every run, and all listed amounts see the same field at different gains.  Each is scored unsaved and, with
+``--stress-jpeg``, re-saved at every quality (``<label>_q<Q>``); the rows follow those of the colour flags in this order, each list
+ascending; a value listed twice is refused.  Noise is not combined with the other families.  ``stress.json`` then lists
+``noise_sigmas``, ``noise_mono_sigmas``, ``speckles``, ``impulses`` and ``noise_seed`` under ``settings``.
 ``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
 it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
 last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
@@ -156,18 +169,19 @@ def _heatmap_writer(a, names, members, rank):
 
 
 def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None,
-                   colour=None):
+                   colour=None, noise=None, names=None):
     """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
     ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None) and the colour flags (``colour``:
-    likewise): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
+    likewise) and the noise flags (``noise``: likewise; every batch's ``noise_keys`` come from its files' ``names``): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
     in batch order) until the run's one extra collective"""
-    from vipcup_amd import ensemble
+    from vipcup_amd import ensemble, pipeline
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians or geometry or colour:
+        if scales or blurs or medians or geometry or colour or noise:
+            keyed = dict(noise, noise_keys=pipeline.noise_keys(names[b0:b1])) if noise else {}     # by file, not by batch position
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
                                             resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius,
-                                            **(geometry or {}), **(colour or {}))
+                                            **(geometry or {}), **(colour or {}), **keyed)
         else:
             rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
@@ -175,13 +189,14 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None):
+def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None,
+                  noise=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}), **(colour or {}))
-    mixed = bool(scales or blurs or medians or geometry or colour)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}), **(colour or {}), **(noise or {}))
+    mixed = bool(scales or blurs or medians or geometry or colour or noise)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -207,6 +222,9 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         summary["settings"].update(geometry)
     if colour:
         summary["settings"].update(colour)
+    if noise:
+        summary["settings"].update({"noise_sigmas": noise["noises"], "noise_mono_sigmas": noise["mono_noises"], "speckles": noise["speckles"],
+                                    "impulses": noise["impulses"], "noise_seed": noise["noise_seed"]})
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
 
@@ -327,6 +345,18 @@ def _int_list(flag, text, lo, hi, banned, what):
     return given
 
 
+def _tenths_list(flag, text, lo, hi, what):
+    """``--stress-noise`` and its kin: a comma-separated list of decimals with at most one fractional digit, as tenths in lo..hi,
+    ascending; a value listed twice is refused"""
+    tokens = text.split(",")
+    if not all(re.fullmatch(r"\d{1,2}(\.\d)?", t) for t in tokens):
+        tokens = []
+    given = sorted(int(t.replace(".", "")) if "." in t else 10 * int(t) for t in tokens)
+    if not given or given[0] < lo or given[-1] > hi or len(set(given)) != len(given):
+        raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of {what}, each listed once")
+    return given
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("input_csv")
@@ -436,6 +466,26 @@ def main(argv=None):
                     help="colour stress test: also score every image under 255 (x / 255) ** G for each listed G (decimals in 0.50..2.00 with "
                          "at most two fractional digits, other than 1; ascending; below 1 brightens; tf.image.adjust_gamma); labels "
                          "gam<PPP>, gam<PPP>_q<Q> with PPP = 100 G; needs --stress-out")
+    ap.add_argument("--stress-noise", default=None, metavar="S[,S...]",
+                    help="noise stress test: also score every image with Gaussian noise of each listed sigma (levels, 0.5..50.0 with at "
+                         "most one fractional digit; ascending; a value listed twice is refused) added to every channel independently, "
+                         "unsaved and - with --stress-jpeg - re-saved at every quality; integer arithmetic from Philox4x32-10 keyed by "
+                         "--stress-noise-seed and the crc32 of the file's basename, so a file gets the same noise in any order, batch "
+                         "size or rank; needs --stress-out, whose table gains the labels n<TTT>, n<TTT>_q<Q> (TTT = ten times sigma)")
+    ap.add_argument("--stress-noise-mono", default=None, metavar="S[,S...]",
+                    help="noise stress test: as --stress-noise with ONE sample per pixel on all three channels (luminance noise); labels "
+                         "nm<TTT>, nm<TTT>_q<Q>; needs --stress-out")
+    ap.add_argument("--stress-speckle", default=None, metavar="P[,P...]",
+                    help="noise stress test: also score every image with every sample multiplied by 1 + P / 100 z, z standard normal "
+                         "(integer percents in 1..50; ascending; a value listed twice is refused); labels spk<PP>, spk<PP>_q<Q>; needs "
+                         "--stress-out")
+    ap.add_argument("--stress-impulse", default=None, metavar="P[,P...]",
+                    help="noise stress test: also score every image with each listed percent of its pixels (0.1..50.0 with at most one "
+                         "fractional digit; ascending; a value listed twice is refused) turned black or white, half each; labels "
+                         "imp<TTT>, imp<TTT>_q<Q> (TTT = ten times the percent); needs --stress-out")
+    ap.add_argument("--stress-noise-seed", type=int, default=0, metavar="N",
+                    help="the seed of the noise stress tests' random field (0..4294967295, default 0); needs one of --stress-noise, "
+                         "--stress-noise-mono, --stress-speckle, --stress-impulse")
     ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
                     help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
                          "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
@@ -466,7 +516,9 @@ def main(argv=None):
     colour_flags = (("--stress-gray", a.stress_gray or None), ("--stress-bgr", a.stress_bgr or None), ("--stress-hue", a.stress_hue),
                     ("--stress-saturation", a.stress_saturation), ("--stress-contrast", a.stress_contrast),
                     ("--stress-brightness", a.stress_brightness), ("--stress-gamma", a.stress_gamma))
-    any_colour = any(v is not None for _, v in colour_flags)
+    noise_flags = (("--stress-noise", a.stress_noise), ("--stress-noise-mono", a.stress_noise_mono), ("--stress-speckle", a.stress_speckle),
+                   ("--stress-impulse", a.stress_impulse))
+    any_colour = any(v is not None for _, v in colour_flags + noise_flags)       # colour or noise: the same refusals below
     if a.occlusion is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
@@ -586,9 +638,33 @@ def main(argv=None):
         if not gammas or gammas[0] < 50 or gammas[-1] > 200 or 100 in gammas:
             raise SystemExit(f"vipcup_amd main: --stress-gamma {a.stress_gamma!r}: expected a comma-separated list of decimals in 0.50..2.00 "
                              "with at most two fractional digits, other than 1")
+    noise = None
+    if any(v is not None for _, v in noise_flags):
+        noise = {"noises": [], "mono_noises": [], "speckles": [], "impulses": [], "noise_seed": a.stress_noise_seed}      # sigmas and percents
+        if a.stress_noise is not None:
+            noise["noises"] = [t / 10 for t in _tenths_list("--stress-noise", a.stress_noise, 5, 500, "sigmas in 0.5..50.0 with at most "
+                                                            "one fractional digit")]
+        if a.stress_noise_mono is not None:
+            noise["mono_noises"] = [t / 10 for t in _tenths_list("--stress-noise-mono", a.stress_noise_mono, 5, 500, "sigmas in 0.5..50.0 "
+                                                                 "with at most one fractional digit")]
+        if a.stress_speckle is not None:
+            tokens = a.stress_speckle.split(",")
+            given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,2}", t) for t in tokens) else []
+            if not given or given[0] < 1 or given[-1] > 50 or len(set(given)) != len(given):
+                raise SystemExit(f"vipcup_amd main: --stress-speckle {a.stress_speckle!r}: expected a comma-separated list of integer "
+                                 "percents in 1..50, each listed once")
+            noise["speckles"] = given
+        if a.stress_impulse is not None:
+            noise["impulses"] = [t / 10 for t in _tenths_list("--stress-impulse", a.stress_impulse, 1, 500, "percents in 0.1..50.0 with at "
+                                                              "most one fractional digit")]
+        if not 0 <= a.stress_noise_seed <= 0xFFFFFFFF:
+            raise SystemExit(f"vipcup_amd main: --stress-noise-seed {a.stress_noise_seed}: expected an integer in 0..4294967295")
+    elif a.stress_noise_seed != 0:
+        raise SystemExit("vipcup_amd main: --stress-noise-seed needs --stress-noise, --stress-noise-mono, --stress-speckle or --stress-impulse")
     for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
                               ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
-                              ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags):
+                              ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags) \
+            + tuple((flag, v, "noise") for flag, v in noise_flags):
         if given is None:
             continue
         if a.stress_out is None:
@@ -605,10 +681,10 @@ def main(argv=None):
         geometry = {"flips": flips or [], "crops": crops or [], "crop_origin": a.stress_crop_origin,
                     "rotations": [t / 10 for t in angles or []], "rotate_fill": a.stress_rotate_fill}
     colour = None
-    if any_colour:
+    if any(v is not None for _, v in colour_flags):
         colour = {"gray": bool(a.stress_gray), "bgr": bool(a.stress_bgr), "hues": hues or [], "saturations": sats or [],
                   "contrasts": cons or [], "brightnesses": bris or [], "gammas": [hh / 100 for hh in gammas or []]}
-    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None
+    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None or noise is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -728,7 +804,8 @@ def main(argv=None):
     blurs = None if sigmas is None else [t / 10 for t in sigmas]
     if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
-                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour)
+                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour,
+                                      noise, names)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -747,7 +824,8 @@ def main(argv=None):
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
     if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {}), **(colour or {})))
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {}), **(colour or {}),
+                                            **(noise or {})))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -763,7 +841,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour)
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour, noise)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

@@ -991,6 +991,142 @@ def gamma(batch: DecodedBatch, g: float) -> DecodedBatch:
     return colour(batch, *colour_gamma(g))
 
 
+NOISE_KINDS = {"gaussian": 0, "mono": 1, "speckle": 2, "impulse": 3}       # the modes of vip_noise_rgb_u8 (include/vipcup_hip.h)
+_NOISE_TABLE: List[np.ndarray] = []
+_NOISE_TABLE_DEV: Dict[int, torch.Tensor] = {}
+
+
+def noise_table() -> np.ndarray:
+    """The Q12 inverse normal CDF of ``vip_noise_rgb_u8``: int32 ``[4097]`` (read-only), ``T[i] = round(4096 Phi^-1(i / 4096))`` for
+    0 < i < 4096 in float64 (the lower half computed, the upper half its mirror image), ``T[0] = -16384``, ``T[4096] = 16384``.
+    Built once; ``noise`` keeps one copy per device."""
+    if not _NOISE_TABLE:
+        from statistics import NormalDist
+        inv = NormalDist().inv_cdf
+        t = np.zeros(4097, np.int32)
+        for i in range(1, 2049):
+            t[i] = math.floor(4096.0 * inv(i / 4096.0) + 0.5)
+            t[4096 - i] = -t[i]
+        t[0], t[4096] = -16384, 16384
+        t.setflags(write=False)
+        _NOISE_TABLE.append(t)
+    return _NOISE_TABLE[0]
+
+
+def _tenths(name: str, v, lo: int, hi: int) -> int:
+    """``v`` as tenths: a number in lo / 10 .. hi / 10 with at most one fractional digit"""
+    ok = not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    tenths = int(round(float(v) * 10)) if ok else 0
+    if not ok or not lo <= tenths <= hi or abs(float(v) * 10 - tenths) > 1e-6:
+        raise ValueError(f"{name} {v!r}: expected a number in {lo / 10}..{hi / 10} with at most one fractional digit")
+    return tenths
+
+
+def noise_amount(kind: str, amount) -> int:
+    """The integer ``vip_noise_rgb_u8`` takes for ``amount`` in the user's units, in exact integer arithmetic: ``a = round(256 sigma)``
+    for "gaussian" and "mono" (sigma in levels, 0.5..50.0 in steps of 0.1), ``a = round(256 P / 100)`` for "speckle" (an integer
+    percent in 1..50), ``thr = round(P / 100 * 2^32)`` for "impulse" (percent, 0.1..50.0 in steps of 0.1).  None of them meets a tie."""
+    if kind not in NOISE_KINDS:
+        raise ValueError(f"kind {kind!r}: expected one of {', '.join(NOISE_KINDS)}")
+    if kind == "speckle":
+        return (256 * _int_arg("percent", amount, 1, 50) + 50) // 100
+    if kind == "impulse":
+        return ((_tenths("percent", amount, 1, 500) << 32) + 500) // 1000
+    return (256 * _tenths("sigma", amount, 5, 500) + 5) // 10
+
+
+def noise_keys(names: Sequence[str]) -> List[int]:
+    """One generator key per file: ``zlib.crc32`` of the basename's UTF-8 bytes - a file keeps its noise whatever directory it is read
+    from, wherever it stands in the CSV and whatever batch or rank it falls into"""
+    import zlib
+    return [zlib.crc32(os.path.basename(str(name)).encode("utf-8")) & 0xFFFFFFFF for name in names]
+
+
+def _noise_keys_arg(keys, n: int) -> np.ndarray:
+    """``keys`` as uint32 ``[n]``; None: 0..n-1"""
+    if keys is None:
+        return np.arange(n, dtype=np.uint32)
+    try:
+        arr = np.asarray(keys)
+    except ValueError:
+        arr = np.zeros((0,))
+    if arr.shape != (n,) or arr.dtype.kind not in "iu" or (n and (int(arr.min()) < 0 or int(arr.max()) > 0xFFFFFFFF)):
+        raise ValueError(f"keys {keys!r}: expected {n} integers in 0..2^32-1, one per image")
+    return arr.astype(np.uint32)
+
+
+def noise(batch: DecodedBatch, kind: str, amount, seed: int = 0, keys=None) -> DecodedBatch:
+    """Noise on every image of the batch (``vip_noise_rgb_u8``, one launch; include/vipcup_hip.h has the arithmetic): ``kind``
+    "gaussian" (``amount`` = sigma in levels, an independent sample per channel), "mono" (one sample on all three channels), "speckle"
+    (``amount`` = percent: every sample is multiplied by 1 + P / 100 z) or "impulse" (``amount`` = percent of the pixels that turn black
+    or white); ranges as ``noise_amount``.  The random field is Philox4x32-10 of the pixel's position in its own image under the key
+    (``seed``, ``keys[i]``): ``seed`` an integer in 0..2^32-1, ``keys`` one such integer per image (None: 0..n-1; ``noise_keys`` makes
+    them from file names) or the int32 device tensor an earlier ``noise_keys_device`` returned.  The same image with the same seed and
+    key gets the same pixels in any batch.  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched.
+    Runs on the current stream."""
+    a = noise_amount(kind, amount)
+    seed = _int_arg("seed", seed, 0, 0xFFFFFFFF)
+    keys_d = keys if isinstance(keys, torch.Tensor) else noise_keys_device(batch, keys)
+    return _noise_into(batch, NOISE_KINDS[kind], a, seed, keys_d, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+
+
+def noise_keys_device(batch: DecodedBatch, keys=None) -> torch.Tensor:
+    """``keys`` (as for ``noise``) on the batch's device: int32 ``[n]`` holding the 32-bit words, for several ``noise`` calls on one batch"""
+    host = _noise_keys_arg(keys, len(batch))
+    return torch.from_numpy(host.view(np.int32).copy()).to(batch.rgb.device)
+
+
+def _noise_into(batch: DecodedBatch, mode: int, a: int, seed: int, keys_d: torch.Tensor, rgb: torch.Tensor,
+                placement: Optional[int] = None) -> DecodedBatch:
+    """``noise``'s launch: image i of ``batch`` into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8 on the batch's device, slots at
+    least as large as the images; only the pixels of the images are written).  ``placement``: None, or the table placement of
+    ``vip_noise_rgb_u8_placed`` (tools/bench_noise.py)."""
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
+    if keys_d.dtype != torch.int32 or tuple(keys_d.shape) != (n,) or not keys_d.is_contiguous() or keys_d.device != device:
+        raise ValueError(f"keys: expected a contiguous int32 [{n}] tensor on {device}, got {keys_d.dtype} {tuple(keys_d.shape)} on "
+                         f"{keys_d.device}")
+    table_d = None
+    if mode != NOISE_KINDS["impulse"]:                  # the impulses read no table
+        key = torch.cuda.current_device() if device.index is None else device.index
+        if key not in _NOISE_TABLE_DEV:
+            _NOISE_TABLE_DEV[key] = torch.from_numpy(noise_table().copy()).to(device)
+        table_d = _NOISE_TABLE_DEV[key]
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), mode, a, seed, _p(keys_d), _p(table_d))
+    if placement is None:
+        _launch("vip_noise_rgb_u8", *args, n)
+    else:
+        _launch("vip_noise_rgb_u8_placed", *args, int(placement), n)
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
+def gaussian_noise(batch: DecodedBatch, sigma: float, seed: int = 0, keys=None) -> DecodedBatch:
+    """The batch with Gaussian noise of standard deviation ``sigma`` levels (0.5..50.0 in steps of 0.1) added to every channel
+    independently, rounded and clamped: sensor-like noise.  ``noise(batch, "gaussian", ...)``.  Returns a new batch."""
+    return noise(batch, "gaussian", sigma, seed, keys)
+
+
+def mono_noise(batch: DecodedBatch, sigma: float, seed: int = 0, keys=None) -> DecodedBatch:
+    """The batch with ONE Gaussian sample of standard deviation ``sigma`` per pixel added to all three channels: luminance noise, the
+    chroma untouched up to the clamp.  ``noise(batch, "mono", ...)``.  Returns a new batch."""
+    return noise(batch, "mono", sigma, seed, keys)
+
+
+def speckle(batch: DecodedBatch, percent: int, seed: int = 0, keys=None) -> DecodedBatch:
+    """The batch with every sample multiplied by ``1 + percent / 100 * z``, z standard normal per channel (an integer percent in
+    1..50): multiplicative noise, strongest in the highlights.  ``noise(batch, "speckle", ...)``.  Returns a new batch."""
+    return noise(batch, "speckle", percent, seed, keys)
+
+
+def impulse(batch: DecodedBatch, percent: float, seed: int = 0, keys=None) -> DecodedBatch:
+    """The batch with ``percent`` % of its pixels (0.1..50.0 in steps of 0.1) replaced by black or white, half each: salt and pepper.
+    ``noise(batch, "impulse", ...)``.  Returns a new batch."""
+    return noise(batch, "impulse", percent, seed, keys)
+
+
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
     """Deterministic form of dataset/augment.py ``apply_augment`` (:153-182): per-image flags instead of the
     reference's TF RNG draws (p=0.8 gate, hflip .5, vflip .5, gray .3) — the caller owns the randomness."""
