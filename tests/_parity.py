@@ -37,6 +37,11 @@ TOL_ENSEMBLE_PROB = 1e-3   # fast mode: the ensemble-mean PROBABILITY main.py th
 # members), 4.8e-3 (config 4's four): fast mode does NOT meet 1e-3 on this axis either; strict mode does.
 FAST_ENSEMBLE_LOGIT_CEILING = {"ensemble": 2.5e-3, "ensemble8": 2.5e-3, "ensemble4": 6.0e-3}
 
+# The whole-member B = 256 tests hold these eight images of the batch against the oracle (eight oracle passes per member, as for
+# 0-7 before): the last M tile of every layer is in image 255, and the tiles a persistent workgroup reaches after its
+# wrap-around (the second pass over a streaming GEMM's LDS weight chunk) lie past the first eight.  One list, one set_name: the fast and the strict test share the cache.
+B256_EDGE_IMAGES = [0, 1, 2, 127, 128, 253, 254, 255]
+
 _CACHE = {}
 
 

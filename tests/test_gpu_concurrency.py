@@ -70,6 +70,13 @@ def _victims():
     cq22 = ops.make_dense_weight(torch.randn(256, 512, generator=g) / 16, torch.zeros(512))
     cpj2 = ops.make_dense_weight(torch.randn(256, 256, generator=g) / 16, torch.zeros(256))
     qgb2 = r(24, 196, 256)
+    # packed instantiations with no other entry here, at their rows of tests/_h2_gemm_cases.py: 256 x 256 pwk tiles, and the direct
+    # kernel on 256-pixel tiles ("strict conv (h2 pwk)" above is its 64-pixel form)
+    with ops.precision("strict"):
+        cw22h = ops.make_dense_weight(torch.randn(520, 1024, generator=g) / 23, torch.zeros(1024))
+        cwd2h = ops.make_dense_weight(torch.randn(128, 192, generator=g) / 11, torch.zeros(192))
+    x22h = ops.pack_h2(torch.randn(16400, 520, generator=g).cuda())
+    xd2h = ops.pack_h2(torch.randn(65535, 128, generator=g).cuda())
     from vipcup_amd import _abi
     exp = {}
     if _abi.lib().vip_experiments_built():          # the opt-in 14 x 14-window fused block (experiments build)
@@ -99,6 +106,8 @@ def _victims():
         "strict gated conv (h2)": lambda: ops.conv2d(xsh, cwh, gate=gateh),
         "strict dwconv 7x7 (h2 lds)": lambda: ops.dwconv2d(xsh, dw7, None, 7, 1, (3, 3, 3, 3)),
         "strict dense (h2 gemm8p)": lambda: ops.dense(x8h, cw8h),
+        "strict dense (h2 pwk_gemm<2,2>)": lambda: ops.dense(x22h, cw22h, act="gelu"),
+        "strict dense (h2 pwk_direct<2>)": lambda: ops.dense(xd2h, cwd2h),
     }
 
 

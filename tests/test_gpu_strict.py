@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import gcvit_ref  # noqa: E402
 from oracle import ops_ref as R  # noqa: E402
+from tests import _h2_gemm_cases as T  # noqa: E402
 from tests import _parity as P  # noqa: E402
 from tools.make_synth import synth_jpeg  # noqa: E402
 
@@ -145,6 +146,76 @@ def test_dense_pwx_h2(M, K, N, act, res, report, monkeypatch):
     assert ops.conv_kernel_name_h2(d, res) == "pwx_kernel"
     got = ops.dense(A(x, "strict"), cw, act=act, residual=A(r, "strict") if res else None)
     check(report, f"dense pwx {M}x{K}x{N}", got, R.act(R.dense(x, w, b), act) + (r if res else 0))
+
+
+def check_worst(report, name, got, ref, tol=TOL_OP):
+    """check() for a packed result that also names the row and channel of its worst element, so that a failure points at its tile"""
+    ops = _ops()
+    assert got.dtype == torch.int32 and tuple(got.shape) == tuple(ref.shape), (name, got.dtype, got.shape, ref.shape)
+    ops.h2_check(name)
+    d = ops.unpack_h2(got).cpu().reshape(-1, got.shape[-1])
+    finite = bool(torch.isfinite(d).all())
+    ref = ref.reshape(-1, ref.shape[-1])
+    scale = ref.abs().max().item() + 1e-6
+    d.sub_(ref).abs_()
+    row, ch = divmod(int(d.argmax()), d.shape[1])
+    err = d[row, ch].item()
+    report(f"[strict-ops] {name}: max_abs_err={err:.3e} at row {row} of {d.shape[0]} (256-row tile {row // 256}), channel {ch} "
+           f"ref_absmax={scale:.3e} rel={err / scale:.3e}")
+    assert finite, name
+    assert err <= tol * scale, f"{name}: err {err} > {tol}*{scale} at row {row}, channel {ch}"
+
+
+@pytest.mark.parametrize("M,K,N,epi,kernel,variant,what", T.DENSE_CASES, ids=T.DENSE_IDS)
+def test_dense_h2_kernels(M, K, N, epi, kernel, variant, what, report):
+    """every GEMM kernel of the packed storage at the smallest shapes that select it under default dispatch (tests/_h2_gemm_cases.py; the
+    table itself is held against the dispatcher in tests/test_h2_dispatch_cpu.py): the dispatcher really picks it, the WHOLE output
+    against the fp32 oracle at TOL_OP, and a second launch bit for bit.  The 2^19-row case (the 156 KB weight slice) is compared in full
+    as well: its fp32 CPU reference takes 2-3 s on 16 threads."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(M + K + N)
+    x = torch.randn(M, K, generator=g)
+    w, b = torch.randn(K, N, generator=g) / math.sqrt(K), torch.randn(N, generator=g) * 0.1
+    act, post, has_res = T.EPILOGUE[epi]
+    r = torch.randn(M, N, generator=g) if has_res else None         # the scale of the product: a dropped residual is 1e5 tolerances
+    with ops.precision("strict"):
+        cw = ops.make_dense_weight(w, b)
+    d, _ = T.dense_desc(M, K, N, epi, cw.ldw)
+    assert ops.conv_kernel_name_h2(d, has_res) == kernel, what
+    xa, ra = A(x, "strict"), (A(r, "strict") if has_res else None)
+    got = ops.dense(xa, cw, act=act, act_post=post, residual=ra)
+    ref = R.act(R.dense(x, w, b), act)
+    if has_res:
+        ref = R.act(ref.add_(r), post)
+    check_worst(report, f"dense h2 {variant.split(' ')[0]} {M}x{K}x{N} {epi}", got, ref)
+    again = ops.dense(xa, cw, act=act, act_post=post, residual=ra)
+    assert torch.equal(got, again), "two launches on the same operands must agree bit for bit"
+
+
+@pytest.mark.parametrize("case,kernel,variant,what", T.CONV_H2_CASES, ids=T.CONV_H2_IDS)
+def test_conv2d_h2_kernels(case, kernel, variant, what, report):
+    """k x k convolutions of the packed storage beyond CONV_CASES' 1 023 rows: im2col staging selected by the row count (plain and
+    grouped), the tile kernel just under that switch, and its <64,128> instantiation"""
+    ops = _ops()
+    B, H, W, Cin, Cout, k, s, pad, groups, act, use_res = case
+    g = torch.Generator().manual_seed(hash(case[:9]) % (2 ** 31))
+    x = torch.randn(B, H, W, Cin, generator=g)
+    w = torch.randn(k, k, Cin // groups, Cout, generator=g) / math.sqrt(k * k * Cin / groups)
+    bias = torch.randn(Cout, generator=g) * 0.1
+    ref = R.act(R.conv2d(x, w, bias, s, pad, groups), act)
+    res = None
+    if use_res:
+        res = torch.randn(*ref.shape, generator=g)
+        ref = ref + res
+    with ops.precision("strict"):
+        cw = ops.make_conv_weight(w, bias, groups=groups)
+    d, _ = T.conv_desc(case, cw.ldw)
+    assert ops.conv_kernel_name_h2(d, use_res) == kernel, what
+    xa, ra = A(x, "strict"), (A(res, "strict") if use_res else None)
+    got = ops.conv2d(xa, cw, stride=s, pad=pad, act=act, residual=ra)
+    check_worst(report, f"conv2d h2 {variant} {case}", got, ref)
+    again = ops.conv2d(xa, cw, stride=s, pad=pad, act=act, residual=ra)
+    assert torch.equal(got, again), "two launches on the same operands must agree bit for bit"
 
 
 @pytest.mark.parametrize("B,HW,Cin,Cout,act,res", [(4, 14, 96, 40, None, False), (3, 14, 96, 160, None, True), (2, 7, 24, 72, "silu", False),
@@ -565,15 +636,18 @@ def test_ensemble_logit_within_north_star(report):
 
 
 def test_member_inside_batch_256_strict(report):
-    """B = 256 (what bench.py's strict leg times): images 0-7 of the batch against the oracle, EVERY member of config 5"""
+    """B = 256 (what bench.py's strict leg times): the batch-EDGE images P.B256_EDGE_IMAGES (first, middle, last - where a wrong last M
+    tile, a wrong tile at a persistent workgroup's wrap-around or a wrong second LDS channel chunk lands) against the oracle, EVERY
+    member of config 5"""
     import vipcup_amd  # noqa: F401
     from vipcup_amd import zoo
+    idx = P.B256_EDGE_IMAGES
     for key in zoo.ENSEMBLE8:
         raws = [synth_jpeg(1000 + i) for i in range(256)]
-        z = P.oracle_logits(key, "b256_first8", raws[:8])
+        z = P.oracle_logits(key, "b256_edges", [raws[i] for i in idx])
         zg = _strict_logits(key, raws, "b256")
-        d = np.abs(zg[:8] - z).max()
-        report(f"[strict] {key:22s} images 0-7 in a 256-batch: max|dz| {d:.3e}")
+        d = np.abs(zg[idx] - z).max()
+        report(f"[strict] {key:22s} images {idx} of a 256-batch: max|dz| {d:.3e}")
         assert np.isfinite(zg).all() and d <= P.TOL_NORTH_STAR
 
 

@@ -1542,7 +1542,9 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
     __syncthreads();
 
     auto compute = [&](int buf, int ks) {
-        const char* ws = smem + buf * STAGE + l15 * ROWB + lq * 16 + ks * 64;
+        // (wave column wn reads ITS NB weight rows of the stage: without the offset the upper half of every 256-channel tile was
+        // computed from the lower half's weights - WN = 2 only, a shape gemm8p has taken since it exists unless K % 64 != 0)
+        const char* ws = smem + buf * STAGE + (WN > 1 ? wn * NB * ROWB : 0) + l15 * ROWB + lq * 16 + ks * 64;
         const char* xl = xs + l15 * ROWB + lq * 16 + ks * 64;
         U4H8 xf[PT];
 #pragma unroll
