@@ -442,12 +442,26 @@ int vip_resample_rgb_u8(const uint8_t* src_u8, const int32_t* src_sizes_hw, int 
  * vip_median_rgb_u8: the same conventions; per channel the element of rank k * k / 2 (0-based) of the mirrored k x k window, exact.
  *   k = 3: sorted columns, then med3(max of the minima, median of the medians, min of the maxima); k = 5: a 99-exchange selection
  *   network; both on packed 16-bit min / max, no data-dependent control flow.  k not 3 or 5 -> VIP_ERR_BAD_ARG.
+ * vip_sharpen_rgb_u8 (device, caller's stream, one launch per batch): an unsharp mask, the sharpening a platform adds after a downscale;
+ *   the conventions, argument checks and weights of vip_blur_gauss_rgb_u8.  Integers only, per byte of the interleaved RGB image, each
+ *   image of the batch on its own:
+ *     B   = vip_blur_gauss_rgb_u8's u8 result for (weights_d, radius), bit for bit
+ *     d   = X - B                                            (-255..255)
+ *     out = X                                                if |d| <= threshold
+ *     out = clamp(X + ((amount_q8 * d + 128) >> 8), 0, 255)  otherwise; >> is an arithmetic shift (floor)
+ *   amount_q8 = round(256 * P / 100) for a gain of P percent, 1..1280 (P = 1..500 gives 3..1280); threshold 0..255; either outside its
+ *   range -> VIP_ERR_BAD_ARG.  Because |amount_q8 / 256 - P / 100| <= 1 / 512 and |d| <= 255, the result is at most one level from
+ *   round(X + P / 100 * (X - B)) clamped.  The Gaussian's kernel with one more epilogue: the vertical pass takes the centre bytes from the
+ *   staged u8 tile, so B never reaches global memory; amount_q8 and threshold travel as kernel arguments.  No extra LDS, no atomics, no
+ *   allocation: bit-reproducible.  (Pillow's UnsharpMask blurs with a box approximation of the Gaussian: close, not a bit-exact yardstick.)
  * ------------------------------------------------------------------------------------------ */
 int vip_blur_weights_h(double sigma, int radius, int32_t* w_h, size_t cap);
 int vip_blur_gauss_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
                           const int32_t* weights_d, int radius, int n, void* stream);
 int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW, int k,
                       int n, void* stream);
+int vip_sharpen_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                       const int32_t* weights_d, int radius, int amount_q8, int threshold, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Geometry of decoded u8 RGB: an inverse affine warp with bilinear taps in integer arithmetic, the one kernel under the flip, crop and

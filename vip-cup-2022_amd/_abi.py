@@ -97,6 +97,7 @@ SIGNATURES = {
     "vip_blur_weights_h": (_i, [C.c_double, _i, _vp, _sz]),
     "vip_blur_gauss_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     "vip_median_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "vip_sharpen_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "vip_warp_affine_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "vip_colour_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vip_noise_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_int64, C.c_uint32, _vp, _vp, _i, _vp]),

@@ -24,6 +24,18 @@
 //             min / max network on packed 16-bit operations: 3 x 3 by sorted columns (max of minima, median of medians, min of maxima),
 //             5 x 5 by a 99-exchange selection network.  No data-dependent control flow.
 // No allocation, no atomics: bit-reproducible.
+//
+// Unsharp mask (pipeline.sharpen, --stress-sharpen, the `shp` step of --stress-chain): the sharpening a platform adds after a downscale.
+// Integers only, per byte of the interleaved RGB image, each image of a mixed-size batch on its own:
+//   B   = the Gaussian above at (sigma, radius): its u8 result, bit for bit (mirrored edges, 8.8 horizontal pass, 2^24 vertical pass)
+//   d   = X - B                                            (-255..255)
+//   out = X                                                if |d| <= T
+//   out = clamp(X + ((a * d + 128) >> 8), 0, 255)          otherwise; >> is an arithmetic shift (floor)
+//   a   = round(256 * P / 100)                             P an integer percent in 1..500 (a in 3..1280), T a threshold in 0..255
+// Because |a / 256 - P / 100| <= 1 / 512 and |d| <= 255, the result is at most one level from round(X + P / 100 * (X - B)) clamped.
+// It is the Gaussian kernel with one more epilogue: the vertical pass's wave takes its lane's four centre bytes from the staged u8 tile
+// (row yy + R, byte offset A: already in LDS), forms d, applies the threshold and the gain and stores through store_row.  a and T travel
+// as kernel arguments.  One launch, no extra LDS, no intermediate in global memory, bit-reproducible.
 #include "common.hpp"
 
 namespace {
@@ -122,10 +134,18 @@ __device__ __forceinline__ void store_row(const TileAt& t, int y, int dstMaxW, i
     }
 }
 
+// one byte of the unsharp mask: X the source sample, B its blurred value
+__device__ __forceinline__ uint32_t sharpen_byte(int X, int B, int amount, int threshold) {
+    const int d = X - B;
+    return (uint32_t)(abs(d) <= threshold ? X : min(max(X + ((amount * d + 128) >> 8), 0), 255));
+}
+
+// SHARPEN: the unsharp mask's epilogue on the blurred value (amount = a, threshold = T); false: the plain Gaussian, which ignores both
+template <bool SHARPEN>
 __global__ __launch_bounds__(WAVES * 64) void blur_gauss_rgb_u8_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ sizes,
                                                                        int maxH, int maxW, uint8_t* __restrict__ dst, int dstMaxH,
                                                                        int dstMaxW, const int32_t* __restrict__ weights, int R,
-                                                                       int tiles_x, int tiles_y) {
+                                                                       int tiles_x, int tiles_y, int amount, int threshold) {
     __shared__ uint32_t stage[STAGE_ROWS * STAGE_DW];                 // u8 tile + halo
     __shared__ uint2 mid[STAGE_ROWS * (TILE_BYTES / 4)];              // u16 plane of the horizontal pass: 4 values per lane
     TileAt t;
@@ -164,7 +184,15 @@ __global__ __launch_bounds__(WAVES * 64) void blur_gauss_rgb_u8_kernel(const uin
             a2 += __umul24(v.y & 0xFFFFu, wj);
             a3 += __umul24(v.y >> 16, wj);
         }
-        const uint32_t pack = min(a0 >> 24, 255u) | (min(a1 >> 24, 255u) << 8) | (min(a2 >> 24, 255u) << 16) | (min(a3 >> 24, 255u) << 24);
+        uint32_t pack = min(a0 >> 24, 255u) | (min(a1 >> 24, 255u) << 8) | (min(a2 >> 24, 255u) << 16) | (min(a3 >> 24, 255u) << 24);
+        if constexpr (SHARPEN) {
+            const uint32_t x = stage[(yy + R) * STAGE_DW + (A >> 2) + lane];    // the lane's own four source bytes: A is a multiple of 4
+            uint32_t sharp = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                sharp |= sharpen_byte((int)((x >> (8 * q)) & 255), (int)((pack >> (8 * q)) & 255), amount, threshold) << (8 * q);
+            pack = sharp;
+        }
         store_row(t, t.y0 + yy, dstMaxW, lane, pack);
     }
 }
@@ -272,9 +300,25 @@ extern "C" int vip_blur_gauss_rgb_u8(const uint8_t* src_u8, const int32_t* sizes
     VIP_REQUIRE(weights_d, VIP_ERR_BAD_ARG, "vip_blur_gauss_rgb_u8: null pointer");
     VIP_REQUIRE(radius >= 1 && radius <= MAX_RADIUS, VIP_ERR_BAD_ARG, "vip_blur_gauss_rgb_u8: radius %d outside 1..%d", radius, MAX_RADIUS);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(weights_d) & 3) == 0, VIP_ERR_ALIGNMENT, "vip_blur_gauss_rgb_u8: weights must be 4-byte aligned");
-    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW, dst_u8,
-                       dstMaxH, dstMaxW, weights_d, radius, tiles_x, tiles_y);
+    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<false>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW,
+                       dst_u8, dstMaxH, dstMaxW, weights_d, radius, tiles_x, tiles_y, 0, 0);
     return vip_launch_status("vip_blur_gauss_rgb_u8");
+}
+
+extern "C" int vip_sharpen_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH,
+                                  int dstMaxW, const int32_t* weights_d, int radius, int amount_q8, int threshold, int n, void* stream) {
+    int tiles_x, tiles_y;
+    unsigned grid;
+    const int st = filter_grid("vip_sharpen_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, &tiles_x, &tiles_y, &grid);
+    if (st != VIP_OK) return st;
+    VIP_REQUIRE(weights_d, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: null pointer");
+    VIP_REQUIRE(radius >= 1 && radius <= MAX_RADIUS, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: radius %d outside 1..%d", radius, MAX_RADIUS);
+    VIP_REQUIRE((reinterpret_cast<uintptr_t>(weights_d) & 3) == 0, VIP_ERR_ALIGNMENT, "vip_sharpen_rgb_u8: weights must be 4-byte aligned");
+    VIP_REQUIRE(amount_q8 >= 1 && amount_q8 <= 1280, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: amount_q8 %d outside 1..1280", amount_q8);
+    VIP_REQUIRE(threshold >= 0 && threshold <= 255, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: threshold %d outside 0..255", threshold);
+    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<true>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW,
+                       dst_u8, dstMaxH, dstMaxW, weights_d, radius, tiles_x, tiles_y, amount_q8, threshold);
+    return vip_launch_status("vip_sharpen_rgb_u8");
 }
 
 extern "C" int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH,

@@ -497,7 +497,8 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
                   rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
                   contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
                   mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
-                  noise_keys=None) -> List[str]:
+                  noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
+                  sharpen_threshold: int = 0, chains: Sequence[str] = ()) -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
     ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
     ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
@@ -512,7 +513,10 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
     and ``nm<TTT>`` for each of ``mono_noises`` (ascending, ``TTT`` = ten times sigma as three digits: 3 -> ``n030``), ``spk<PP>`` for each
     percent of ``speckles`` (ascending, two digits), ``imp<TTT>`` for each percent of ``impulses`` (ascending, ten times the percent: 1 ->
     ``imp010``), each followed by its ``_q<Q>`` labels (``noise_seed`` and ``noise_keys`` are ``stress_batch``'s and do not change a
-    label)."""
+    label), then the sharpening: ``shp<PPP>`` for each percent of ``sharpens`` (ascending, three digits: 80 -> ``shp080``), each followed
+    by its ``_q<Q>`` labels (``sharpen_sigma``, ``sharpen_radius`` and ``sharpen_threshold`` are ``stress_batch``'s and do not change a
+    label), and last the ``chains`` in the order given, each under its own text (``r50+shp080+q75``) and never followed by ``_q<Q>``
+    labels."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
@@ -526,10 +530,11 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
     geometry = [f"flip{ax}" for ax in sorted(str(ax) for ax in flips)] + [f"crop{pc:02d}" for pc in sorted((int(pc) for pc in crops), reverse=True)] \
         + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
     for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)] \
-            + [v[0] for v in _noise_variants(noises, mono_noises, speckles, impulses)]:
+            + [v[0] for v in _noise_variants(noises, mono_noises, speckles, impulses)] \
+            + [f"shp{pc:03d}" for pc in sorted(int(pc) for pc in sharpens)]:
         labels.append(v)
         labels += [f"{v}_q{int(q)}" for q in qualities]
-    return labels
+    return labels + [str(text) for text in chains]
 
 
 def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
@@ -538,7 +543,8 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
                  rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
                  mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
-                 noise_keys=None):
+                 noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
+                 sharpen_threshold: int = 0, chains: Sequence[str] = ()):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -567,7 +573,17 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     scored unsaved and re-saved at every quality, one noisy batch alive at a time; noise is not composed with the other families.
     ``noise_seed`` and ``noise_keys`` (one integer per image, None: 0..n-1; ``pipeline.noise_keys`` of the file names makes a file's noise
     independent of its batch) select the random field, which all noise variants of a batch share.  Then too the result is ``(rows,
-    labels)``."""
+    labels)``.
+    With ``sharpens`` (integer percents 1..500, ascending here; ``sharpen_sigma``, ``sharpen_radius`` None = three sigma,
+    ``sharpen_threshold``) the decoded batch is also sharpened by an unsharp mask (``pipeline.sharpen``, one launch per variant) and scored
+    unsaved and re-saved at every quality, one sharpened batch alive at a time; sharpening is not combined with the other families
+    except through a chain.  V percents cost V (1 + Q) plain runs.
+    With ``chains`` (chain texts, ``pipeline.parse_chain``: ``"r50+shp080+q75"``; scored in the order given) the decoded batch also goes
+    through each chain's steps left to right (``pipeline.apply_chain`` with this call's ``subsampling``, ``resize_filter``,
+    ``blur_radius``, ``crop_origin``, ``rotate_fill``, ``sharpen_*``, ``noise_seed`` and ``noise_keys``) and the result is scored ONCE,
+    exactly as the chain is written: ``qualities`` do not multiply chain rows, a chain that should end in a re-save ends in a ``q``
+    step.  One chain's batch is alive at a time; C chains cost C plain runs.  The chain rows come last.  Then too the result is
+    ``(rows, labels)``."""
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
@@ -614,13 +630,27 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(grainy, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(grainy, int(q), subsampling), members))
+    sharpens = sorted(int(pc) for pc in sharpens)
+    for pc in sharpens:
+        sharp = pipeline.sharpen(batch, pc, sharpen_sigma, sharpen_radius, sharpen_threshold)      # one alive at a time
+        rows.append(_score_batch(sharp, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(sharp, int(q), subsampling), members))
+    chains = [str(text) for text in chains]
+    for text in chains:                                          # scored once, as written: the qualities do not multiply chain rows
+        rows.append(_score_batch(pipeline.apply_chain(
+            batch, pipeline.parse_chain(text), subsampling=subsampling, resize_filter=resize_filter, blur_radius=blur_radius,
+            crop_origin=crop_origin, rotate_fill=rotate_fill, sharpen_sigma=sharpen_sigma, sharpen_radius=sharpen_radius,
+            sharpen_threshold=sharpen_threshold, noise_seed=noise_seed, noise_keys=keys_d if keys_d is not None else noise_keys), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours and not noisy:
+    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours and not noisy and \
+            not sharpens and not chains:
         return torch.stack(rows)
     return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations, gray=gray, bgr=bgr, hues=hues,
                                             saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas,
-                                            noises=noises, mono_noises=mono_noises, speckles=speckles, impulses=impulses)
+                                            noises=noises, mono_noises=mono_noises, speckles=speckles, impulses=impulses,
+                                            sharpens=sharpens, chains=chains)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,
@@ -655,7 +685,9 @@ def stress_table(names: Sequence[str], scores: np.ndarray, qualities: Sequence, 
     files whose decision differs and the mean ``|p_q - p|``, plus the number of stable files.
     ``qualities`` may instead be the label list of ``stress_labels`` (``q<Q>``, ``r<P>``, ``r<P>_q<Q>``, ``b<TT>...``, ``m<K>...``,
     ``flip<A>...``, ``crop<PP>...``, ``rot<TTT>...``, ``gray...``, ``bgr...``, ``hue<DDD>...``, ``sat<PPP>...``, ``con<PPP>...``,
-    ``bri<PP>...``, ``gam<PPP>...``, ``n<TTT>...``, ``nm<TTT>...``, ``spk<PP>...``, ``imp<TTT>...``).
+    ``bri<PP>...``, ``gam<PPP>...``, ``n<TTT>...``, ``nm<TTT>...``, ``spk<PP>...``, ``imp<TTT>...``, ``shp<PPP>...`` and chain labels such as
+    ``r50+shp080+q75``, which count for ``stable`` and ``flips`` like any variant and never for ``flips_at``, even when they start with a
+    ``q`` step).
     With ``q`` labels alone the result is the one above.  With rescaled, smoothed or warped variants ``p_q`` / ``decision_q`` are ``[F, V]`` over
     all variants, ``stable`` is taken over all of them, ``flips_at`` keeps its meaning (the ``q`` labels, i.e. the rows at 100 %, only),
     ``table`` gains ``labels`` and ``flips`` (per file the ``;``-joined labels whose decision differs), and ``summary`` gains ``variants``

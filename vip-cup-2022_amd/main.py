@@ -13,6 +13,9 @@
                                      [--stress-contrast P[,P...]] [--stress-brightness P[,P...]] [--stress-gamma G[,G...]]   (--stress-out FILE.csv)
                                      [--stress-noise S[,S...]] [--stress-noise-mono S[,S...]] [--stress-speckle P[,P...]]
                                      [--stress-impulse P[,P...]] [--stress-noise-seed N]                                     (--stress-out FILE.csv)
+                                     [--stress-sharpen P[,P...]] [--stress-sharpen-sigma S] [--stress-sharpen-radius R]
+                                     [--stress-sharpen-threshold T]                                                          (--stress-out FILE.csv)
+                                     [--stress-chain STEP+STEP[+STEP...][,CHAIN...]]                                         (--stress-out FILE.csv)
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
                                                       [--occlusion-format npy|png] [--occlusion-members]]
@@ -77,6 +80,30 @@ size, on any rank, in every run, and all listed amounts see the same field at di
 ``--stress-jpeg``, re-saved at every quality (``<label>_q<Q>``); the rows follow those of the colour flags in this order, each list
 ascending; a value listed twice is refused.  Noise is not combined with the other families.  ``stress.json`` then lists
 ``noise_sigmas``, ``noise_mono_sigmas``, ``speckles``, ``impulses`` and ``noise_seed`` under ``settings``.
+``--stress-sharpen 80,150 --stress-out stress.csv`` is the sharpening perturbation - the unsharp mask a platform adds after a downscale; the
+reference has none - on the decoded image at its own size, per byte and in integers: with ``B`` the Gaussian of ``--stress-blur`` at
+``--stress-sharpen-sigma`` (0.3..5.0, default 1.0) and ``--stress-sharpen-radius`` (1..15, default three sigma), bit for bit, and ``d = X -
+B``, a sample stays ``X`` where ``|d| <= T`` (``--stress-sharpen-threshold``, 0..255, default 0) and becomes ``clamp(X + ((a d + 128) >> 8),
+0, 255)`` elsewhere, ``a = round(256 P / 100)``, P an integer percent in 1..500 - at most one level from ``round(X + P / 100 (X - B))``
+clamped, one launch (Pillow's ``UnsharpMask`` blurs with a box approximation: close, not bit for bit).  ``shp<PPP>`` is scored unsaved and,
+with ``--stress-jpeg``, re-saved at every quality (``shp<PPP>_q<Q>``); the rows follow those of the noise flags, ascending; a value listed
+twice is refused.  Sharpening is not combined with the other families except through a chain.  ``stress.json`` then lists
+``sharpen_percents``, ``sharpen_sigma``, ``sharpen_radius`` and ``sharpen_threshold`` under ``settings``.
+``--stress-chain r50+shp080+q75,q90+crop95+q75 --stress-out stress.csv`` scores every image after a SEQUENCE of perturbations, as files
+are laundered in practice (downscale, sharpen, re-save; a second JPEG on a shifted block grid).  A chain is 2..8 steps joined by ``+``;
+up to 16 chains, separated by commas, keep the order given; a chain listed twice is refused.  A step is exactly a single-variant label
+of the flags above in its canonical spelling and range, matched against the whole token: ``q<Q>``, ``r<P>``, ``b<TT>``, ``m3``, ``m5``,
+``fliph``, ``flipv``, ``crop<PP>``, ``rot<TTT>``, ``rotm<TTT>``, ``gray``, ``bgr``, ``hue<DDD>``, ``huem<DDD>``, ``sat<PPP>``, ``con<PPP>``, ``bri<PP>``,
+``brim<PP>``, ``gam<PPP>``, ``n<TTT>``, ``nm<TTT>``, ``spk<PP>``, ``imp<TTT>``, ``shp<PPP>``; a one-step chain is refused with the name of the
+flag that gives that row; the ``r`` percents of a chain must multiply to 10..400 %.  The steps run left to right on the decoded image
+at its own size, each with the options of its family's flags (``--stress-subsampling`` for ``q``, ``--stress-resize-filter`` for ``r``,
+``--stress-blur-radius`` for ``b``, ``--stress-crop-origin`` for ``crop``, ``--stress-rotate-fill`` for ``rot``, ``--stress-sharpen-sigma`` /
+``-radius`` / ``-threshold`` for ``shp``, ``--stress-noise-seed`` for the noise steps), which are accepted when a chain holds the step they
+govern.  A ``con`` step takes the mean colour of the image as it reaches that step; the k-th noise step of a chain draws from seed + k on
+the image as it reaches that step, so ``n030+q75`` sees the field of the row ``n030``.  The result is scored once, as written:
+``--stress-jpeg`` does not multiply chain rows.  The chain rows come last under the chain's text (``p_<chain>``, ``decision_<chain>``), count
+for ``stable`` and ``flips`` and not for ``flips_at``; ``stress.json`` keys them by label and lists ``chains`` under ``settings``.  C chains
+cost C plain runs.
 ``--tiles-out tiles.csv`` additionally scores every image that is at least ``--tile-size`` (200) pixels high and wide at its own resolution:
 it is cut into ``tile x tile`` crops - ``--tile-stride`` apart at most (default: the tile size), spread so that the first starts at 0 and the
 last ends at the image's edge, at most ``--tile-max`` per image (beyond that the grid is an evenly spaced sample with gaps) - and each
@@ -169,19 +196,22 @@ def _heatmap_writer(a, names, members, rank):
 
 
 def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None,
-                   colour=None, noise=None, names=None):
+                   colour=None, noise=None, names=None, sharpen=None, chains=None):
     """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
     ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None) and the colour flags (``colour``:
-    likewise) and the noise flags (``noise``: likewise; every batch's ``noise_keys`` come from its files' ``names``): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``,
-    in batch order) until the run's one extra collective"""
+    likewise) and the noise flags (``noise``: likewise; every batch's ``noise_keys`` come from its files' ``names``), ``--stress-sharpen``
+    (``sharpen``: likewise) and ``--stress-chain`` (``chains``: ``{"chains": texts}`` plus the options of the steps that no family flag
+    of this run carries, or None): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed
+    batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble, pipeline
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians or geometry or colour or noise:
-            keyed = dict(noise, noise_keys=pipeline.noise_keys(names[b0:b1])) if noise else {}     # by file, not by batch position
+        if scales or blurs or medians or geometry or colour or noise or sharpen or chains:
+            more = _label_keywords(geometry, colour, noise, sharpen, chains)
+            if noise or chains:                                                                     # by file, not by batch position
+                more["noise_keys"] = pipeline.noise_keys(names[b0:b1])
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
-                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius,
-                                            **(geometry or {}), **(colour or {}), **keyed)
+                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius, **more)
         else:
             rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
         kept.append(rows[1:])
@@ -190,13 +220,13 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
 
 
 def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None,
-                  noise=None):
+                  noise=None, sharpen=None, chains=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **(geometry or {}), **(colour or {}), **(noise or {}))
-    mixed = bool(scales or blurs or medians or geometry or colour or noise)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **_label_keywords(geometry, colour, noise, sharpen, chains))
+    mixed = bool(scales or blurs or medians or geometry or colour or noise or sharpen or chains)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -225,8 +255,27 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
     if noise:
         summary["settings"].update({"noise_sigmas": noise["noises"], "noise_mono_sigmas": noise["mono_noises"], "speckles": noise["speckles"],
                                     "impulses": noise["impulses"], "noise_seed": noise["noise_seed"]})
+    if sharpen:
+        summary["settings"].update({"sharpen_percents": sharpen["sharpens"], "sharpen_sigma": sharpen["sharpen_sigma"],
+                                    "sharpen_radius": sharpen["sharpen_radius"], "sharpen_threshold": sharpen["sharpen_threshold"]})
+    if chains:
+        from vipcup_amd import chain as grammar
+        summary["settings"]["chains"] = list(chains["chains"])
+        kinds = grammar.chain_kinds(chains["chains"])
+        for key in ("crop_origin", "rotate_fill", "noise_seed"):          # the options of chain steps whose family flag is absent
+            if key in chains:
+                summary["settings"].setdefault(key, chains[key])
+        if "rescale" in kinds:
+            summary["settings"].setdefault("resize_filter", a.stress_resize_filter)
+        if "blur" in kinds:
+            summary["settings"].setdefault("blur_radius", a.stress_blur_radius)
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
+
+
+def _label_keywords(geometry, colour, noise, sharpen, chains):
+    """the keywords of ``stress_labels`` (and ``stress_batch``) from the CLI's per-family dictionaries"""
+    return {**(geometry or {}), **(colour or {}), **(noise or {}), **(sharpen or {}), **(chains or {})}
 
 
 def _tile_scorer(a, kept, kept_tiles):
@@ -486,6 +535,33 @@ def main(argv=None):
     ap.add_argument("--stress-noise-seed", type=int, default=0, metavar="N",
                     help="the seed of the noise stress tests' random field (0..4294967295, default 0); needs one of --stress-noise, "
                          "--stress-noise-mono, --stress-speckle, --stress-impulse")
+    ap.add_argument("--stress-sharpen", default=None, metavar="P[,P...]",
+                    help="sharpening stress test: also score every image under an unsharp mask of each listed gain (integer percents in "
+                         "1..500; ascending; a value listed twice is refused): out = X + P / 100 (X - blurred X) where |X - blurred X| "
+                         "exceeds the threshold, in integers on the Gaussian of --stress-blur (one launch; close to Pillow's UnsharpMask, "
+                         "which blurs with a box approximation, not bit for bit), unsaved and - with --stress-jpeg - re-saved at every "
+                         "quality; needs --stress-out, whose table gains the labels shp<PPP>, shp<PPP>_q<Q> after the noise rows")
+    ap.add_argument("--stress-sharpen-sigma", default=None, metavar="S",
+                    help="sigma of the unsharp mask's Gaussian in pixels (0.3..5.0 with at most one fractional digit, default 1.0); needs "
+                         "--stress-sharpen or a --stress-chain with a shp step")
+    ap.add_argument("--stress-sharpen-radius", type=int, default=None, metavar="R",
+                    help="cut the unsharp mask's Gaussian off R pixels from its centre (1..15; default ceil(3 sigma)); needs "
+                         "--stress-sharpen or a --stress-chain with a shp step")
+    ap.add_argument("--stress-sharpen-threshold", type=int, default=None, metavar="T",
+                    help="leave a sample as it is where it differs from its blurred value by at most T levels (0..255, default 0); needs "
+                         "--stress-sharpen or a --stress-chain with a shp step")
+    ap.add_argument("--stress-chain", default=None, metavar="STEP+STEP[+STEP...][,CHAIN...]",
+                    help="stress chains: also score every image after a SEQUENCE of perturbations, e.g. r50+shp080+q75 (downscale, "
+                         "sharpen, re-save: what a messenger does) or q90+crop95+q75 (double compression on a shifted block grid).  A "
+                         "chain is 2..8 steps joined by +, up to 16 chains separated by commas, kept in the order given; a chain listed "
+                         "twice is refused.  A step is a single-variant label of the other stress flags in its canonical spelling: q<Q>, "
+                         "r<P>, b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, "
+                         "con<PPP>, bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>; it takes the options of its "
+                         "family's flags (--stress-subsampling, --stress-resize-filter, --stress-blur-radius, --stress-crop-origin, "
+                         "--stress-rotate-fill, --stress-sharpen-sigma / -radius / -threshold, --stress-noise-seed), which are accepted "
+                         "when a chain holds the step they govern.  The result is scored once, as written: --stress-jpeg does not "
+                         "multiply chain rows.  Needs --stress-out, whose table gains one column pair per chain under the chain's text, "
+                         "after all other rows; they count for stable and flips, not for flips_at")
     ap.add_argument("--tiles-out", default=None, metavar="FILE.csv",
                     help="native-resolution tiles: also score every image at least --tile-size pixels high and wide as a grid of tile x "
                          "tile crops, each taken as an image of its own; per input file: filename, width, height, tiles, grid, p, decision, "
@@ -513,12 +589,21 @@ def main(argv=None):
     ap.add_argument("--occlusion-members", action="store_true",
                     help="also write every member's [grid, grid] cells and per-variant scores: DIR/<name>.members.npz")
     a = ap.parse_args(argv)
+    chains, in_chain = None, set()                      # the chain texts, and the step kinds they hold
+    if a.stress_chain is not None:
+        from vipcup_amd import chain as grammar         # text handling only: nothing heavy is imported
+        try:
+            chains = grammar.parse_chains(a.stress_chain)
+        except ValueError as e:
+            raise SystemExit(f"vipcup_amd main: --stress-chain {a.stress_chain!r}: {e}")
+        in_chain = grammar.chain_kinds(chains)
     colour_flags = (("--stress-gray", a.stress_gray or None), ("--stress-bgr", a.stress_bgr or None), ("--stress-hue", a.stress_hue),
                     ("--stress-saturation", a.stress_saturation), ("--stress-contrast", a.stress_contrast),
                     ("--stress-brightness", a.stress_brightness), ("--stress-gamma", a.stress_gamma))
     noise_flags = (("--stress-noise", a.stress_noise), ("--stress-noise-mono", a.stress_noise_mono), ("--stress-speckle", a.stress_speckle),
                    ("--stress-impulse", a.stress_impulse))
-    any_colour = any(v is not None for _, v in colour_flags + noise_flags)       # colour or noise: the same refusals below
+    any_colour = any(v is not None for _, v in colour_flags + noise_flags) or a.stress_sharpen is not None or chains is not None
+    # colour, noise, sharpening or chains: the same refusals below
     if a.occlusion is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
@@ -574,7 +659,7 @@ def main(argv=None):
         if a.heatmaps is not None:
             raise SystemExit("vipcup_amd main: --stress-resize and --heatmaps cannot be combined (both replace the batch scorer): "
                              "run them one after the other")
-    elif a.stress_resize_filter != "bicubic":
+    elif a.stress_resize_filter != "bicubic" and "rescale" not in in_chain:
         raise SystemExit("vipcup_amd main: --stress-resize-filter needs --stress-resize P[,P...]")
     sigmas = medians = None                             # sigmas in tenths of a pixel
     if a.stress_blur is not None:
@@ -585,10 +670,10 @@ def main(argv=None):
         if not sigmas or sigmas[0] < 3 or sigmas[-1] > 50:
             raise SystemExit(f"vipcup_amd main: --stress-blur {a.stress_blur!r}: expected a comma-separated list of sigmas in 0.3..5.0 with at "
                              "most one fractional digit")
-        if a.stress_blur_radius is not None and not 1 <= a.stress_blur_radius <= 15:
-            raise SystemExit(f"vipcup_amd main: --stress-blur-radius {a.stress_blur_radius}: expected an integer in 1..15")
-    elif a.stress_blur_radius is not None:
+    elif a.stress_blur_radius is not None and "blur" not in in_chain:
         raise SystemExit("vipcup_amd main: --stress-blur-radius needs --stress-blur S[,S...]")
+    if a.stress_blur_radius is not None and not 1 <= a.stress_blur_radius <= 15:
+        raise SystemExit(f"vipcup_amd main: --stress-blur-radius {a.stress_blur_radius}: expected an integer in 1..15")
     if a.stress_median is not None:
         try:
             medians = sorted({int(t) for t in a.stress_median.split(",")})
@@ -608,7 +693,7 @@ def main(argv=None):
             crops = []
         if not crops or crops[-1] < 50 or crops[0] > 99:
             raise SystemExit(f"vipcup_amd main: --stress-crop {a.stress_crop!r}: expected a comma-separated list of integer percents in 50..99")
-    elif a.stress_crop_origin != "centre":
+    elif a.stress_crop_origin != "centre" and "crop" not in in_chain:
         raise SystemExit("vipcup_amd main: --stress-crop-origin needs --stress-crop P[,P...]")
     if a.stress_rotate is not None:
         tokens = a.stress_rotate.split(",")
@@ -619,7 +704,7 @@ def main(argv=None):
         if not angles or angles[0] < -450 or angles[-1] > 450 or 0 in angles:
             raise SystemExit(f"vipcup_amd main: --stress-rotate {a.stress_rotate!r}: expected a comma-separated list of non-zero angles in "
                              "-45..45 with at most one fractional digit")
-    elif a.stress_rotate_fill != "crop":
+    elif a.stress_rotate_fill != "crop" and "rotate" not in in_chain:
         raise SystemExit("vipcup_amd main: --stress-rotate-fill needs --stress-rotate D[,D...]")
     hues = sats = cons = bris = gammas = None           # gammas in hundredths
     if a.stress_hue is not None:
@@ -657,14 +742,39 @@ def main(argv=None):
         if a.stress_impulse is not None:
             noise["impulses"] = [t / 10 for t in _tenths_list("--stress-impulse", a.stress_impulse, 1, 500, "percents in 0.1..50.0 with at "
                                                               "most one fractional digit")]
-        if not 0 <= a.stress_noise_seed <= 0xFFFFFFFF:
-            raise SystemExit(f"vipcup_amd main: --stress-noise-seed {a.stress_noise_seed}: expected an integer in 0..4294967295")
-    elif a.stress_noise_seed != 0:
+    elif a.stress_noise_seed != 0 and not in_chain & set(("gaussian", "mono", "speckle", "impulse")):
         raise SystemExit("vipcup_amd main: --stress-noise-seed needs --stress-noise, --stress-noise-mono, --stress-speckle or --stress-impulse")
+    if not 0 <= a.stress_noise_seed <= 0xFFFFFFFF:
+        raise SystemExit(f"vipcup_amd main: --stress-noise-seed {a.stress_noise_seed}: expected an integer in 0..4294967295")
+    sharpen = None                                      # the sharpening keywords of stress_batch: with --stress-sharpen or a shp step
+    if a.stress_sharpen is not None or "sharpen" in in_chain:
+        sharpen = {"sharpens": [], "sharpen_sigma": 1.0, "sharpen_radius": a.stress_sharpen_radius,
+                   "sharpen_threshold": 0 if a.stress_sharpen_threshold is None else a.stress_sharpen_threshold}
+        if a.stress_sharpen is not None:
+            tokens = a.stress_sharpen.split(",")
+            given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,3}", t) for t in tokens) else []
+            if not given or given[0] < 1 or given[-1] > 500 or len(set(given)) != len(given):
+                raise SystemExit(f"vipcup_amd main: --stress-sharpen {a.stress_sharpen!r}: expected a comma-separated list of integer "
+                                 "percents in 1..500, each listed once")
+            sharpen["sharpens"] = given
+        if a.stress_sharpen_sigma is not None:
+            t = a.stress_sharpen_sigma
+            tenths = (int(t.replace(".", "")) if "." in t else 10 * int(t)) if re.fullmatch(r"\d{1,2}(\.\d)?", t) else 0
+            if not 3 <= tenths <= 50:
+                raise SystemExit(f"vipcup_amd main: --stress-sharpen-sigma {t!r}: expected a sigma in 0.3..5.0 with at most one fractional digit")
+            sharpen["sharpen_sigma"] = tenths / 10
+        if a.stress_sharpen_radius is not None and not 1 <= a.stress_sharpen_radius <= 15:
+            raise SystemExit(f"vipcup_amd main: --stress-sharpen-radius {a.stress_sharpen_radius}: expected an integer in 1..15")
+        if not 0 <= sharpen["sharpen_threshold"] <= 255:
+            raise SystemExit(f"vipcup_amd main: --stress-sharpen-threshold {a.stress_sharpen_threshold}: expected an integer in 0..255")
+    elif a.stress_sharpen_sigma is not None or a.stress_sharpen_radius is not None or a.stress_sharpen_threshold is not None:
+        raise SystemExit("vipcup_amd main: --stress-sharpen-sigma / --stress-sharpen-radius / --stress-sharpen-threshold need --stress-sharpen "
+                         "P[,P...] or a --stress-chain with a shp step")
     for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
                               ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
                               ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags) \
-            + tuple((flag, v, "noise") for flag, v in noise_flags):
+            + tuple((flag, v, "noise") for flag, v in noise_flags) + (("--stress-sharpen", a.stress_sharpen, "sharpening"),
+                                                                      ("--stress-chain", chains, "chained")):
         if given is None:
             continue
         if a.stress_out is None:
@@ -684,7 +794,15 @@ def main(argv=None):
     if any(v is not None for _, v in colour_flags):
         colour = {"gray": bool(a.stress_gray), "bgr": bool(a.stress_bgr), "hues": hues or [], "saturations": sats or [],
                   "contrasts": cons or [], "brightnesses": bris or [], "gammas": [hh / 100 for hh in gammas or []]}
-    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None or noise is not None
+    chained = None                                      # --stress-chain: the texts, and the options of steps whose family flag is absent
+    if chains is not None:
+        chained = {"chains": chains}
+        if geometry is None and in_chain & {"crop", "rotate"}:
+            chained.update({"crop_origin": a.stress_crop_origin, "rotate_fill": a.stress_rotate_fill})
+        if noise is None and in_chain & {"gaussian", "mono", "speckle", "impulse"}:
+            chained["noise_seed"] = a.stress_noise_seed
+    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None or noise is not None or \
+        sharpen is not None or chains is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -702,7 +820,7 @@ def main(argv=None):
         if a.heatmaps is not None:
             raise SystemExit("vipcup_amd main: --stress-jpeg and --heatmaps cannot be combined (both replace the batch scorer): "
                              "run them one after the other")
-    elif (a.stress_out is not None and scales is None and not smoothed) or a.stress_subsampling != "420":
+    elif (a.stress_out is not None and scales is None and not smoothed) or (a.stress_subsampling != "420" and "recompress" not in in_chain):
         raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]"
                          + (" (--stress-out alone also goes with --stress-resize P[,P...])" if a.stress_out is not None else ""))
     if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
@@ -805,7 +923,7 @@ def main(argv=None):
     if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
                                       scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour,
-                                      noise, names)
+                                      noise, names, sharpen, chained)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -824,8 +942,8 @@ def main(argv=None):
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
     if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (), **(geometry or {}), **(colour or {}),
-                                            **(noise or {})))
+        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (),
+                                            **_label_keywords(geometry, colour, noise, sharpen, chained)))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -841,7 +959,8 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour, noise)
+            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour, noise,
+                          sharpen, chained)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

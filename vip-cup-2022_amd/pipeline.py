@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from .chain import chain_noise_seeds, parse_chain, parse_chains  # noqa: F401  (the chain grammar: torch-free, re-exported here)
 from .ops import _launch, _p
 
 _TABLE_DEV: Dict[int, torch.Tensor] = {}
@@ -654,8 +655,28 @@ def median(batch: DecodedBatch, k: int) -> DecodedBatch:
     return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "median", int(k))
 
 
+def sharpen_amount(percent: int) -> int:
+    """The gain ``vip_sharpen_rgb_u8`` takes for ``percent`` (an integer in 1..500): ``a = round(256 percent / 100)`` in exact integer
+    arithmetic (64 percent / 25 never meets a tie): 1 -> 3, 100 -> 256, 500 -> 1280"""
+    return (256 * _int_arg("percent", percent, 1, 500) + 50) // 100
+
+
+def sharpen(batch: DecodedBatch, percent: int, sigma: float = 1.0, radius: Optional[int] = None, threshold: int = 0) -> DecodedBatch:
+    """The batch under an unsharp mask, the sharpening a platform adds after a downscale: with ``B = blur(batch, sigma, radius)`` (its
+    uint8 pixels, bit for bit) and ``d = X - B``, every sample becomes ``clamp(X + ((a d + 128) >> 8), 0, 255)`` where ``|d| >
+    threshold`` and stays ``X`` elsewhere; ``a = sharpen_amount(percent)``, ``percent`` an integer in 1..500, ``threshold`` an integer in
+    0..255, ``sigma`` and ``radius`` as for ``blur``.  Integer arithmetic, at most one level from ``round(X + percent / 100 (X - B))``
+    clamped (``vip_sharpen_rgb_u8``: ONE launch, the blurred image never reaches global memory).  Pillow's ``UnsharpMask`` blurs with
+    a box approximation of the Gaussian: close to this, not bit for bit.  Returns a new batch of the same sizes, pixels outside an
+    image 0; ``batch`` is not touched.  Runs on the current stream; only the weights (cached on the device) come from the host."""
+    a = sharpen_amount(percent)
+    key = _blur_args(sigma, radius) + (a, _int_arg("threshold", threshold, 0, 255))
+    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "sharpen", key)
+
+
 def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> DecodedBatch:
-    """``blur``'s (``kind`` "gauss", ``arg`` = (round(sigma * 10), radius)) and ``median``'s (``kind`` "median", ``arg`` = k) launch:
+    """``blur``'s (``kind`` "gauss", ``arg`` = (round(sigma * 10), radius)), ``median``'s (``kind`` "median", ``arg`` = k) and
+    ``sharpen``'s (``kind`` "sharpen", ``arg`` = (round(sigma * 10), radius, ``sharpen_amount``, threshold)) launch:
     image i of ``batch`` filtered into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8 on the batch's device, slots at least as large
     as the images; only the pixels of the images are written)."""
     n, maxH, maxW, _ = batch.rgb.shape
@@ -663,12 +684,16 @@ def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> Deco
     assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
     assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
     src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    if kind == "gauss":
-        dkey = (device.index or 0,) + tuple(arg)
+    if kind in ("gauss", "sharpen"):
+        dkey = (device.index or 0,) + tuple(arg[:2])
         if dkey not in _BLUR_WEIGHTS_DEV:
             _BLUR_WEIGHTS_DEV[dkey] = torch.from_numpy(blur_weights(arg[0] / 10, arg[1]).copy()).to(device)
-        _launch("vip_blur_gauss_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
-                _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), n)
+        if kind == "gauss":
+            _launch("vip_blur_gauss_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+                    _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), n)
+        else:
+            _launch("vip_sharpen_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+                    _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), int(arg[2]), int(arg[3]), n)
     else:
         _launch("vip_median_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), int(arg), n)
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
@@ -1125,6 +1150,49 @@ def impulse(batch: DecodedBatch, percent: float, seed: int = 0, keys=None) -> De
     """The batch with ``percent`` % of its pixels (0.1..50.0 in steps of 0.1) replaced by black or white, half each: salt and pepper.
     ``noise(batch, "impulse", ...)``.  Returns a new batch."""
     return noise(batch, "impulse", percent, seed, keys)
+
+
+def apply_chain(batch: DecodedBatch, steps, *, subsampling: str = "4:2:0", resize_filter: str = "bicubic", blur_radius: Optional[int] = None,
+                crop_origin: str = "centre", rotate_fill: str = "crop", sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
+                sharpen_threshold: int = 0, noise_seed: int = 0, noise_keys=None) -> DecodedBatch:
+    """The batch after the ``steps`` of a stress chain (``parse_chain(text)``, or the chain's text), applied left to right to the decoded
+    pixels at their own size, each through the ``pipeline`` function of its family with that family's options: ``recompress``
+    (``subsampling``), ``rescale`` (``resize_filter``), ``blur`` (``blur_radius``), ``crop`` (``crop_origin``), ``rotate``
+    (``rotate_fill``), ``sharpen`` (``sharpen_sigma``, ``sharpen_radius``, ``sharpen_threshold``).  A ``contrast`` step takes the mean
+    colour of the batch as it reaches that step.  A noise step uses ``noise_keys`` (as for ``noise``: one integer per image, None:
+    0..n-1, or ``noise_keys_device``'s tensor) and positions in the image as it reaches that step; the k-th noise step of the chain draws
+    from seed ``(noise_seed + k) mod 2^32`` (``chain_noise_seeds``).  Intermediate batches are dropped as the chain proceeds.  Returns a
+    new batch; ``batch`` is not touched."""
+    steps = parse_chain(steps) if isinstance(steps, str) else list(steps)
+    seeds = chain_noise_seeds(steps, _int_arg("noise_seed", noise_seed, 0, 0xFFFFFFFF))
+    one_argument = {"median": median, "flip": flip, "hue": hue, "saturation": saturation, "contrast": contrast, "brightness": brightness,
+                    "gamma": gamma}
+    keys_d = None
+    cur = batch
+    for (kind, arg), seed in zip(steps, seeds):
+        if seed is not None:
+            if keys_d is None:                          # once per chain: no step changes the number of images
+                keys_d = noise_keys if isinstance(noise_keys, torch.Tensor) else noise_keys_device(batch, noise_keys)
+            cur = noise(cur, kind, arg, seed, keys_d)
+        elif kind == "recompress":
+            cur = recompress(cur, arg, subsampling)
+        elif kind == "rescale":
+            cur = rescale(cur, arg, resize_filter)
+        elif kind == "blur":
+            cur = blur(cur, arg, blur_radius)
+        elif kind == "crop":
+            cur = crop(cur, arg, crop_origin)
+        elif kind == "rotate":
+            cur = rotate(cur, arg, rotate_fill)
+        elif kind == "sharpen":
+            cur = sharpen(cur, arg, sharpen_sigma, sharpen_radius, sharpen_threshold)
+        elif kind in ("gray", "bgr"):
+            cur = gray(cur) if kind == "gray" else bgr(cur)
+        elif kind in one_argument:
+            cur = one_argument[kind](cur, arg)
+        else:
+            raise ValueError(f"chain step kind {kind!r}: not a step of parse_chain")
+    return cur
 
 
 def apply_augment(x: torch.Tensor, hflip, vflip, gray) -> torch.Tensor:
