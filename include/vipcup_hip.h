@@ -573,6 +573,63 @@ int vip_noise_rgb_u8_placed(const uint8_t* src_u8, const int32_t* sizes_hw, int 
                             int mode, int64_t amount, uint32_t seed, const uint32_t* keys_u32, const int32_t* table_i32, int placement,
                             int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tone of decoded u8 RGB: curves MEASURED from the picture's histogram - auto-contrast, equalisation and contrast-limited adaptive
+ * equalisation (CLAHE) - the kernels under the tone stress perturbations.  dataset/augment.py has nothing of the kind; this goes beyond
+ * the reference.  Every image keeps its size.  A variant is three launches on the caller's stream, without a host round trip:
+ * vip_tone_hist_u8 -> vip_tone_lut_u8 -> vip_tone_apply_rgb_u8.  All arithmetic is integer except the one float64 expression below.
+ *
+ * Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Pillow's convert("L").
+ * Modes: VIP_TONE_AC 0 (auto-contrast per channel), VIP_TONE_ACL 1 (auto-contrast, one table from Y on all three channels),
+ *   VIP_TONE_EQ 2 (equalisation per channel), VIP_TONE_CLAHE 3.  Histogram channels C: 3 in modes 0 and 2 (R, G, B), 1 in modes 1 and
+ *   3 (Y).  Parameter: the cutoff C% in 0..49 (modes 0, 1), 0 (mode 2), TT = ten times the clip limit in 10..99 (mode 3).
+ * Grid (per axis of `side` pixels, G = grid in 1..16): g = min(G, max(1, side / 16)); tile k covers [b[k], b[k + 1]) with b[k] =
+ *   (k side) / g; every tile is at least 16 pixels wide unless g = 1.  Tile (ky, kx) of an image with gy x gx tiles is slot
+ *   ky gx + kx of that image.
+ *
+ * vip_tone_hist_u8: src_u8 [n][maxH][maxW][3], sizes_hw[i] = (h, w) -> hist_i32 int32 [n][slots][channels][256], per image and tile
+ *   the histogram of its pixels' R, G and B (channels = 3) or Y (channels = 1).  EVERY slot is written, one without a tile (slot >= gy
+ *   gx; an image whose size is not positive or exceeds the slot, or whose gy gx exceeds `slots`) with zeros: the buffer need not be
+ *   cleared, and the sum over an image's slots is the histogram of the whole image whatever `grid` is.  Nothing but the images' pixels
+ *   is read.  One workgroup per slot, LDS atomics on integer counts: the result does not depend on the order.
+ * vip_tone_lut_u8: hist_i32 [n][slots][C][256] (C by mode) -> lut_u8 uint8 [n][C][256] (modes 0..2, from the SUM h of the image's
+ *   slots) or [n][slots][256] (mode 3, one table per slot).  One workgroup per table.  With N = sum h:
+ *   modes 0, 1   cut = (N * cutoff) / 100 in 64 bits; lo = the smallest i with sum(h[0..i]) > cut, hi = the largest i with
+ *                sum(h[i..255]) > cut; hi <= lo (or N = 0): lut[i] = i; otherwise
+ *                  lut[i] = clamp(trunc(i * scale + offset), 0, 255), scale = 255.0 / (hi - lo), offset = -lo * scale
+ *                in IEEE float64, the division, the two products and the sum each rounded to nearest on its own (no fused
+ *                multiply-add), trunc towards zero: Pillow's ImageOps.autocontrast(cutoff) bit for bit.
+ *   mode 2       fewer than two non-zero bins: lut[i] = i; otherwise step = (N - (the last non-zero bin)) / 255; step = 0: lut[i] =
+ *                i; otherwise lut[i] = min((step / 2 + sum(h[0..i-1])) / step, 255): Pillow's ImageOps.equalize bit for bit.
+ *   mode 3       A = N (the tile's area; A = 0: lut[i] = i), clip = max(1, (TT * A) / 2560) in 64 bits, h'[i] = min(h[i], clip),
+ *                E = A - sum h', h''[i] = h'[i] + E / 256 + [(i (E % 256)) / 256 != ((i + 1) (E % 256)) / 256]  (sum h'' = A),
+ *                T[i] = (sum(h''[0..i]) * 255 + A / 2) / A in 64 bits.
+ * vip_tone_apply_rgb_u8: src_u8 -> dst_u8 [n][dstMaxH][dstMaxW][3] (a pitch of its own; the two must not overlap) through lut_u8 as
+ *   vip_tone_lut_u8 wrote it for `mode`.  Modes 0, 2: out_c = lut[i][c][X_c]; mode 1: out_c = lut[i][0][X_c].  Mode 3, per axis with
+ *   pixel x, X2 = 2 x + 1 and c2[k] = b[k] + b[k + 1]: X2 < c2[0] -> both neighbours tile 0; X2 >= c2[g - 1] -> both g - 1; otherwise k
+ *   with c2[k] <= X2 < c2[k + 1], neighbours k and k + 1, wq = ((X2 - c2[k]) << 8) / (c2[k + 1] - c2[k]) in 0..255; then
+ *     V     = ((256 - wyq) ((256 - wxq) T00[Y] + wxq T01[Y]) + wyq ((256 - wxq) T10[Y] + wxq T11[Y]) + 32768) >> 16
+ *     out_c = clamp(X_c + V - Y, 0, 255)
+ *   (CLAHE of the Y of YCbCr with the chroma kept).  `grid` and `slots` are those of the histogram call (read in mode 3 only; an image
+ *   whose gy gx exceeds `slots` is skipped).  Only the h x w pixels of an image are written and nothing but the images' pixels is read;
+ *   an image whose size is not positive or exceeds the source or the destination slot is skipped.  A workgroup owns 128 pixels x 8 rows
+ *   and moves them as vip_colour_rgb_u8 does.  The image's table(s) are copied into LDS; in mode 3 the four tile tables are gathered
+ *   from global memory through the vector L1 (README.md has the measurement against an LDS copy).
+ * vip_tone_apply_rgb_u8_placed: the same with the placement of mode 3's tables chosen by the caller (0: global gathers, 1: the at
+ *   most 3 x 10 tables a workgroup's pixels touch copied into LDS), for tools/bench_tone.py and the tests; both write the same bytes.
+ * All three: a null pointer, n or a slot side not positive or above 2^26, a mode, parameter, grid (1..16), channels, placement or
+ *   slots (1..256) out of range, src_u8 and dst_u8 overlapping -> VIP_ERR_BAD_ARG; sizes_hw, hist_i32 or lut_u8 not 4-byte aligned ->
+ *   VIP_ERR_ALIGNMENT; all before any work: a refused call launches nothing.  No allocation, no global atomics: bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+enum { VIP_TONE_AC = 0, VIP_TONE_ACL = 1, VIP_TONE_EQ = 2, VIP_TONE_CLAHE = 3 };
+int vip_tone_hist_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int n, int maxH, int maxW, int grid, int channels, int32_t* hist_i32,
+                     int slots, void* stream);
+int vip_tone_lut_u8(const int32_t* hist_i32, int n, int slots, int mode, int param, uint8_t* lut_u8, void* stream);
+int vip_tone_apply_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                          const uint8_t* lut_u8, int mode, int grid, int slots, int n, void* stream);
+int vip_tone_apply_rgb_u8_placed(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH, int dstMaxW,
+                                 const uint8_t* lut_u8, int mode, int grid, int slots, int placement, int n, void* stream);
+
 /* PNG (dataset/dataset.py:22-30, build_decoder(ext='png') -> tf.image.decode_png(channels=3)): the host inflates, the
  * GPU undoes the scanline filters and expands to 8-bit RGB.  Same output as vip_jpeg_idct_rgb_u8. */
 typedef struct vip_png_desc {

@@ -102,6 +102,10 @@ SIGNATURES = {
     "vip_colour_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "vip_noise_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_int64, C.c_uint32, _vp, _vp, _i, _vp]),
     "vip_noise_rgb_u8_placed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, C.c_int64, C.c_uint32, _vp, _vp, _i, _i, _vp]),
+    "vip_tone_hist_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "vip_tone_lut_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "vip_tone_apply_rgb_u8": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "vip_tone_apply_rgb_u8_placed": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),

@@ -36,8 +36,9 @@ def _sources():
 # shipped kernel free of that form.
 # -ffp-contract=off: resample_host.cpp builds coefficient tables that are compared with Pillow's bit for bit; a fused multiply-add in the
 # filter polynomials would move a coefficient by one unit.  blur_host.cpp: the same for the Gaussian weights and their restatement.
+# tone.hip: the same for the float64 auto-contrast table, which is compared with Pillow's expression bit for bit.
 EXTRA_FLAGS = {"se_gate.hip": ["-fno-slp-vectorize"], "jpeg_pipeline.hip": ["-fno-slp-vectorize"],
-               "resample_host.cpp": ["-ffp-contract=off"], "blur_host.cpp": ["-ffp-contract=off"]}
+               "resample_host.cpp": ["-ffp-contract=off"], "blur_host.cpp": ["-ffp-contract=off"], "tone.hip": ["-ffp-contract=off"]}
 
 # sources that #include another SOURCE file (one kernel family, two arithmetic modes)
 INCLUDES_SOURCE = {"conv_h2.hip": ["conv_igemm.hip"]}

@@ -17,16 +17,21 @@ label's ranges, in that canonical spelling only, matched against the whole token
                  spk<PP>                                percent 01..50
                  imp<TTT>                               ten times the percent, 001..500
     sharpening   shp<PPP>                               percent 001..500
+    tone         ac<PP>  acl<PP>                        cutoff percent 00..49 (acl: one curve from the luma)
+                 eq
+                 clahe<TT>                              ten times the clip limit, 10..99
 
 ``parse_chain`` returns ``(kind, arg)`` per step: ``kind`` names the ``pipeline`` function (``recompress``, ``rescale``, ``blur``,
 ``median``, ``flip``, ``crop``, ``rotate``, ``gray``, ``bgr``, ``hue``, ``saturation``, ``contrast``, ``brightness``, ``gamma``,
-``sharpen``) or, for the noise steps, the kind of ``pipeline.noise`` (``gaussian``, ``mono``, ``speckle``, ``impulse``); ``arg`` is that
-function's argument in the user's units (None for ``gray`` and ``bgr``)."""
+``sharpen``) or, for the noise steps, the kind of ``pipeline.noise`` (``gaussian``, ``mono``, ``speckle``, ``impulse``) and, for the tone
+steps, the mode of ``pipeline.tone`` (``autocontrast``, ``autocontrast_luma``, ``equalize``, ``clahe``); ``arg`` is that function's
+argument in the user's units (None for ``gray``, ``bgr`` and ``equalize``)."""
 import re
 from typing import List, Optional, Sequence, Tuple
 
 MIN_STEPS, MAX_STEPS, MAX_CHAINS = 2, 8, 16
 NOISE_STEPS = ("gaussian", "mono", "speckle", "impulse")
+TONE_STEPS = ("autocontrast", "autocontrast_luma", "equalize", "clahe")
 
 # (pattern of the whole token, kind, lowest, highest, banned value, units per one of the argument, the family's own flag); a pattern's
 # optional "m" group marks a negative value; scale None: the step has no number
@@ -50,6 +55,10 @@ _STEPS = (
     (r"spk(\d\d)", "speckle", 1, 50, None, 1, "--stress-speckle"),
     (r"imp(\d{3})", "impulse", 1, 500, None, 10, "--stress-impulse"),
     (r"shp(\d{3})", "sharpen", 1, 500, None, 1, "--stress-sharpen"),
+    (r"ac(\d\d)", "autocontrast", 0, 49, None, 1, "--stress-autocontrast"),
+    (r"acl(\d\d)", "autocontrast_luma", 0, 49, None, 1, "--stress-autocontrast-luma"),
+    (r"(eq)", "equalize", None, None, None, None, "--stress-equalize"),
+    (r"clahe(\d\d)", "clahe", 10, 99, None, 10, "--stress-clahe"),
 )
 STEP_FLAGS = {kind: flag for _, kind, _, _, _, _, flag in _STEPS}
 
@@ -60,7 +69,7 @@ def parse_step(token: str) -> Tuple[str, object]:
         m = re.fullmatch(pattern, token, re.ASCII) if isinstance(token, str) else None
         if m is None:
             continue
-        if scale is None:                                 # flip<axis>, gray, bgr
+        if scale is None:                                 # flip<axis>, gray, bgr, eq
             return kind, (m.group(1) if kind == "flip" else None)
         v = int(m.group(m.lastindex))
         if not lo <= v <= hi or v == banned:
@@ -69,7 +78,7 @@ def parse_step(token: str) -> Tuple[str, object]:
         return kind, (v if scale == 1 else v / scale)
     raise ValueError(f"chain step {token!r}: expected a single-variant stress label in its canonical spelling and range (q<Q>, r<P>, "
                      "b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, con<PPP>, "
-                     "bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>)")
+                     "bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, clahe<TT>)")
 
 
 def parse_chain(text: str) -> List[Tuple[str, object]]:

@@ -492,13 +492,24 @@ def _noise_variants(noises=(), mono_noises=(), speckles=(), impulses=()) -> List
     return out
 
 
+def _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes) -> List[Tuple[str, str, object]]:
+    """``(label, mode of pipeline.tone, argument)`` of the tone variants in row order: ``ac<PP>`` and ``acl<PP>`` for each cutoff (ascending,
+    two digits), ``eq``, ``clahe<TT>`` for each clip limit (ascending, ``TT`` = ten times the limit: 2 -> ``clahe20``)"""
+    out = [(f"ac{pc:02d}", "autocontrast", pc) for pc in sorted(int(pc) for pc in autocontrasts)]
+    out += [(f"acl{pc:02d}", "autocontrast_luma", pc) for pc in sorted(int(pc) for pc in autocontrast_lumas)]
+    out += [("eq", "equalize", None)] if equalize else []
+    out += [(f"clahe{tt:02d}", "clahe", tt / 10) for tt in sorted(int(round(float(lm) * 10)) for lm in clahes)]
+    return out
+
+
 def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = (),
                   flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
                   rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
                   contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
                   mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
                   noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
-                  sharpen_threshold: int = 0, chains: Sequence[str] = ()) -> List[str]:
+                  sharpen_threshold: int = 0, chains: Sequence[str] = (), autocontrasts: Sequence[int] = (),
+                  autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8) -> List[str]:
     """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
     ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
     ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
@@ -515,8 +526,10 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
     ``imp010``), each followed by its ``_q<Q>`` labels (``noise_seed`` and ``noise_keys`` are ``stress_batch``'s and do not change a
     label), then the sharpening: ``shp<PPP>`` for each percent of ``sharpens`` (ascending, three digits: 80 -> ``shp080``), each followed
     by its ``_q<Q>`` labels (``sharpen_sigma``, ``sharpen_radius`` and ``sharpen_threshold`` are ``stress_batch``'s and do not change a
-    label), and last the ``chains`` in the order given, each under its own text (``r50+shp080+q75``) and never followed by ``_q<Q>``
-    labels."""
+    label), then the tone: ``ac<PP>`` for each cutoff of ``autocontrasts`` and ``acl<PP>`` for each of ``autocontrast_lumas`` (ascending,
+    two digits), ``eq`` with ``equalize``, ``clahe<TT>`` for each clip limit of ``clahes`` (ascending, ``TT`` = ten times the limit: 2 ->
+    ``clahe20``), each followed by its ``_q<Q>`` labels (``clahe_grid`` is ``stress_batch``'s and does not change a label), and last the
+    ``chains`` in the order given, each under its own text (``r50+shp080+q75``) and never followed by ``_q<Q>`` labels."""
     labels = [f"q{int(q)}" for q in qualities]
     for pc in scales:
         labels.append(f"r{int(pc)}")
@@ -531,7 +544,8 @@ def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: S
         + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
     for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)] \
             + [v[0] for v in _noise_variants(noises, mono_noises, speckles, impulses)] \
-            + [f"shp{pc:03d}" for pc in sorted(int(pc) for pc in sharpens)]:
+            + [f"shp{pc:03d}" for pc in sorted(int(pc) for pc in sharpens)] \
+            + [v[0] for v in _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes)]:
         labels.append(v)
         labels += [f"{v}_q{int(q)}" for q in qualities]
     return labels + [str(text) for text in chains]
@@ -544,7 +558,8 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
                  mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
                  noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
-                 sharpen_threshold: int = 0, chains: Sequence[str] = ()):
+                 sharpen_threshold: int = 0, chains: Sequence[str] = (), autocontrasts: Sequence[int] = (),
+                 autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8):
     """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
     bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
     (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
@@ -578,9 +593,13 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     ``sharpen_threshold``) the decoded batch is also sharpened by an unsharp mask (``pipeline.sharpen``, one launch per variant) and scored
     unsaved and re-saved at every quality, one sharpened batch alive at a time; sharpening is not combined with the other families
     except through a chain.  V percents cost V (1 + Q) plain runs.
+    With ``autocontrasts`` / ``autocontrast_lumas`` (integer cutoff percents 0..49), ``equalize`` and ``clahes`` (clip limits 1.0..9.9;
+    ``clahe_grid`` tiles per axis; each list ascending here) the decoded batch also goes through a tone curve measured from each image's
+    own histogram (``pipeline.tone``: histograms, tables and pixels in three launches, nothing returns to the host) and is scored
+    unsaved and re-saved at every quality, one batch alive at a time; the tone rows follow the sharpening rows.
     With ``chains`` (chain texts, ``pipeline.parse_chain``: ``"r50+shp080+q75"``; scored in the order given) the decoded batch also goes
     through each chain's steps left to right (``pipeline.apply_chain`` with this call's ``subsampling``, ``resize_filter``,
-    ``blur_radius``, ``crop_origin``, ``rotate_fill``, ``sharpen_*``, ``noise_seed`` and ``noise_keys``) and the result is scored ONCE,
+    ``blur_radius``, ``crop_origin``, ``rotate_fill``, ``sharpen_*``, ``noise_seed``, ``noise_keys`` and ``clahe_grid``) and the result is scored ONCE,
     exactly as the chain is written: ``qualities`` do not multiply chain rows, a chain that should end in a re-save ends in a ``q``
     step.  One chain's batch is alive at a time; C chains cost C plain runs.  The chain rows come last.  Then too the result is
     ``(rows, labels)``."""
@@ -636,21 +655,29 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         rows.append(_score_batch(sharp, members))
         for q in qualities:
             rows.append(_score_batch(pipeline.recompress(sharp, int(q), subsampling), members))
+    toned = _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes)
+    for _, mode, arg in toned:
+        curved = pipeline.tone(batch, mode, arg, clahe_grid)                                       # one alive at a time
+        rows.append(_score_batch(curved, members))
+        for q in qualities:
+            rows.append(_score_batch(pipeline.recompress(curved, int(q), subsampling), members))
     chains = [str(text) for text in chains]
     for text in chains:                                          # scored once, as written: the qualities do not multiply chain rows
         rows.append(_score_batch(pipeline.apply_chain(
             batch, pipeline.parse_chain(text), subsampling=subsampling, resize_filter=resize_filter, blur_radius=blur_radius,
             crop_origin=crop_origin, rotate_fill=rotate_fill, sharpen_sigma=sharpen_sigma, sharpen_radius=sharpen_radius,
-            sharpen_threshold=sharpen_threshold, noise_seed=noise_seed, noise_keys=keys_d if keys_d is not None else noise_keys), members))
+            sharpen_threshold=sharpen_threshold, noise_seed=noise_seed, noise_keys=keys_d if keys_d is not None else noise_keys,
+            clahe_grid=clahe_grid), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
     if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours and not noisy and \
-            not sharpens and not chains:
+            not sharpens and not chains and not toned:
         return torch.stack(rows)
     return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations, gray=gray, bgr=bgr, hues=hues,
                                             saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas,
                                             noises=noises, mono_noises=mono_noises, speckles=speckles, impulses=impulses,
-                                            sharpens=sharpens, chains=chains)
+                                            sharpens=sharpens, chains=chains, autocontrasts=autocontrasts,
+                                            autocontrast_lumas=autocontrast_lumas, equalize=equalize, clahes=clahes)
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,

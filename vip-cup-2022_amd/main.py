@@ -15,6 +15,8 @@
                                      [--stress-impulse P[,P...]] [--stress-noise-seed N]                                     (--stress-out FILE.csv)
                                      [--stress-sharpen P[,P...]] [--stress-sharpen-sigma S] [--stress-sharpen-radius R]
                                      [--stress-sharpen-threshold T]                                                          (--stress-out FILE.csv)
+                                     [--stress-autocontrast C[,C...]] [--stress-autocontrast-luma C[,C...]] [--stress-equalize]
+                                     [--stress-clahe L[,L...]] [--stress-clahe-grid G]                                       (--stress-out FILE.csv)
                                      [--stress-chain STEP+STEP[+STEP...][,CHAIN...]]                                         (--stress-out FILE.csv)
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
@@ -89,17 +91,27 @@ clamped, one launch (Pillow's ``UnsharpMask`` blurs with a box approximation: cl
 with ``--stress-jpeg``, re-saved at every quality (``shp<PPP>_q<Q>``); the rows follow those of the noise flags, ascending; a value listed
 twice is refused.  Sharpening is not combined with the other families except through a chain.  ``stress.json`` then lists
 ``sharpen_percents``, ``sharpen_sigma``, ``sharpen_radius`` and ``sharpen_threshold`` under ``settings``.
+``--stress-autocontrast 2 --stress-autocontrast-luma 2 --stress-equalize --stress-clahe 2,4 --stress-out stress.csv`` is the tone
+perturbation - what a gallery's "auto", a messenger's "enhance" or a scanner does: a curve MEASURED from the picture's own histogram.
+``ac<PP>`` is Pillow's ``ImageOps.autocontrast(cutoff=PP)`` per channel and ``acl<PP>`` its ``preserve_tone=True`` form (one curve from the
+luma), cutoffs integer percents 0..49; ``eq`` is ``ImageOps.equalize``; all three bit for bit.  ``clahe<TT>`` (clip limits 1.0..9.9, ``TT`` =
+ten times the limit) is contrast-limited adaptive equalisation of the luma on ``--stress-clahe-grid`` (1..16, default 8) tiles per axis
+of at least 16 pixels, the tile tables blended bilinearly and the chroma kept, in integers (include/vipcup_hip.h).  Each variant is
+three launches - histograms, tables, pixels - and nothing returns to the host.  The rows follow the sharpening rows in the order
+``ac``, ``acl``, ``eq``, ``clahe``, each list ascending, unsaved and - with ``--stress-jpeg`` - re-saved (``<label>_q<Q>``); a value listed twice is
+refused.  ``stress.json`` then lists ``autocontrast_cutoffs``, ``autocontrast_luma_cutoffs``, ``equalize``, ``clahe_limits`` and ``clahe_grid``
+under ``settings``.
 ``--stress-chain r50+shp080+q75,q90+crop95+q75 --stress-out stress.csv`` scores every image after a SEQUENCE of perturbations, as files
 are laundered in practice (downscale, sharpen, re-save; a second JPEG on a shifted block grid).  A chain is 2..8 steps joined by ``+``;
 up to 16 chains, separated by commas, keep the order given; a chain listed twice is refused.  A step is exactly a single-variant label
 of the flags above in its canonical spelling and range, matched against the whole token: ``q<Q>``, ``r<P>``, ``b<TT>``, ``m3``, ``m5``,
 ``fliph``, ``flipv``, ``crop<PP>``, ``rot<TTT>``, ``rotm<TTT>``, ``gray``, ``bgr``, ``hue<DDD>``, ``huem<DDD>``, ``sat<PPP>``, ``con<PPP>``, ``bri<PP>``,
-``brim<PP>``, ``gam<PPP>``, ``n<TTT>``, ``nm<TTT>``, ``spk<PP>``, ``imp<TTT>``, ``shp<PPP>``; a one-step chain is refused with the name of the
+``brim<PP>``, ``gam<PPP>``, ``n<TTT>``, ``nm<TTT>``, ``spk<PP>``, ``imp<TTT>``, ``shp<PPP>``, ``ac<PP>``, ``acl<PP>``, ``eq``, ``clahe<TT>``; a one-step chain is refused with the name of the
 flag that gives that row; the ``r`` percents of a chain must multiply to 10..400 %.  The steps run left to right on the decoded image
 at its own size, each with the options of its family's flags (``--stress-subsampling`` for ``q``, ``--stress-resize-filter`` for ``r``,
 ``--stress-blur-radius`` for ``b``, ``--stress-crop-origin`` for ``crop``, ``--stress-rotate-fill`` for ``rot``, ``--stress-sharpen-sigma`` /
-``-radius`` / ``-threshold`` for ``shp``, ``--stress-noise-seed`` for the noise steps), which are accepted when a chain holds the step they
-govern.  A ``con`` step takes the mean colour of the image as it reaches that step; the k-th noise step of a chain draws from seed + k on
+``-radius`` / ``-threshold`` for ``shp``, ``--stress-noise-seed`` for the noise steps, ``--stress-clahe-grid`` for ``clahe``), which are accepted when a chain holds the step they
+govern.  A ``con`` step takes the mean colour, and a tone step the histogram, of the image as it reaches that step; the k-th noise step of a chain draws from seed + k on
 the image as it reaches that step, so ``n030+q75`` sees the field of the row ``n030``.  The result is scored once, as written:
 ``--stress-jpeg`` does not multiply chain rows.  The chain rows come last under the chain's text (``p_<chain>``, ``decision_<chain>``), count
 for ``stable`` and ``flips`` and not for ``flips_at``; ``stress.json`` keys them by label and lists ``chains`` under ``settings``.  C chains
@@ -196,18 +208,18 @@ def _heatmap_writer(a, names, members, rank):
 
 
 def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None,
-                   colour=None, noise=None, names=None, sharpen=None, chains=None):
+                   colour=None, noise=None, names=None, sharpen=None, chains=None, tone=None):
     """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
     ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None) and the colour flags (``colour``:
     likewise) and the noise flags (``noise``: likewise; every batch's ``noise_keys`` come from its files' ``names``), ``--stress-sharpen``
-    (``sharpen``: likewise) and ``--stress-chain`` (``chains``: ``{"chains": texts}`` plus the options of the steps that no family flag
+    (``sharpen``: likewise), the tone flags (``tone``: likewise) and ``--stress-chain`` (``chains``: ``{"chains": texts}`` plus the options of the steps that no family flag
     of this run carries, or None): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed
     batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble, pipeline
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians or geometry or colour or noise or sharpen or chains:
-            more = _label_keywords(geometry, colour, noise, sharpen, chains)
+        if scales or blurs or medians or geometry or colour or noise or sharpen or chains or tone:
+            more = _label_keywords(geometry, colour, noise, sharpen, chains, tone)
             if noise or chains:                                                                     # by file, not by batch position
                 more["noise_keys"] = pipeline.noise_keys(names[b0:b1])
             rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
@@ -220,13 +232,14 @@ def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicub
 
 
 def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None,
-                  noise=None, sharpen=None, chains=None):
+                  noise=None, sharpen=None, chains=None, tone=None):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (), **_label_keywords(geometry, colour, noise, sharpen, chains))
-    mixed = bool(scales or blurs or medians or geometry or colour or noise or sharpen or chains)
+    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (),
+                                    **_label_keywords(geometry, colour, noise, sharpen, chains, tone))
+    mixed = bool(scales or blurs or medians or geometry or colour or noise or sharpen or chains or tone)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -258,11 +271,14 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
     if sharpen:
         summary["settings"].update({"sharpen_percents": sharpen["sharpens"], "sharpen_sigma": sharpen["sharpen_sigma"],
                                     "sharpen_radius": sharpen["sharpen_radius"], "sharpen_threshold": sharpen["sharpen_threshold"]})
+    if tone:
+        summary["settings"].update({"autocontrast_cutoffs": tone["autocontrasts"], "autocontrast_luma_cutoffs": tone["autocontrast_lumas"],
+                                    "equalize": tone["equalize"], "clahe_limits": tone["clahes"], "clahe_grid": tone["clahe_grid"]})
     if chains:
         from vipcup_amd import chain as grammar
         summary["settings"]["chains"] = list(chains["chains"])
         kinds = grammar.chain_kinds(chains["chains"])
-        for key in ("crop_origin", "rotate_fill", "noise_seed"):          # the options of chain steps whose family flag is absent
+        for key in ("crop_origin", "rotate_fill", "noise_seed", "clahe_grid"):          # the options of chain steps whose family flag is absent
             if key in chains:
                 summary["settings"].setdefault(key, chains[key])
         if "rescale" in kinds:
@@ -273,9 +289,9 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
         json.dump(summary, f, indent=1)
 
 
-def _label_keywords(geometry, colour, noise, sharpen, chains):
+def _label_keywords(geometry, colour, noise, sharpen, chains, tone=None):
     """the keywords of ``stress_labels`` (and ``stress_batch``) from the CLI's per-family dictionaries"""
-    return {**(geometry or {}), **(colour or {}), **(noise or {}), **(sharpen or {}), **(chains or {})}
+    return {**(geometry or {}), **(colour or {}), **(noise or {}), **(sharpen or {}), **(chains or {}), **(tone or {})}
 
 
 def _tile_scorer(a, kept, kept_tiles):
@@ -550,15 +566,37 @@ def main(argv=None):
     ap.add_argument("--stress-sharpen-threshold", type=int, default=None, metavar="T",
                     help="leave a sample as it is where it differs from its blurred value by at most T levels (0..255, default 0); needs "
                          "--stress-sharpen or a --stress-chain with a shp step")
+    ap.add_argument("--stress-autocontrast", default=None, metavar="C[,C...]",
+                    help="tone stress test: also score every image after Pillow's ImageOps.autocontrast(cutoff=C) per channel, bit for bit "
+                         "(integer percents 0..49; ascending; a value listed twice is refused): the levels stretched to the full range "
+                         "after C %% of the pixels are cut off either end of the image's own histogram; three launches (histograms, "
+                         "tables, pixels), unsaved and - with --stress-jpeg - re-saved at every quality; needs --stress-out, whose table "
+                         "gains the labels ac<PP>, ac<PP>_q<Q> after the sharpening rows")
+    ap.add_argument("--stress-autocontrast-luma", default=None, metavar="C[,C...]",
+                    help="tone stress test: the same with ONE curve from the luma's histogram on all three channels "
+                         "(autocontrast(cutoff=C, preserve_tone=True)); labels acl<PP>, acl<PP>_q<Q>; needs --stress-out")
+    ap.add_argument("--stress-equalize", action="store_true",
+                    help="tone stress test: also score every image with its histogram flattened per channel (Pillow's ImageOps.equalize, "
+                         "bit for bit); labels eq, eq_q<Q>; needs --stress-out")
+    ap.add_argument("--stress-clahe", default=None, metavar="L[,L...]",
+                    help="tone stress test: also score every image after contrast-limited adaptive equalisation of its luma at each listed "
+                         "clip limit (1.0..9.9 with at most one fractional digit; ascending; a value listed twice is refused), per tile "
+                         "with the tile tables blended bilinearly and the chroma kept, in integers; labels clahe<TT>, clahe<TT>_q<Q> (TT = "
+                         "ten times the limit); needs --stress-out")
+    ap.add_argument("--stress-clahe-grid", type=int, default=None, metavar="G",
+                    help="tiles per axis of --stress-clahe (1..16, default 8; fewer on an axis shorter than 16 G pixels, a tile is at "
+                         "least 16 pixels wide); needs --stress-clahe or a --stress-chain with a clahe step")
     ap.add_argument("--stress-chain", default=None, metavar="STEP+STEP[+STEP...][,CHAIN...]",
                     help="stress chains: also score every image after a SEQUENCE of perturbations, e.g. r50+shp080+q75 (downscale, "
                          "sharpen, re-save: what a messenger does) or q90+crop95+q75 (double compression on a shifted block grid).  A "
                          "chain is 2..8 steps joined by +, up to 16 chains separated by commas, kept in the order given; a chain listed "
                          "twice is refused.  A step is a single-variant label of the other stress flags in its canonical spelling: q<Q>, "
                          "r<P>, b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, "
-                         "con<PPP>, bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>; it takes the options of its "
+                         "con<PPP>, bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, "
+                         "clahe<TT>; it takes the options of its "
                          "family's flags (--stress-subsampling, --stress-resize-filter, --stress-blur-radius, --stress-crop-origin, "
-                         "--stress-rotate-fill, --stress-sharpen-sigma / -radius / -threshold, --stress-noise-seed), which are accepted "
+                         "--stress-rotate-fill, --stress-sharpen-sigma / -radius / -threshold, --stress-noise-seed, --stress-clahe-grid), which "
+                         "are accepted "
                          "when a chain holds the step they govern.  The result is scored once, as written: --stress-jpeg does not "
                          "multiply chain rows.  Needs --stress-out, whose table gains one column pair per chain under the chain's text, "
                          "after all other rows; they count for stable and flips, not for flips_at")
@@ -602,8 +640,10 @@ def main(argv=None):
                     ("--stress-brightness", a.stress_brightness), ("--stress-gamma", a.stress_gamma))
     noise_flags = (("--stress-noise", a.stress_noise), ("--stress-noise-mono", a.stress_noise_mono), ("--stress-speckle", a.stress_speckle),
                    ("--stress-impulse", a.stress_impulse))
-    any_colour = any(v is not None for _, v in colour_flags + noise_flags) or a.stress_sharpen is not None or chains is not None
-    # colour, noise, sharpening or chains: the same refusals below
+    tone_flags = (("--stress-autocontrast", a.stress_autocontrast), ("--stress-autocontrast-luma", a.stress_autocontrast_luma),
+                  ("--stress-equalize", a.stress_equalize or None), ("--stress-clahe", a.stress_clahe))
+    any_colour = any(v is not None for _, v in colour_flags + noise_flags + tone_flags) or a.stress_sharpen is not None or chains is not None
+    # colour, noise, sharpening, tone or chains: the same refusals below
     if a.occlusion is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
@@ -770,11 +810,32 @@ def main(argv=None):
     elif a.stress_sharpen_sigma is not None or a.stress_sharpen_radius is not None or a.stress_sharpen_threshold is not None:
         raise SystemExit("vipcup_amd main: --stress-sharpen-sigma / --stress-sharpen-radius / --stress-sharpen-threshold need --stress-sharpen "
                          "P[,P...] or a --stress-chain with a shp step")
+    tone = None                                         # the tone keywords of stress_batch: with a tone flag
+    if any(v is not None for _, v in tone_flags):
+        tone = {"autocontrasts": [], "autocontrast_lumas": [], "equalize": bool(a.stress_equalize), "clahes": [],
+                "clahe_grid": 8 if a.stress_clahe_grid is None else a.stress_clahe_grid}
+        for flag, text, key in (("--stress-autocontrast", a.stress_autocontrast, "autocontrasts"),
+                                ("--stress-autocontrast-luma", a.stress_autocontrast_luma, "autocontrast_lumas")):
+            if text is not None:
+                tokens = text.split(",")
+                given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,2}", t) for t in tokens) else []
+                if not given or given[-1] > 49 or len(set(given)) != len(given):
+                    raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of integer cutoff percents in "
+                                     "0..49, each listed once")
+                tone[key] = given
+        if a.stress_clahe is not None:
+            tone["clahes"] = [t / 10 for t in _tenths_list("--stress-clahe", a.stress_clahe, 10, 99, "clip limits in 1.0..9.9 with at most "
+                                                           "one fractional digit")]
+    if a.stress_clahe_grid is not None:
+        if a.stress_clahe is None and "clahe" not in in_chain:
+            raise SystemExit("vipcup_amd main: --stress-clahe-grid needs --stress-clahe L[,L...] or a --stress-chain with a clahe step")
+        if not 1 <= a.stress_clahe_grid <= 16:
+            raise SystemExit(f"vipcup_amd main: --stress-clahe-grid {a.stress_clahe_grid}: expected an integer in 1..16")
     for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
                               ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
                               ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags) \
-            + tuple((flag, v, "noise") for flag, v in noise_flags) + (("--stress-sharpen", a.stress_sharpen, "sharpening"),
-                                                                      ("--stress-chain", chains, "chained")):
+            + tuple((flag, v, "noise") for flag, v in noise_flags) + (("--stress-sharpen", a.stress_sharpen, "sharpening"),) \
+            + tuple((flag, v, "tone") for flag, v in tone_flags) + (("--stress-chain", chains, "chained"),):
         if given is None:
             continue
         if a.stress_out is None:
@@ -801,8 +862,10 @@ def main(argv=None):
             chained.update({"crop_origin": a.stress_crop_origin, "rotate_fill": a.stress_rotate_fill})
         if noise is None and in_chain & {"gaussian", "mono", "speckle", "impulse"}:
             chained["noise_seed"] = a.stress_noise_seed
+        if tone is None and "clahe" in in_chain:
+            chained["clahe_grid"] = 8 if a.stress_clahe_grid is None else a.stress_clahe_grid
     smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None or noise is not None or \
-        sharpen is not None or chains is not None
+        sharpen is not None or chains is not None or tone is not None
     qualities = None
     if a.stress_jpeg is not None:
         try:
@@ -923,7 +986,7 @@ def main(argv=None):
     if qualities is not None or scales is not None or smoothed:
         batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
                                       scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour,
-                                      noise, names, sharpen, chained)
+                                      noise, names, sharpen, chained, tone)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -943,7 +1006,7 @@ def main(argv=None):
     stressed = None
     if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
         n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (),
-                                            **_label_keywords(geometry, colour, noise, sharpen, chained)))
+                                            **_label_keywords(geometry, colour, noise, sharpen, chained, tone)))
         stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
@@ -960,7 +1023,7 @@ def main(argv=None):
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
             _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour, noise,
-                          sharpen, chained)
+                          sharpen, chained, tone)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

@@ -1152,19 +1152,136 @@ def impulse(batch: DecodedBatch, percent: float, seed: int = 0, keys=None) -> De
     return noise(batch, "impulse", percent, seed, keys)
 
 
+TONE_MODES = {"autocontrast": 0, "autocontrast_luma": 1, "equalize": 2, "clahe": 3}     # VIP_TONE_* (include/vipcup_hip.h)
+TONE_MAX_GRID = 16
+# the tiles over which the histogram launch of the three whole-image modes spreads an image (their sum is the image's histogram
+# whatever the grid): more workgroups per image against more histograms to write and add up (README.md has the measurement)
+_TONE_GLOBAL_GRID = 4
+
+
+def tone_grid(h: int, w: int, grid: int = 8) -> Tuple[int, int]:
+    """``(gy, gx)``, the tiles of an ``h x w`` image under ``clahe(..., grid=grid)``: per axis ``min(grid, max(1, side // 16))``, so that a
+    tile is at least 16 pixels wide; tile k of an axis covers ``occlusion_bounds(side, g)[k:k + 2]``.  Pure host arithmetic."""
+    grid = _int_arg("grid", grid, 1, TONE_MAX_GRID)
+    return min(grid, max(1, int(h) // 16)), min(grid, max(1, int(w) // 16))
+
+
+def _tone_args(mode, arg, grid) -> Tuple[int, int, int]:
+    """``(mode, parameter, grid)`` as the entry points take them, validated"""
+    if not isinstance(mode, str) or mode not in TONE_MODES:
+        raise ValueError(f"mode {mode!r}: expected one of {', '.join(TONE_MODES)}")
+    grid = _int_arg("grid", grid, 1, TONE_MAX_GRID)
+    if mode == "equalize":
+        if arg is not None:
+            raise ValueError(f"arg {arg!r}: equalize takes no argument (None)")
+        return TONE_MODES[mode], 0, grid
+    if mode == "clahe":
+        return TONE_MODES[mode], _tenths("limit", arg, 10, 99), grid
+    return TONE_MODES[mode], _int_arg("cutoff", arg, 0, 49), grid
+
+
+def tone_histograms(batch: DecodedBatch, grid: int, channels: int) -> torch.Tensor:
+    """int32 ``[n, slots, channels, 256]`` on the device: per image and tile of ``tone_grid(h, w, grid)`` (tile ``(ky, kx)`` in slot
+    ``ky * gx + kx``; ``slots`` = the batch's largest ``gy * gx``, the others zero) the histogram of R, G and B (``channels`` 3) or of the
+    luma (1).  ``vip_tone_hist_u8``, one launch on the current stream; the padding of the slots is not read."""
+    grid = _int_arg("grid", grid, 1, TONE_MAX_GRID)
+    if channels not in (1, 3):
+        raise ValueError(f"channels {channels!r}: expected 3 (R, G, B) or 1 (luma)")
+    n, maxH, maxW, _ = batch.rgb.shape
+    slots = max(min(grid, max(1, h // 16)) * min(grid, max(1, w // 16)) for h, w in set(batch.sizes_host))      # tone_grid, per distinct size
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    hist = torch.empty((n, slots, channels, 256), dtype=torch.int32, device=batch.rgb.device)
+    _launch("vip_tone_hist_u8", _p(src), _p(batch.sizes), n, maxH, maxW, grid, channels, _p(hist), slots)
+    return hist
+
+
+def tone_tables(hist: torch.Tensor, mode: str, arg=None) -> torch.Tensor:
+    """The uint8 tables of ``mode`` from ``tone_histograms``' int32 ``[n, slots, C, 256]`` (C = 3 for "autocontrast" and "equalize", 1
+    for "autocontrast_luma" and "clahe"): ``[n, C, 256]`` from the sum of an image's slots, for "clahe" ``[n, slots, 256]``, one table per
+    tile.  ``vip_tone_lut_u8``, one launch on the current stream."""
+    m, param, _ = _tone_args(mode, arg, 1)
+    c = 3 if m in (0, 2) else 1
+    if hist.dtype != torch.int32 or hist.dim() != 4 or hist.shape[2] != c or hist.shape[3] != 256 or not hist.is_contiguous() or \
+            not 1 <= hist.shape[1] <= TONE_MAX_GRID ** 2 or hist.shape[0] < 1:
+        raise ValueError(f"hist: expected a contiguous int32 [n, 1..{TONE_MAX_GRID ** 2}, {c}, 256] tensor for {mode}, got {hist.dtype} "
+                         f"{tuple(hist.shape)}")
+    n, slots = int(hist.shape[0]), int(hist.shape[1])
+    lut = torch.empty((n, slots if m == 3 else c, 256), dtype=torch.uint8, device=hist.device)
+    _launch("vip_tone_lut_u8", _p(hist), n, slots, m, param, _p(lut))
+    return lut
+
+
+def tone(batch: DecodedBatch, mode: str, arg=None, grid: int = 8) -> DecodedBatch:
+    """A tone curve MEASURED from each image's own histogram, on the decoded pixels at their own size (include/vipcup_hip.h has the
+    arithmetic).  ``mode`` "autocontrast" (``arg`` = cutoff, an integer percent 0..49: Pillow's ``ImageOps.autocontrast`` per channel, bit
+    for bit), "autocontrast_luma" (one table from the luma's histogram on all three channels: ``preserve_tone=True``), "equalize" (``arg``
+    None: ``ImageOps.equalize``, bit for bit) or "clahe" (``arg`` = clip limit 1.0..9.9 in steps of 0.1, ``grid`` 1..16 tiles per axis, at
+    least 16 pixels each - ``tone_grid``: contrast-limited equalisation of the luma per tile, the tile tables blended bilinearly, the
+    chroma kept; ``grid`` is validated and otherwise unused in the other modes).  Three launches on the current stream - histograms,
+    tables, pixels - with no host round trip.  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not
+    touched."""
+    _, _, grid = _tone_args(mode, arg, grid)              # every argument is checked before the first launch
+    return _tone_into(batch, mode, arg, grid, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+
+
+def _tone_into(batch: DecodedBatch, mode: str, arg, grid: int, rgb: torch.Tensor, placement: Optional[int] = None) -> DecodedBatch:
+    """``tone``'s launches: image i of ``batch`` into its slot of ``rgb`` [n, H, W, 3] (contiguous uint8 on the batch's device, slots at
+    least as large as the images; only the pixels of the images are written).  ``placement``: None, or the table placement of
+    ``vip_tone_apply_rgb_u8_placed`` (tools/bench_tone.py)."""
+    m = TONE_MODES[mode]
+    n, maxH, maxW, _ = batch.rgb.shape
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == batch.rgb.device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in set(batch.sizes_host))
+    g = grid if m == 3 else _TONE_GLOBAL_GRID
+    hist = tone_histograms(batch, g, 3 if m in (0, 2) else 1)
+    lut = tone_tables(hist, mode, arg)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), _p(lut), m, g, int(hist.shape[1]))
+    if placement is None:
+        _launch("vip_tone_apply_rgb_u8", *args, n)
+    else:
+        _launch("vip_tone_apply_rgb_u8_placed", *args, int(placement), n)
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
+def autocontrast(batch: DecodedBatch, cutoff: int, luma: bool = False) -> DecodedBatch:
+    """The batch with every image's levels stretched to the full range after ``cutoff`` % of its pixels (an integer in 0..49) are cut
+    off either end of the histogram - per channel (Pillow's ``ImageOps.autocontrast(cutoff=...)``), or with ``luma`` one curve from the
+    luma on all three channels (``preserve_tone=True``).  ``tone(batch, "autocontrast" / "autocontrast_luma", cutoff)``.  Returns a new
+    batch."""
+    if not isinstance(luma, (bool, np.bool_)):
+        raise ValueError(f"luma {luma!r}: expected a bool")
+    return tone(batch, "autocontrast_luma" if luma else "autocontrast", cutoff)
+
+
+def equalize(batch: DecodedBatch) -> DecodedBatch:
+    """The batch with every image's histogram flattened per channel (Pillow's ``ImageOps.equalize``).  ``tone(batch, "equalize")``.
+    Returns a new batch."""
+    return tone(batch, "equalize")
+
+
+def clahe(batch: DecodedBatch, limit: float, grid: int = 8) -> DecodedBatch:
+    """The batch with its local contrast lifted tile by tile: contrast-limited adaptive equalisation of the luma with clip limit
+    ``limit`` (1.0..9.9 in steps of 0.1) on ``tone_grid(h, w, grid)`` tiles, the chroma kept - the "HDR look" of an enhance button.
+    ``tone(batch, "clahe", limit, grid)``.  Returns a new batch."""
+    return tone(batch, "clahe", limit, grid)
+
+
 def apply_chain(batch: DecodedBatch, steps, *, subsampling: str = "4:2:0", resize_filter: str = "bicubic", blur_radius: Optional[int] = None,
                 crop_origin: str = "centre", rotate_fill: str = "crop", sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
-                sharpen_threshold: int = 0, noise_seed: int = 0, noise_keys=None) -> DecodedBatch:
+                sharpen_threshold: int = 0, noise_seed: int = 0, noise_keys=None, clahe_grid: int = 8) -> DecodedBatch:
     """The batch after the ``steps`` of a stress chain (``parse_chain(text)``, or the chain's text), applied left to right to the decoded
     pixels at their own size, each through the ``pipeline`` function of its family with that family's options: ``recompress``
     (``subsampling``), ``rescale`` (``resize_filter``), ``blur`` (``blur_radius``), ``crop`` (``crop_origin``), ``rotate``
     (``rotate_fill``), ``sharpen`` (``sharpen_sigma``, ``sharpen_radius``, ``sharpen_threshold``).  A ``contrast`` step takes the mean
     colour of the batch as it reaches that step.  A noise step uses ``noise_keys`` (as for ``noise``: one integer per image, None:
     0..n-1, or ``noise_keys_device``'s tensor) and positions in the image as it reaches that step; the k-th noise step of the chain draws
-    from seed ``(noise_seed + k) mod 2^32`` (``chain_noise_seeds``).  Intermediate batches are dropped as the chain proceeds.  Returns a
-    new batch; ``batch`` is not touched."""
+    from seed ``(noise_seed + k) mod 2^32`` (``chain_noise_seeds``).  A tone step (``autocontrast``, ``autocontrast_luma``, ``equalize``,
+    ``clahe`` with ``clahe_grid`` tiles per axis) measures the batch as it reaches that step.  Intermediate batches are dropped as the
+    chain proceeds.  Returns a new batch; ``batch`` is not touched."""
     steps = parse_chain(steps) if isinstance(steps, str) else list(steps)
     seeds = chain_noise_seeds(steps, _int_arg("noise_seed", noise_seed, 0, 0xFFFFFFFF))
+    clahe_grid = _int_arg("clahe_grid", clahe_grid, 1, TONE_MAX_GRID)
     one_argument = {"median": median, "flip": flip, "hue": hue, "saturation": saturation, "contrast": contrast, "brightness": brightness,
                     "gamma": gamma}
     keys_d = None
@@ -1188,6 +1305,8 @@ def apply_chain(batch: DecodedBatch, steps, *, subsampling: str = "4:2:0", resiz
             cur = sharpen(cur, arg, sharpen_sigma, sharpen_radius, sharpen_threshold)
         elif kind in ("gray", "bgr"):
             cur = gray(cur) if kind == "gray" else bgr(cur)
+        elif kind in TONE_MODES:
+            cur = tone(cur, kind, arg, clahe_grid)
         elif kind in one_argument:
             cur = one_argument[kind](cur, arg)
         else:
