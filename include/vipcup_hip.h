@@ -156,6 +156,11 @@ int vip_gemm_split2_f16(const void* A, const void* W, const float* bias, void* C
  * with streamed weights; act = GELU, hidden % 32 == 0, M >= 8192); otherwise use two vip_gemm_bias_act_f16 calls.
  * ------------------------------------------------------------------------------------------ */
 int vip_mlp_fused_supported(int M, int C, int hidden, int act);
+/* Dry run of that launch (nothing is launched; the launcher calls the same function): returns the number of token tiles the kernel
+ * walks (0: shape not supported), *workgroups = the workgroups that walk them (tile += workgroups: min(tiles, CUs) - asks the current
+ * device for its CU count), *tile_rows = tokens per tile (512 with LDS-resident weights, 256 with streamed ones).  Either pointer may
+ * be NULL.  More tiles than workgroups means a workgroup runs several passes of its tile loop. */
+int vip_mlp_fused_plan(int M, int C, int hidden, int act, int* workgroups, int* tile_rows);
 int vip_mlp_fused_f16(const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w1,
                       const float* b1, const void* w2, const float* b2, const void* residual, void* y, int M, int C,
                       int hidden, int ldx, int ldw1, int ldw2, int ldy, int ldr, int act, void* stream);
@@ -193,6 +198,11 @@ int vip_dwconv2d_nhwc_f16(const void* x, const float* w, const float* bias, void
  * in a fixed order (no atomics: bit-reproducible).  vip_se_gate_pooled_f16 finishes the mean from them instead of reading
  * the whole map again. */
 int vip_dwconv2d_pool_parts(int B, int H, int W, int C, int k, int stride, int Ho, int Wo);
+/* Dry run of the stride-1 register-tiled depthwise launch (plain form, or with pooled != 0 the pooling form): returns the number of
+ * tile groups a channel block's workgroups walk (0: the tile kernel does not take the shape), *workgroups = those workgroups
+ * (gridDim.x; at the cap each XCD walks one band of groups), geom[4] = {channel chunks per block, tiles per block, channel blocks
+ * (gridDim.y), workgroup cap}.  workgroups / geom may be NULL.  Pure host arithmetic: no device is needed. */
+long vip_dwconv2d_tile_plan(int B, int H, int W, int C, int k, int stride, int Ho, int Wo, int pooled, int* workgroups, int* geom);
 int vip_dwconv2d_pool_nhwc_f16(const void* x, const float* w, const float* bias, void* y, float* partials, int parts,
                                int B, int H, int W, int C, int k, int stride, int pt, int pl, int Ho, int Wo, int act,
                                void* stream);
@@ -808,11 +818,18 @@ int vip_dwconv2d_nhwc_h2(const void* x, const float* w, const float* bias, void*
  * ldr in logical elements), w1 [hidden][ldw1 halfs] and w2 [C][ldw2 halfs] packed and pre-scaled as for vip_conv2d_nhwc_h2 (b = bias *
  * scale, out_scale = 1 / scale); ln_gamma / ln_beta NULL: no LayerNorm. */
 int vip_mlp_fused_supported_h2(int M, int C, int hidden, int act);
+/* dry run, as vip_mlp_fused_plan: tiles (0: unsupported), *workgroups (CUs x workgroups per CU, at most), *tile_rows (32 per wave of the
+ * instantiation the host picks: 128 or 256) */
+int vip_mlp_fused_plan_h2(int M, int C, int hidden, int act, int* workgroups, int* tile_rows);
 int vip_mlp_fused_h2(const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w1, const float* b1, float out_scale1,
                      const void* w2, const float* b2, float out_scale2, const void* residual, void* y, int M, int C, int hidden, int ldx,
                      int ldw1, int ldw2, int ldy, int ldr, int act, int* status, void* stream);
 int vip_dw_filter_quad_major(const float* w, float* w_quad, int k, int C, void* stream);
 int vip_dwconv2d_s1_supported_h2(int B, int H, int W, int C, int k, int Ho, int Wo);
+/* dry run of vip_dwconv2d_s1_h2 / _pool_h2: returns the work items (region group x 16-channel block; 0: shape not taken), *workgroups =
+ * the workgroups that share them as contiguous runs (min(2 x CUs, items) - asks the current device), geom[6] = {sub-regions per wave,
+ * tile rows, tile columns of a sub-region, sub-regions per image in y, in x, 16-channel blocks}.  workgroups / geom may be NULL. */
+long vip_dwconv2d_s1_plan_h2(int B, int H, int W, int C, int k, int Ho, int Wo, int* workgroups, int* geom);
 int vip_dwconv2d_s1_h2(const void* x, const float* w_quad, const float* bias, void* y, int B, int H, int W, int C, int k, int pt, int pl,
                        int Ho, int Wo, int act, int* status, void* stream);
 /* The pooling form (strict counterpart of vip_dwconv2d_pool_nhwc_f16 + vip_se_gate_pooled_f16): also leaves partials[B][parts][C] fp32,

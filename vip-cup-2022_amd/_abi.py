@@ -54,12 +54,14 @@ SIGNATURES = {
     "vip_ln_gemm_supported": (_i, [_i, _i, _i, _i]),
     "vip_ln_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 4 + [_i] * 9 + [_vp]),
     "vip_mlp_fused_supported": (_i, [_i, _i, _i, _i]),
+    "vip_mlp_fused_plan": (_i, [_i] * 4 + [C.POINTER(_i)] * 2),
     "vip_mlp_fused_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 6 + [_i] * 9 + [_vp]),
     "vip_se_gate_f16": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
     "vip_gemm_split_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "vip_gemm_split2_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
     "vip_dwconv2d_nhwc_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),
     "vip_dwconv2d_pool_parts": (_i, [_i] * 8),
+    "vip_dwconv2d_tile_plan": (C.c_long, [_i] * 9 + [C.POINTER(_i)] * 2),
     "vip_dwconv2d_pool_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 12 + [_vp]),
     "vip_se_gate_pooled_f16": (_i, [_vp, _i] + [_vp] * 5 + [_i] * 10 + [_vp]),
     "vip_layernorm_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
@@ -146,9 +148,11 @@ SIGNATURES = {
     "vip_conv2d_kernel_name_h2": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "vip_dwconv2d_nhwc_h2": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _vp]),
     "vip_mlp_fused_supported_h2": (_i, [_i] * 4),
+    "vip_mlp_fused_plan_h2": (_i, [_i] * 4 + [C.POINTER(_i)] * 2),
     "vip_mlp_fused_h2": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     "vip_dw_filter_quad_major": (_i, [_vp, _vp, _i, _i, _vp]),
     "vip_dwconv2d_s1_supported_h2": (_i, [_i] * 7),
+    "vip_dwconv2d_s1_plan_h2": (C.c_long, [_i] * 7 + [C.POINTER(_i)] * 2),
     "vip_dwconv2d_s1_h2": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp, _vp]),
     "vip_dwconv2d_s1_pool_parts_h2": (_i, [_i] * 7),
     "vip_dwconv2d_s1_pool_h2": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _vp]),

@@ -46,6 +46,8 @@ static inline int vip_launch_status(const char* what) {
 int vip_dwconv_tiled(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k,
                      int pt, int pl, int Ho, int Wo, int act, hipStream_t s, float* partials = nullptr, int parts = 0);
 int vip_dwconv_tiled_parts(int B, int H, int W, int C, int k, int Ho, int Wo);
+// dry run of that launch: tile groups (0: shape not handled), *workgroups = blocks per channel block, geom[4] optional
+long vip_dwconv_tiled_plan(int B, int H, int W, int C, int k, int Ho, int Wo, int pooled, int* workgroups, int* geom);
 // the same on the packed STRICT storage (dwconv.hip); returns 1 when the shape is not handled there
 int vip_dwconv_tiled_h2(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k, int pt, int pl, int Ho,
                         int Wo, int act, int* status, hipStream_t s);

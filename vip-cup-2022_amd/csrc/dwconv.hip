@@ -393,50 +393,73 @@ int launch_tile_h2(const void* x, const float* w, const float* bias, void* y, in
     return vip_launch_status("vip_dwconv2d_nhwc_h2(tile)");
 }
 
+// Launch geometry of dwconv_tile_kernel for T x TW register tiles, the one place it is computed: launch_tile, the pooling form's
+// partial-sum rows (tile_parts) and the dry run vip_dwconv2d_tile_plan() read it.  Pure arithmetic: the workgroup cap is sized for 256 CUs.
+struct DwTilePlan {
+    int cb;                  // channel chunks (8 channels) per block
+    int tiles_x, tiles_y;
+    long n_tiles;
+    int tiles_per_block;
+    int gyc;                 // channel blocks: gridDim.y
+    int gpi;                 // image-aligned tile groups per image (pooling form)
+    long groups;             // tile groups: the work units of a channel block
+    long gx_cap;             // ~resident blocks of the whole chip, per channel block
+    long gx;                 // gridDim.x: the blocks that walk the groups
+};
+
+template <int T, int TW>
+DwTilePlan tile_plan(int B, int Ho, int Wo, int C, bool pool) {
+    DwTilePlan p;
+    const int C8 = C / 8;
+    // channel chunks per block: a divisor-friendly width <= 16 chunks (128 channels) that wastes few lanes
+    p.cb = C8 < 16 ? C8 : 16;
+    if (C8 % 12 == 0 && C8 % 16 != 0) p.cb = 12;                 // ConvNeXt widths 96/192/384/768
+    p.tiles_x = (Wo + TW - 1) / TW;
+    p.tiles_y = (Ho + T - 1) / T;
+    p.n_tiles = (long)B * p.tiles_x * p.tiles_y;
+    p.tiles_per_block = 256 / p.cb;
+    p.gyc = (C8 + p.cb - 1) / p.cb;
+    p.gpi = (p.tiles_x * p.tiles_y + p.tiles_per_block - 1) / p.tiles_per_block;       // image-aligned tile groups (pooling form)
+    p.groups = pool ? (long)B * p.gpi : (p.n_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
+    p.gx_cap = (256L * VIP_DW_BLOCKS_PER_CU + p.gyc - 1) / p.gyc;     // ~resident blocks of the whole chip
+    p.gx = p.groups > p.gx_cap ? p.gx_cap : p.groups;
+    return p;
+}
+
 template <int K, int T, int TW, bool WHOLE>
 int launch_tile(const f16* x, const float* w, const float* bias, f16* y, int B, int H, int W, int C, int pt, int pl,
                 int Ho, int Wo, int act, hipStream_t s, float* partials = nullptr, int parts = 0) {
-    const int C8 = C / 8;
-    // channel chunks per block: a divisor-friendly width <= 16 chunks (128 channels) that wastes few lanes
-    int cb = C8 < 16 ? C8 : 16;
-    if (C8 % 12 == 0 && C8 % 16 != 0) cb = 12;                   // ConvNeXt widths 96/192/384/768
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + T - 1) / T;
-    const long n_tiles = (long)B * tiles_x * tiles_y;
-    const int tiles_per_block = 256 / cb;
-    const int gyc = (C8 + cb - 1) / cb;
-    const int gpi = (tiles_x * tiles_y + tiles_per_block - 1) / tiles_per_block;       // image-aligned tile groups (pooling form)
-    long gx = partials ? (long)B * gpi : (n_tiles + tiles_per_block - 1) / tiles_per_block;
-    const long gx_cap = (256L * VIP_DW_BLOCKS_PER_CU + gyc - 1) / gyc;     // ~resident blocks of the whole chip
-    if (gx > gx_cap) gx = gx_cap;
-    const size_t smem = (size_t)K * K * cb * 8 * sizeof(float);
+    const DwTilePlan p = tile_plan<T, TW>(B, Ho, Wo, C, partials != nullptr);
+    const size_t smem = (size_t)K * K * p.cb * 8 * sizeof(float);
     if (partials) {
-        if (parts != gpi) {
-            vip_set_error("vip_dwconv2d_pool_nhwc_f16: partials sized for %d rows per image, the kernel writes %d", parts, gpi);
+        if (parts != p.gpi) {
+            vip_set_error("vip_dwconv2d_pool_nhwc_f16: partials sized for %d rows per image, the kernel writes %d", parts, p.gpi);
             return VIP_ERR_BAD_ARG;
         }
-        hipLaunchKernelGGL((dwconv_tile_kernel<K, T, TW, WHOLE, true>), dim3((unsigned)gx, (unsigned)gyc), dim3(256),
-                           smem + (size_t)tiles_per_block * cb * 8 * sizeof(float), s, x, w, bias, y, B, H, W, C, pt, pl, Ho, Wo, act,
-                           cb, tiles_x, tiles_y, n_tiles, 2L * B * H * W * C, partials, gpi);
+        hipLaunchKernelGGL((dwconv_tile_kernel<K, T, TW, WHOLE, true>), dim3((unsigned)p.gx, (unsigned)p.gyc), dim3(256),
+                           smem + (size_t)p.tiles_per_block * p.cb * 8 * sizeof(float), s, x, w, bias, y, B, H, W, C, pt, pl, Ho, Wo, act,
+                           p.cb, p.tiles_x, p.tiles_y, p.n_tiles, 2L * B * H * W * C, partials, p.gpi);
         return vip_launch_status("vip_dwconv2d_pool_nhwc_f16(tile)");
     }
-    hipLaunchKernelGGL((dwconv_tile_kernel<K, T, TW, WHOLE, false>), dim3((unsigned)gx, (unsigned)gyc), dim3(256), smem, s, x, w, bias,
-                       y, B, H, W, C, pt, pl, Ho, Wo, act, cb, tiles_x, tiles_y, n_tiles, 2L * B * H * W * C, (float*)nullptr, 0);
+    hipLaunchKernelGGL((dwconv_tile_kernel<K, T, TW, WHOLE, false>), dim3((unsigned)p.gx, (unsigned)p.gyc), dim3(256), smem, s, x, w, bias,
+                       y, B, H, W, C, pt, pl, Ho, Wo, act, p.cb, p.tiles_x, p.tiles_y, p.n_tiles, 2L * B * H * W * C, (float*)nullptr, 0);
     return vip_launch_status("vip_dwconv2d_nhwc_f16(tile)");
 }
 
 // rows of partial sums per image the pooling form writes for this shape (the launcher's own tiling)
 template <int T, int TW>
 int tile_parts(int Ho, int Wo, int C) {
-    const int C8 = C / 8;
-    int cb = C8 < 16 ? C8 : 16;
-    if (C8 % 12 == 0 && C8 % 16 != 0) cb = 12;
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + T - 1) / T;
-    const int tiles_per_block = 256 / cb;
-    const int gpi = (tiles_x * tiles_y + tiles_per_block - 1) / tiles_per_block;
+    const DwTilePlan p = tile_plan<T, TW>(1, Ho, Wo, C, true);
     // image-aligned groups idle the tail of each image's last group: below ~85 % lane use the depthwise kernel loses more than the
     // gate kernel saves (7x7 maps: 8 tiles in 16 slots; measured on EfficientNetV2-T, +0.2 ms per 256 images) - plain calls there
-    if (tiles_x * tiles_y * 100 < gpi * tiles_per_block * 85) return 0;
-    return gpi;
+    if (p.tiles_x * p.tiles_y * 100 < p.gpi * p.tiles_per_block * 85) return 0;
+    return p.gpi;
+}
+
+// the shapes vip_dwconv_tiled takes (and the register tile it picks per k)
+bool tile_shape_ok(int B, int H, int W, int C, int Ho, int Wo) {
+    const long gx = ((long)B * ((Wo + 1) / 2) * ((Ho + 1) / 2) + 15) / 16;
+    return !(gx >= (1L << 31) || 2L * B * H * W * C >= 0xFFFFFFF0L);
 }
 
 }  // namespace
@@ -447,8 +470,7 @@ int vip_dwconv_tiled(const void* x, const float* w, const float* bias, void* y, 
     const f16* xi = (const f16*)x;
     const float* wi = w;
     f16* yo = (f16*)y;
-    const long gx = ((long)B * ((Wo + 1) / 2) * ((Ho + 1) / 2) + 15) / 16;
-    if (gx >= (1L << 31) || 2L * B * H * W * C >= 0xFFFFFFF0L) return 1;
+    if (!tile_shape_ok(B, H, W, C, Ho, Wo)) return 1;
     // tile widths chosen so that accumulators + one fp32 patch row stay well under 256 VGPRs (no scratch)
     // register tiles (rows x cols per thread) picked by measurement on the ensemble's layer shapes (tools/bench_dw.py):
     // smaller tiles -> fewer VGPRs -> more resident waves, which beats the extra halo loads for k = 3 / 5
@@ -476,10 +498,29 @@ int vip_dwconv_tiled_h2(const void* x, const float* w, const float* bias, void* 
 
 // partial-sum rows per image of the pooling form (same register tiles as above), 0 if the shape is not handled by the tile kernel
 int vip_dwconv_tiled_parts(int B, int H, int W, int C, int k, int Ho, int Wo) {
-    const long gx = ((long)B * ((Wo + 1) / 2) * ((Ho + 1) / 2) + 15) / 16;
-    if (gx >= (1L << 31) || 2L * B * H * W * C >= 0xFFFFFFF0L || C % 8 != 0) return 0;
+    if (!tile_shape_ok(B, H, W, C, Ho, Wo) || C % 8 != 0) return 0;
     if (k == 3) return tile_parts<2, 4>(Ho, Wo, C);
     if (k == 5) return tile_parts<2, 2>(Ho, Wo, C);
     if (k == 7) return tile_parts<2, 4>(Ho, Wo, C);
     return 0;
+}
+
+// dry run of launch_tile (plain or pooling form): tile groups, the blocks per channel block that walk them, and optionally
+// geom[4] = {cb, tiles per block, channel blocks, block cap}; 0 when vip_dwconv_tiled does not take the shape
+long vip_dwconv_tiled_plan(int B, int H, int W, int C, int k, int Ho, int Wo, int pooled, int* workgroups, int* geom) {
+    if (!tile_shape_ok(B, H, W, C, Ho, Wo) || C % 8 != 0) return 0;
+    if (pooled && vip_dwconv_tiled_parts(B, H, W, C, k, Ho, Wo) <= 0) return 0;
+    DwTilePlan p;
+    if (k == 3) p = tile_plan<2, 4>(B, Ho, Wo, C, pooled != 0);          // the register tiles of vip_dwconv_tiled
+    else if (k == 5) p = tile_plan<2, 2>(B, Ho, Wo, C, pooled != 0);
+    else if (k == 7) p = tile_plan<2, 4>(B, Ho, Wo, C, pooled != 0);
+    else return 0;
+    if (workgroups) *workgroups = (int)p.gx;
+    if (geom) {
+        geom[0] = p.cb;
+        geom[1] = p.tiles_per_block;
+        geom[2] = p.gyc;
+        geom[3] = (int)p.gx_cap;
+    }
+    return p.groups;
 }

@@ -345,14 +345,16 @@ bool pick_config(int B, int Ho, int Wo, int K, DwLdsArgs& a) {
     return best > 0.0;
 }
 
-template <int K>
-int launch_lds(DwLdsArgs a, hipStream_t s) {
-    const size_t smem = (size_t)4 * a.IMG * a.PH * a.PWP * 16;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_lds_h2_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        attr_set = true;
-    }
+// Work items and launch grid of a shape, the one place they are computed: the launch below and the dry run vip_dwconv2d_s1_plan_h2()
+// read them.  Fills the lane packing (pick_config), the item count and the division constants of `a`; false: shape not taken.
+bool lds_plan(int B, int Ho, int Wo, int C, int k, DwLdsArgs& a, long& grid) {
+    if (!pick_config(B, Ho, Wo, k, a)) return false;
+    a.n_cblk = (C + 15) / 16;
+    a.n_items = (long)((a.n_sub + a.IMG - 1) / a.IMG) * a.n_cblk;
+    a.m_prow = magic_of(2 * a.PWID);
+    a.m_ph = magic_of(a.PH);
+    a.m_orow = magic_of(2 * a.RW);
+    a.m_oh = magic_of(a.RH);
     static int n_cu = 0;
     if (!n_cu) {
         int dev = 0;
@@ -360,8 +362,19 @@ int launch_lds(DwLdsArgs a, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
         if (n_cu <= 0) n_cu = 256;
     }
-    long grid = 2L * n_cu;
+    grid = 2L * n_cu;                                // each workgroup takes a contiguous run of items
     if (grid > a.n_items) grid = a.n_items;
+    return true;
+}
+
+template <int K>
+int launch_lds(DwLdsArgs a, long grid, hipStream_t s) {
+    const size_t smem = (size_t)4 * a.IMG * a.PH * a.PWP * 16;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv_lds_h2_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        attr_set = true;
+    }
     hipLaunchKernelGGL((dwconv_lds_h2_kernel<K>), dim3((unsigned)grid), dim3(256), smem, s, a, a.w, a.bias);
     return vip_launch_status("vip_dwconv2d_nhwc_h2(lds)");
 }
@@ -389,6 +402,23 @@ extern "C" int vip_dwconv2d_s1_supported_h2(int B, int H, int W, int C, int k, i
     if (4L * B * H * W * C >= 0xFFFFFFE0L || 4L * B * Ho * Wo * C >= 0xFFFFFFE0L) return 0;
     DwLdsArgs a;
     return pick_config(B, Ho, Wo, k, a) ? 1 : 0;
+}
+
+extern "C" long vip_dwconv2d_s1_plan_h2(int B, int H, int W, int C, int k, int Ho, int Wo, int* workgroups, int* geom) {
+    if (!vip_dwconv2d_s1_supported_h2(B, H, W, C, k, Ho, Wo)) return 0;
+    DwLdsArgs a;
+    long grid = 0;
+    if (!lds_plan(B, Ho, Wo, C, k, a, grid)) return 0;
+    if (workgroups) *workgroups = (int)grid;
+    if (geom) {
+        geom[0] = a.IMG;
+        geom[1] = a.LTY;
+        geom[2] = a.LTX;
+        geom[3] = a.RGY;
+        geom[4] = a.RGX;
+        geom[5] = a.n_cblk;
+    }
+    return a.n_items;
 }
 
 static int dwconv_s1_h2_impl(const void* x, const float* w_quad, const float* bias, void* y, float* partials, int B, int H, int W, int C, int k,
@@ -433,14 +463,9 @@ static int dwconv_s1_h2_impl(const void* x, const float* w_quad, const float* bi
     a.status = status;
     a.partials = partials;
     a.dbg = getenv("VIP_DW_LDS_DBG") ? atoi(getenv("VIP_DW_LDS_DBG")) : 0;
-    if (!pick_config(B, Ho, Wo, k, a)) return VIP_ERR_UNSUPPORTED;
-    a.n_cblk = (C + 15) / 16;
-    a.n_items = (long)((a.n_sub + a.IMG - 1) / a.IMG) * a.n_cblk;
-    a.m_prow = magic_of(2 * a.PWID);
-    a.m_ph = magic_of(a.PH);
-    a.m_orow = magic_of(2 * a.RW);
-    a.m_oh = magic_of(a.RH);
-    if (k == 3) return launch_lds<3>(a, s);
-    if (k == 5) return launch_lds<5>(a, s);
-    return launch_lds<7>(a, s);
+    long grid = 0;
+    if (!lds_plan(B, Ho, Wo, C, k, a, grid)) return VIP_ERR_UNSUPPORTED;
+    if (k == 3) return launch_lds<3>(a, grid, s);
+    if (k == 5) return launch_lds<5>(a, grid, s);
+    return launch_lds<7>(a, grid, s);
 }

@@ -251,14 +251,8 @@ static int mlp_stride(int chunks) {
     return chunks * 16;
 }
 
-template <int CK>
-int launch_mlp(MlpArgs a, hipStream_t s) {
-    constexpr int C = 32 * CK;
-    a.s1 = mlp_stride(CK * 4);
-    a.s2 = mlp_stride(a.Hd >> 3);
-    const size_t smem = (size_t)a.Hd * a.s1 + (size_t)C * a.s2;
-    if (smem > 160 * 1024) return 1;
-    a.n_tiles = (a.M + 511) / 512;
+// compute units of the current device (256 when it cannot be asked)
+static int mlp_cu_count() {
     static int n_cu = 0;
     if (!n_cu) {
         int dev = 0;
@@ -266,15 +260,57 @@ int launch_mlp(MlpArgs a, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
         if (n_cu <= 0) n_cu = 256;
     }
+    return n_cu;
+}
+
+// Launch geometry of both kernels, the one place it is computed: the launchers below and the dry run vip_mlp_fused_plan() read it.
+struct MlpPlan {
+    int s1, s2;      // LDS row strides (bytes)
+    size_t smem;     // dynamic LDS bytes
+    int tile;        // tokens per tile
+    int n_tiles;     // work units
+    int grid;        // workgroups that walk them (tile += gridDim.x)
+};
+
+// LDS-resident weights (C = 64 / 96): 512-token tiles, one workgroup per CU; false when the two matrices do not fit
+static bool mlp_plan_resident(int C, int M, int Hd, MlpPlan& p) {
+    p.s1 = mlp_stride(C / 8);
+    p.s2 = mlp_stride(Hd >> 3);
+    p.smem = (size_t)Hd * p.s1 + (size_t)C * p.s2;
+    if (p.smem > 160 * 1024) return false;
+    p.tile = 512;
+    p.n_tiles = (M + 511) / 512;
+    const int n_cu = mlp_cu_count();
+    p.grid = p.n_tiles < n_cu ? p.n_tiles : n_cu;
+    return true;
+}
+
+// streamed weights (C = 128 / 192 / 256): 256-token tiles, one workgroup per CU
+static void mlp_plan_stream(int C, int M, MlpPlan& p) {
+    p.s1 = mlp_stride(C / 8);
+    p.s2 = mlp_stride(4);
+    p.smem = 2 * ((size_t)32 * p.s1 + (size_t)C * p.s2);
+    p.tile = 256;
+    p.n_tiles = (M + 255) / 256;
+    const int n_cu = mlp_cu_count();
+    p.grid = p.n_tiles < n_cu ? p.n_tiles : n_cu;
+}
+
+template <int CK>
+int launch_mlp(MlpArgs a, hipStream_t s) {
+    MlpPlan p;
+    if (!mlp_plan_resident(32 * CK, a.M, a.Hd, p)) return 1;
+    a.s1 = p.s1;
+    a.s2 = p.s2;
+    a.n_tiles = p.n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fused_kernel<CK, VIP_ACT_GELU, 2>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
     // 16 waves x 32 tokens (<= 128 VGPRs, four waves per SIMD) measured 2-8 % ahead of 8 waves x 64 tokens
-    hipLaunchKernelGGL((mlp_fused_kernel<CK, VIP_ACT_GELU, 2>), dim3(grid), dim3(1024), smem, s, a);
+    hipLaunchKernelGGL((mlp_fused_kernel<CK, VIP_ACT_GELU, 2>), dim3(p.grid), dim3(1024), p.smem, s, a);
     return vip_launch_status("vip_mlp_fused_f16");
 }
 
@@ -446,26 +482,18 @@ __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
 
 template <int CK>
 int launch_mlp_stream(MlpArgs a, hipStream_t s) {
-    constexpr int C = 32 * CK;
-    a.s1 = mlp_stride(C / 8);
-    a.s2 = mlp_stride(4);
-    const size_t smem = 2 * ((size_t)32 * a.s1 + (size_t)C * a.s2);
-    a.n_tiles = (a.M + 255) / 256;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
+    MlpPlan p;
+    mlp_plan_stream(32 * CK, a.M, p);
+    a.s1 = p.s1;
+    a.s2 = p.s2;
+    a.n_tiles = p.n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_stream_kernel<CK, VIP_ACT_GELU>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
-    hipLaunchKernelGGL((mlp_stream_kernel<CK, VIP_ACT_GELU>), dim3(grid), dim3(512), smem, s, a);
+    hipLaunchKernelGGL((mlp_stream_kernel<CK, VIP_ACT_GELU>), dim3(p.grid), dim3(512), p.smem, s, a);
     return vip_launch_status("vip_mlp_fused_f16(stream)");
 }
 
@@ -477,6 +505,16 @@ extern "C" int vip_mlp_fused_supported(int M, int C, int hidden, int act) {
     if (C != 64 && C != 96) return 0;
     const long s1 = mlp_stride(C / 8), s2 = mlp_stride(hidden >> 3);      // LDS-resident weights
     return (long)hidden * s1 + (long)C * s2 <= 160 * 1024;
+}
+
+extern "C" int vip_mlp_fused_plan(int M, int C, int hidden, int act, int* workgroups, int* tile_rows) {
+    if (!vip_mlp_fused_supported(M, C, hidden, act)) return 0;
+    MlpPlan p;
+    if (C == 192) mlp_plan_stream(C, M, p);
+    else if (!mlp_plan_resident(C, M, hidden, p)) return 0;
+    if (workgroups) *workgroups = p.grid;
+    if (tile_rows) *tile_rows = p.tile;
+    return p.n_tiles;
 }
 
 extern "C" int vip_mlp_fused_f16(const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w1,

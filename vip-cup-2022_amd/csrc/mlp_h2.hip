@@ -297,13 +297,22 @@ int mlp_h2_stride(int chunks) {
     return chunks * 16;
 }
 
-template <int CK, int NW>
-int launch_mlp_h2(MlpH2Args a, hipStream_t s) {
-    constexpr int C = 32 * CK;
-    a.s1 = mlp_h2_stride(C / 4);
-    a.s2 = mlp_h2_stride(8);
-    const size_t smem = 2 * ((size_t)32 * a.s1 + (size_t)C * a.s2);
-    a.n_tiles = (a.M + 32 * NW - 1) / (32 * NW);
+// Launch geometry, the one place it is computed: launch_mlp_h2 and the dry run vip_mlp_fused_plan_h2() read it.
+struct MlpH2Plan {
+    int s1, s2;      // LDS row strides (bytes)
+    size_t smem;     // dynamic LDS bytes
+    int tile;        // tokens per tile: 32 per wave
+    int n_tiles;     // work units
+    int grid;        // workgroups that walk them (tile += gridDim.x)
+};
+
+MlpH2Plan mlp_h2_plan(int C, int nw, int M) {
+    MlpH2Plan p;
+    p.s1 = mlp_h2_stride(C / 4);
+    p.s2 = mlp_h2_stride(8);
+    p.smem = 2 * ((size_t)32 * p.s1 + (size_t)C * p.s2);
+    p.tile = 32 * nw;
+    p.n_tiles = (M + p.tile - 1) / p.tile;
     static int n_cu = 0;
     if (!n_cu) {
         int dev = 0;
@@ -311,19 +320,36 @@ int launch_mlp_h2(MlpH2Args a, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
         if (n_cu <= 0) n_cu = 256;
     }
+    // workgroups per CU: what the LDS images allow (two waves per SIMD either way).  Two independent 4-wave workgroups drift apart in
+    // phase - one in its MFMA runs while the other evaluates GELU - where one 8-wave workgroup is locked to a barrier per slice
+    int per_cu = (int)((160 * 1024) / (p.smem + 1024));
+    if (per_cu > 8 / nw * 2) per_cu = 8 / nw * 2;
+    if (per_cu < 1) per_cu = 1;
+    const int cap = n_cu * per_cu;
+    p.grid = p.n_tiles < cap ? p.n_tiles : cap;
+    return p;
+}
+
+// waves per workgroup, measured (profiles/r04_mlp_h2_ab.log): C = 64 / 128 prefer two 4-wave workgroups per CU (307 vs 346 us,
+// 239 vs 273 us), C = 96 one 8-wave workgroup (1 843 vs 1 985 us: half the weight traffic out of L2).  VIP_MLP_H2_WAVES overrides.
+int mlp_h2_waves(int C) {
+    static const int nw_env = getenv("VIP_MLP_H2_WAVES") ? atoi(getenv("VIP_MLP_H2_WAVES")) : 0;
+    const int nw = nw_env ? nw_env : (C == 96 ? 8 : 4);
+    return nw == 8 ? 8 : 4;
+}
+
+template <int CK, int NW>
+int launch_mlp_h2(MlpH2Args a, hipStream_t s) {
+    const MlpH2Plan p = mlp_h2_plan(32 * CK, NW, a.M);
+    a.s1 = p.s1;
+    a.s2 = p.s2;
+    a.n_tiles = p.n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_h2_kernel<CK, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    // workgroups per CU: what the LDS images allow (two waves per SIMD either way).  Two independent 4-wave workgroups drift apart in
-    // phase - one in its MFMA runs while the other evaluates GELU - where one 8-wave workgroup is locked to a barrier per slice
-    int per_cu = (int)((160 * 1024) / (smem + 1024));
-    if (per_cu > 8 / NW * 2) per_cu = 8 / NW * 2;
-    if (per_cu < 1) per_cu = 1;
-    const int cap = n_cu * per_cu;
-    const int grid = a.n_tiles < cap ? a.n_tiles : cap;
-    hipLaunchKernelGGL((mlp_h2_kernel<CK, NW>), dim3(grid), dim3(64 * NW), smem, s, a);
+    hipLaunchKernelGGL((mlp_h2_kernel<CK, NW>), dim3(p.grid), dim3(64 * NW), p.smem, s, a);
     return vip_launch_status("vip_mlp_fused_h2");
 }
 
@@ -332,6 +358,14 @@ int launch_mlp_h2(MlpH2Args a, hipStream_t s) {
 extern "C" int vip_mlp_fused_supported_h2(int M, int C, int hidden, int act) {
     if (act != VIP_ACT_GELU || hidden % 32 != 0 || hidden <= 0 || M < 8192) return 0;
     return C == 64 || C == 96 || C == 128;
+}
+
+extern "C" int vip_mlp_fused_plan_h2(int M, int C, int hidden, int act, int* workgroups, int* tile_rows) {
+    if (!vip_mlp_fused_supported_h2(M, C, hidden, act)) return 0;
+    const MlpH2Plan p = mlp_h2_plan(C, mlp_h2_waves(C), M);
+    if (workgroups) *workgroups = p.grid;
+    if (tile_rows) *tile_rows = p.tile;
+    return p.n_tiles;
 }
 
 extern "C" int vip_mlp_fused_h2(const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* w1, const float* b1,
@@ -358,10 +392,7 @@ extern "C" int vip_mlp_fused_h2(const void* x, const float* ln_gamma, const floa
     a.M = M; a.Hd = hidden; a.ldx = ldx; a.ldy = ldy; a.ldr = ldr; a.ldw1 = ldw1; a.ldw2 = ldw2;
     a.s1 = a.s2 = a.n_tiles = 0;
     a.status = status;
-    // waves per workgroup, measured (profiles/r04_mlp_h2_ab.log): C = 64 / 128 prefer two 4-wave workgroups per CU (307 vs 346 us,
-    // 239 vs 273 us), C = 96 one 8-wave workgroup (1 843 vs 1 985 us: half the weight traffic out of L2).  VIP_MLP_H2_WAVES overrides.
-    static const int nw_env = getenv("VIP_MLP_H2_WAVES") ? atoi(getenv("VIP_MLP_H2_WAVES")) : 0;
-    const int nw = nw_env ? nw_env : (C == 96 ? 8 : 4);
+    const int nw = mlp_h2_waves(C);
     hipStream_t s = (hipStream_t)stream;
     if (nw == 8) {
         if (C == 64) return launch_mlp_h2<2, 8>(a, s);

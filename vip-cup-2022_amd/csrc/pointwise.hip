@@ -397,6 +397,11 @@ extern "C" int vip_dwconv2d_pool_parts(int B, int H, int W, int C, int k, int st
     return vip_dwconv_tiled_parts(B, H, W, C, k, Ho, Wo);
 }
 
+extern "C" long vip_dwconv2d_tile_plan(int B, int H, int W, int C, int k, int stride, int Ho, int Wo, int pooled, int* workgroups, int* geom) {
+    if (stride != 1 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return 0;
+    return vip_dwconv_tiled_plan(B, H, W, C, k, Ho, Wo, pooled, workgroups, geom);
+}
+
 extern "C" int vip_dwconv2d_pool_nhwc_f16(const void* x, const float* w, const float* bias, void* y, float* partials, int parts,
                                           int B, int H, int W, int C, int k, int stride, int pt, int pl, int Ho, int Wo, int act,
                                           void* stream) {

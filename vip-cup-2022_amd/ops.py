@@ -544,6 +544,37 @@ def conv_kernel_name_h2(d: "_abi.ConvDesc", has_residual: bool) -> Optional[str]
     return buf.value.decode() if st == 0 else None
 
 
+# Dry runs of the persistent launches (nothing is launched; each launcher calls the function its query calls).  A plan is
+# ``(units, workgroups, ...)``: a workgroup walks ceil(units / workgroups) units at the most - its "passes".  None: shape not taken.
+def mlp_plan(M: int, C_: int, hidden: int, packed: bool = False, act="gelu"):
+    """``(tiles, workgroups, tokens per tile)`` of the fused MLP launch ``mlp`` makes for [M, C_] rows (``packed``: the strict storage).
+    Asks the current device for its CU count."""
+    wg, rows = C.c_int(0), C.c_int(0)
+    fn = _abi.lib().vip_mlp_fused_plan_h2 if packed else _abi.lib().vip_mlp_fused_plan
+    n = fn(M, C_, hidden, _act(act), C.byref(wg), C.byref(rows))
+    return (n, wg.value, rows.value) if n > 0 else None
+
+
+def dwconv_tile_plan(B: int, H: int, W: int, Cc: int, k: int, pad=None, pooled: bool = False):
+    """``(tile groups, workgroups per channel block, {cb, tiles_per_block, channel_blocks, cap})`` of the fp16 stride-1 depthwise
+    launch (``pooled``: the pooling form ``dwconv2d_se`` uses).  Host arithmetic only: works without a GPU."""
+    pad = (k // 2,) * 4 if pad is None else pad
+    Ho, Wo = _out_hw(H, W, k, k, 1, 1, pad)
+    wg, geom = C.c_int(0), (C.c_int * 4)()
+    n = _abi.lib().vip_dwconv2d_tile_plan(B, H, W, Cc, k, 1, Ho, Wo, int(pooled), C.byref(wg), geom)
+    return (n, wg.value, dict(zip(("cb", "tiles_per_block", "channel_blocks", "cap"), geom))) if n > 0 else None
+
+
+def dwconv_lds_plan(B: int, H: int, W: int, Cc: int, k: int, pad=None):
+    """``(items, workgroups, {img, lty, ltx, rgy, rgx, channel_blocks})`` of the LDS-staged packed depthwise launch (plain and pooling
+    form share it).  Asks the current device for its CU count."""
+    pad = (k // 2,) * 4 if pad is None else pad
+    Ho, Wo = _out_hw(H, W, k, k, 1, 1, pad)
+    wg, geom = C.c_int(0), (C.c_int * 6)()
+    n = _abi.lib().vip_dwconv2d_s1_plan_h2(B, H, W, Cc, k, Ho, Wo, C.byref(wg), geom)
+    return (n, wg.value, dict(zip(("img", "lty", "ltx", "rgy", "rgx", "channel_blocks"), geom))) if n > 0 else None
+
+
 # ---- named terms of the fusion decisions below -------------------------------------------------------------------------------------
 SE_FUSED_MAX_WEIGHTS = 256 * 1024      # the one-launch gate kernels re-read both matrices per image: beyond this the batched GEMMs win
 
