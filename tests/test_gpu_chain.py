@@ -189,3 +189,67 @@ def test_cli_chains_end_to_end(tmp_path, report):
     assert s["chains"] == labels and s["qualities"] == [] and s["subsampling"] == "4:2:0" and len(s["members"]) == 2
     assert s["resize_filter"] == "bicubic" and s["crop_origin"] == "topleft"
     assert s["sharpen_percents"] == [] and s["sharpen_sigma"] == 1.0 and s["sharpen_radius"] is None and s["sharpen_threshold"] == 0
+
+
+def test_cli_every_family_end_to_end(tmp_path):
+    """one value of every stress flag, every option off its default and two chains in ONE run, two batches: the CSVs of a plain run
+    unchanged, the table's columns and the settings, and every column == ``stress_batch`` called with the same keywords on each batch"""
+    import pandas as pd
+    import vipcup_amd  # noqa: F401
+    from vipcup_amd import ensemble, pipeline, zoo
+    from vipcup_amd import main as cli
+    names = [f"img_{i:05d}.jpg" for i in range(100, 104)]                  # 200 x 200 each
+    for i, name in zip(range(100, 104), names):
+        (tmp_path / name).write_bytes(synth_jpeg(i))
+    (tmp_path / "test.csv").write_text("filename\n" + "\n".join(names) + "\n")
+    cfg = tmp_path / "ckpts.json"
+    cfg.write_text(json.dumps([[zoo.MEMBERS["resnet_rs50"].ckpt_name, [zoo.MEMBERS["resnet_rs50"].input_hw] * 2, 0]]))
+    extra = ["--synthetic", "--ckpt-cfg", str(cfg), "--batch-size", "2", "--precision", "fast"]
+    chains = ["n030+q75", "r50+con120+q75"]
+    csv = str(tmp_path / "test.csv")
+    cli.main([csv, str(tmp_path / "o0.csv"), "--scores-out", str(tmp_path / "s0.csv"), *extra])
+    cli.main([csv, str(tmp_path / "o1.csv"), "--scores-out", str(tmp_path / "s1.csv"), *extra, "--stress-out", str(tmp_path / "stress.csv"),
+              "--stress-jpeg", "80", "--stress-subsampling", "444", "--stress-resize", "50", "--stress-resize-filter", "lanczos",
+              "--stress-blur", "1", "--stress-blur-radius", "2", "--stress-median", "3", "--stress-flip", "h", "--stress-crop", "90",
+              "--stress-crop-origin", "topleft", "--stress-rotate", "7.5", "--stress-rotate-fill", "black", "--stress-gray", "--stress-bgr",
+              "--stress-hue", "30", "--stress-saturation", "50", "--stress-contrast", "150", "--stress-brightness=-10", "--stress-gamma", "0.8",
+              "--stress-noise", "3", "--stress-noise-mono", "3", "--stress-speckle", "20", "--stress-impulse", "1", "--stress-noise-seed", "9",
+              "--stress-sharpen", "150", "--stress-sharpen-sigma", "0.8", "--stress-sharpen-radius", "2", "--stress-sharpen-threshold", "3",
+              "--stress-autocontrast", "2", "--stress-autocontrast-luma", "1", "--stress-equalize", "--stress-clahe", "2",
+              "--stress-clahe-grid", "4", "--stress-chain", ",".join(chains)])
+    assert (tmp_path / "o0.csv").read_bytes() == (tmp_path / "o1.csv").read_bytes()
+    assert (tmp_path / "s0.csv").read_bytes() == (tmp_path / "s1.csv").read_bytes()
+    labels = ["q80", "r50", "r50_q80", "b10", "b10_q80", "m3", "m3_q80", "fliph", "fliph_q80", "crop90", "crop90_q80", "rot075", "rot075_q80",
+              "gray", "gray_q80", "bgr", "bgr_q80", "hue030", "hue030_q80", "sat050", "sat050_q80", "con150", "con150_q80", "brim10", "brim10_q80",
+              "gam080", "gam080_q80", "n030", "n030_q80", "nm030", "nm030_q80", "spk20", "spk20_q80", "imp010", "imp010_q80", "shp150",
+              "shp150_q80", "ac02", "ac02_q80", "acl01", "acl01_q80", "eq", "eq_q80", "clahe20", "clahe20_q80", "n030+q75", "r50+con120+q75"]
+    table = pd.read_csv(tmp_path / "stress.csv", dtype={"flips_at": str, "flips": str}, keep_default_na=False)
+    assert list(table.columns) == ["filename", "p", "decision"] + [f"p_{v}" for v in labels] + [f"decision_{v}" for v in labels] + \
+        ["stable", "flips_at", "flips"]
+    assert table.filename.tolist() == names
+    info = json.loads((tmp_path / "stress.json").read_text())
+    assert info["variants"] == labels
+    assert info["settings"] == {
+        "qualities": [80], "subsampling": "4:4:4", "threshold": 0.487, "precision": "fast", "batch_size": 2, "n_images": 4,
+        "members": ["resnet_rs50"], "scales": [50], "resize_filter": "lanczos", "blur_sigmas": [1.0], "blur_radius": 2, "medians": [3],
+        "flips": ["h"], "crops": [90], "crop_origin": "topleft", "rotations": [7.5], "rotate_fill": "black", "gray": True, "bgr": True,
+        "hues": [30], "saturations": [50], "contrasts": [150], "brightnesses": [-10], "gammas": [0.8], "noise_sigmas": [3.0],
+        "noise_mono_sigmas": [3.0], "speckles": [20], "impulses": [1.0], "noise_seed": 9, "sharpen_percents": [150], "sharpen_sigma": 0.8,
+        "sharpen_radius": 2, "sharpen_threshold": 3, "autocontrast_cutoffs": [2], "autocontrast_luma_cutoffs": [1], "equalize": True,
+        "clahe_limits": [2.0], "clahe_grid": 4, "chains": chains}
+    keywords = dict(subsampling="4:4:4", scales=[50], resize_filter="lanczos", blurs=[1.0], blur_radius=2, medians=[3], flips=["h"], crops=[90],
+                    crop_origin="topleft", rotations=[7.5], rotate_fill="black", gray=True, bgr=True, hues=[30], saturations=[50],
+                    contrasts=[150], brightnesses=[-10], gammas=[0.8], noises=[3.0], mono_noises=[3.0], speckles=[20], impulses=[1.0],
+                    noise_seed=9, sharpens=[150], sharpen_sigma=0.8, sharpen_radius=2, sharpen_threshold=3, autocontrasts=[2],
+                    autocontrast_lumas=[1], equalize=True, clahes=[2.0], clahe_grid=4, chains=chains)
+    members = _one_member()
+    for b0 in (0, 2):                                                      # the second batch: noise keys by file, not by batch position
+        batch = names[b0:b0 + 2]
+        rows, got = ensemble.stress_batch([(tmp_path / n).read_bytes() for n in batch], members, [80], noise_keys=pipeline.noise_keys(batch),
+                                          **keywords)
+        assert got == labels
+        rows = rows.cpu().numpy()
+        assert np.array_equal(table.p.to_numpy(np.float32)[b0:b0 + 2], ensemble.aggregate(batch, rows[0])[1])
+        for k, v in enumerate(labels):
+            want = ensemble.aggregate(batch, rows[1 + k])[1]
+            assert np.array_equal(table[f"p_{v}"].to_numpy(np.float32)[b0:b0 + 2], want), (v, b0)

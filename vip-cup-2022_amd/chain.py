@@ -27,55 +27,93 @@ label's ranges, in that canonical spelling only, matched against the whole token
 steps, the mode of ``pipeline.tone`` (``autocontrast``, ``autocontrast_luma``, ``equalize``, ``clahe``); ``arg`` is that function's
 argument in the user's units (None for ``gray``, ``bgr`` and ``equalize``)."""
 import re
+from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 MIN_STEPS, MAX_STEPS, MAX_CHAINS = 2, 8, 16
-NOISE_STEPS = ("gaussian", "mono", "speckle", "impulse")
-TONE_STEPS = ("autocontrast", "autocontrast_luma", "equalize", "clahe")
 
-# (pattern of the whole token, kind, lowest, highest, banned value, units per one of the argument, the family's own flag); a pattern's
-# optional "m" group marks a negative value; scale None: the step has no number
-_STEPS = (
-    (r"q([1-9]\d{0,2})", "recompress", 1, 100, None, 1, "--stress-jpeg"),
-    (r"r([1-9]\d{1,2})", "rescale", 10, 400, 100, 1, "--stress-resize"),
-    (r"b(\d\d)", "blur", 3, 50, None, 10, "--stress-blur"),
-    (r"m([35])", "median", 3, 5, None, 1, "--stress-median"),
-    (r"flip([hv])", "flip", None, None, None, None, "--stress-flip"),
-    (r"crop(\d\d)", "crop", 50, 99, None, 1, "--stress-crop"),
-    (r"rot(m?)(\d{3})", "rotate", 1, 450, None, 10, "--stress-rotate"),
-    (r"(gray)", "gray", None, None, None, None, "--stress-gray"),
-    (r"(bgr)", "bgr", None, None, None, None, "--stress-bgr"),
-    (r"hue(m?)(\d{3})", "hue", 1, 180, None, 1, "--stress-hue"),
-    (r"sat(\d{3})", "saturation", 0, 200, 100, 1, "--stress-saturation"),
-    (r"con(\d{3})", "contrast", 0, 200, 100, 1, "--stress-contrast"),
-    (r"bri(m?)(\d\d)", "brightness", 1, 50, None, 1, "--stress-brightness"),
-    (r"gam(\d{3})", "gamma", 50, 200, 100, 100, "--stress-gamma"),
-    (r"n(\d{3})", "gaussian", 5, 500, None, 10, "--stress-noise"),
-    (r"nm(\d{3})", "mono", 5, 500, None, 10, "--stress-noise-mono"),
-    (r"spk(\d\d)", "speckle", 1, 50, None, 1, "--stress-speckle"),
-    (r"imp(\d{3})", "impulse", 1, 500, None, 10, "--stress-impulse"),
-    (r"shp(\d{3})", "sharpen", 1, 500, None, 1, "--stress-sharpen"),
-    (r"ac(\d\d)", "autocontrast", 0, 49, None, 1, "--stress-autocontrast"),
-    (r"acl(\d\d)", "autocontrast_luma", 0, 49, None, 1, "--stress-autocontrast-luma"),
-    (r"(eq)", "equalize", None, None, None, None, "--stress-equalize"),
-    (r"clahe(\d\d)", "clahe", 10, 99, None, 10, "--stress-clahe"),
-)
-STEP_FLAGS = {kind: flag for _, kind, _, _, _, _, flag in _STEPS}
+# Everything that is particular to a step kind, one row per kind IN ROW ORDER: ``ensemble.stress_batch`` scores its variants kind by kind
+# in the order of this table.
+#   prefix, digits, signed   the label: the prefix, "m" for a negative value of a signed kind, the number in label units as that many
+#                            digits (0: as it is, no leading zeros; None: the kind has no number)
+#   lo, hi, banned           the range of the number's magnitude in label units, and the one value in it that is no step
+#   scale                    label units per one of the argument (10: the label counts tenths)
+#   flag                     the command-line flag that gives the kind's rows
+#   keyword, order           the keyword of ``stress_batch`` / ``stress_labels`` that lists the kind's values (a bool for a kind without
+#                            a number), and how a list is put in row order: "asc", "desc" ("h" before "v" is "asc"); ``recompress`` has
+#                            no keyword of this kind: the qualities multiply the other rows and stay as given, the CLI lists them "desc"
+#   family                   the word for the kind's family in the CLI's refusals; the flags of one family share their ``stress.json`` settings
+Step = namedtuple("Step", "prefix digits signed kind lo hi banned scale flag keyword order family")
+STEPS = {row.kind: row for row in (
+    Step("q", 0, False, "recompress", 1, 100, None, 1, "--stress-jpeg", None, "desc", "recompression"),
+    Step("r", 0, False, "rescale", 10, 400, 100, 1, "--stress-resize", "scales", "desc", "resize"),
+    Step("b", 2, False, "blur", 3, 50, None, 10, "--stress-blur", "blurs", "asc", "smoothing"),
+    Step("m", 1, False, "median", 3, 5, 4, 1, "--stress-median", "medians", "asc", "smoothing"),
+    Step("flip", None, False, "flip", None, None, None, None, "--stress-flip", "flips", "asc", "geometric"),
+    Step("crop", 2, False, "crop", 50, 99, None, 1, "--stress-crop", "crops", "desc", "geometric"),
+    Step("rot", 3, True, "rotate", 1, 450, None, 10, "--stress-rotate", "rotations", "asc", "geometric"),
+    Step("gray", None, False, "gray", None, None, None, None, "--stress-gray", "gray", None, "colour"),
+    Step("bgr", None, False, "bgr", None, None, None, None, "--stress-bgr", "bgr", None, "colour"),
+    Step("hue", 3, True, "hue", 1, 180, None, 1, "--stress-hue", "hues", "asc", "colour"),
+    Step("sat", 3, False, "saturation", 0, 200, 100, 1, "--stress-saturation", "saturations", "asc", "colour"),
+    Step("con", 3, False, "contrast", 0, 200, 100, 1, "--stress-contrast", "contrasts", "asc", "colour"),
+    Step("bri", 2, True, "brightness", 1, 50, None, 1, "--stress-brightness", "brightnesses", "asc", "colour"),
+    Step("gam", 3, False, "gamma", 50, 200, 100, 100, "--stress-gamma", "gammas", "asc", "colour"),
+    Step("n", 3, False, "gaussian", 5, 500, None, 10, "--stress-noise", "noises", "asc", "noise"),
+    Step("nm", 3, False, "mono", 5, 500, None, 10, "--stress-noise-mono", "mono_noises", "asc", "noise"),
+    Step("spk", 2, False, "speckle", 1, 50, None, 1, "--stress-speckle", "speckles", "asc", "noise"),
+    Step("imp", 3, False, "impulse", 1, 500, None, 10, "--stress-impulse", "impulses", "asc", "noise"),
+    Step("shp", 3, False, "sharpen", 1, 500, None, 1, "--stress-sharpen", "sharpens", "asc", "sharpening"),
+    Step("ac", 2, False, "autocontrast", 0, 49, None, 1, "--stress-autocontrast", "autocontrasts", "asc", "tone"),
+    Step("acl", 2, False, "autocontrast_luma", 0, 49, None, 1, "--stress-autocontrast-luma", "autocontrast_lumas", "asc", "tone"),
+    Step("eq", None, False, "equalize", None, None, None, None, "--stress-equalize", "equalize", None, "tone"),
+    Step("clahe", 2, False, "clahe", 10, 99, None, 10, "--stress-clahe", "clahes", "asc", "tone"),
+)}
+STEP_FLAGS = {kind: row.flag for kind, row in STEPS.items()}
+NOISE_STEPS = tuple(kind for kind, row in STEPS.items() if row.family == "noise")
+TONE_STEPS = tuple(kind for kind, row in STEPS.items() if row.family == "tone")
+
+
+def step_units(kind: str, arg) -> int:
+    """the number of a step's label: ``arg`` in label units (7.5 degrees -> 75); the signed integer that orders the kind's rows"""
+    scale = STEPS[kind].scale
+    return int(arg) if scale == 1 else int(round(float(arg) * scale))
+
+
+def step_arg(kind: str, units: int):
+    """the argument of the ``pipeline`` function for a number in label units: an int where the label counts ones, else a float"""
+    scale = STEPS[kind].scale
+    return units if scale == 1 else units / scale
+
+
+def step_label(kind: str, arg=None) -> str:
+    """``(kind, arg)`` -> the single-variant label: the inverse of ``parse_step``, and the only place that spells a label.  Formats what
+    it is given: the ranges are ``parse_step``'s"""
+    row = STEPS[kind]
+    if row.digits is None:
+        return row.prefix + (str(arg) if kind == "flip" else "")
+    v = step_units(kind, arg)
+    return f"{row.prefix}{'m' if row.signed and v < 0 else ''}{abs(v) if row.signed else v:0{row.digits}d}"
+
+
+def _pattern(row: Step) -> str:
+    if row.digits is None:
+        return row.prefix + ("([hv])" if row.kind == "flip" else "")
+    return row.prefix + ("(m?)" if row.signed else "()") + (rf"(\d{{{row.digits}}})" if row.digits else r"([1-9]\d{0,2})")
 
 
 def parse_step(token: str) -> Tuple[str, object]:
     """one step of a chain -> ``(kind, arg)``; ValueError naming the token when it is no canonical single-variant label in range"""
-    for pattern, kind, lo, hi, banned, scale, _ in _STEPS:
-        m = re.fullmatch(pattern, token, re.ASCII) if isinstance(token, str) else None
+    for kind, row in STEPS.items():
+        m = re.fullmatch(_pattern(row), token, re.ASCII) if isinstance(token, str) else None
         if m is None:
             continue
-        if scale is None:                                 # flip<axis>, gray, bgr, eq
+        if row.digits is None:                            # flip<axis>, gray, bgr, eq
             return kind, (m.group(1) if kind == "flip" else None)
-        v = int(m.group(m.lastindex))
-        if not lo <= v <= hi or v == banned:
+        v = int(m.group(2))
+        if not row.lo <= v <= row.hi or v == row.banned:
             break
-        v = -v if m.lastindex == 2 and m.group(1) else v
-        return kind, (v if scale == 1 else v / scale)
+        return kind, step_arg(kind, -v if m.group(1) else v)
     raise ValueError(f"chain step {token!r}: expected a single-variant stress label in its canonical spelling and range (q<Q>, r<P>, "
                      "b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, con<PPP>, "
                      "bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, clahe<TT>)")

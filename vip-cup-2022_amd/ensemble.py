@@ -11,10 +11,13 @@ With N > 1 processes the work is a grid of (member, image-shard) units dealt to 
 ``hybrid`` (longest-processing-time-first packing of the units by measured ms/image).  In every mode the only exchange step
 is ONE all-gather of the ranks' score payloads at the end.
 """
+import inspect
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from . import chain
 
 THR = 0.487          # main.py:225
 REF_BATCH = 128      # 8 * NAME2BS.get(name, 16) for every shipped member (main.py:43-56,85)
@@ -466,89 +469,39 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     return acc / float(len(flags))
 
 
-def _rot_tenths(rotations) -> List[int]:
-    return sorted(int(round(float(d) * 10)) for d in rotations)
-
-
-def _colour_variants(gray=False, bgr=False, hues=(), saturations=(), contrasts=(), brightnesses=(), gammas=()) -> List[Tuple[str, str, object]]:
-    """``(label, pipeline function, argument)`` of every colour variant, in row order"""
-    out = [("gray", "gray", None)] if gray else []
-    out += [("bgr", "bgr", None)] if bgr else []
-    out += [(f"hue{'m' if d < 0 else ''}{abs(d):03d}", "hue", d) for d in sorted(int(d) for d in hues)]
-    out += [(f"sat{pc:03d}", "saturation", pc) for pc in sorted(int(pc) for pc in saturations)]
-    out += [(f"con{pc:03d}", "contrast", pc) for pc in sorted(int(pc) for pc in contrasts)]
-    out += [(f"bri{'m' if pc < 0 else ''}{abs(pc):02d}", "brightness", pc) for pc in sorted(int(pc) for pc in brightnesses)]
-    out += [(f"gam{hh:03d}", "gamma", hh / 100) for hh in sorted(int(round(float(g) * 100)) for g in gammas)]
+def stress_variants(spec) -> List[Tuple[str, str, object]]:
+    """``(label, kind, arg)`` of every single-variant row that ``spec`` asks for, in row order.  ``spec`` maps keywords of ``stress_batch``
+    to their values; only the lists and switches of ``chain.STEPS`` are read, an absent one is empty.  The rows go kind by kind in the
+    order of that table, each list in the table's order for its kind (sorted, never de-duplicated); ``(kind, arg)`` is what
+    ``chain.parse_step(label)`` gives and what ``pipeline.apply_step`` takes."""
+    out = []
+    for kind, row in chain.STEPS.items():
+        given = spec.get(row.keyword, ()) if row.keyword else ()
+        if row.order is None:                                    # gray, bgr, equalize: a switch
+            args = [None] if given else []
+        elif kind == "flip":
+            args = sorted(str(axis) for axis in given)
+        else:
+            args = [chain.step_arg(kind, u) for u in sorted((chain.step_units(kind, v) for v in given), reverse=row.order == "desc")]
+        out += [(chain.step_label(kind, arg), kind, arg) for arg in args]
     return out
 
 
-def _noise_variants(noises=(), mono_noises=(), speckles=(), impulses=()) -> List[Tuple[str, str, object]]:
-    """``(label, kind of pipeline.noise, amount)`` of every noise variant, in row order"""
-    tenths = lambda vs: sorted(int(round(float(v) * 10)) for v in vs)   # noqa: E731
-    out = [(f"n{tt:03d}", "gaussian", tt / 10) for tt in tenths(noises)]
-    out += [(f"nm{tt:03d}", "mono", tt / 10) for tt in tenths(mono_noises)]
-    out += [(f"spk{pc:02d}", "speckle", pc) for pc in sorted(int(pc) for pc in speckles)]
-    out += [(f"imp{tt:03d}", "impulse", tt / 10) for tt in tenths(impulses)]
-    return out
+def _row_labels(qualities, variants, chains) -> List[str]:
+    resaved = [chain.step_label("recompress", q) for q in qualities]
+    return resaved + [v for label, _, _ in variants for v in [label] + [f"{label}_{q}" for q in resaved]] + [str(text) for text in chains]
 
 
-def _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes) -> List[Tuple[str, str, object]]:
-    """``(label, mode of pipeline.tone, argument)`` of the tone variants in row order: ``ac<PP>`` and ``acl<PP>`` for each cutoff (ascending,
-    two digits), ``eq``, ``clahe<TT>`` for each clip limit (ascending, ``TT`` = ten times the limit: 2 -> ``clahe20``)"""
-    out = [(f"ac{pc:02d}", "autocontrast", pc) for pc in sorted(int(pc) for pc in autocontrasts)]
-    out += [(f"acl{pc:02d}", "autocontrast_luma", pc) for pc in sorted(int(pc) for pc in autocontrast_lumas)]
-    out += [("eq", "equalize", None)] if equalize else []
-    out += [(f"clahe{tt:02d}", "clahe", tt / 10) for tt in sorted(int(round(float(lm) * 10)) for lm in clahes)]
-    return out
-
-
-def stress_labels(qualities: Sequence[int], scales: Sequence[int] = (), blurs: Sequence[float] = (), medians: Sequence[int] = (),
-                  flips: Sequence[str] = (), crops: Sequence[int] = (), rotations: Sequence[float] = (), crop_origin: str = "centre",
-                  rotate_fill: str = "crop", gray: bool = False, bgr: bool = False, hues: Sequence[int] = (), saturations: Sequence[int] = (),
-                  contrasts: Sequence[int] = (), brightnesses: Sequence[int] = (), gammas: Sequence[float] = (), noises: Sequence[float] = (),
-                  mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
-                  noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
-                  sharpen_threshold: int = 0, chains: Sequence[str] = (), autocontrasts: Sequence[int] = (),
-                  autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8) -> List[str]:
-    """The variant labels of ``stress_batch`` rows 1.., in row order: ``q<Q>`` for every quality at 100 %, then for each percent of
-    ``scales`` ``r<P>`` (rescaled, not re-saved) and ``r<P>_q<Q>`` (rescaled, then re-saved), then for each sigma of ``blurs`` (ascending)
-    ``b<TT>`` and ``b<TT>_q<Q>`` with ``TT`` = ``round(sigma * 10)`` as two digits (0.5 -> ``b05``, 2.5 -> ``b25``), then for each window
-    of ``medians`` (ascending) ``m<K>`` and ``m<K>_q<Q>``, then the geometry: ``fliph`` / ``flipv`` for the axes of ``flips`` (h first), ``crop<PP>``
-    for each percent of ``crops`` (descending), ``rot<TTT>`` / ``rotm<TTT>`` for each angle of ``rotations`` (ascending by signed angle; ``m``
-    marks a negative angle, ``TTT`` = ten times |degrees| as three digits: 7.5 -> ``rot075``, -12.3 -> ``rotm123``), each followed by its
-    ``_q<Q>`` labels (``crop_origin`` and ``rotate_fill`` are ``stress_batch``'s and do not change a label), then the colour: ``gray``,
-    ``bgr``, ``hue<DDD>`` / ``huem<DDD>`` for each angle of ``hues`` (ascending by signed angle; ``m`` marks a negative one, three digits),
-    ``sat<PPP>`` and ``con<PPP>`` for each percent of ``saturations`` / ``contrasts`` (ascending, three digits), ``bri<PP>`` / ``brim<PP>``
-    for each percent of ``brightnesses`` (ascending by signed value, two digits), ``gam<PPP>`` for each of ``gammas`` (ascending, ``PPP``
-    = 100 times gamma: 0.8 -> ``gam080``), each followed by its ``_q<Q>`` labels, then the noise: ``n<TTT>`` for each sigma of ``noises``
-    and ``nm<TTT>`` for each of ``mono_noises`` (ascending, ``TTT`` = ten times sigma as three digits: 3 -> ``n030``), ``spk<PP>`` for each
-    percent of ``speckles`` (ascending, two digits), ``imp<TTT>`` for each percent of ``impulses`` (ascending, ten times the percent: 1 ->
-    ``imp010``), each followed by its ``_q<Q>`` labels (``noise_seed`` and ``noise_keys`` are ``stress_batch``'s and do not change a
-    label), then the sharpening: ``shp<PPP>`` for each percent of ``sharpens`` (ascending, three digits: 80 -> ``shp080``), each followed
-    by its ``_q<Q>`` labels (``sharpen_sigma``, ``sharpen_radius`` and ``sharpen_threshold`` are ``stress_batch``'s and do not change a
-    label), then the tone: ``ac<PP>`` for each cutoff of ``autocontrasts`` and ``acl<PP>`` for each of ``autocontrast_lumas`` (ascending,
-    two digits), ``eq`` with ``equalize``, ``clahe<TT>`` for each clip limit of ``clahes`` (ascending, ``TT`` = ten times the limit: 2 ->
-    ``clahe20``), each followed by its ``_q<Q>`` labels (``clahe_grid`` is ``stress_batch``'s and does not change a label), and last the
-    ``chains`` in the order given, each under its own text (``r50+shp080+q75``) and never followed by ``_q<Q>`` labels."""
-    labels = [f"q{int(q)}" for q in qualities]
-    for pc in scales:
-        labels.append(f"r{int(pc)}")
-        labels += [f"r{int(pc)}_q{int(q)}" for q in qualities]
-    for tt in sorted(int(round(float(s) * 10)) for s in blurs):
-        labels.append(f"b{tt:02d}")
-        labels += [f"b{tt:02d}_q{int(q)}" for q in qualities]
-    for k in sorted(int(k) for k in medians):
-        labels.append(f"m{k}")
-        labels += [f"m{k}_q{int(q)}" for q in qualities]
-    geometry = [f"flip{ax}" for ax in sorted(str(ax) for ax in flips)] + [f"crop{pc:02d}" for pc in sorted((int(pc) for pc in crops), reverse=True)] \
-        + [f"rot{'m' if tt < 0 else ''}{abs(tt):03d}" for tt in _rot_tenths(rotations)]
-    for v in geometry + [v[0] for v in _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)] \
-            + [v[0] for v in _noise_variants(noises, mono_noises, speckles, impulses)] \
-            + [f"shp{pc:03d}" for pc in sorted(int(pc) for pc in sharpens)] \
-            + [v[0] for v in _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes)]:
-        labels.append(v)
-        labels += [f"{v}_q{int(q)}" for q in qualities]
-    return labels + [str(text) for text in chains]
+def stress_labels(*args, **keywords) -> List[str]:
+    """``stress_labels(qualities, scales=(), blurs=(), ...)``: the variant labels of ``stress_batch`` rows 1.., in row order.  Takes
+    ``stress_batch``'s keywords in ``stress_batch``'s order, less the batch, the members, ``after_fork``, ``subsampling``,
+    ``resize_filter`` and ``blur_radius``; the remaining options are accepted and change no label.
+    ``q<Q>`` for every quality as given, then every single-variant label of ``stress_variants`` (spelled by ``chain.step_label``: the
+    grammar is in ``chain``'s docstring; ``scales`` and ``crops`` largest first, every other list ascending by signed value, ``h``
+    before ``v``), each followed by its ``_q<Q>`` labels, and last the ``chains`` in the order given, each under its own text
+    (``r50+shp080+q75``) and never followed by ``_q<Q>`` labels."""
+    spec = _LABEL_SIGNATURE.bind(*args, **keywords).arguments
+    return _row_labels(spec["qualities"], stress_variants(spec), spec.get("chains", ()))
 
 
 def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "4:2:0", after_fork=None, scales: Sequence[int] = (),
@@ -560,124 +513,72 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
                  noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
                  sharpen_threshold: int = 0, chains: Sequence[str] = (), autocontrasts: Sequence[int] = (),
                  autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8):
-    """Recompression stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is
-    bit for bit what a plain run returns - and then on the batch re-saved as JPEG at every quality of ``qualities``
-    (``pipeline.recompress``: each image at its own size, before any member's resize; dataset/augment.py:110-113).  ``staged`` as for
-    ``_score_batch``; it is decoded once.  Returns ``[1 + Q, M, n]`` fp32 (device), rows 1.. in the order of ``qualities``.
-    With ``scales`` (percents, sorted largest first here) the batch is also rescaled to each percent of its size with ``resize_filter``
-    (``pipeline.rescale``) and scored unsaved and re-saved at every quality - rescale first, ``recompress`` second, the order in which
-    the challenge's test images were made.  Then the result is ``(rows [1 + V, M, n], labels)`` with ``labels`` =
-    ``stress_labels(qualities, scales)``, the names of rows 1.. .
-    With ``blurs`` (sigmas, sorted ascending here; ``blur_radius`` None = three sigma) and ``medians`` (windows, ascending) the decoded
-    batch AT FULL SIZE is also smoothed (``pipeline.blur`` / ``pipeline.median``; dataset/augment.py:131-140) and scored unsaved and
-    re-saved at every quality; smoothing is not composed with ``scales``, so the grid stays linear in the number of variants.  The
-    result is ``(rows, labels)`` whenever ``scales``, ``blurs`` or ``medians`` is non-empty, ``labels`` = ``stress_labels(qualities,
-    scales, blurs, medians)``.
-    With ``flips`` (axes "h" / "v"), ``crops`` (percents, largest first here; ``crop_origin`` "centre" or "topleft") and ``rotations``
-    (degrees, ascending here; ``rotate_fill`` "crop", "mirror" or "black") the decoded batch is also mirrored, cropped and rotated
-    (``pipeline.flip`` / ``crop`` / ``rotate``; dataset/augment.py:68-120) and scored unsaved and re-saved at every quality, one warped
-    batch alive at a time; geometry is not composed with resizing or smoothing.  The result is ``(rows, labels)`` whenever any of the
-    lists but ``qualities`` is non-empty, ``labels`` = ``stress_labels(qualities, scales, blurs, medians, flips, crops, rotations)``.
-    With ``gray``, ``bgr``, ``hues`` (integer degrees), ``saturations`` / ``contrasts`` (percents), ``brightnesses`` (percents of full
-    scale) and ``gammas`` (each list ascending here) the decoded batch is also recoloured (``pipeline.gray`` / ``bgr`` / ``hue`` /
-    ``saturation`` / ``contrast`` / ``brightness`` / ``gamma``; dataset/augment.py:122-129, :142-151) and scored unsaved and re-saved at
-    every quality, one coloured batch alive at a time and the batch's mean colour computed at most once; colour is not composed with
-    resizing, smoothing or geometry.  Then too the result is ``(rows, labels)``, ``labels`` = ``stress_labels`` of the same keywords.
-    With ``noises`` / ``mono_noises`` (sigmas in levels), ``speckles`` and ``impulses`` (percents; each list ascending here) the decoded
-    batch also gets Gaussian noise per channel, Gaussian luminance noise, speckle and salt-and-pepper impulses (``pipeline.noise``) and is
-    scored unsaved and re-saved at every quality, one noisy batch alive at a time; noise is not composed with the other families.
-    ``noise_seed`` and ``noise_keys`` (one integer per image, None: 0..n-1; ``pipeline.noise_keys`` of the file names makes a file's noise
-    independent of its batch) select the random field, which all noise variants of a batch share.  Then too the result is ``(rows,
-    labels)``.
-    With ``sharpens`` (integer percents 1..500, ascending here; ``sharpen_sigma``, ``sharpen_radius`` None = three sigma,
-    ``sharpen_threshold``) the decoded batch is also sharpened by an unsharp mask (``pipeline.sharpen``, one launch per variant) and scored
-    unsaved and re-saved at every quality, one sharpened batch alive at a time; sharpening is not combined with the other families
-    except through a chain.  V percents cost V (1 + Q) plain runs.
-    With ``autocontrasts`` / ``autocontrast_lumas`` (integer cutoff percents 0..49), ``equalize`` and ``clahes`` (clip limits 1.0..9.9;
-    ``clahe_grid`` tiles per axis; each list ascending here) the decoded batch also goes through a tone curve measured from each image's
-    own histogram (``pipeline.tone``: histograms, tables and pixels in three launches, nothing returns to the host) and is scored
-    unsaved and re-saved at every quality, one batch alive at a time; the tone rows follow the sharpening rows.
-    With ``chains`` (chain texts, ``pipeline.parse_chain``: ``"r50+shp080+q75"``; scored in the order given) the decoded batch also goes
-    through each chain's steps left to right (``pipeline.apply_chain`` with this call's ``subsampling``, ``resize_filter``,
-    ``blur_radius``, ``crop_origin``, ``rotate_fill``, ``sharpen_*``, ``noise_seed``, ``noise_keys`` and ``clahe_grid``) and the result is scored ONCE,
-    exactly as the chain is written: ``qualities`` do not multiply chain rows, a chain that should end in a re-save ends in a ``q``
-    step.  One chain's batch is alive at a time; C chains cost C plain runs.  The chain rows come last.  Then too the result is
-    ``(rows, labels)``."""
+    """Stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is bit for bit what a
+    plain run returns - and then on perturbed copies of the decoded pixels, each image at its own size, before any member's resize.
+    ``staged`` as for ``_score_batch``; it is decoded once.
+    Rows 1..Q: the batch re-saved as JPEG at every quality of ``qualities``, in the order given (``pipeline.recompress`` with
+    ``subsampling``; dataset/augment.py:110-113).  With nothing else asked for the result is these rows, ``[1 + Q, M, n]`` fp32 (device).
+    Then the variants of ``stress_variants``: every value of every list below, kind by kind in the order of ``chain.STEPS``, each made
+    from the decoded batch by ``pipeline.apply_step``, scored unsaved and then re-saved at every quality - perturb first, ``recompress``
+    second, the order in which the challenge's test images were made.  Kinds are combined only through a chain, so the grid stays linear:
+    V variants cost V (1 + Q) plain runs, one perturbed batch alive at a time.
+      ``scales`` (percents, largest first): ``pipeline.rescale`` with ``resize_filter``
+      ``blurs`` (sigmas; ``blur_radius`` None = three sigma), ``medians`` (windows): ``pipeline.blur`` / ``median`` (dataset/augment.py:131-140)
+      ``flips`` (axes "h" / "v"), ``crops`` (percents, largest first; ``crop_origin`` "centre" or "topleft"), ``rotations`` (degrees;
+        ``rotate_fill`` "crop", "mirror" or "black"): ``pipeline.flip`` / ``crop`` / ``rotate`` (dataset/augment.py:68-120)
+      ``gray``, ``bgr``, ``hues`` (integer degrees), ``saturations`` / ``contrasts`` (percents), ``brightnesses`` (percents of full scale),
+        ``gammas``: the ``pipeline`` function of that name (dataset/augment.py:122-129, :142-151); the batch's mean colour, which
+        ``contrast`` takes, is computed at most once
+      ``noises`` / ``mono_noises`` (sigmas in levels), ``speckles``, ``impulses`` (percents): ``pipeline.noise``.  ``noise_seed`` and
+        ``noise_keys`` (one integer per image, None: 0..n-1; ``pipeline.noise_keys`` of the file names makes a file's noise independent
+        of its batch) select the random field, which all noise variants of a batch share; the keys go to the device at most once
+      ``sharpens`` (integer percents 1..500): ``pipeline.sharpen`` with ``sharpen_sigma``, ``sharpen_radius`` (None = three sigma) and
+        ``sharpen_threshold``, one launch per variant
+      ``autocontrasts`` / ``autocontrast_lumas`` (integer cutoff percents 0..49), ``equalize``, ``clahes`` (clip limits 1.0..9.9;
+        ``clahe_grid`` tiles per axis): ``pipeline.tone``, a curve measured from each image's own histogram, nothing returns to the host
+    Every list but ``scales`` and ``crops`` is taken ascending; no list is de-duplicated.
+    Last the ``chains`` (chain texts, ``pipeline.parse_chain``: ``"r50+shp080+q75"``; scored in the order given): the decoded batch goes
+    through each chain's steps left to right (``pipeline.apply_chain`` with this call's options, ``noise_seed`` and ``noise_keys``) and
+    the result is scored ONCE, exactly as the chain is written: ``qualities`` do not multiply chain rows, a chain that should end in a
+    re-save ends in a ``q`` step.  One chain's batch is alive at a time; C chains cost C plain runs.
+    With any variant or chain the result is ``(rows [1 + V, M, n], labels)``, ``labels`` = ``stress_labels`` of the same keywords, the
+    names of rows 1.. ."""
+    spec = dict(locals())                                        # the keywords above by name: the variants' lists and the steps' options
     from . import ops, pipeline
     if isinstance(staged, pipeline.DecodedBatch):
         batch = staged
     else:
         batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
             isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
-    scales = sorted((int(pc) for pc in scales), reverse=True)
-    blurs = sorted(int(round(float(sg) * 10)) / 10 for sg in blurs)
-    medians = sorted(int(k) for k in medians)
-    flips = sorted(str(ax) for ax in flips)
-    crops = sorted((int(pc) for pc in crops), reverse=True)
-    rotations = [tt / 10 for tt in _rot_tenths(rotations)]
+    variants = stress_variants(spec)
+    kinds = {kind for _, kind, _ in variants}
+    qualities, chains = [int(q) for q in qualities], [str(text) for text in chains]
     rows = [_score_batch(batch, members, None, after_fork=after_fork)]
-    for q in qualities:
-        rows.append(_score_batch(pipeline.recompress(batch, int(q), subsampling), members))
-    for pc in scales:
-        small = pipeline.rescale(batch, pc, resize_filter)
-        rows.append(_score_batch(small, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(small, int(q), subsampling), members))
-    for kind, arg in [("blur", sg) for sg in blurs] + [("median", k) for k in medians]:          # one smoothed batch alive at a time
-        smooth = pipeline.blur(batch, arg, blur_radius) if kind == "blur" else pipeline.median(batch, arg)
-        rows.append(_score_batch(smooth, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(smooth, int(q), subsampling), members))
-    for kind, arg in [("flip", ax) for ax in flips] + [("crop", pc) for pc in crops] + [("rotate", dg) for dg in rotations]:
-        warped = pipeline.flip(batch, arg) if kind == "flip" else pipeline.crop(batch, arg, crop_origin) if kind == "crop" else \
-            pipeline.rotate(batch, arg, rotate_fill)             # one warped batch alive at a time
-        rows.append(_score_batch(warped, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(warped, int(q), subsampling), members))
-    colours = _colour_variants(gray, bgr, hues, saturations, contrasts, brightnesses, gammas)
-    mean = batch.mean_colour() if any(kind == "contrast" for _, kind, _ in colours) else None     # once per batch
-    for _, kind, arg in colours:
-        fn = getattr(pipeline, kind)
-        coloured = fn(batch) if arg is None else fn(batch, arg, mean) if kind == "contrast" else fn(batch, arg)   # one alive at a time
-        rows.append(_score_batch(coloured, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(coloured, int(q), subsampling), members))
-    noisy = _noise_variants(noises, mono_noises, speckles, impulses)
-    keys_d = pipeline.noise_keys_device(batch, noise_keys) if noisy else None                      # once per batch
-    for _, kind, arg in noisy:
-        grainy = pipeline.noise(batch, kind, arg, noise_seed, keys_d)                              # one alive at a time
-        rows.append(_score_batch(grainy, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(grainy, int(q), subsampling), members))
-    sharpens = sorted(int(pc) for pc in sharpens)
-    for pc in sharpens:
-        sharp = pipeline.sharpen(batch, pc, sharpen_sigma, sharpen_radius, sharpen_threshold)      # one alive at a time
-        rows.append(_score_batch(sharp, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(sharp, int(q), subsampling), members))
-    toned = _tone_variants(autocontrasts, autocontrast_lumas, equalize, clahes)
-    for _, mode, arg in toned:
-        curved = pipeline.tone(batch, mode, arg, clahe_grid)                                       # one alive at a time
-        rows.append(_score_batch(curved, members))
-        for q in qualities:
-            rows.append(_score_batch(pipeline.recompress(curved, int(q), subsampling), members))
-    chains = [str(text) for text in chains]
+    rows += [_score_batch(pipeline.apply_step(batch, "recompress", q, spec), members) for q in qualities]
+    mean = keys_d = None
+    for _, kind, arg in variants:                                # one perturbed batch alive at a time
+        if mean is None and "contrast" in kinds and chain.STEPS[kind].family == "colour":
+            mean = batch.mean_colour()                           # once per batch, in front of the colour rows
+        if keys_d is None and kind in chain.NOISE_STEPS:
+            keys_d = pipeline.noise_keys_device(batch, noise_keys)                                 # once per batch
+        made = pipeline.apply_step(batch, kind, arg, spec, mean, keys_d)
+        rows.append(_score_batch(made, members))
+        rows += [_score_batch(pipeline.apply_step(made, "recompress", q, spec), members) for q in qualities]
     for text in chains:                                          # scored once, as written: the qualities do not multiply chain rows
-        rows.append(_score_batch(pipeline.apply_chain(
-            batch, pipeline.parse_chain(text), subsampling=subsampling, resize_filter=resize_filter, blur_radius=blur_radius,
-            crop_origin=crop_origin, rotate_fill=rotate_fill, sharpen_sigma=sharpen_sigma, sharpen_radius=sharpen_radius,
-            sharpen_threshold=sharpen_threshold, noise_seed=noise_seed, noise_keys=keys_d if keys_d is not None else noise_keys,
-            clahe_grid=clahe_grid), members))
+        rows.append(_score_batch(pipeline.apply_chain(batch, pipeline.parse_chain(text), noise_keys=keys_d if keys_d is not None else noise_keys,
+                                                      **{key: spec[key] for key in pipeline.STEP_OPTIONS}), members))
     if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
         ops.h2_check("stress_batch")                             # no activation of a re-saved image left the packed storage's range
-    if not scales and not blurs and not medians and not flips and not crops and not rotations and not colours and not noisy and \
-            not sharpens and not chains and not toned:
+    if not variants and not chains:
         return torch.stack(rows)
-    return torch.stack(rows), stress_labels(qualities, scales, blurs, medians, flips, crops, rotations, gray=gray, bgr=bgr, hues=hues,
-                                            saturations=saturations, contrasts=contrasts, brightnesses=brightnesses, gammas=gammas,
-                                            noises=noises, mono_noises=mono_noises, speckles=speckles, impulses=impulses,
-                                            sharpens=sharpens, chains=chains, autocontrasts=autocontrasts,
-                                            autocontrast_lumas=autocontrast_lumas, equalize=equalize, clahes=clahes)
+    return torch.stack(rows), _row_labels(qualities, variants, chains)
+
+
+# stress_labels' parameters: stress_batch's, in their order, less the batch, the members, after_fork and the three options of the
+# re-save, the resize and the blur, which it has never taken
+_LABEL_SIGNATURE = inspect.Signature([p for name, p in inspect.signature(stress_batch).parameters.items()
+                                      if name not in ("staged", "members", "subsampling", "after_fork", "resize_filter", "blur_radius")])
+stress_labels.__signature__ = _LABEL_SIGNATURE
 
 
 def gather_stress_rows(kept: Sequence[torch.Tensor], n_q: int, n_members: int, n_images: int, rank: int = 0, world: int = 1,

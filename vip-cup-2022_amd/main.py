@@ -147,11 +147,13 @@ The reference ships none (README.md:13) and raises when a directory is empty (ma
 unless ``--synthetic`` asks for the seeded synthetic checkpoints.
 """
 import argparse
+import inspect
 import json
 import os
 import re
 import sys
 import time
+from collections import namedtuple
 from glob import glob
 
 import numpy as np
@@ -160,6 +162,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from vipcup_amd import chain as grammar  # noqa: E402  (text handling only: nothing heavy is imported)
 
 
 def _heatmap_writer(a, names, members, rank):
@@ -207,39 +211,157 @@ def _heatmap_writer(a, names, members, rank):
     return score
 
 
-def _stress_scorer(qualities, subsampling, kept, scales=(), resize_filter="bicubic", blurs=(), medians=(), blur_radius=None, geometry=None,
-                   colour=None, noise=None, names=None, sharpen=None, chains=None, tone=None):
-    """the ``batch_scorer`` of ``--stress-jpeg`` / ``--stress-resize`` / ``--stress-blur`` / ``--stress-median`` / ``--stress-flip`` /
-    ``--stress-crop`` / ``--stress-rotate`` (``geometry``: their ``stress_batch`` keywords, or None) and the colour flags (``colour``:
-    likewise) and the noise flags (``noise``: likewise; every batch's ``noise_keys`` come from its files' ``names``), ``--stress-sharpen``
-    (``sharpen``: likewise), the tone flags (``tone``: likewise) and ``--stress-chain`` (``chains``: ``{"chains": texts}`` plus the options of the steps that no family flag
-    of this run carries, or None): ``stress_batch`` on every batch; the unperturbed row is handed on unchanged, the rows of the perturbed
-    batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
+# ---- the --stress-* flags ------------------------------------------------------------------------------------------------------------------
+# A step kind's label, range, keyword, row order and family are rows of ``chain.STEPS``; what is left for the CLI is per kind, in ``_LISTS``:
+# the syntax of a list token (None: whatever ``int()`` reads), what becomes of a value listed twice (ONCE: the list is refused; DROP: the
+# copies go; DROP_BANNED: so does the one value that is no step, without a word), the refusal's words for what a list holds, and the key
+# of the list in ``stress.json``'s settings.  The switches (--stress-gray, --stress-bgr, --stress-equalize) are stored under their keyword.
+DROP, DROP_BANNED, ONCE = "drop", "drop, the banned value too", "once"
+_TENTHS, _PERCENT = r"\d{1,2}(\.\d)?", r"-?\d{1,3}"
+_List = namedtuple("_List", "syntax twice expected setting")
+_LISTS = {kind: _List(*row) for kind, row in {
+    "recompress": (None, DROP, "integer qualities in 1..100", "qualities"),
+    "rescale": (None, DROP_BANNED, "integer percents in 10..400", "scales"),
+    "blur": (_TENTHS, DROP, "sigmas in 0.3..5.0 with at most one fractional digit", "blur_sigmas"),
+    "median": (None, DROP, "windows, each 3 or 5", "medians"),
+    "flip": (r"[hv]", DROP, None, "flips"),
+    "crop": (None, DROP, "integer percents in 50..99", "crops"),
+    "rotate": ("-?" + _TENTHS, DROP, "non-zero angles in -45..45 with at most one fractional digit", "rotations"),
+    "hue": (_PERCENT, DROP, "non-zero integer degrees in -180..180", "hues"),
+    "saturation": (_PERCENT, DROP, "integer percents in 0..200 other than 100", "saturations"),
+    "contrast": (_PERCENT, DROP, "integer percents in 0..200 other than 100", "contrasts"),
+    "brightness": (_PERCENT, DROP, "non-zero integer percents in -50..50", "brightnesses"),
+    "gamma": (r"\d(\.\d{1,2})?", DROP, "decimals in 0.50..2.00 with at most two fractional digits, other than 1", "gammas"),
+    "gaussian": (_TENTHS, ONCE, "sigmas in 0.5..50.0 with at most one fractional digit", "noise_sigmas"),
+    "mono": (_TENTHS, ONCE, "sigmas in 0.5..50.0 with at most one fractional digit", "noise_mono_sigmas"),
+    "speckle": (r"\d{1,2}", ONCE, "integer percents in 1..50", "speckles"),
+    "impulse": (_TENTHS, ONCE, "percents in 0.1..50.0 with at most one fractional digit", "impulses"),
+    "sharpen": (r"\d{1,3}", ONCE, "integer percents in 1..500", "sharpen_percents"),
+    "autocontrast": (r"\d{1,2}", ONCE, "integer cutoff percents in 0..49", "autocontrast_cutoffs"),
+    "autocontrast_luma": (r"\d{1,2}", ONCE, "integer cutoff percents in 0..49", "autocontrast_luma_cutoffs"),
+    "clahe": (_TENTHS, ONCE, "clip limits in 1.0..9.9 with at most one fractional digit", "clahe_limits"),
+}.items()}
+# An option flag: its keyword of ``stress_batch``, the step kind whose flag it is read after (and written after, in the settings), the kinds
+# it governs - it is accepted with the flag of one of them or with a chain that holds one -, the refusal otherwise, its integer range
+# and the value that stands for "not given".
+_SHARPEN_NEEDS = ("--stress-sharpen-sigma / --stress-sharpen-radius / --stress-sharpen-threshold need --stress-sharpen P[,P...] or a "
+                  "--stress-chain with a shp step")
+_Option = namedtuple("_Option", "flag keyword after kinds needs lo hi unset")
+_OPTIONS = tuple(_Option(*row) for row in (
+    ("--stress-resize-filter", "resize_filter", "rescale", ("rescale",), "--stress-resize-filter needs --stress-resize P[,P...]", None, None, None),
+    ("--stress-blur-radius", "blur_radius", "blur", ("blur",), "--stress-blur-radius needs --stress-blur S[,S...]", 1, 15, None),
+    ("--stress-crop-origin", "crop_origin", "crop", ("crop",), "--stress-crop-origin needs --stress-crop P[,P...]", None, None, None),
+    ("--stress-rotate-fill", "rotate_fill", "rotate", ("rotate",), "--stress-rotate-fill needs --stress-rotate D[,D...]", None, None, None),
+    ("--stress-noise-seed", "noise_seed", "impulse", grammar.NOISE_STEPS,
+     "--stress-noise-seed needs --stress-noise, --stress-noise-mono, --stress-speckle or --stress-impulse", 0, 0xFFFFFFFF, None),
+    ("--stress-sharpen-sigma", "sharpen_sigma", "sharpen", ("sharpen",), _SHARPEN_NEEDS, None, None, 1.0),
+    ("--stress-sharpen-radius", "sharpen_radius", "sharpen", ("sharpen",), _SHARPEN_NEEDS, 1, 15, None),
+    ("--stress-sharpen-threshold", "sharpen_threshold", "sharpen", ("sharpen",), _SHARPEN_NEEDS, 0, 255, 0),
+    ("--stress-clahe-grid", "clahe_grid", "clahe", ("clahe",),
+     "--stress-clahe-grid needs --stress-clahe L[,L...] or a --stress-chain with a clahe step", 1, 16, 8),
+))
+# the options a chain's steps add to the settings when the family whose flags carry them is absent, in the order these keys have always had
+_CHAIN_SETTINGS = ("crop_origin", "rotate_fill", "noise_seed", "clahe_grid", "resize_filter", "blur_radius")
+
+
+def _dest(flag):
+    return flag[2:].replace("-", "_")
+
+
+def _units(token, syntax, scale):
+    """a token of a list in label units (``2.5`` at 10 units per one -> 25); None when it is not in the flag's syntax"""
+    if syntax is None:
+        try:
+            return int(token)
+        except ValueError:
+            return None
+    if not re.fullmatch(syntax, token):
+        return None
+    whole, _, frac = token.lstrip("-").partition(".")
+    v = int(whole) * scale + int((frac + "00")[:len(str(scale)) - 1] or 0)
+    return -v if token[0] == "-" else v
+
+
+def _stress_list(kind, text):
+    """the values of one ``--stress-*`` list as ``stress_batch`` takes them, in row order; the range is ``chain.STEPS``'s"""
+    row, (syntax, twice, expected, _) = grammar.STEPS[kind], _LISTS[kind]
+    tokens = text.split(",")
+    if kind == "flip":
+        if not all(re.fullmatch(syntax, t) for t in tokens):
+            raise SystemExit(f"vipcup_amd main: {row.flag} {text!r}: expected h, v or h,v")
+        return sorted(set(tokens))
+    units = [_units(t, syntax, row.scale) for t in tokens]
+    bad = None in units or not all(row.lo <= (abs(v) if row.signed else v) <= row.hi for v in units)
+    if twice == ONCE:
+        bad = bad or len(set(units)) != len(units)
+    elif twice == DROP_BANNED:
+        units = [v for v in units if v != row.banned]
+    if bad or row.banned in units:
+        raise SystemExit(f"vipcup_amd main: {row.flag} {text!r}: expected a comma-separated list of {expected}"
+                         + (", each listed once" if twice == ONCE else ""))
+    if not units:
+        raise SystemExit(f"vipcup_amd main: {row.flag} {text!r}: nothing left after dropping {row.banned} (the unperturbed row)")
+    return [grammar.step_arg(kind, v) for v in sorted(units if twice == ONCE else set(units), reverse=row.order == "desc")]
+
+
+def _stress_option(option, value, default, present):
+    """the value of an option flag for ``stress_batch``; ``present``: the step kinds of this run's flags and chains"""
+    flag, lo, hi = option.flag, option.lo, option.hi
+    if value != default:
+        if not present & set(option.kinds):
+            raise SystemExit("vipcup_amd main: " + option.needs)
+        if option.keyword == "sharpen_sigma":                   # a decimal: the sigmas of --stress-blur
+            blur = grammar.STEPS["blur"]
+            units = _units(value, _TENTHS, blur.scale)
+            if units is None or not blur.lo <= units <= blur.hi:
+                raise SystemExit(f"vipcup_amd main: {flag} {value!r}: expected a sigma in 0.3..5.0 with at most one fractional digit")
+            return grammar.step_arg("blur", units)
+        if lo is not None and not lo <= value <= hi:
+            raise SystemExit(f"vipcup_amd main: {flag} {value}: expected an integer in {lo}..{hi}")
+    return option.unset if value is None else value
+
+
+def _refuse_context(a, flag, family):
+    """what every stress flag asks of the run: --stress-out, --shard images and --tta 1, no --heatmaps"""
+    if a.stress_out is None:
+        raise SystemExit(f"vipcup_amd main: {flag} needs --stress-out FILE.csv")
+    if a.shard != "images" or a.tta > 1:
+        # the scores of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
+        one = family in ("recompression", "resize")
+        raise SystemExit(f"vipcup_amd main: {flag} works with --shard images and --tta 1 only (got --shard {a.shard} --tta {a.tta}): "
+                         f"the {family} stress test{'' if one else 's'} under member sharding or TTA {'is' if one else 'are'} not implemented")
+    if a.heatmaps is not None:
+        raise SystemExit(f"vipcup_amd main: {flag} and --heatmaps cannot be combined (both replace the batch scorer): "
+                         "run them one after the other")
+
+
+def _stress_labels(spec):
+    """the labels of the rows that ``spec`` (the keywords of ``stress_batch``) asks for"""
+    from vipcup_amd import ensemble
+    return ensemble.stress_labels(**{k: v for k, v in spec.items() if k in inspect.signature(ensemble.stress_labels).parameters})
+
+
+def _stress_scorer(spec, names, kept):
+    """the ``batch_scorer`` of the ``--stress-*`` flags: ``stress_batch`` with ``spec``, the run's keywords, on every batch (every batch's
+    ``noise_keys`` come from its files' ``names``: by file, not by batch position); the unperturbed row is handed on unchanged, the rows
+    of the perturbed batches ``[V, M, n]`` stay on this rank (``kept``, in batch order) until the run's one extra collective"""
     from vipcup_amd import ensemble, pipeline
 
     def score(staged, sub, b0, b1, after_fork):
-        if scales or blurs or medians or geometry or colour or noise or sharpen or chains or tone:
-            more = _label_keywords(geometry, colour, noise, sharpen, chains, tone)
-            if noise or chains:                                                                     # by file, not by batch position
-                more["noise_keys"] = pipeline.noise_keys(names[b0:b1])
-            rows, _ = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork, scales=scales,
-                                            resize_filter=resize_filter, blurs=blurs, medians=medians, blur_radius=blur_radius, **more)
-        else:
-            rows = ensemble.stress_batch(staged, sub, qualities, subsampling, after_fork=after_fork)
+        rows = ensemble.stress_batch(staged, sub, after_fork=after_fork, noise_keys=pipeline.noise_keys(names[b0:b1]), **spec)
+        rows = rows[0] if isinstance(rows, tuple) else rows      # (rows, labels) with any variant but the qualities
         kept.append(rows[1:])
         return rows[0]
     return score
 
 
-def _write_stress(a, names, members, per_model, stressed, qualities, mode, scales=(), blurs=None, medians=None, geometry=None, colour=None,
-                  noise=None, sharpen=None, chains=None, tone=None):
+def _write_stress(a, names, members, per_model, stressed, spec, mode):
     """``--stress-out``: the per-file table as CSV and, next to it, the summary and settings as JSON"""
     import pandas as pd
     from vipcup_amd import ensemble
     scores = np.concatenate([per_model[None].astype(np.float32), stressed.astype(np.float32)], axis=0)
-    labels = ensemble.stress_labels(qualities, scales, blurs or (), medians or (),
-                                    **_label_keywords(geometry, colour, noise, sharpen, chains, tone))
-    mixed = bool(scales or blurs or medians or geometry or colour or noise or sharpen or chains or tone)
+    qualities, labels = spec["qualities"], _stress_labels(spec)
+    mixed = len(labels) > len(qualities)
     table, summary = ensemble.stress_table(names, scores, labels if mixed else qualities)
     cols = {"filename": table["filename"], "p": table["p"], "decision": table["decision"]}
     for k, v in enumerate(labels):
@@ -251,47 +373,29 @@ def _write_stress(a, names, members, per_model, stressed, qualities, mode, scale
     if mixed:
         cols["flips"] = table["flips"]
     pd.DataFrame(cols).to_csv(a.stress_out, index=False)
-    summary["settings"] = {"qualities": list(qualities), "subsampling": {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling],
-                           "threshold": ensemble.THR, "precision": mode, "batch_size": a.batch_size, "n_images": len(names),
-                           "members": [spec.name for spec, _ in members]}
-    if scales:
-        summary["settings"]["scales"] = list(scales)
-        summary["settings"]["resize_filter"] = a.stress_resize_filter
-    if blurs is not None or medians is not None:
-        summary["settings"]["blur_sigmas"] = list(blurs or ())
-        summary["settings"]["blur_radius"] = a.stress_blur_radius
-        summary["settings"]["medians"] = list(medians or ())
-    if geometry:
-        summary["settings"].update(geometry)
-    if colour:
-        summary["settings"].update(colour)
-    if noise:
-        summary["settings"].update({"noise_sigmas": noise["noises"], "noise_mono_sigmas": noise["mono_noises"], "speckles": noise["speckles"],
-                                    "impulses": noise["impulses"], "noise_seed": noise["noise_seed"]})
-    if sharpen:
-        summary["settings"].update({"sharpen_percents": sharpen["sharpens"], "sharpen_sigma": sharpen["sharpen_sigma"],
-                                    "sharpen_radius": sharpen["sharpen_radius"], "sharpen_threshold": sharpen["sharpen_threshold"]})
-    if tone:
-        summary["settings"].update({"autocontrast_cutoffs": tone["autocontrasts"], "autocontrast_luma_cutoffs": tone["autocontrast_lumas"],
-                                    "equalize": tone["equalize"], "clahe_limits": tone["clahes"], "clahe_grid": tone["clahe_grid"]})
-    if chains:
-        from vipcup_amd import chain as grammar
-        summary["settings"]["chains"] = list(chains["chains"])
-        kinds = grammar.chain_kinds(chains["chains"])
-        for key in ("crop_origin", "rotate_fill", "noise_seed", "clahe_grid"):          # the options of chain steps whose family flag is absent
-            if key in chains:
-                summary["settings"].setdefault(key, chains[key])
-        if "rescale" in kinds:
-            summary["settings"].setdefault("resize_filter", a.stress_resize_filter)
-        if "blur" in kinds:
-            summary["settings"].setdefault("blur_radius", a.stress_blur_radius)
+    settings = {"qualities": list(qualities), "subsampling": spec["subsampling"], "threshold": ensemble.THR, "precision": mode,
+                "batch_size": a.batch_size, "n_images": len(names), "members": [member.name for member, _ in members]}
+    in_chain = grammar.chain_kinds(spec.get("chains", ()))
+    rows = [row for kind, row in grammar.STEPS.items() if kind != "recompress"]
+    # a family with one of its flags given writes all its lists (empty ones too) and options; sharpening also with a shp step in a chain
+    present = {row.family for row in rows if row.keyword in spec} | ({"sharpening"} if "sharpen" in in_chain else set())
+    for row in rows:
+        if row.family in present:
+            if row.kind in _LISTS:
+                settings[_LISTS[row.kind].setting] = spec.get(row.keyword, [])
+            else:
+                settings[row.keyword] = spec.get(row.keyword, False)
+            settings.update({option.keyword: spec[option.keyword] for option in _OPTIONS if option.after == row.kind})
+    if "chains" in spec:
+        settings["chains"] = list(spec["chains"])
+        for key in _CHAIN_SETTINGS:                     # the options of chain steps whose family's flags are absent
+            family = next(grammar.STEPS[option.after].family for option in _OPTIONS if option.keyword == key)
+            governed = {kind for option in _OPTIONS if grammar.STEPS[option.after].family == family for kind in option.kinds}
+            if family not in present and in_chain & governed:
+                settings[key] = spec[key]
+    summary["settings"] = settings
     with open(os.path.splitext(a.stress_out)[0] + ".json", "w") as f:
         json.dump(summary, f, indent=1)
-
-
-def _label_keywords(geometry, colour, noise, sharpen, chains, tone=None):
-    """the keywords of ``stress_labels`` (and ``stress_batch``) from the CLI's per-family dictionaries"""
-    return {**(geometry or {}), **(colour or {}), **(noise or {}), **(sharpen or {}), **(chains or {}), **(tone or {})}
 
 
 def _tile_scorer(a, kept, kept_tiles):
@@ -397,29 +501,6 @@ def _write_occlusion(a, names, members, per_model, rows, mode):
                            "members": [spec.name for spec, _ in members]}
     with open(os.path.join(a.occlusion, "occlusion.json"), "w") as f:
         json.dump(summary, f, indent=1)
-
-
-def _int_list(flag, text, lo, hi, banned, what):
-    """``--stress-hue`` and its kin: a comma-separated list of integers in lo..hi other than ``banned``, ascending, duplicates dropped"""
-    tokens = text.split(",")
-    if not all(re.fullmatch(r"-?\d{1,3}", t) for t in tokens):
-        tokens = []
-    given = sorted({int(t) for t in tokens})
-    if not given or given[0] < lo or given[-1] > hi or banned in given:
-        raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of {what}")
-    return given
-
-
-def _tenths_list(flag, text, lo, hi, what):
-    """``--stress-noise`` and its kin: a comma-separated list of decimals with at most one fractional digit, as tenths in lo..hi,
-    ascending; a value listed twice is refused"""
-    tokens = text.split(",")
-    if not all(re.fullmatch(r"\d{1,2}(\.\d)?", t) for t in tokens):
-        tokens = []
-    given = sorted(int(t.replace(".", "")) if "." in t else 10 * int(t) for t in tokens)
-    if not given or given[0] < lo or given[-1] > hi or len(set(given)) != len(given):
-        raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of {what}, each listed once")
-    return given
 
 
 def main(argv=None):
@@ -629,29 +710,19 @@ def main(argv=None):
     a = ap.parse_args(argv)
     chains, in_chain = None, set()                      # the chain texts, and the step kinds they hold
     if a.stress_chain is not None:
-        from vipcup_amd import chain as grammar         # text handling only: nothing heavy is imported
         try:
             chains = grammar.parse_chains(a.stress_chain)
         except ValueError as e:
             raise SystemExit(f"vipcup_amd main: --stress-chain {a.stress_chain!r}: {e}")
         in_chain = grammar.chain_kinds(chains)
-    colour_flags = (("--stress-gray", a.stress_gray or None), ("--stress-bgr", a.stress_bgr or None), ("--stress-hue", a.stress_hue),
-                    ("--stress-saturation", a.stress_saturation), ("--stress-contrast", a.stress_contrast),
-                    ("--stress-brightness", a.stress_brightness), ("--stress-gamma", a.stress_gamma))
-    noise_flags = (("--stress-noise", a.stress_noise), ("--stress-noise-mono", a.stress_noise_mono), ("--stress-speckle", a.stress_speckle),
-                   ("--stress-impulse", a.stress_impulse))
-    tone_flags = (("--stress-autocontrast", a.stress_autocontrast), ("--stress-autocontrast-luma", a.stress_autocontrast_luma),
-                  ("--stress-equalize", a.stress_equalize or None), ("--stress-clahe", a.stress_clahe))
-    any_colour = any(v is not None for _, v in colour_flags + noise_flags + tone_flags) or a.stress_sharpen is not None or chains is not None
-    # colour, noise, sharpening, tone or chains: the same refusals below
+    flagged = {kind for kind, row in grammar.STEPS.items() if getattr(a, _dest(row.flag)) not in (None, False)}
+    stress_run = bool(flagged) or chains is not None    # the one question: does any stress flag replace the batch scorer
     if a.occlusion is not None:
         if a.shard != "images" or a.tta > 1:
             # as for the heat maps: the scores of one image would be spread over ranks or over augmented copies
             raise SystemExit("vipcup_amd main: --occlusion works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): occlusion maps under member sharding or TTA are not implemented")
-        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
-                a.tiles_out is not None or a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or \
-                a.stress_crop is not None or a.stress_rotate is not None or any_colour:
+        if a.heatmaps is not None or stress_run or a.stress_out is not None or a.tiles_out is not None:
             raise SystemExit("vipcup_amd main: --occlusion cannot be combined with --heatmaps, --stress-* or --tiles-out (each replaces the "
                              "batch scorer): run them one after the other")
         if not 2 <= a.occlusion_grid <= 32:
@@ -666,9 +737,7 @@ def main(argv=None):
             # as for the stress runs: the scores of one image would be spread over ranks or over augmented copies
             raise SystemExit("vipcup_amd main: --tiles-out works with --shard images and --tta 1 only (got --shard "
                              f"{a.shard} --tta {a.tta}): tile scoring under member sharding or TTA is not implemented")
-        if a.heatmaps is not None or a.stress_jpeg is not None or a.stress_resize is not None or a.stress_out is not None or \
-                a.stress_blur is not None or a.stress_median is not None or a.stress_flip is not None or a.stress_crop is not None or \
-                a.stress_rotate is not None or any_colour:
+        if a.heatmaps is not None or stress_run or a.stress_out is not None:
             raise SystemExit("vipcup_amd main: --tiles-out cannot be combined with --heatmaps or --stress-* (each replaces the batch scorer): "
                              "run them one after the other")
         if not 16 <= a.tile_size <= 1024:
@@ -679,211 +748,34 @@ def main(argv=None):
             raise SystemExit(f"vipcup_amd main: --tile-max {a.tile_max}: expected an integer in 1..4096")
     elif a.tile_size != 200 or a.tile_stride is not None or a.tile_max != 256 or a.tile_agg != "mean":
         raise SystemExit("vipcup_amd main: --tile-size / --tile-stride / --tile-max / --tile-agg need --tiles-out FILE.csv")
-    scales = None
-    if a.stress_resize is not None:
-        try:
-            given = [int(t) for t in a.stress_resize.split(",")]
-        except ValueError:
-            given = []
-        if not given or min(given) < 10 or max(given) > 400:
-            raise SystemExit(f"vipcup_amd main: --stress-resize {a.stress_resize!r}: expected a comma-separated list of integer percents in 10..400")
-        scales = sorted({pc for pc in given if pc != 100}, reverse=True)
-        if not scales:
-            raise SystemExit(f"vipcup_amd main: --stress-resize {a.stress_resize!r}: nothing left after dropping 100 (the unperturbed row)")
-        if a.stress_out is None:
-            raise SystemExit("vipcup_amd main: --stress-resize needs --stress-out FILE.csv")
-        if a.shard != "images" or a.tta > 1:
-            # as for --stress-jpeg: the scores of one image would be spread over ranks or over augmented copies
-            raise SystemExit("vipcup_amd main: --stress-resize works with --shard images and --tta 1 only (got --shard "
-                             f"{a.shard} --tta {a.tta}): the resize stress test under member sharding or TTA is not implemented")
-        if a.heatmaps is not None:
-            raise SystemExit("vipcup_amd main: --stress-resize and --heatmaps cannot be combined (both replace the batch scorer): "
-                             "run them one after the other")
-    elif a.stress_resize_filter != "bicubic" and "rescale" not in in_chain:
-        raise SystemExit("vipcup_amd main: --stress-resize-filter needs --stress-resize P[,P...]")
-    sigmas = medians = None                             # sigmas in tenths of a pixel
-    if a.stress_blur is not None:
-        tokens = a.stress_blur.split(",")
-        if not all(re.fullmatch(r"\d{1,2}(\.\d)?", t) for t in tokens):
-            tokens = []
-        sigmas = sorted({int(t.replace(".", "")) if "." in t else 10 * int(t) for t in tokens})
-        if not sigmas or sigmas[0] < 3 or sigmas[-1] > 50:
-            raise SystemExit(f"vipcup_amd main: --stress-blur {a.stress_blur!r}: expected a comma-separated list of sigmas in 0.3..5.0 with at "
-                             "most one fractional digit")
-    elif a.stress_blur_radius is not None and "blur" not in in_chain:
-        raise SystemExit("vipcup_amd main: --stress-blur-radius needs --stress-blur S[,S...]")
-    if a.stress_blur_radius is not None and not 1 <= a.stress_blur_radius <= 15:
-        raise SystemExit(f"vipcup_amd main: --stress-blur-radius {a.stress_blur_radius}: expected an integer in 1..15")
-    if a.stress_median is not None:
-        try:
-            medians = sorted({int(t) for t in a.stress_median.split(",")})
-        except ValueError:
-            medians = []
-        if not medians or any(k not in (3, 5) for k in medians):
-            raise SystemExit(f"vipcup_amd main: --stress-median {a.stress_median!r}: expected a comma-separated list of windows, each 3 or 5")
-    flips = crops = angles = None                       # angles in tenths of a degree
-    if a.stress_flip is not None:
-        flips = sorted(set(a.stress_flip.split(",")))
-        if not set(flips) <= {"h", "v"}:
-            raise SystemExit(f"vipcup_amd main: --stress-flip {a.stress_flip!r}: expected h, v or h,v")
-    if a.stress_crop is not None:
-        try:
-            crops = sorted({int(t) for t in a.stress_crop.split(",")}, reverse=True)
-        except ValueError:
-            crops = []
-        if not crops or crops[-1] < 50 or crops[0] > 99:
-            raise SystemExit(f"vipcup_amd main: --stress-crop {a.stress_crop!r}: expected a comma-separated list of integer percents in 50..99")
-    elif a.stress_crop_origin != "centre" and "crop" not in in_chain:
-        raise SystemExit("vipcup_amd main: --stress-crop-origin needs --stress-crop P[,P...]")
-    if a.stress_rotate is not None:
-        tokens = a.stress_rotate.split(",")
-        if not all(re.fullmatch(r"-?\d{1,2}(\.\d)?", t) for t in tokens):
-            tokens = []
-        angles = sorted({(-1 if t[0] == "-" else 1) * (int(t.lstrip("-").replace(".", "")) if "." in t else 10 * int(t.lstrip("-")))
-                         for t in tokens})
-        if not angles or angles[0] < -450 or angles[-1] > 450 or 0 in angles:
-            raise SystemExit(f"vipcup_amd main: --stress-rotate {a.stress_rotate!r}: expected a comma-separated list of non-zero angles in "
-                             "-45..45 with at most one fractional digit")
-    elif a.stress_rotate_fill != "crop" and "rotate" not in in_chain:
-        raise SystemExit("vipcup_amd main: --stress-rotate-fill needs --stress-rotate D[,D...]")
-    hues = sats = cons = bris = gammas = None           # gammas in hundredths
-    if a.stress_hue is not None:
-        hues = _int_list("--stress-hue", a.stress_hue, -180, 180, 0, "non-zero integer degrees in -180..180")
-    if a.stress_saturation is not None:
-        sats = _int_list("--stress-saturation", a.stress_saturation, 0, 200, 100, "integer percents in 0..200 other than 100")
-    if a.stress_contrast is not None:
-        cons = _int_list("--stress-contrast", a.stress_contrast, 0, 200, 100, "integer percents in 0..200 other than 100")
-    if a.stress_brightness is not None:
-        bris = _int_list("--stress-brightness", a.stress_brightness, -50, 50, 0, "non-zero integer percents in -50..50")
-    if a.stress_gamma is not None:
-        tokens = a.stress_gamma.split(",")
-        if not all(re.fullmatch(r"\d(\.\d{1,2})?", t) for t in tokens):
-            tokens = []
-        gammas = sorted({int(t[0]) * 100 + int((t[2:] + "0")[:2] if "." in t else 0) for t in tokens})
-        if not gammas or gammas[0] < 50 or gammas[-1] > 200 or 100 in gammas:
-            raise SystemExit(f"vipcup_amd main: --stress-gamma {a.stress_gamma!r}: expected a comma-separated list of decimals in 0.50..2.00 "
-                             "with at most two fractional digits, other than 1")
-    noise = None
-    if any(v is not None for _, v in noise_flags):
-        noise = {"noises": [], "mono_noises": [], "speckles": [], "impulses": [], "noise_seed": a.stress_noise_seed}      # sigmas and percents
-        if a.stress_noise is not None:
-            noise["noises"] = [t / 10 for t in _tenths_list("--stress-noise", a.stress_noise, 5, 500, "sigmas in 0.5..50.0 with at most "
-                                                            "one fractional digit")]
-        if a.stress_noise_mono is not None:
-            noise["mono_noises"] = [t / 10 for t in _tenths_list("--stress-noise-mono", a.stress_noise_mono, 5, 500, "sigmas in 0.5..50.0 "
-                                                                 "with at most one fractional digit")]
-        if a.stress_speckle is not None:
-            tokens = a.stress_speckle.split(",")
-            given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,2}", t) for t in tokens) else []
-            if not given or given[0] < 1 or given[-1] > 50 or len(set(given)) != len(given):
-                raise SystemExit(f"vipcup_amd main: --stress-speckle {a.stress_speckle!r}: expected a comma-separated list of integer "
-                                 "percents in 1..50, each listed once")
-            noise["speckles"] = given
-        if a.stress_impulse is not None:
-            noise["impulses"] = [t / 10 for t in _tenths_list("--stress-impulse", a.stress_impulse, 1, 500, "percents in 0.1..50.0 with at "
-                                                              "most one fractional digit")]
-    elif a.stress_noise_seed != 0 and not in_chain & set(("gaussian", "mono", "speckle", "impulse")):
-        raise SystemExit("vipcup_amd main: --stress-noise-seed needs --stress-noise, --stress-noise-mono, --stress-speckle or --stress-impulse")
-    if not 0 <= a.stress_noise_seed <= 0xFFFFFFFF:
-        raise SystemExit(f"vipcup_amd main: --stress-noise-seed {a.stress_noise_seed}: expected an integer in 0..4294967295")
-    sharpen = None                                      # the sharpening keywords of stress_batch: with --stress-sharpen or a shp step
-    if a.stress_sharpen is not None or "sharpen" in in_chain:
-        sharpen = {"sharpens": [], "sharpen_sigma": 1.0, "sharpen_radius": a.stress_sharpen_radius,
-                   "sharpen_threshold": 0 if a.stress_sharpen_threshold is None else a.stress_sharpen_threshold}
-        if a.stress_sharpen is not None:
-            tokens = a.stress_sharpen.split(",")
-            given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,3}", t) for t in tokens) else []
-            if not given or given[0] < 1 or given[-1] > 500 or len(set(given)) != len(given):
-                raise SystemExit(f"vipcup_amd main: --stress-sharpen {a.stress_sharpen!r}: expected a comma-separated list of integer "
-                                 "percents in 1..500, each listed once")
-            sharpen["sharpens"] = given
-        if a.stress_sharpen_sigma is not None:
-            t = a.stress_sharpen_sigma
-            tenths = (int(t.replace(".", "")) if "." in t else 10 * int(t)) if re.fullmatch(r"\d{1,2}(\.\d)?", t) else 0
-            if not 3 <= tenths <= 50:
-                raise SystemExit(f"vipcup_amd main: --stress-sharpen-sigma {t!r}: expected a sigma in 0.3..5.0 with at most one fractional digit")
-            sharpen["sharpen_sigma"] = tenths / 10
-        if a.stress_sharpen_radius is not None and not 1 <= a.stress_sharpen_radius <= 15:
-            raise SystemExit(f"vipcup_amd main: --stress-sharpen-radius {a.stress_sharpen_radius}: expected an integer in 1..15")
-        if not 0 <= sharpen["sharpen_threshold"] <= 255:
-            raise SystemExit(f"vipcup_amd main: --stress-sharpen-threshold {a.stress_sharpen_threshold}: expected an integer in 0..255")
-    elif a.stress_sharpen_sigma is not None or a.stress_sharpen_radius is not None or a.stress_sharpen_threshold is not None:
-        raise SystemExit("vipcup_amd main: --stress-sharpen-sigma / --stress-sharpen-radius / --stress-sharpen-threshold need --stress-sharpen "
-                         "P[,P...] or a --stress-chain with a shp step")
-    tone = None                                         # the tone keywords of stress_batch: with a tone flag
-    if any(v is not None for _, v in tone_flags):
-        tone = {"autocontrasts": [], "autocontrast_lumas": [], "equalize": bool(a.stress_equalize), "clahes": [],
-                "clahe_grid": 8 if a.stress_clahe_grid is None else a.stress_clahe_grid}
-        for flag, text, key in (("--stress-autocontrast", a.stress_autocontrast, "autocontrasts"),
-                                ("--stress-autocontrast-luma", a.stress_autocontrast_luma, "autocontrast_lumas")):
-            if text is not None:
-                tokens = text.split(",")
-                given = sorted(int(t) for t in tokens) if all(re.fullmatch(r"\d{1,2}", t) for t in tokens) else []
-                if not given or given[-1] > 49 or len(set(given)) != len(given):
-                    raise SystemExit(f"vipcup_amd main: {flag} {text!r}: expected a comma-separated list of integer cutoff percents in "
-                                     "0..49, each listed once")
-                tone[key] = given
-        if a.stress_clahe is not None:
-            tone["clahes"] = [t / 10 for t in _tenths_list("--stress-clahe", a.stress_clahe, 10, 99, "clip limits in 1.0..9.9 with at most "
-                                                           "one fractional digit")]
-    if a.stress_clahe_grid is not None:
-        if a.stress_clahe is None and "clahe" not in in_chain:
-            raise SystemExit("vipcup_amd main: --stress-clahe-grid needs --stress-clahe L[,L...] or a --stress-chain with a clahe step")
-        if not 1 <= a.stress_clahe_grid <= 16:
-            raise SystemExit(f"vipcup_amd main: --stress-clahe-grid {a.stress_clahe_grid}: expected an integer in 1..16")
-    for flag, given, what in (("--stress-blur", sigmas, "smoothing"), ("--stress-median", medians, "smoothing"),
-                              ("--stress-flip", flips, "geometric"), ("--stress-crop", crops, "geometric"),
-                              ("--stress-rotate", angles, "geometric")) + tuple((flag, v, "colour") for flag, v in colour_flags) \
-            + tuple((flag, v, "noise") for flag, v in noise_flags) + (("--stress-sharpen", a.stress_sharpen, "sharpening"),) \
-            + tuple((flag, v, "tone") for flag, v in tone_flags) + (("--stress-chain", chains, "chained"),):
-        if given is None:
-            continue
-        if a.stress_out is None:
-            raise SystemExit(f"vipcup_amd main: {flag} needs --stress-out FILE.csv")
-        if a.shard != "images" or a.tta > 1:
-            # as for --stress-jpeg: the scores of one image would be spread over ranks or over augmented copies
-            raise SystemExit(f"vipcup_amd main: {flag} works with --shard images and --tta 1 only (got --shard "
-                             f"{a.shard} --tta {a.tta}): the {what} stress tests under member sharding or TTA are not implemented")
-        if a.heatmaps is not None:
-            raise SystemExit(f"vipcup_amd main: {flag} and --heatmaps cannot be combined (both replace the batch scorer): "
-                             "run them one after the other")
-    geometry = None
-    if flips is not None or crops is not None or angles is not None:
-        geometry = {"flips": flips or [], "crops": crops or [], "crop_origin": a.stress_crop_origin,
-                    "rotations": [t / 10 for t in angles or []], "rotate_fill": a.stress_rotate_fill}
-    colour = None
-    if any(v is not None for _, v in colour_flags):
-        colour = {"gray": bool(a.stress_gray), "bgr": bool(a.stress_bgr), "hues": hues or [], "saturations": sats or [],
-                  "contrasts": cons or [], "brightnesses": bris or [], "gammas": [hh / 100 for hh in gammas or []]}
-    chained = None                                      # --stress-chain: the texts, and the options of steps whose family flag is absent
+    # the run's keywords of stress_batch / stress_labels: the list or switch of every flag given, every option, the chains
+    stress = {"qualities": [], "subsampling": {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling]}
+    waiting = []                                        # (flag, family) whose shared refusals follow once every list is read
+
+    def read(kind):
+        row = grammar.STEPS[kind]
+        if kind in flagged:
+            stress[row.keyword or "qualities"] = _stress_list(kind, getattr(a, _dest(row.flag))) if kind in _LISTS else True
+            if row.family in ("recompression", "resize"):
+                _refuse_context(a, row.flag, row.family)
+            else:
+                waiting.append((row.flag, row.family))
+        for option in _OPTIONS:
+            if option.after == kind:
+                dest = _dest(option.flag)
+                stress[option.keyword] = _stress_option(option, getattr(a, dest), ap.get_default(dest), flagged | in_chain)
+
+    for kind in grammar.STEPS:                          # in row order; the qualities last, after the others' shared refusals
+        if kind != "recompress":
+            read(kind)
     if chains is not None:
-        chained = {"chains": chains}
-        if geometry is None and in_chain & {"crop", "rotate"}:
-            chained.update({"crop_origin": a.stress_crop_origin, "rotate_fill": a.stress_rotate_fill})
-        if noise is None and in_chain & {"gaussian", "mono", "speckle", "impulse"}:
-            chained["noise_seed"] = a.stress_noise_seed
-        if tone is None and "clahe" in in_chain:
-            chained["clahe_grid"] = 8 if a.stress_clahe_grid is None else a.stress_clahe_grid
-    smoothed = sigmas is not None or medians is not None or geometry is not None or colour is not None or noise is not None or \
-        sharpen is not None or chains is not None or tone is not None
-    qualities = None
-    if a.stress_jpeg is not None:
-        try:
-            qualities = sorted({int(t) for t in a.stress_jpeg.split(",")}, reverse=True)
-        except ValueError:
-            qualities = []
-        if not qualities or qualities[-1] < 1 or qualities[0] > 100:
-            raise SystemExit(f"vipcup_amd main: --stress-jpeg {a.stress_jpeg!r}: expected a comma-separated list of integer qualities in 1..100")
-        if a.stress_out is None:
-            raise SystemExit("vipcup_amd main: --stress-jpeg needs --stress-out FILE.csv")
-        if a.shard != "images" or a.tta > 1:
-            # the scores of one image would be spread over ranks (members / hybrid) or over augmented copies (TTA): not built
-            raise SystemExit("vipcup_amd main: --stress-jpeg works with --shard images and --tta 1 only (got --shard "
-                             f"{a.shard} --tta {a.tta}): the recompression stress test under member sharding or TTA is not implemented")
-        if a.heatmaps is not None:
-            raise SystemExit("vipcup_amd main: --stress-jpeg and --heatmaps cannot be combined (both replace the batch scorer): "
-                             "run them one after the other")
-    elif (a.stress_out is not None and scales is None and not smoothed) or (a.stress_subsampling != "420" and "recompress" not in in_chain):
+        stress["chains"] = chains
+        waiting.append(("--stress-chain", "chained"))
+    for flag, family in waiting:
+        _refuse_context(a, flag, family)
+    read("recompress")
+    if a.stress_jpeg is None and ((a.stress_out is not None and not stress_run) or
+                                  (a.stress_subsampling != "420" and "recompress" not in in_chain)):
         raise SystemExit("vipcup_amd main: --stress-out / --stress-subsampling need --stress-jpeg Q[,Q...]"
                          + (" (--stress-out alone also goes with --stress-resize P[,P...])" if a.stress_out is not None else ""))
     if a.heatmaps is not None and (a.shard != "images" or a.tta > 1):
@@ -982,11 +874,8 @@ def main(argv=None):
     if a.heatmaps is not None:
         batch_scorer = _heatmap_writer(a, names, members, rank)
     stress_rows = []
-    blurs = None if sigmas is None else [t / 10 for t in sigmas]
-    if qualities is not None or scales is not None or smoothed:
-        batch_scorer = _stress_scorer(qualities or [], {"420": "4:2:0", "444": "4:4:4"}[a.stress_subsampling], stress_rows,
-                                      scales or (), a.stress_resize_filter, blurs or (), medians or (), a.stress_blur_radius, geometry, colour,
-                                      noise, names, sharpen, chained, tone)
+    if stress_run:
+        batch_scorer = _stress_scorer(stress, names, stress_rows)
     tile_rows, tile_scores = [], []
     if a.tiles_out is not None:
         batch_scorer = _tile_scorer(a, tile_rows, tile_scores)
@@ -1004,10 +893,8 @@ def main(argv=None):
                                      tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
-    if qualities is not None or scales is not None or smoothed:     # the one extra collective of a stress run: every rank's [V, M, n_local] rows
-        n_rows = len(ensemble.stress_labels(qualities or [], scales or (), blurs or (), medians or (),
-                                            **_label_keywords(geometry, colour, noise, sharpen, chained, tone)))
-        stressed = ensemble.gather_stress_rows(stress_rows, n_rows, len(members), len(paths), rank, world, dist)
+    if stress_run:                                      # the one extra collective of a stress run: every rank's [V, M, n_local] rows
+        stressed = ensemble.gather_stress_rows(stress_rows, len(_stress_labels(stress)), len(members), len(paths), rank, world, dist)
     tiled = None
     if a.tiles_out is not None:                         # the one extra collective of a tile run: every rank's [3 + 2, M + 1, n_local] rows
         tiled = ensemble.gather_stress_rows(tile_rows, 5, len(members) + 1, len(paths), rank, world, dist)
@@ -1022,8 +909,7 @@ def main(argv=None):
                 cols[spec.name] = row
             pd.DataFrame(cols).to_csv(a.scores_out, index=False)
         if stressed is not None:
-            _write_stress(a, names, members, per_model, stressed, qualities or [], mode, scales or (), blurs, medians, geometry, colour, noise,
-                          sharpen, chained, tone)
+            _write_stress(a, names, members, per_model, stressed, stress, mode)
             print(f"> STRESS TABLE SAVED TO {a.stress_out}")
         if tiled is not None:
             per_tile = None

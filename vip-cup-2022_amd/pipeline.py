@@ -1267,50 +1267,64 @@ def clahe(batch: DecodedBatch, limit: float, grid: int = 8) -> DecodedBatch:
     return tone(batch, "clahe", limit, grid)
 
 
+# what apply_step reads from its options: apply_chain's keywords but noise_keys
+STEP_OPTIONS = ("subsampling", "resize_filter", "blur_radius", "crop_origin", "rotate_fill", "sharpen_sigma", "sharpen_radius", "sharpen_threshold",
+                "noise_seed", "clahe_grid")
+
+
+def apply_step(batch: DecodedBatch, kind: str, arg, options, mean: Optional[torch.Tensor] = None, keys=None, seed: Optional[int] = None) -> DecodedBatch:
+    """The batch after ONE perturbation: ``(kind, arg)`` as ``parse_step`` gives it, through the ``pipeline`` function of its family with
+    that family's entry of ``options`` (a mapping with ``apply_chain``'s keywords).  The one place where a step kind meets its function:
+    a row of ``ensemble.stress_batch`` and a step of ``apply_chain`` are this call.  ``mean``: the batch's mean colour for a ``contrast``
+    step (None: measured here); ``keys``: as for ``noise``; ``seed``: a noise step's seed when it is not ``options["noise_seed"]``."""
+    if kind in NOISE_KINDS:
+        return noise(batch, kind, arg, options["noise_seed"] if seed is None else seed, keys)
+    if kind in TONE_MODES:
+        return tone(batch, kind, arg, options["clahe_grid"])
+    if kind == "recompress":
+        return recompress(batch, arg, options["subsampling"])
+    if kind == "rescale":
+        return rescale(batch, arg, options["resize_filter"])
+    if kind == "blur":
+        return blur(batch, arg, options["blur_radius"])
+    if kind == "crop":
+        return crop(batch, arg, options["crop_origin"])
+    if kind == "rotate":
+        return rotate(batch, arg, options["rotate_fill"])
+    if kind == "sharpen":
+        return sharpen(batch, arg, options["sharpen_sigma"], options["sharpen_radius"], options["sharpen_threshold"])
+    if kind == "contrast":
+        return contrast(batch, arg) if mean is None else contrast(batch, arg, mean)
+    if kind in ("gray", "bgr"):
+        return gray(batch) if kind == "gray" else bgr(batch)
+    one_argument = {"median": median, "flip": flip, "hue": hue, "saturation": saturation, "brightness": brightness, "gamma": gamma}
+    if kind not in one_argument:
+        raise ValueError(f"chain step kind {kind!r}: not a step of parse_chain")
+    return one_argument[kind](batch, arg)
+
+
 def apply_chain(batch: DecodedBatch, steps, *, subsampling: str = "4:2:0", resize_filter: str = "bicubic", blur_radius: Optional[int] = None,
                 crop_origin: str = "centre", rotate_fill: str = "crop", sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
                 sharpen_threshold: int = 0, noise_seed: int = 0, noise_keys=None, clahe_grid: int = 8) -> DecodedBatch:
     """The batch after the ``steps`` of a stress chain (``parse_chain(text)``, or the chain's text), applied left to right to the decoded
-    pixels at their own size, each through the ``pipeline`` function of its family with that family's options: ``recompress``
-    (``subsampling``), ``rescale`` (``resize_filter``), ``blur`` (``blur_radius``), ``crop`` (``crop_origin``), ``rotate``
+    pixels at their own size, each through the ``pipeline`` function of its family with that family's options (``apply_step``):
+    ``recompress`` (``subsampling``), ``rescale`` (``resize_filter``), ``blur`` (``blur_radius``), ``crop`` (``crop_origin``), ``rotate``
     (``rotate_fill``), ``sharpen`` (``sharpen_sigma``, ``sharpen_radius``, ``sharpen_threshold``).  A ``contrast`` step takes the mean
     colour of the batch as it reaches that step.  A noise step uses ``noise_keys`` (as for ``noise``: one integer per image, None:
     0..n-1, or ``noise_keys_device``'s tensor) and positions in the image as it reaches that step; the k-th noise step of the chain draws
     from seed ``(noise_seed + k) mod 2^32`` (``chain_noise_seeds``).  A tone step (``autocontrast``, ``autocontrast_luma``, ``equalize``,
     ``clahe`` with ``clahe_grid`` tiles per axis) measures the batch as it reaches that step.  Intermediate batches are dropped as the
     chain proceeds.  Returns a new batch; ``batch`` is not touched."""
+    options = dict(locals())                            # the keywords above, by name
     steps = parse_chain(steps) if isinstance(steps, str) else list(steps)
     seeds = chain_noise_seeds(steps, _int_arg("noise_seed", noise_seed, 0, 0xFFFFFFFF))
-    clahe_grid = _int_arg("clahe_grid", clahe_grid, 1, TONE_MAX_GRID)
-    one_argument = {"median": median, "flip": flip, "hue": hue, "saturation": saturation, "contrast": contrast, "brightness": brightness,
-                    "gamma": gamma}
+    options["clahe_grid"] = _int_arg("clahe_grid", clahe_grid, 1, TONE_MAX_GRID)
     keys_d = None
     cur = batch
     for (kind, arg), seed in zip(steps, seeds):
-        if seed is not None:
-            if keys_d is None:                          # once per chain: no step changes the number of images
-                keys_d = noise_keys if isinstance(noise_keys, torch.Tensor) else noise_keys_device(batch, noise_keys)
-            cur = noise(cur, kind, arg, seed, keys_d)
-        elif kind == "recompress":
-            cur = recompress(cur, arg, subsampling)
-        elif kind == "rescale":
-            cur = rescale(cur, arg, resize_filter)
-        elif kind == "blur":
-            cur = blur(cur, arg, blur_radius)
-        elif kind == "crop":
-            cur = crop(cur, arg, crop_origin)
-        elif kind == "rotate":
-            cur = rotate(cur, arg, rotate_fill)
-        elif kind == "sharpen":
-            cur = sharpen(cur, arg, sharpen_sigma, sharpen_radius, sharpen_threshold)
-        elif kind in ("gray", "bgr"):
-            cur = gray(cur) if kind == "gray" else bgr(cur)
-        elif kind in TONE_MODES:
-            cur = tone(cur, kind, arg, clahe_grid)
-        elif kind in one_argument:
-            cur = one_argument[kind](cur, arg)
-        else:
-            raise ValueError(f"chain step kind {kind!r}: not a step of parse_chain")
+        if seed is not None and keys_d is None:         # once per chain: no step changes the number of images
+            keys_d = noise_keys if isinstance(noise_keys, torch.Tensor) else noise_keys_device(batch, noise_keys)
+        cur = apply_step(cur, kind, arg, options, keys=keys_d, seed=seed)
     return cur
 
 
