@@ -4,9 +4,11 @@ launch_pw_k / gemm8p_eligible applies to 2 K: short_k is K <= 128, pwk_direct en
 at K = 512, launch_pw_k picks KS = 2 ceil(K / 32) of 8.
 
 The dry run (vip_conv2d_kernel_name_h2) confirms the kernel NAME of every row in tests/test_h2_dispatch_cpu.py, before any GPU time is
-spent; the name is coarser than the instantiation, so `dense_variant` / `conv_variant` restate the host-side rules that pick the template
-arguments and the same test holds every row's `variant` against them.  A change of those rules fails that test: re-derive the shapes then,
-never the expected kernel."""
+spent; the name is coarser than the instantiation, so `dense_variant` / `conv_variant` apply the host-side rules that pick the template
+arguments (restated in tests/_gemm_rules.py for both storages) and the same test holds every row's `variant` against them.  A change of
+those rules fails that test: re-derive the shapes then, never the expected kernel."""
+
+from tests import _gemm_rules as _rules
 
 ALL = ("none", "gelu", "res", "res_relu")      # the epilogue families of the pointwise kernels: plain, activation, residual, residual + ReLU
 NONE = ("none",)
@@ -94,44 +96,12 @@ def conv_desc(case, ldw):
                          act_post=0), use_res
 
 
-def _cdiv(a, b):
-    return (a + b - 1) // b
-
-
 def dense_variant(M, K, N, has_res=False):
     """the instantiation and tile grid conv2d_impl's host code reaches for a packed Dense [M, K] x [K, N] (csrc/conv_igemm.hip with H2,
-    default environment), restated in logical K"""
-    k2 = 2 * K                                                    # a.K in halfs
-    if M <= 256 and not has_res:
-        return "rows_gemm"
-    if k2 <= 256 and M >= 65536:                                  # launch_pw_k / launch_pw
-        ks = min(8, 2 * _cdiv(k2, 64))
-        s16 = ks * 4
-        while s16 & 3 != 2:
-            s16 += 1
-        lds = (156 if M >= 1 << 19 else 72) * 1024
-        max_rows = (lds // (s16 * 16 + 4)) & ~63
-        cout64 = _cdiv(N, 64) * 64
-        chunks = _cdiv(cout64, max_rows)
-        return f"pw_gemm<KS={ks}> {chunks} x {_cdiv(cout64 // 64, chunks) * 64}"
-    mt = _cdiv(M, 256)
-    if k2 >= 1024 and k2 % 64 == 0 and N % 256 == 0 and mt * (N // 256) >= 128:
-        return f"gemm8p<{'pipe' if k2 % 128 == 0 else 'basic'}> {mt} x {N // 256}"
-    if k2 < 768:                                                  # launch_pwk_direct
-        ng = 1 if N <= 64 else 2
-        return f"pwk_direct<{ng}> PT={1 if mt * _cdiv(N, 64 * ng) < 256 else 4}"
-    if N <= 64:
-        return f"pwk_gemm<1,1> {mt} x 1"
-    if N % 256 == 0 and k2 >= 1024 and mt * (N // 256) >= 256:
-        return f"pwk_gemm<2,2> {mt} x {N // 256}"
-    return f"pwk_gemm<2,1> {mt} x {_cdiv(N, 128)}"
+    default environment): the rules of tests/_gemm_rules.py at two halfs per logical k"""
+    return _rules.dense_variant(M, K, N, has_res, halfs=2)
 
 
 def conv_variant(case):
     """the same for a k x k case that is not a pointwise launch (k > 1 or stride > 1)"""
-    B, H, W, Cin, Cout, k, s, pad, groups, act, use_res = case
-    Ho, Wo = (H + pad[0] + pad[1] - k) // s + 1, (W + pad[2] + pad[3] - k) // s + 1
-    cin_g, cout_g = Cin // groups, Cout // groups
-    if (cin_g <= 16 or B * Ho * Wo >= 32768) and not (use_res and act):
-        return f"im2col<{1 if cout_g <= 64 else 2}>"
-    return f"conv_igemm<{64 if 2 * k * k * cin_g <= 256 else 128},{64 if cout_g <= 64 else 128}>"
+    return _rules.case_variant(case, halfs=2)

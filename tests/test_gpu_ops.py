@@ -101,6 +101,9 @@ PW_CASES = [
     ((1, 300, 221), 160, 960, "silu", False),
     ((1, 256, 257), 256, 768, "gelu", True),
     ((3, 150, 150), 40, 8, "sigmoid", False),
+    # (an activation AND a residual is conv_igemm_kernel's epilogue: the two such shapes above never streamed.  Their residual-only twins do.)
+    ((1, 257, 257), 64, 256, None, True),
+    ((1, 257, 256), 256, 768, None, True),
 ]
 
 
@@ -131,8 +134,10 @@ def split_gate(g32):
 
 
 # squeeze-excite gate (split: ~22 bits) folded into the pointwise conv's activation load vs scale_add_act then conv
-@pytest.mark.parametrize("B,H,W,Cin,Cout,use_res", [(3, 14, 14, 672, 112, True), (2, 57, 56, 144, 32, False),
-                                                    (2, 7, 7, 1632, 272, True), (4, 9, 9, 200, 72, False)])
+GATED_CASES = [(3, 14, 14, 672, 112, True), (2, 57, 56, 144, 32, False), (2, 7, 7, 1632, 272, True), (4, 9, 9, 200, 72, False)]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,use_res", GATED_CASES)
 def test_conv2d_gated(B, H, W, Cin, Cout, use_res, report):
     ops = _ops()
     g = torch.Generator().manual_seed(Cin + Cout)
@@ -195,8 +200,12 @@ def test_conv2d_act_post_and_channel_slices(report):
     assert out[..., :48].abs().max().item() == 0.0
 
 
-@pytest.mark.parametrize("M,K,N", [(256, 64, 16), (1000, 256, 768), (197 * 3, 192, 576), (5, 2048, 8), (4096, 768, 3072),
-                                   (300, 200, 136), (12544, 1248, 208), (777, 72, 40), (2500, 1536, 384)])
+# (GELU and a residual: the one epilogue the pointwise kernels do not carry, so these run on conv_igemm_kernel)
+DENSE_SHAPES = [(256, 64, 16), (1000, 256, 768), (197 * 3, 192, 576), (5, 2048, 8), (4096, 768, 3072), (300, 200, 136), (12544, 1248, 208),
+                (777, 72, 40), (2500, 1536, 384)]
+
+
+@pytest.mark.parametrize("M,K,N", DENSE_SHAPES)
 def test_dense(M, K, N, report):
     ops = _ops()
     g = torch.Generator().manual_seed(M + K + N)
@@ -211,8 +220,12 @@ def test_dense(M, K, N, report):
 
 
 # at most 256 rows (squeeze-excite / ECA layers, M = batch): the barrier-free rows kernel; ragged M, N, K tails
-@pytest.mark.parametrize("act", ["relu", "sigmoid", "silu", None])
-@pytest.mark.parametrize("M,K,N", [(256, 2048, 512), (256, 72, 1632), (200, 1536, 1536), (16, 1248, 56), (1, 64, 8), (256, 40, 104)])
+FEW_ROWS_SHAPES = [(256, 2048, 512), (256, 72, 1632), (200, 1536, 1536), (16, 1248, 56), (1, 64, 8), (256, 40, 104)]
+FEW_ROWS_ACTS = ["relu", "sigmoid", "silu", None]
+
+
+@pytest.mark.parametrize("act", FEW_ROWS_ACTS)
+@pytest.mark.parametrize("M,K,N", FEW_ROWS_SHAPES)
 def test_dense_few_rows(M, K, N, act, report):
     ops = _ops()
     g = torch.Generator().manual_seed(M * 3 + K + N)
@@ -872,3 +885,123 @@ def test_conv2d_two_term_weights(B, H, W, Cin, Cout, act, use_res, report):
     assert coh2 < 0.25 * coh1, (coh1, coh2)
     with pytest.raises(Exception):
         ops.conv2d(dev(x), cw, gate=split_gate(torch.rand(B, Cin)))   # gated layers cannot carry them
+
+
+# ---- every fp16 GEMM / convolution instantiation by name, under default dispatch (tests/_f16_gemm_cases.py) ----
+# (named test_f16_*: test_conv2d_im2col_pointwise_kernel_all_cases re-runs every "test_conv2d*" under VIP_PWK_CONV=1, which is not default dispatch)
+from tests import _f16_gemm_cases as T  # noqa: E402
+
+_dense_ref = {}
+
+
+def dense_operands(M, K, N):
+    """seeded fp16-rounded operands of a table row and the oracle's x @ w + b, computed once per shape and shared by the row's epilogue
+    cases (one shape is kept: the cases of a row are consecutive); nothing here is written to afterwards"""
+    if (M, K, N) not in _dense_ref:
+        _dense_ref.clear()
+        g = torch.Generator().manual_seed(M + K + N)
+        x = h(torch.randn(M, K, generator=g))
+        w = h(torch.randn(K, N, generator=g) / math.sqrt(K))
+        b = torch.randn(N, generator=g) * 0.1
+        res = h(torch.randn(M, N, generator=g))          # the scale of the product: a dropped residual is hundreds of tolerances
+        _dense_ref[(M, K, N)] = (x, w, b, res, R.dense(x, w, b))
+    return _dense_ref[(M, K, N)]
+
+
+def check_rows(report, name, got, ref):
+    """the file's check(), after a line that names the row and channel of the worst element, so that a failure points at its tile"""
+    d = (got.float().cpu().reshape(-1, got.shape[-1]) - ref.reshape(-1, ref.shape[-1])).abs_()
+    row, ch = divmod(int(d.argmax()), d.shape[1])
+    report(f"[ops] {name}: worst element at row {row} of {d.shape[0]} (256-row tile {row // 256}), channel {ch}")
+    check(report, name, got, ref)
+
+
+@pytest.mark.parametrize("M,K,N,epi,kernel,variant,what", T.DENSE_CASES, ids=T.DENSE_IDS)
+def test_f16_dense_kernels(M, K, N, epi, kernel, variant, what, report):
+    """every GEMM kernel of the fp16 storage at the smallest shapes that select each instantiation under default dispatch (the table is
+    held against the dispatcher in tests/test_f16_dispatch_cpu.py): the dispatcher really picks it, the WHOLE output against the fp32
+    oracle at check()'s 2e-3 of the output scale, and a second launch bit for bit"""
+    ops = _ops()
+    x, w, b, res, y = dense_operands(M, K, N)
+    act, post, has_res = T.EPILOGUE[epi]
+    cw = ops.make_dense_weight(w, b)
+    d, _ = T.dense_desc(M, K, N, epi, cw.ldw)
+    assert ops.conv_kernel_name(d, has_res) == kernel, what
+    ref = R.act(y, act)
+    if has_res:
+        ref = R.act(ref + res, post)
+    xd, rd = dev(x), (dev(res) if has_res else None)
+    got = ops.dense(xd, cw, act=act, act_post=post, residual=rd)
+    torch.cuda.synchronize()
+    assert got.shape == ref.shape
+    check_rows(report, f"dense f16 {kernel} {variant} {M}x{K}x{N} {epi}", got, ref)
+    again = ops.dense(xd, cw, act=act, act_post=post, residual=rd)
+    assert torch.equal(got, again), "two launches on the same operands must agree bit for bit"
+
+
+@pytest.mark.parametrize("B,K,N,use_res,kernel,variant,what", T.GATED_CASES, ids=T.GATED_IDS)
+def test_f16_gated_conv_kernels(B, K, N, use_res, kernel, variant, what, report):
+    """the gated pointwise kernel on 256-pixel tiles (test_conv2d_gated's shapes all run 64-pixel ones): 7 x 7 maps, so the image index
+    of the gate changes five times inside a tile; the deep-K loop; as test_conv2d_gated, against the oracle on the fp16-rounded product
+    and against scale_add_act followed by the ungated convolution"""
+    ops = _ops()
+    H, W = T.GATE_HW
+    case = T.gated_case(B, K, N, use_res)
+    g = torch.Generator().manual_seed(B + K + N)
+    x = h(torch.randn(B, H, W, K, generator=g))
+    gate = torch.rand(B, K, generator=g)                     # fp32: the gate is NOT representable in fp16
+    w = h(torch.randn(1, 1, K, N, generator=g) / math.sqrt(K))
+    bias = torch.randn(N, generator=g) * 0.1
+    res = h(torch.randn(B, H, W, N, generator=g)) if use_res else None
+    gd = split_gate(gate)
+    geff = (gd[:, 0].float() + gd[:, 1].float()).cpu()
+    assert (geff - gate).abs().max().item() < 1e-6
+    xs = h(x * geff[:, None, None, :])
+    ref = R.conv2d(xs, w, bias, 1, (0, 0, 0, 0), 1)
+    if use_res:
+        ref = ref + res
+    cw = ops.make_conv_weight(w, bias)
+    d, _ = T.conv_desc(case, cw.ldw)
+    assert ops.conv_kernel_name(d, use_res, has_gate=True) == kernel, what
+    xd = dev(x)
+    rd = None if res is None else dev(res)
+    got = ops.conv2d(xd, cw, residual=rd, gate=gd)
+    xg = ops.scale_add_act(xd, gd, None, None)
+    two = ops.conv2d(xg, cw, residual=rd)
+    torch.cuda.synchronize()
+    assert torch.equal(xg.cpu().float(), xs), "scale_add_act with a split gate must be the correctly rounded product"
+    check_rows(report, f"conv2d gated f16 {kernel} {variant} {B}x{H}x{W}x{K}->{N}{' res' if use_res else ''}", got, ref)
+    # (fma(x, hi, x * lo) in fp16 against x * (hi + lo) rounded from fp32: see test_conv2d_gated)
+    dd = (got.float() - two.float()).abs().max().item()
+    report(f"[ops] conv2d gated f16 {variant} vs scale-then-conv: max diff {dd:.3e}")
+    assert dd <= 2e-3 * ref.abs().max().item()
+    g16 = torch.stack([gd[:, 0], torch.zeros_like(gd[:, 0])], 1).contiguous()
+    assert torch.equal(ops.conv2d(xd, cw, residual=rd, gate=g16), ops.conv2d(ops.scale_add_act(xd, g16, None, None), cw, residual=rd))
+    assert torch.equal(got, ops.conv2d(xd, cw, residual=rd, gate=gd)), "two launches on the same operands must agree bit for bit"
+
+
+@pytest.mark.parametrize("case,kernel,variant,what", T.CONV_F16_CASES, ids=T.CONV_F16_IDS)
+def test_f16_conv_kernels(case, kernel, variant, what, report):
+    """k x k convolutions beyond CONV_CASES' 1 023 rows: im2col staging selected by the row count (plain, grouped, strided, 2 x 2 / 2),
+    the tile kernel on both sides of that switch (activation + residual stays on it at any size), and its <64,128> instantiation"""
+    ops = _ops()
+    B, H, W, Cin, Cout, k, s, pad, groups, act, use_res = case
+    g = torch.Generator().manual_seed(hash(case[:9]) % (2 ** 31))
+    x = h(torch.randn(B, H, W, Cin, generator=g))
+    w = h(torch.randn(k, k, Cin // groups, Cout, generator=g) / math.sqrt(k * k * Cin / groups))
+    bias = torch.randn(Cout, generator=g) * 0.1
+    ref = R.act(R.conv2d(x, w, bias, s, pad, groups), act)
+    res = None
+    if use_res:
+        res = h(torch.randn(*ref.shape, generator=g))
+        ref = ref + res
+    cw = ops.make_conv_weight(w, bias, groups=groups)
+    d, _ = T.conv_desc(case, cw.ldw)
+    assert ops.conv_kernel_name(d, use_res) == kernel, what
+    xd, rd = dev(x), (None if res is None else dev(res))
+    got = ops.conv2d(xd, cw, stride=s, pad=pad, act=act, residual=rd)
+    torch.cuda.synchronize()
+    assert got.shape == ref.shape
+    check_rows(report, f"conv2d f16 {kernel} {variant} {case}", got, ref)
+    again = ops.conv2d(xd, cw, stride=s, pad=pad, act=act, residual=rd)
+    assert torch.equal(got, again), "two launches on the same operands must agree bit for bit"
