@@ -2,9 +2,8 @@
 // dataset/augment.py:131-140 (`Blur`: tfa.image.gaussian_filter2d / median_filter2d) as stress perturbations (pipeline.blur,
 // pipeline.median, --stress-blur, --stress-median).  Each image of a mixed-size batch is filtered on its own, each channel separately.
 //
-// Edges: REFLECT without repeating the edge sample (tfa's default, scipy's mode='mirror').  Sample i of an axis of n samples is
-//   n == 1: 0;   otherwise p = 2 (n - 1), i = i mod p (non-negative), i = p - i if i >= n
-// which reflects repeatedly, so a side shorter than the radius is handled by the same formula.
+// Edges: REFLECT without repeating the edge sample (tfa's default, scipy's mode='mirror'): rgb_tile.hpp's `mirror`, which reflects
+// repeatedly, so a side shorter than the radius is handled by the same formula.
 //
 // Gaussian, all in unsigned 32-bit integers with the 2R + 1 weights of vip_blur_weights_h (non-negative, sum 2^16):
 //   horizontal pass   t   = (sum_j w[j] * px[mirror(x + j)] + 128) >> 8           8.8 fixed point, <= 65280: held as u16
@@ -36,7 +35,7 @@
 // It is the Gaussian kernel with one more epilogue: the vertical pass's wave takes its lane's four centre bytes from the staged u8 tile
 // (row yy + R, byte offset A: already in LDS), forms d, applies the threshold and the gain and stores through store_row.  a and T travel
 // as kernel arguments.  One launch, no extra LDS, no intermediate in global memory, bit-reproducible.
-#include "common.hpp"
+#include "rgb_tile.hpp"
 
 namespace {
 
@@ -46,13 +45,8 @@ constexpr int STAGE_ROWS = TILE_ROWS + 2 * MAX_RADIUS;
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int mirror(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i >= n ? p - i : i;
-}
+using rgb_tile::mirror;
+using rgb_tile::Grid, rgb_tile::check_slots, rgb_tile::COUNT_SOURCE;
 
 // halo in bytes to the left of the tile: 3 R rounded up to a dword
 __device__ __host__ constexpr int halo_bytes(int R) { return (3 * R + 3) & ~3; }
@@ -123,15 +117,8 @@ __device__ __forceinline__ uint32_t bytes_at(const uint32_t* row_lane, int o) {
 
 // 256 contiguous bytes per wave: whole dwords where the row and the destination's alignment allow
 __device__ __forceinline__ void store_row(const TileAt& t, int y, int dstMaxW, int lane, uint32_t pack) {
-    const int b = t.b0 + lane * 4, row_bytes = t.w * 3;
-    uint8_t* out = t.dimg + (long)y * dstMaxW * 3 + b;
-    if (b + 4 <= row_bytes && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
-        *reinterpret_cast<uint32_t*>(out) = pack;
-    } else {                                                          // the row's tail, or a slot row at an odd pitch
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (b + q < row_bytes) out[q] = (uint8_t)(pack >> (8 * q));
-    }
+    const int b = t.b0 + lane * 4;
+    rgb_tile::store_pack(t.dimg + (long)y * dstMaxW * 3 + b, b, t.w * 3, pack);
 }
 
 // one byte of the unsharp mask: X the source sample, B its blurred value
@@ -272,67 +259,47 @@ __global__ __launch_bounds__(WAVES * 64) void median_rgb_u8_kernel(const uint8_t
     }
 }
 
-// shared argument checks of the two entry points; the grid is (tiles of the largest image) x n
-int filter_grid(const char* what, const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, const uint8_t* dst_u8, int dstMaxH,
-                int dstMaxW, int n, int* tiles_x, int* tiles_y, unsigned* grid) {
-    VIP_REQUIRE(src_u8 && sizes_hw && dst_u8, VIP_ERR_BAD_ARG, "%s: null pointer", what);
-    VIP_REQUIRE(n > 0 && maxH > 0 && maxW > 0 && dstMaxH > 0 && dstMaxW > 0, VIP_ERR_BAD_ARG, "%s: bad size", what);
-    VIP_REQUIRE((reinterpret_cast<uintptr_t>(sizes_hw) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: sizes must be 4-byte aligned", what);
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_u8), s1 = s0 + (size_t)n * maxH * maxW * 3;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_u8), d1 = d0 + (size_t)n * dstMaxH * dstMaxW * 3;
-    VIP_REQUIRE(s1 <= d0 || d1 <= s0, VIP_ERR_BAD_ARG, "%s: source and destination overlap (the filter cannot run in place)", what);
-    *tiles_x = (maxW * 3 + TILE_BYTES - 1) / TILE_BYTES;
-    *tiles_y = (maxH + TILE_ROWS - 1) / TILE_ROWS;
-    const long total = (long)*tiles_x * *tiles_y * n;
-    VIP_REQUIRE(total <= 0x7FFFFFFFL, VIP_ERR_UNSUPPORTED, "%s: %ld tiles exceed one launch's grid", what, total);
-    *grid = (unsigned)total;
-    return VIP_OK;
-}
-
 }  // namespace
 
 extern "C" int vip_blur_gauss_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH,
                                      int dstMaxW, const int32_t* weights_d, int radius, int n, void* stream) {
-    int tiles_x, tiles_y;
-    unsigned grid;
-    const int st = filter_grid("vip_blur_gauss_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, &tiles_x, &tiles_y, &grid);
-    if (st != VIP_OK) return st;
+    Grid g;                                                         // (tiles of the source slot) x n
+    if (int st = check_slots("vip_blur_gauss_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, COUNT_SOURCE, TILE_ROWS, TILE_BYTES, &g))
+        return st;
     VIP_REQUIRE(weights_d, VIP_ERR_BAD_ARG, "vip_blur_gauss_rgb_u8: null pointer");
     VIP_REQUIRE(radius >= 1 && radius <= MAX_RADIUS, VIP_ERR_BAD_ARG, "vip_blur_gauss_rgb_u8: radius %d outside 1..%d", radius, MAX_RADIUS);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(weights_d) & 3) == 0, VIP_ERR_ALIGNMENT, "vip_blur_gauss_rgb_u8: weights must be 4-byte aligned");
-    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<false>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW,
-                       dst_u8, dstMaxH, dstMaxW, weights_d, radius, tiles_x, tiles_y, 0, 0);
+    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<false>, dim3((unsigned)g.total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw,
+                       maxH, maxW, dst_u8, dstMaxH, dstMaxW, weights_d, radius, g.tiles_x, g.tiles_y, 0, 0);
     return vip_launch_status("vip_blur_gauss_rgb_u8");
 }
 
 extern "C" int vip_sharpen_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH,
                                   int dstMaxW, const int32_t* weights_d, int radius, int amount_q8, int threshold, int n, void* stream) {
-    int tiles_x, tiles_y;
-    unsigned grid;
-    const int st = filter_grid("vip_sharpen_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, &tiles_x, &tiles_y, &grid);
-    if (st != VIP_OK) return st;
+    Grid g;                                                         // (tiles of the source slot) x n
+    if (int st = check_slots("vip_sharpen_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, COUNT_SOURCE, TILE_ROWS, TILE_BYTES, &g))
+        return st;
     VIP_REQUIRE(weights_d, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: null pointer");
     VIP_REQUIRE(radius >= 1 && radius <= MAX_RADIUS, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: radius %d outside 1..%d", radius, MAX_RADIUS);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(weights_d) & 3) == 0, VIP_ERR_ALIGNMENT, "vip_sharpen_rgb_u8: weights must be 4-byte aligned");
     VIP_REQUIRE(amount_q8 >= 1 && amount_q8 <= 1280, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: amount_q8 %d outside 1..1280", amount_q8);
     VIP_REQUIRE(threshold >= 0 && threshold <= 255, VIP_ERR_BAD_ARG, "vip_sharpen_rgb_u8: threshold %d outside 0..255", threshold);
-    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<true>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW,
-                       dst_u8, dstMaxH, dstMaxW, weights_d, radius, tiles_x, tiles_y, amount_q8, threshold);
+    hipLaunchKernelGGL(blur_gauss_rgb_u8_kernel<true>, dim3((unsigned)g.total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw,
+                       maxH, maxW, dst_u8, dstMaxH, dstMaxW, weights_d, radius, g.tiles_x, g.tiles_y, amount_q8, threshold);
     return vip_launch_status("vip_sharpen_rgb_u8");
 }
 
 extern "C" int vip_median_rgb_u8(const uint8_t* src_u8, const int32_t* sizes_hw, int maxH, int maxW, uint8_t* dst_u8, int dstMaxH,
                                  int dstMaxW, int k, int n, void* stream) {
-    int tiles_x, tiles_y;
-    unsigned grid;
-    const int st = filter_grid("vip_median_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, &tiles_x, &tiles_y, &grid);
-    if (st != VIP_OK) return st;
+    Grid g;                                                         // (tiles of the source slot) x n
+    if (int st = check_slots("vip_median_rgb_u8", src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, COUNT_SOURCE, TILE_ROWS, TILE_BYTES, &g))
+        return st;
     VIP_REQUIRE(k == 3 || k == 5, VIP_ERR_BAD_ARG, "vip_median_rgb_u8: window %d: expected 3 or 5", k);
     if (k == 3)
-        hipLaunchKernelGGL(median_rgb_u8_kernel<3>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW, dst_u8,
-                           dstMaxH, dstMaxW, tiles_x, tiles_y);
+        hipLaunchKernelGGL(median_rgb_u8_kernel<3>, dim3((unsigned)g.total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH,
+                           maxW, dst_u8, dstMaxH, dstMaxW, g.tiles_x, g.tiles_y);
     else
-        hipLaunchKernelGGL(median_rgb_u8_kernel<5>, dim3(grid), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH, maxW, dst_u8,
-                           dstMaxH, dstMaxW, tiles_x, tiles_y);
+        hipLaunchKernelGGL(median_rgb_u8_kernel<5>, dim3((unsigned)g.total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH,
+                           maxW, dst_u8, dstMaxH, dstMaxW, g.tiles_x, g.tiles_y);
     return vip_launch_status("vip_median_rgb_u8");
 }

@@ -22,26 +22,22 @@
 //     3 impulse   w3 < thr (unsigned): all three channels (w2 & 1) ? 255 : 0; else a copy    thr = round(P / 100 * 2^32) in 4294967..2^31
 //   No sum leaves 32 bits.
 //
-// One launch per variant per batch.  The byte movement is colour.hip's - that file's tile scheme is REPEATED here on purpose (a shared
-// header is a refactor of its own, with its own bit-exactness check; colour.hip is untouched): a workgroup (4 waves) owns 128 pixels x 8
-// rows; (1) every tile row is fetched as the ALIGNED dwords of the source that cover it into an LDS image that keeps the row's byte phase,
-// the head and the tail of a row - dwords that also hold a neighbour's bytes - byte by byte, so nothing outside the image's pixels is
-// read; (2) a lane takes one pixel: three byte reads at the source phase, the generator, three byte writes into a second LDS image at the
-// DESTINATION row's phase; (3) that image leaves as the aligned dwords of the destination, head and tail byte by byte, so nothing outside
-// the image's pixels is written.
-// What is new is about 100 integer operations of Philox per pixel and, in modes 0..2, two table reads per normal sample.  The 16 KB table
+// One launch per variant per batch.  The byte movement is rgb_tile.hpp's streaming tile, shared with colour.hip and tone.hip (a
+// workgroup owns 128 pixels x 8 rows; aligned dwords in, an LDS image per side that keeps the row's byte phase, aligned dwords out;
+// nothing outside an image's pixels is read or written); what is here is one pixel's generator.
+// That is about 100 integer operations of Philox per pixel and, in modes 0..2, two table reads per normal sample.  The 16 KB table
 // has two placements, chosen by a template parameter: gathers from global memory through the vector L1 (one tile per workgroup, as
 // colour.hip), or a copy in LDS with the workgroup looping over GROUP consecutive tiles so that the copy - more bytes than a tile - is
 // amortised.  The gathers measured faster (256 images of 200 x 200; README.md, profiles/noise_bench.log) and are what vip_noise_rgb_u8
 // launches; vip_noise_rgb_u8_placed chooses explicitly, for the benchmark and the tests.  Mode 3 reads no table and copies none.  A tile outside
 // its image is skipped, so the launch needs nothing from the host but the slot shapes: no copy, no allocation, no atomics,
 // bit-reproducible.
-#include "common.hpp"
+#include "rgb_tile.hpp"
 
 namespace {
 
-constexpr int TILE_W = 128, TILE_H = 8, WAVES = 4;
-constexpr int ROW_DW = TILE_W * 3 / 4 + 1;                        // 96 dwords of interleaved RGB + one for the row's phase (0..3 bytes)
+using namespace rgb_tile;
+
 constexpr int TABLE_N = 4097;
 constexpr int GROUP = 8;                                          // tiles per workgroup when the table sits in LDS
 constexpr int TAB_NONE = -1, TAB_GLOBAL = 0, TAB_LDS = 1;
@@ -74,106 +70,56 @@ __device__ __forceinline__ int normal_q12(uint32_t w, Table T) {
 }
 
 template <int MODE, int TAB>
-__global__ __launch_bounds__(WAVES * 64) void noise_rgb_u8_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ sizes,
-                                                                  int maxH, int maxW, uint8_t* __restrict__ dst, int dstMaxH, int dstMaxW,
-                                                                  uint32_t amount, uint32_t seed, const uint32_t* __restrict__ keys,
-                                                                  const int32_t* __restrict__ table, int tiles_x, int tiles_y, long total) {
+__global__ __launch_bounds__(THREADS) void noise_rgb_u8_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ sizes,
+                                                               int maxH, int maxW, uint8_t* __restrict__ dst, int dstMaxH, int dstMaxW,
+                                                               uint32_t amount, uint32_t seed, const uint32_t* __restrict__ keys,
+                                                               const int32_t* __restrict__ table, int tiles_x, int tiles_y, long total) {
     __shared__ uint32_t tin[TILE_H * ROW_DW], tout[TILE_H * ROW_DW];
     __shared__ int32_t tab_s[TAB == TAB_LDS ? TABLE_N : 1];
     constexpr int PER_GROUP = TAB == TAB_LDS ? GROUP : 1;
-    uint8_t* tin_u8 = reinterpret_cast<uint8_t*>(tin);
-    uint8_t* tout_u8 = reinterpret_cast<uint8_t*>(tout);
-    const int per_image = tiles_x * tiles_y;
-    const long spitch = (long)maxW * 3, dpitch = (long)dstMaxW * 3;
 
     if constexpr (TAB == TAB_LDS)                                  // read after the first barrier below
-        for (int k = threadIdx.x; k < TABLE_N; k += WAVES * 64) tab_s[k] = table[k];
+        for (int k = threadIdx.x; k < TABLE_N; k += THREADS) tab_s[k] = table[k];
 
     for (int g = 0; g < PER_GROUP; ++g) {                          // every condition up to the barriers is uniform over the workgroup
         const long tile = (long)blockIdx.x * PER_GROUP + g;
         if (tile >= total) break;
-        const int img = (int)(tile / per_image);
-        const int t = (int)(tile - (long)img * per_image);
-        const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int h = sizes[img * 2], w = sizes[img * 2 + 1];
-        if (h < 1 || w < 1 || h > maxH || w > maxW || h > dstMaxH || w > dstMaxW) continue;   // skipped image
-        const int x0 = tx * TILE_W, y0 = ty * TILE_H;
-        if (x0 >= w || y0 >= h) continue;
-        const int rows = min(TILE_H, h - y0), cols = min(TILE_W, w - x0);
-        const int row_bytes = cols * 3;
-        const uint8_t* stile = src + (((long)img * maxH + y0) * maxW + x0) * 3;
-        uint8_t* dtile = dst + (((long)img * dstMaxH + y0) * dstMaxW + x0) * 3;
-
-        // ---- (1) the source rows as aligned dwords; the LDS row keeps the phase of its global row ----
-        for (int k = threadIdx.x; k < rows * ROW_DW; k += WAVES * 64) {
-            const int r = k / ROW_DW, j = k - r * ROW_DW;
-            const uint8_t* row = stile + r * spitch;
-            const int ph = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-            const int b = j * 4 - ph;                              // the row byte at this dword's first byte
-            if (b >= row_bytes) continue;
-            if (b >= 0 && b + 4 <= row_bytes) {
-                tin[k] = *reinterpret_cast<const uint32_t*>(row + b);
-            } else {                                               // the row's head or tail: only its own bytes
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (b + q >= 0 && b + q < row_bytes) tin_u8[k * 4 + q] = row[b + q];
-            }
-        }
-        const uint32_t key = keys[img];                            // wave-uniform
+        Tile t;
+        if (!locate(tile, src, sizes, maxH, maxW, dst, dstMaxH, dstMaxW, tiles_x, tiles_y, t)) continue;
+        load_rows(t, tin);
+        const uint32_t key = keys[t.img];                          // wave-uniform
         __syncthreads();
-        // ---- (2) one pixel per lane: from the source phase to the destination phase ----
-        const int px = threadIdx.x & (TILE_W - 1);
-        if (px < cols) {
-            for (int r = threadIdx.x / TILE_W; r < rows; r += WAVES * 64 / TILE_W) {
-                const int sph = (int)(reinterpret_cast<uintptr_t>(stile + r * spitch) & 3);
-                const int dph = (int)(reinterpret_cast<uintptr_t>(dtile + r * dpitch) & 3);
-                const uint8_t* p = tin_u8 + r * (ROW_DW * 4) + sph + px * 3;
-                uint8_t* o = tout_u8 + r * (ROW_DW * 4) + dph + px * 3;
-                uint32_t wd[4];
-                philox4x32_10((uint32_t)(x0 + px), (uint32_t)(y0 + r), seed, key, wd);
-                if constexpr (MODE == MODE_IMPULSE) {
-                    const bool hit = wd[3] < amount;
-                    const uint8_t v = (wd[2] & 1u) ? 255 : 0;
+        for_each_pixel(t, tin, tout, [&](int r, int px, const uint8_t* p, uint8_t* o) {
+            uint32_t wd[4];
+            philox4x32_10((uint32_t)(t.x0 + px), (uint32_t)(t.y0 + r), seed, key, wd);
+            if constexpr (MODE == MODE_IMPULSE) {
+                const bool hit = wd[3] < amount;
+                const uint8_t v = (wd[2] & 1u) ? 255 : 0;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) o[c] = hit ? v : p[c];
+                for (int c = 0; c < 3; ++c) o[c] = hit ? v : p[c];
+            } else {
+                int z[3];
+                if constexpr (TAB == TAB_LDS) {
+                    z[0] = normal_q12(wd[0], tab_s);
+                    if constexpr (MODE != MODE_MONO) z[1] = normal_q12(wd[1], tab_s), z[2] = normal_q12(wd[2], tab_s);
                 } else {
-                    int z[3];
-                    if constexpr (TAB == TAB_LDS) {
-                        z[0] = normal_q12(wd[0], tab_s);
-                        if constexpr (MODE != MODE_MONO) z[1] = normal_q12(wd[1], tab_s), z[2] = normal_q12(wd[2], tab_s);
-                    } else {
-                        z[0] = normal_q12(wd[0], table);
-                        if constexpr (MODE != MODE_MONO) z[1] = normal_q12(wd[1], table), z[2] = normal_q12(wd[2], table);
-                    }
-                    if constexpr (MODE == MODE_MONO) z[1] = z[2] = z[0];
+                    z[0] = normal_q12(wd[0], table);
+                    if constexpr (MODE != MODE_MONO) z[1] = normal_q12(wd[1], table), z[2] = normal_q12(wd[2], table);
+                }
+                if constexpr (MODE == MODE_MONO) z[1] = z[2] = z[0];
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int X = p[c];
-                        const int az = (int)amount * z[c];
-                        const int d = ((MODE == MODE_SPECKLE ? X * az : az) + (1 << 19)) >> 20;
-                        o[c] = (uint8_t)min(max(X + d, 0), 255);
-                    }
+                for (int c = 0; c < 3; ++c) {
+                    const int X = p[c];
+                    const int az = (int)amount * z[c];
+                    const int d = ((MODE == MODE_SPECKLE ? X * az : az) + (1 << 19)) >> 20;
+                    o[c] = (uint8_t)min(max(X + d, 0), 255);
                 }
             }
-        }
+        });
         __syncthreads();
-        // ---- (3) the destination rows as aligned dwords ----
-        for (int k = threadIdx.x; k < rows * ROW_DW; k += WAVES * 64) {
-            const int r = k / ROW_DW, j = k - r * ROW_DW;
-            uint8_t* row = dtile + r * dpitch;
-            const int ph = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-            const int b = j * 4 - ph;
-            if (b >= row_bytes) continue;
-            if (b >= 0 && b + 4 <= row_bytes) {
-                *reinterpret_cast<uint32_t*>(row + b) = tout[k];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (b + q >= 0 && b + q < row_bytes) row[b + q] = tout_u8[k * 4 + q];
-            }
-        }
-        // the next tile's (1) writes tin, which every thread has finished reading at the barrier above; its (2) writes tout after the
-        // barrier that follows its (1), which no thread passes before it has left this (3)
+        store_rows(t, tout);
+        // the next tile's load_rows writes tin, which every thread has finished reading at the barrier above; its pixels are written to tout after the
+        // barrier that follows its load_rows, which no thread passes before it has left this store_rows
     }
 }
 
@@ -181,7 +127,7 @@ template <int MODE, int TAB>
 void launch(long total, hipStream_t s, const uint8_t* src, const int32_t* sizes, int maxH, int maxW, uint8_t* dst, int dstMaxH, int dstMaxW,
             uint32_t amount, uint32_t seed, const uint32_t* keys, const int32_t* table, int tiles_x, int tiles_y) {
     const long groups = TAB == TAB_LDS ? (total + GROUP - 1) / GROUP : total;
-    hipLaunchKernelGGL((noise_rgb_u8_kernel<MODE, TAB>), dim3((unsigned)groups), dim3(WAVES * 64), 0, s, src, sizes, maxH, maxW, dst, dstMaxH,
+    hipLaunchKernelGGL((noise_rgb_u8_kernel<MODE, TAB>), dim3((unsigned)groups), dim3(THREADS), 0, s, src, sizes, maxH, maxW, dst, dstMaxH,
                        dstMaxW, amount, seed, keys, table, tiles_x, tiles_y, total);
 }
 
@@ -192,11 +138,9 @@ extern "C" int vip_noise_rgb_u8_placed(const uint8_t* src_u8, const int32_t* siz
                                        int placement, int n, void* stream) {
     const char* what = "vip_noise_rgb_u8";
     const bool tabled = mode != MODE_IMPULSE;
-    VIP_REQUIRE(src_u8 && sizes_hw && dst_u8 && keys_u32 && (table_i32 || !tabled), VIP_ERR_BAD_ARG, "%s: null pointer", what);
-    VIP_REQUIRE(n > 0 && maxH > 0 && maxW > 0 && dstMaxH > 0 && dstMaxW > 0, VIP_ERR_BAD_ARG, "%s: bad size", what);
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_u8), s1 = s0 + (size_t)n * maxH * maxW * 3;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_u8), d1 = d0 + (size_t)n * dstMaxH * dstMaxW * 3;
-    VIP_REQUIRE(s1 <= d0 || d1 <= s0, VIP_ERR_BAD_ARG, "%s: source and destination overlap (the kernel cannot run in place)", what);
+    Grid g;
+    if (int st = check_slots(what, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, COUNT_BOTH, TILE_H, TILE_W * 3, &g)) return st;
+    VIP_REQUIRE(keys_u32 && (table_i32 || !tabled), VIP_ERR_BAD_ARG, "%s: null pointer", what);
     VIP_REQUIRE(mode >= MODE_GAUSSIAN && mode <= MODE_IMPULSE, VIP_ERR_BAD_ARG, "%s: mode %d: no amount is defined for it (modes are 0..3)",
                 what, mode);
     const int64_t lo = mode == MODE_IMPULSE ? 4294967 : mode == MODE_SPECKLE ? 3 : 128;
@@ -205,17 +149,12 @@ extern "C" int vip_noise_rgb_u8_placed(const uint8_t* src_u8, const int32_t* siz
                 mode, (long long)lo, (long long)hi);
     VIP_REQUIRE(placement == TAB_GLOBAL || placement == TAB_LDS, VIP_ERR_BAD_ARG, "%s: placement %d: expected 0 (global) or 1 (LDS)", what,
                 placement);
-    VIP_REQUIRE((reinterpret_cast<uintptr_t>(sizes_hw) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: sizes must be 4-byte aligned", what);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(keys_u32) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: keys must be 4-byte aligned", what);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(table_i32) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: table must be 4-byte aligned", what);
-    // an image that is written fits both slots
-    const int tiles_x = ((maxW < dstMaxW ? maxW : dstMaxW) + TILE_W - 1) / TILE_W, tiles_y = ((maxH < dstMaxH ? maxH : dstMaxH) + TILE_H - 1) / TILE_H;
-    const long total = (long)tiles_x * tiles_y * n;
-    VIP_REQUIRE(total <= 0x7FFFFFFFL, VIP_ERR_UNSUPPORTED, "%s: %ld tiles exceed one launch's grid", what, total);
     hipStream_t s = (hipStream_t)stream;
     const uint32_t a = (uint32_t)amount;
 #define VIP_NOISE_LAUNCH(MODE, TAB) \
-    launch<MODE, TAB>(total, s, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, a, seed, keys_u32, table_i32, tiles_x, tiles_y)
+    launch<MODE, TAB>(g.total, s, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, a, seed, keys_u32, table_i32, g.tiles_x, g.tiles_y)
     if (mode == MODE_IMPULSE) VIP_NOISE_LAUNCH(MODE_IMPULSE, TAB_NONE);
     else if (placement == TAB_LDS) {
         if (mode == MODE_GAUSSIAN) VIP_NOISE_LAUNCH(MODE_GAUSSIAN, TAB_LDS);

@@ -18,7 +18,7 @@
 // output rows whose window fits - the same kernel, the same arithmetic, no second launch and no intermediate in global memory.  Only a
 // single output row whose own window exceeds WINDOW_ROWS cannot be held: the entry point refuses such a batch (VIP_ERR_UNSUPPORTED)
 // instead of falling back; at 10 % Lanczos, the strongest shrink pipeline.rescale accepts, a row's window is at most 85 rows.
-#include "common.hpp"
+#include "rgb_tile.hpp"
 
 namespace {
 
@@ -157,14 +157,7 @@ __global__ __launch_bounds__(WAVES * 64) void resample_rgb_u8_kernel(const uint8
                 pack = win[(y - win0) * (TILE_BYTES / 4) + lane];
             }
             const int b = b0 + lane * 4;
-            uint8_t* out = dimg + (long)y * maxWo * 3 + b;
-            if (b + 4 <= row_bytes && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
-                *reinterpret_cast<uint32_t*>(out) = pack;
-            } else {                                                   // the row's tail, or a slot row at an odd pitch
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (b + q < row_bytes) out[q] = (uint8_t)(pack >> (8 * q));
-            }
+            rgb_tile::store_pack(dimg + (long)y * maxWo * 3 + b, b, row_bytes, pack);
         }
         __syncthreads();
         ya = yb;

@@ -12,18 +12,17 @@
 //                          inclusive scan (shuffles inside a wave, the waves' totals through LDS), then the mode's rule.  The auto-contrast table is Pillow's float64 expression: 255.0 / d
 //                          comes from a table the compiler folds (IEEE round to nearest), the two products and the sum are rounded one
 //                          by one (__dmul_rn / __dadd_rn, contraction off).
-//   vip_tone_apply_rgb_u8  streams the pixels as colour.hip does (aligned dwords in, an LDS image per side that keeps the row's byte
-//                          phase, aligned dwords out; heads and tails byte by byte) and applies the image's table(s) from LDS.  CLAHE
-//                          reads the four neighbouring tile tables at Y and blends them; the tables are either gathered from global
+//   vip_tone_apply_rgb_u8  streams the pixels through rgb_tile.hpp's streaming tile, as colour.hip and noise.hip do, and applies the
+//                          image's table(s) from LDS.  CLAHE reads the four neighbouring tile tables at Y and blends them; the tables are either gathered from global
 //                          memory through the vector L1 or the at most 3 x 10 tables a workgroup's 128 x 8 pixels can touch are copied
 //                          into LDS first (placement 0 / 1; README.md has the measurement).
 // No allocation, no global atomics: bit-reproducible.
-#include "common.hpp"
+#include "rgb_tile.hpp"
 
 namespace {
 
-constexpr int TILE_W = 128, TILE_H = 8, WAVES = 4, THREADS = WAVES * 64;
-constexpr int ROW_DW = TILE_W * 3 / 4 + 1;                        // 96 dwords of interleaved RGB + one for the row's phase (0..3 bytes)
+using namespace rgb_tile;                                         // the streaming tile of the apply kernel, and THREADS
+
 constexpr int MAX_SIDE = 1 << 26;                                  // 16 * side stays below 2^31
 constexpr int MAX_GRID = 16;
 // the tile tables a workgroup's pixels can touch: tiles are at least 16 pixels wide, so their centres lie at least 16 pixels apart; 128
@@ -210,23 +209,11 @@ __global__ __launch_bounds__(THREADS) void tone_apply_kernel(const uint8_t* __re
     __shared__ uint32_t tin[TILE_H * ROW_DW], tout[TILE_H * ROW_DW];
     __shared__ uint32_t lut_s[LUT_DW];
     __shared__ int nx_s[CLAHE ? TILE_W : 1], ny_s[CLAHE ? TILE_H : 1];
-    const int per_image = tiles_x * tiles_y;
-    const int img = (int)blockIdx.x / per_image;
-    const int t = (int)blockIdx.x - img * per_image;
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    const int h = sizes[img * 2], w = sizes[img * 2 + 1];
-    if (h < 1 || w < 1 || h > maxH || w > maxW || h > dstMaxH || w > dstMaxW) return;   // skipped image
-    const int x0 = tx * TILE_W, y0 = ty * TILE_H;
-    if (x0 >= w || y0 >= h) return;
+    Tile t;
+    if (!locate((int)blockIdx.x, src, sizes, maxH, maxW, dst, dstMaxH, dstMaxW, tiles_x, tiles_y, t)) return;
+    const int img = t.img, h = t.h, w = t.w, x0 = t.x0, y0 = t.y0, rows = t.rows, cols = t.cols;
     const int gy = CLAHE ? axis_grid(h, G) : 1, gx = CLAHE ? axis_grid(w, G) : 1;
     if (CLAHE && gy * gx > slots) return;                          // its tables do not exist: skipped like an image that does not fit
-    const int rows = min(TILE_H, h - y0), cols = min(TILE_W, w - x0);
-    const int row_bytes = cols * 3;
-    const uint8_t* stile = src + (((long)img * maxH + y0) * maxW + x0) * 3;
-    uint8_t* dtile = dst + (((long)img * dstMaxH + y0) * dstMaxW + x0) * 3;
-    const long spitch = (long)maxW * 3, dpitch = (long)dstMaxW * 3;
-    uint8_t* tin_u8 = reinterpret_cast<uint8_t*>(tin);
-    uint8_t* tout_u8 = reinterpret_cast<uint8_t*>(tout);
     const uint8_t* lut_u8 = reinterpret_cast<const uint8_t*>(lut_s);
     const uint8_t* tables = lut + (long)img * slots * 256;         // CLAHE: the image's tile tables
 
@@ -238,21 +225,7 @@ __global__ __launch_bounds__(THREADS) void tone_apply_kernel(const uint8_t* __re
         if (threadIdx.x < cols) nx_s[threadIdx.x] = axis_neighbours(x0 + (int)threadIdx.x, w, gx);
         else if (threadIdx.x >= TILE_W && (int)threadIdx.x - TILE_W < rows) ny_s[threadIdx.x - TILE_W] = axis_neighbours(y0 + (int)threadIdx.x - TILE_W, h, gy);
     }
-    // ---- (1) the source rows as aligned dwords; the LDS row keeps the phase of its global row ----
-    for (int k = threadIdx.x; k < rows * ROW_DW; k += THREADS) {
-        const int r = k / ROW_DW, j = k - r * ROW_DW;
-        const uint8_t* row = stile + r * spitch;
-        const int ph = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-        const int b = j * 4 - ph;                                  // the row byte at this dword's first byte
-        if (b >= row_bytes) continue;
-        if (b >= 0 && b + 4 <= row_bytes) {
-            tin[k] = *reinterpret_cast<const uint32_t*>(row + b);
-        } else {                                                   // the row's head or tail: only its own bytes
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (b + q >= 0 && b + q < row_bytes) tin_u8[k * 4 + q] = row[b + q];
-        }
-    }
+    load_rows(t, tin);
     int kx_lo = 0, ky_lo = 0, nkx = 1;
     bool staged = false;
     if (KIND == 3) {
@@ -270,58 +243,36 @@ __global__ __launch_bounds__(THREADS) void tone_apply_kernel(const uint8_t* __re
         }
     }
     __syncthreads();
-    // ---- (2) one pixel per lane: from the source phase to the destination phase ----
-    const int px = threadIdx.x & (TILE_W - 1);
-    if (px < cols) {
-        for (int r = threadIdx.x / TILE_W; r < rows; r += THREADS / TILE_W) {
-            const int sph = (int)(reinterpret_cast<uintptr_t>(stile + r * spitch) & 3);
-            const int dph = (int)(reinterpret_cast<uintptr_t>(dtile + r * dpitch) & 3);
-            const uint8_t* p = tin_u8 + r * (ROW_DW * 4) + sph + px * 3;
-            uint8_t* o = tout_u8 + r * (ROW_DW * 4) + dph + px * 3;
-            const int R = p[0], Gr = p[1], B = p[2];
-            if (KIND == 0) {
-                o[0] = lut_u8[R], o[1] = lut_u8[256 + Gr], o[2] = lut_u8[512 + B];
-            } else if (KIND == 1) {
-                o[0] = lut_u8[R], o[1] = lut_u8[Gr], o[2] = lut_u8[B];
-            } else {
-                const int Y = luma_u8(R, Gr, B);
-                const int ax = nx_s[px], ay = ny_s[r];
-                const int kx0 = ax & 255, kx1 = (ax >> 8) & 255, wx = ax >> 16;
-                const int ky0 = ay & 255, ky1 = (ay >> 8) & 255, wy = ay >> 16;
-                int t00, t01, t10, t11;
-                if (KIND == 3 && staged) {
-                    const uint8_t* r0 = lut_u8 + (ky0 - ky_lo) * nkx * 256 + Y, *r1 = lut_u8 + (ky1 - ky_lo) * nkx * 256 + Y;
-                    t00 = r0[(kx0 - kx_lo) * 256], t01 = r0[(kx1 - kx_lo) * 256];
-                    t10 = r1[(kx0 - kx_lo) * 256], t11 = r1[(kx1 - kx_lo) * 256];
-                } else {
-                    const uint8_t* r0 = tables + (long)ky0 * gx * 256 + Y, *r1 = tables + (long)ky1 * gx * 256 + Y;
-                    t00 = r0[kx0 * 256], t01 = r0[kx1 * 256];
-                    t10 = r1[kx0 * 256], t11 = r1[kx1 * 256];
-                }
-                const int V = ((256 - wy) * ((256 - wx) * t00 + wx * t01) + wy * ((256 - wx) * t10 + wx * t11) + 32768) >> 16;
-                const int d = V - Y;
-                o[0] = (uint8_t)min(max(R + d, 0), 255);
-                o[1] = (uint8_t)min(max(Gr + d, 0), 255);
-                o[2] = (uint8_t)min(max(B + d, 0), 255);
-            }
-        }
-    }
-    __syncthreads();
-    // ---- (3) the destination rows as aligned dwords ----
-    for (int k = threadIdx.x; k < rows * ROW_DW; k += THREADS) {
-        const int r = k / ROW_DW, j = k - r * ROW_DW;
-        uint8_t* row = dtile + r * dpitch;
-        const int ph = (int)(reinterpret_cast<uintptr_t>(row) & 3);
-        const int b = j * 4 - ph;
-        if (b >= row_bytes) continue;
-        if (b >= 0 && b + 4 <= row_bytes) {
-            *reinterpret_cast<uint32_t*>(row + b) = tout[k];
+    for_each_pixel(t, tin, tout, [&](int r, int px, const uint8_t* p, uint8_t* o) {
+        const int R = p[0], Gr = p[1], B = p[2];
+        if (KIND == 0) {
+            o[0] = lut_u8[R], o[1] = lut_u8[256 + Gr], o[2] = lut_u8[512 + B];
+        } else if (KIND == 1) {
+            o[0] = lut_u8[R], o[1] = lut_u8[Gr], o[2] = lut_u8[B];
         } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (b + q >= 0 && b + q < row_bytes) row[b + q] = tout_u8[k * 4 + q];
+            const int Y = luma_u8(R, Gr, B);
+            const int ax = nx_s[px], ay = ny_s[r];
+            const int kx0 = ax & 255, kx1 = (ax >> 8) & 255, wx = ax >> 16;
+            const int ky0 = ay & 255, ky1 = (ay >> 8) & 255, wy = ay >> 16;
+            int t00, t01, t10, t11;
+            if (KIND == 3 && staged) {
+                const uint8_t* r0 = lut_u8 + (ky0 - ky_lo) * nkx * 256 + Y, *r1 = lut_u8 + (ky1 - ky_lo) * nkx * 256 + Y;
+                t00 = r0[(kx0 - kx_lo) * 256], t01 = r0[(kx1 - kx_lo) * 256];
+                t10 = r1[(kx0 - kx_lo) * 256], t11 = r1[(kx1 - kx_lo) * 256];
+            } else {
+                const uint8_t* r0 = tables + (long)ky0 * gx * 256 + Y, *r1 = tables + (long)ky1 * gx * 256 + Y;
+                t00 = r0[kx0 * 256], t01 = r0[kx1 * 256];
+                t10 = r1[kx0 * 256], t11 = r1[kx1 * 256];
+            }
+            const int V = ((256 - wy) * ((256 - wx) * t00 + wx * t01) + wy * ((256 - wx) * t10 + wx * t11) + 32768) >> 16;
+            const int d = V - Y;
+            o[0] = (uint8_t)min(max(R + d, 0), 255);
+            o[1] = (uint8_t)min(max(Gr + d, 0), 255);
+            o[2] = (uint8_t)min(max(B + d, 0), 255);
         }
-    }
+    });
+    __syncthreads();
+    store_rows(t, tout);
 }
 
 int check_mode(const char* what, int mode, int param) {
@@ -377,9 +328,10 @@ extern "C" int vip_tone_apply_rgb_u8_placed(const uint8_t* src_u8, const int32_t
                                             int dstMaxW, const uint8_t* lut_u8, int mode, int grid, int slots, int placement, int n,
                                             void* stream) {
     const char* what = "vip_tone_apply_rgb_u8";
-    VIP_REQUIRE(src_u8 && sizes_hw && dst_u8 && lut_u8, VIP_ERR_BAD_ARG, "%s: null pointer", what);
-    VIP_REQUIRE(n > 0 && maxH > 0 && maxW > 0 && dstMaxH > 0 && dstMaxW > 0 && maxH <= MAX_SIDE && maxW <= MAX_SIDE, VIP_ERR_BAD_ARG,
-                "%s: bad size", what);
+    VIP_REQUIRE(maxH <= MAX_SIDE && maxW <= MAX_SIDE, VIP_ERR_BAD_ARG, "%s: bad size", what);
+    Grid g;
+    if (int st = check_slots(what, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, COUNT_BOTH, TILE_H, TILE_W * 3, &g)) return st;
+    VIP_REQUIRE(lut_u8, VIP_ERR_BAD_ARG, "%s: null pointer", what);
     VIP_REQUIRE(mode >= VIP_TONE_AC && mode <= VIP_TONE_CLAHE, VIP_ERR_BAD_ARG, "%s: mode %d: expected 0 (ac), 1 (acl), 2 (eq) or 3 (clahe)", what,
                 mode);
     VIP_REQUIRE(placement == 0 || placement == 1, VIP_ERR_BAD_ARG, "%s: placement %d: expected 0 (global gathers) or 1 (LDS copy)", what, placement);
@@ -387,19 +339,12 @@ extern "C" int vip_tone_apply_rgb_u8_placed(const uint8_t* src_u8, const int32_t
         VIP_REQUIRE(grid >= 1 && grid <= MAX_GRID, VIP_ERR_BAD_ARG, "%s: grid %d: expected 1..%d", what, grid, MAX_GRID);
         VIP_REQUIRE(slots >= 1 && slots <= MAX_GRID * MAX_GRID, VIP_ERR_BAD_ARG, "%s: slots %d: expected 1..%d", what, slots, MAX_GRID * MAX_GRID);
     }
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_u8), s1 = s0 + (size_t)n * maxH * maxW * 3;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_u8), d1 = d0 + (size_t)n * dstMaxH * dstMaxW * 3;
-    VIP_REQUIRE(s1 <= d0 || d1 <= s0, VIP_ERR_BAD_ARG, "%s: source and destination overlap (the kernel cannot run in place)", what);
-    VIP_REQUIRE((reinterpret_cast<uintptr_t>(sizes_hw) & 3) == 0 && (reinterpret_cast<uintptr_t>(lut_u8) & 3) == 0, VIP_ERR_ALIGNMENT,
-                "%s: sizes and tables must be 4-byte aligned", what);
-    // an image that is written fits both slots
-    const int tiles_x = ((maxW < dstMaxW ? maxW : dstMaxW) + TILE_W - 1) / TILE_W, tiles_y = ((maxH < dstMaxH ? maxH : dstMaxH) + TILE_H - 1) / TILE_H;
-    const long total = (long)tiles_x * tiles_y * n;
-    VIP_REQUIRE(total <= 0x7FFFFFFFL, VIP_ERR_UNSUPPORTED, "%s: %ld tiles exceed one launch's grid", what, total);
-    const dim3 g((unsigned)total), b(THREADS);
+    VIP_REQUIRE((reinterpret_cast<uintptr_t>(lut_u8) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: tables must be 4-byte aligned", what);
+    const dim3 grid_dim((unsigned)g.total), block_dim(THREADS);
     hipStream_t s = (hipStream_t)stream;
 #define VIP_TONE_APPLY(KIND) \
-    hipLaunchKernelGGL(tone_apply_kernel<KIND>, g, b, 0, s, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, lut_u8, grid, slots, tiles_x, tiles_y)
+    hipLaunchKernelGGL(tone_apply_kernel<KIND>, grid_dim, block_dim, 0, s, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, lut_u8, grid, slots, \
+                       g.tiles_x, g.tiles_y)
     if (mode == VIP_TONE_AC || mode == VIP_TONE_EQ) VIP_TONE_APPLY(0);
     else if (mode == VIP_TONE_ACL) VIP_TONE_APPLY(1);
     else if (placement == 0) VIP_TONE_APPLY(2);

@@ -10,8 +10,8 @@
 //   top = p[iy][ix] (1024 - wx) + p[iy][ix + 1] wx,  bot likewise on row iy + 1
 //   out = (top (1024 - wy) + bot wy + 2^19) >> 20                   <= 255 * 2^20 + 2^19: unsigned 32 bits
 // A tap outside the source is 0 (fill 0, black: tfa's `constant`) or the mirrored sample (fill 1: reflect without repeating the edge
-// sample, as blur.hip; every tap of a 1-pixel axis is index 0).  With A = D = +-2^24, B = C = 0 and whole-pixel offsets both weights
-// are 0 and the warp is an exact copy: flips and crops.
+// sample - rgb_tile.hpp's `mirror`, as in blur.hip; every tap of a 1-pixel axis is index 0).  With A = D = +-2^24, B = C = 0 and
+// whole-pixel offsets both weights are 0 and the warp is an exact copy: flips and crops.
 //
 // One launch per batch.  The kernel is a gather bound by memory, so a workgroup (4 waves) owns a compact 2-D output tile, 64 pixels x
 // 16 rows: under a rotation its source footprint is a tilted rectangle of about the same area, which the CU's L1 holds, and the 64
@@ -21,21 +21,14 @@
 // consecutive addresses, where the row's end and the destination's alignment allow.  The 1-D grid is (tiles of the destination slot)
 // x n and a tile outside its image returns at once (as blur.hip), so the launch needs nothing from the host but the slot shapes.
 // No allocation, no atomics: bit-reproducible.
-#include "common.hpp"
+#include "rgb_tile.hpp"
 
 namespace {
 
 constexpr int TILE_W = 64, TILE_H = 16, WAVES = 4;
 constexpr int ROW_DW = TILE_W * 3 / 4;                            // 48 dwords of interleaved RGB per tile row
 
-// reflect without repeating the edge sample, for any 64-bit index
-__device__ __forceinline__ int mirror64(long i, int n) {
-    if (n == 1) return 0;
-    const long p = 2L * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return (int)(i >= n ? p - i : i);
-}
+using rgb_tile::mirror;                                           // reflect without repeating the edge sample, here of a 64-bit index
 
 // the two taps i, i + 1 of an axis of n samples: indices that are safe to read, and whether each counts (black fill: outside = 0)
 __device__ __forceinline__ void taps_of(long i, int n, int fill, int& i0, int& i1, bool& ok0, bool& ok1) {
@@ -44,8 +37,8 @@ __device__ __forceinline__ void taps_of(long i, int n, int fill, int& i0, int& i
         i1 = i0 + 1;
         ok0 = ok1 = true;
     } else if (fill == VIP_WARP_FILL_MIRROR) {
-        i0 = mirror64(i, n);
-        i1 = mirror64(i + 1, n);
+        i0 = mirror(i, n);
+        i1 = mirror(i + 1, n);
         ok0 = ok1 = true;
     } else {
         ok0 = i >= 0 && i < n;
@@ -106,15 +99,7 @@ __global__ __launch_bounds__(WAVES * 64) void warp_affine_rgb_u8_kernel(const ui
     for (int k = threadIdx.x; k < rows * ROW_DW; k += WAVES * 64) {
         const int r = k / ROW_DW, b = (k - r * ROW_DW) * 4;
         if (b >= row_bytes) continue;
-        const uint32_t pack = tile[k];
-        uint8_t* out = dimg + ((long)(y0 + r) * dstMaxW + x0) * 3 + b;
-        if (b + 4 <= row_bytes && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(out) = pack;
-        } else {                                                   // the row's tail, or a slot row at an odd pitch
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (b + q < row_bytes) out[q] = (uint8_t)(pack >> (8 * q));
-        }
+        rgb_tile::store_pack(dimg + ((long)(y0 + r) * dstMaxW + x0) * 3 + b, b, row_bytes, tile[k]);
     }
 }
 
@@ -124,20 +109,16 @@ extern "C" int vip_warp_affine_rgb_u8(const uint8_t* src_u8, const int32_t* size
                                       const int32_t* dst_sizes_hw, int dstMaxH, int dstMaxW, const int64_t* xform_d, int fill, int n,
                                       void* stream) {
     const char* what = "vip_warp_affine_rgb_u8";
-    VIP_REQUIRE(src_u8 && sizes_hw && dst_u8 && dst_sizes_hw && xform_d, VIP_ERR_BAD_ARG, "%s: null pointer", what);
-    VIP_REQUIRE(n > 0 && maxH > 0 && maxW > 0 && dstMaxH > 0 && dstMaxW > 0, VIP_ERR_BAD_ARG, "%s: bad size", what);
+    rgb_tile::Grid g;                                               // the grid is (tiles of the destination slot) x n
+    if (int st = rgb_tile::check_slots(what, src_u8, sizes_hw, maxH, maxW, dst_u8, dstMaxH, dstMaxW, n, rgb_tile::COUNT_DESTINATION, TILE_H,
+                                       TILE_W * 3, &g))
+        return st;
+    VIP_REQUIRE(dst_sizes_hw && xform_d, VIP_ERR_BAD_ARG, "%s: null pointer", what);
     VIP_REQUIRE(fill == VIP_WARP_FILL_BLACK || fill == VIP_WARP_FILL_MIRROR, VIP_ERR_BAD_ARG, "%s: fill %d: expected 0 (black) or 1 (mirror)",
                 what, fill);
-    VIP_REQUIRE((reinterpret_cast<uintptr_t>(sizes_hw) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst_sizes_hw) & 3) == 0, VIP_ERR_ALIGNMENT,
-                "%s: sizes must be 4-byte aligned", what);
+    VIP_REQUIRE((reinterpret_cast<uintptr_t>(dst_sizes_hw) & 3) == 0, VIP_ERR_ALIGNMENT, "%s: sizes must be 4-byte aligned", what);
     VIP_REQUIRE((reinterpret_cast<uintptr_t>(xform_d) & 7) == 0, VIP_ERR_ALIGNMENT, "%s: transforms must be 8-byte aligned", what);
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src_u8), s1 = s0 + (size_t)n * maxH * maxW * 3;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst_u8), d1 = d0 + (size_t)n * dstMaxH * dstMaxW * 3;
-    VIP_REQUIRE(s1 <= d0 || d1 <= s0, VIP_ERR_BAD_ARG, "%s: source and destination overlap (the warp cannot run in place)", what);
-    const int tiles_x = (dstMaxW + TILE_W - 1) / TILE_W, tiles_y = (dstMaxH + TILE_H - 1) / TILE_H;
-    const long total = (long)tiles_x * tiles_y * n;
-    VIP_REQUIRE(total <= 0x7FFFFFFFL, VIP_ERR_UNSUPPORTED, "%s: %ld tiles exceed one launch's grid", what, total);
-    hipLaunchKernelGGL(warp_affine_rgb_u8_kernel, dim3((unsigned)total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH,
-                       maxW, dst_u8, dst_sizes_hw, dstMaxH, dstMaxW, xform_d, fill, tiles_x, tiles_y);
+    hipLaunchKernelGGL(warp_affine_rgb_u8_kernel, dim3((unsigned)g.total), dim3(WAVES * 64), 0, (hipStream_t)stream, src_u8, sizes_hw, maxH,
+                       maxW, dst_u8, dst_sizes_hw, dstMaxH, dstMaxW, xform_d, fill, g.tiles_x, g.tiles_y);
     return vip_launch_status(what);
 }

@@ -587,19 +587,30 @@ def resample_plan(sizes_host: Sequence[Tuple[int, int]], new_sizes: Sequence[Tup
     return tab, tables, tiles, max_window
 
 
+def _slot_pair(batch: DecodedBatch, rgb: torch.Tensor, sizes_host) -> Tuple[torch.Tensor, int, int]:
+    """What every ``_..._into`` launch starts with: ``rgb`` is checked to be a destination [n, H, W, 3] for ``batch`` (contiguous uint8 on the
+    batch's device) whose slots hold images of ``sizes_host``; returns the batch's pixels, contiguous, and ``(H, W)``."""
+    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == batch.rgb.shape[0] and rgb.shape[3] == 3 and \
+        rgb.device == batch.rgb.device
+    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in sizes_host)
+    return (batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()), int(rgb.shape[1]), int(rgb.shape[2])
+
+
+def _blank_like(batch: DecodedBatch) -> torch.Tensor:
+    """the zeroed destination of a perturbation that keeps every image's size: the batch's slots, contiguous"""
+    return torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format)
+
+
 def _resample_into(batch: DecodedBatch, new_sizes: List[Tuple[int, int]], filter: str, rgb: torch.Tensor) -> DecodedBatch:
     """``rescale``'s launch: image i of ``batch`` resampled to ``new_sizes[i]`` = (h, w) into its slot of ``rgb`` [n, maxHo, maxWo, 3]
     (contiguous uint8 on the batch's device; only the pixels of the images are written)."""
     n, maxH, maxW, _ = batch.rgb.shape
     device = batch.rgb.device
-    maxHo, maxWo = int(rgb.shape[1]), int(rgb.shape[2])
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3
-    assert all(1 <= h <= maxHo and 1 <= w <= maxWo for h, w in new_sizes)
+    src, maxHo, maxWo = _slot_pair(batch, rgb, new_sizes)
     tab, tables, tiles, max_window = resample_plan(batch.sizes_host, new_sizes, filter)
     tab_d = torch.from_numpy(tab).to(device)
     tables_d = torch.from_numpy(tables).to(device)
     sizes = torch.tensor(new_sizes, dtype=torch.int32, device=device)
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
     _launch("vip_resample_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), _p(sizes), maxHo, maxWo, _p(tab_d), _p(tables_d), n,
             tiles, max_window)
     return DecodedBatch(rgb, sizes, list(new_sizes))
@@ -643,7 +654,7 @@ def blur(batch: DecodedBatch, sigma: float, radius: Optional[int] = None) -> Dec
     (``vip_blur_gauss_rgb_u8``, one launch).  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched.
     Runs on the current stream; only the weights (at most 31 integers, cached on the device) come from the host."""
     key = _blur_args(sigma, radius)
-    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "gauss", key)
+    return _filter_into(batch, _blank_like(batch), "gauss", key)
 
 
 def median(batch: DecodedBatch, k: int) -> DecodedBatch:
@@ -652,7 +663,7 @@ def median(batch: DecodedBatch, k: int) -> DecodedBatch:
     (``vip_median_rgb_u8``, one launch).  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched."""
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) not in (3, 5):
         raise ValueError(f"k {k!r}: expected 3 or 5")
-    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "median", int(k))
+    return _filter_into(batch, _blank_like(batch), "median", int(k))
 
 
 def sharpen_amount(percent: int) -> int:
@@ -671,7 +682,7 @@ def sharpen(batch: DecodedBatch, percent: int, sigma: float = 1.0, radius: Optio
     image 0; ``batch`` is not touched.  Runs on the current stream; only the weights (cached on the device) come from the host."""
     a = sharpen_amount(percent)
     key = _blur_args(sigma, radius) + (a, _int_arg("threshold", threshold, 0, 255))
-    return _filter_into(batch, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format), "sharpen", key)
+    return _filter_into(batch, _blank_like(batch), "sharpen", key)
 
 
 def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> DecodedBatch:
@@ -681,21 +692,19 @@ def _filter_into(batch: DecodedBatch, rgb: torch.Tensor, kind: str, arg) -> Deco
     as the images; only the pixels of the images are written)."""
     n, maxH, maxW, _ = batch.rgb.shape
     device = batch.rgb.device
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
-    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    src, dstH, dstW = _slot_pair(batch, rgb, batch.sizes_host)
     if kind in ("gauss", "sharpen"):
         dkey = (device.index or 0,) + tuple(arg[:2])
         if dkey not in _BLUR_WEIGHTS_DEV:
             _BLUR_WEIGHTS_DEV[dkey] = torch.from_numpy(blur_weights(arg[0] / 10, arg[1]).copy()).to(device)
         if kind == "gauss":
-            _launch("vip_blur_gauss_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+            _launch("vip_blur_gauss_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW,
                     _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), n)
         else:
-            _launch("vip_sharpen_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+            _launch("vip_sharpen_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW,
                     _p(_BLUR_WEIGHTS_DEV[dkey]), int(arg[1]), int(arg[2]), int(arg[3]), n)
     else:
-        _launch("vip_median_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), int(arg), n)
+        _launch("vip_median_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW, int(arg), n)
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
 
 
@@ -747,12 +756,10 @@ def _warp_into(batch: DecodedBatch, xf: np.ndarray, out_sizes: List[Tuple[int, i
     on the batch's device, slots at least as large as the output sizes; only the pixels of the images are written)."""
     n, maxH, maxW, _ = batch.rgb.shape
     device = batch.rgb.device
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
-    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in out_sizes)
+    src, dstH, dstW = _slot_pair(batch, rgb, out_sizes)
     sizes = torch.tensor(out_sizes, dtype=torch.int32, device=device)
     xf_d = torch.from_numpy(xf).to(device)
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    _launch("vip_warp_affine_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), _p(sizes), int(rgb.shape[1]), int(rgb.shape[2]),
+    _launch("vip_warp_affine_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), _p(sizes), dstH, dstW,
             _p(xf_d), int(fill), n)
     return DecodedBatch(rgb, sizes, list(out_sizes))
 
@@ -869,7 +876,7 @@ def colour(batch: DecodedBatch, M, K=None, O=None, lut=None, mean: Optional[torc
     Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not touched.  Runs on the current stream; the
     coefficients travel as kernel arguments, a table is copied to the device once and cached (the 32 tables used last)."""
     coef, lut = _colour_coef(M, K, O, lut)
-    return _colour_into(batch, coef, lut, mean, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+    return _colour_into(batch, coef, lut, mean, _blank_like(batch))
 
 
 def _colour_into(batch: DecodedBatch, coef: np.ndarray, lut: Optional[np.ndarray], mean: Optional[torch.Tensor],
@@ -879,8 +886,7 @@ def _colour_into(batch: DecodedBatch, coef: np.ndarray, lut: Optional[np.ndarray
     n, maxH, maxW, _ = batch.rgb.shape
     device = batch.rgb.device
     assert coef.dtype == np.int32 and coef.shape == (15,) and coef.flags.c_contiguous
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
-    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
+    src, dstH, dstW = _slot_pair(batch, rgb, batch.sizes_host)
     if coef[9:12].any():
         if mean is None:
             mean = batch.mean_colour()
@@ -896,8 +902,7 @@ def _colour_into(batch: DecodedBatch, coef: np.ndarray, lut: Optional[np.ndarray
         _LUT_DEV[key] = lut_d                           # most recently used last
         while len(_LUT_DEV) > _LUT_DEV_MAX:
             del _LUT_DEV[next(iter(_LUT_DEV))]
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    _launch("vip_colour_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]),
+    _launch("vip_colour_rgb_u8", _p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW,
             coef.ctypes.data_as(C.c_void_p), _p(mean), _p(lut_d), n)
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
 
@@ -1092,7 +1097,7 @@ def noise(batch: DecodedBatch, kind: str, amount, seed: int = 0, keys=None) -> D
     a = noise_amount(kind, amount)
     seed = _int_arg("seed", seed, 0, 0xFFFFFFFF)
     keys_d = keys if isinstance(keys, torch.Tensor) else noise_keys_device(batch, keys)
-    return _noise_into(batch, NOISE_KINDS[kind], a, seed, keys_d, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+    return _noise_into(batch, NOISE_KINDS[kind], a, seed, keys_d, _blank_like(batch))
 
 
 def noise_keys_device(batch: DecodedBatch, keys=None) -> torch.Tensor:
@@ -1108,8 +1113,7 @@ def _noise_into(batch: DecodedBatch, mode: int, a: int, seed: int, keys_d: torch
     ``vip_noise_rgb_u8_placed`` (tools/bench_noise.py)."""
     n, maxH, maxW, _ = batch.rgb.shape
     device = batch.rgb.device
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == device
-    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in batch.sizes_host)
+    src, dstH, dstW = _slot_pair(batch, rgb, batch.sizes_host)
     if keys_d.dtype != torch.int32 or tuple(keys_d.shape) != (n,) or not keys_d.is_contiguous() or keys_d.device != device:
         raise ValueError(f"keys: expected a contiguous int32 [{n}] tensor on {device}, got {keys_d.dtype} {tuple(keys_d.shape)} on "
                          f"{keys_d.device}")
@@ -1119,8 +1123,7 @@ def _noise_into(batch: DecodedBatch, mode: int, a: int, seed: int, keys_d: torch
         if key not in _NOISE_TABLE_DEV:
             _NOISE_TABLE_DEV[key] = torch.from_numpy(noise_table().copy()).to(device)
         table_d = _NOISE_TABLE_DEV[key]
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), mode, a, seed, _p(keys_d), _p(table_d))
+    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW, mode, a, seed, _p(keys_d), _p(table_d))
     if placement is None:
         _launch("vip_noise_rgb_u8", *args, n)
     else:
@@ -1221,7 +1224,7 @@ def tone(batch: DecodedBatch, mode: str, arg=None, grid: int = 8) -> DecodedBatc
     tables, pixels - with no host round trip.  Returns a new batch of the same sizes, pixels outside an image 0; ``batch`` is not
     touched."""
     _, _, grid = _tone_args(mode, arg, grid)              # every argument is checked before the first launch
-    return _tone_into(batch, mode, arg, grid, torch.zeros_like(batch.rgb, memory_format=torch.contiguous_format))
+    return _tone_into(batch, mode, arg, grid, _blank_like(batch))
 
 
 def _tone_into(batch: DecodedBatch, mode: str, arg, grid: int, rgb: torch.Tensor, placement: Optional[int] = None) -> DecodedBatch:
@@ -1230,13 +1233,11 @@ def _tone_into(batch: DecodedBatch, mode: str, arg, grid: int, rgb: torch.Tensor
     ``vip_tone_apply_rgb_u8_placed`` (tools/bench_tone.py)."""
     m = TONE_MODES[mode]
     n, maxH, maxW, _ = batch.rgb.shape
-    assert rgb.is_contiguous() and rgb.dtype == torch.uint8 and rgb.shape[0] == n and rgb.shape[3] == 3 and rgb.device == batch.rgb.device
-    assert all(1 <= h <= rgb.shape[1] and 1 <= w <= rgb.shape[2] for h, w in set(batch.sizes_host))
+    src, dstH, dstW = _slot_pair(batch, rgb, set(batch.sizes_host))
     g = grid if m == 3 else _TONE_GLOBAL_GRID
     hist = tone_histograms(batch, g, 3 if m in (0, 2) else 1)
     lut = tone_tables(hist, mode, arg)
-    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
-    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), int(rgb.shape[1]), int(rgb.shape[2]), _p(lut), m, g, int(hist.shape[1]))
+    args = (_p(src), _p(batch.sizes), maxH, maxW, _p(rgb), dstH, dstW, _p(lut), m, g, int(hist.shape[1]))
     if placement is None:
         _launch("vip_tone_apply_rgb_u8", *args, n)
     else:
