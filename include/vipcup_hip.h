@@ -801,6 +801,7 @@ int vip_unpack_h2(const void* x, float* y, long n, void* stream);
 int vip_conv2d_nhwc_h2(const void* x, const void* w, const float* bias, const void* residual, void* y, const vip_conv_desc* d,
                        float out_scale, int* status, void* stream);
 int vip_conv2d_kernel_name_h2(const vip_conv_desc* d, int has_residual, char* name, size_t cap);
+int vip_conv2d_kernel_variant_h2(const vip_conv_desc* d, int has_residual, char* variant, size_t cap);   /* see vip_conv2d_kernel_variant */
 /* vip_conv2d_gated_nhwc_f16 on the packed storage: gate packed [B][Cin] (vip_se_gate_h2), multiplied into the activation operand in fp32
  * and split again in registers; 1x1 stride-1 ungrouped, (activation) or (residual [+ReLU]) epilogue, cin_off = 0, ldx = Cin. */
 int vip_conv2d_gated_nhwc_h2(const void* x, const void* gate, const void* w, const float* bias, const void* residual, void* y,
@@ -964,6 +965,11 @@ int vip_cam_overlay_u8(const uint8_t* rgb_u8, const uint8_t* map_u8, const uint8
  * the dispatcher itself in a dry run, nothing is launched.  Used to label profiler records (bench.py roofline). */
 int vip_conv2d_kernel_name(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* name_h,
                            size_t cap);
+/* The same dry run, down to the instantiation: template arguments and, where the kernel tiles M x N, the tile grid - "rows_gemm",
+ * "pw_gemm<KS=8> 2 x 128" (channel chunks x channels per chunk), "pw_gemm<KS=4,hilo> 1 x 256", "pwk_direct<2,gated> PT=4",
+ * "pwk_gemm<2,2> 65 x 4", "gemm8p<pipe> 34 x 4", "im2col<2>", "conv_igemm<128,128>", "pwx<4,2>", "pwx_ln<6,2>" (KSC, PT). */
+int vip_conv2d_kernel_variant(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* variant_h,
+                              size_t cap);
 
 /* Scratch memory an entry point needs from its caller (bytes); 0 for every operator that works in place on its
  * operands.  op = one of VIP_OP_*; dims as documented per op. */

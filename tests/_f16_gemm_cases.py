@@ -1,17 +1,16 @@
 """Shapes that select each GEMM and convolution kernel of the fp16 storage (csrc/conv_igemm.hip; the default precision, the one bench.py
 times) under DEFAULT dispatch - no environment switch.  The fp16 twin of tests/_h2_gemm_cases.py: here a.K is the logical K, so short_k
 is K <= 256, pwk_direct ends below K = 768 (gated launches stay on it at any K), the 256 x 256 pwk tiles and gemm8p start at K = 1024,
-launch_pw_k picks KS = ceil(K / 32) of {1, 2, 3, 4, 6, 8}.
+plan_pw picks KS = ceil(K / 32) of {1, 2, 3, 4, 6, 8}.
 
-The dry run (vip_conv2d_kernel_name) confirms the kernel NAME of every row in tests/test_f16_dispatch_cpu.py, before any GPU time is
-spent; the name is coarser than the instantiation, so the same test holds every row's `variant` against the host-side rules restated in
-tests/_gemm_rules.py.  A change of those rules fails that test: re-derive the shapes then, never the expected kernel.  The GPU tests
+The dry run confirms every row in tests/test_f16_dispatch_cpu.py, before any GPU time is spent: vip_conv2d_kernel_name the kernel,
+vip_conv2d_kernel_variant the instantiation and its tile grid (`variant`) - both are plan() of csrc/conv_igemm.hip, the code that the
+launch goes through.  A change of its rules fails that test: re-derive the shapes then, never the expected kernel.  The GPU tests
 (test_f16_dense_kernels, test_f16_gated_conv_kernels, test_f16_conv_kernels in tests/test_gpu_ops.py) run every row against the
 oracle."""
-from tests import _gemm_rules as _rules
-from tests._h2_gemm_cases import ALL, EPILOGUE, NONE  # noqa: F401  (the epilogue families are those of the packed table)
+import re
 
-HALFS = 1
+from tests._h2_gemm_cases import ALL, EPILOGUE, NONE  # noqa: F401  (the epilogue families are those of the packed table)
 
 # (M, K, N, epilogues, expected kernel, variant, what it hits)
 _DENSE_ROWS = [
@@ -135,12 +134,14 @@ def conv_desc(case, ldw):
                          act_post=0), use_res
 
 
-def dense_variant(M, K, N, epi="none", gated=False):
-    """the instantiation and tile grid conv2d_impl's host code reaches for an fp16 Dense [M, K] x [K, N] with that epilogue family"""
-    act, post, res = EPILOGUE[epi]
-    return _rules.dense_variant(M, K, N, res, HALFS, gated, act, post)
+def instantiation(variant):
+    """a variant string without its tile grid: 'pwk_gemm<2,2> 65 x 4' -> 'pwk_gemm<2,2>'; 'pwk_direct<2> PT=4' stays (PT is a template
+    argument)"""
+    return re.sub(r" \d+ x \d+$", "", variant)
 
 
-def conv_variant(case, gated=False):
-    """the same for a CONV_CASES tuple"""
-    return _rules.case_variant(case, HALFS, gated)
+def same_kernel(name, variant):
+    """do the name query and the variant query speak of one kernel?  'gemm8p_kernel' and 'gemm8p<pipe> 34 x 4', 'pwk_gemm_kernel(im2col)'
+    and 'im2col<2>'"""
+    family = re.match(r"\w+", variant).group(0)
+    return name == ("pwk_gemm_kernel(im2col)" if family == "im2col" else family + "_kernel")

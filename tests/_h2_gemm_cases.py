@@ -1,14 +1,11 @@
 """Shapes that select each GEMM kernel of the packed strict storage (csrc/conv_h2.hip = conv_igemm.hip with VIP_GEMM_H2) under DEFAULT
-dispatch - no environment switch.  In that build a.K, a.ldx and a.Cin_g are in halfs, so every K threshold of conv2d_impl / launch_pw /
-launch_pw_k / gemm8p_eligible applies to 2 K: short_k is K <= 128, pwk_direct ends below K = 384, the 256 x 256 pwk tiles and gemm8p start
-at K = 512, launch_pw_k picks KS = 2 ceil(K / 32) of 8.
+dispatch - no environment switch.  In that build a.K, a.ldx and a.Cin_g are in halfs, so every K threshold of plan() / plan_pw() /
+gemm8p_eligible applies to 2 K: short_k is K <= 128, pwk_direct ends below K = 384, the 256 x 256 pwk tiles and gemm8p start
+at K = 512, plan_pw picks KS = 2 ceil(K / 32) of 8.
 
-The dry run (vip_conv2d_kernel_name_h2) confirms the kernel NAME of every row in tests/test_h2_dispatch_cpu.py, before any GPU time is
-spent; the name is coarser than the instantiation, so `dense_variant` / `conv_variant` apply the host-side rules that pick the template
-arguments (restated in tests/_gemm_rules.py for both storages) and the same test holds every row's `variant` against them.  A change of
-those rules fails that test: re-derive the shapes then, never the expected kernel."""
-
-from tests import _gemm_rules as _rules
+The dry run confirms every row in tests/test_h2_dispatch_cpu.py, before any GPU time is spent: vip_conv2d_kernel_name_h2 the kernel,
+vip_conv2d_kernel_variant_h2 the instantiation and its tile grid (`variant`) - both are plan() of csrc/conv_igemm.hip, the code that the
+launch goes through.  A change of its rules fails that test: re-derive the shapes then, never the expected kernel."""
 
 ALL = ("none", "gelu", "res", "res_relu")      # the epilogue families of the pointwise kernels: plain, activation, residual, residual + ReLU
 NONE = ("none",)
@@ -94,14 +91,3 @@ def conv_desc(case, ldw):
     return _abi.ConvDesc(B=B, H=H, W=W, Cin=Cin, Cout=Cout, kh=k, kw=k, sh=s, sw=s, pt=pad[0], pl=pad[2], Ho=Ho, Wo=Wo, groups=groups,
                          ldx=Cin, cin_off=0, ldy=Cout, cout_off=0, ldr=Cout if use_res else 0, res_off=0, ldw=ldw, act_pre=ops._act(act),
                          act_post=0), use_res
-
-
-def dense_variant(M, K, N, has_res=False):
-    """the instantiation and tile grid conv2d_impl's host code reaches for a packed Dense [M, K] x [K, N] (csrc/conv_igemm.hip with H2,
-    default environment): the rules of tests/_gemm_rules.py at two halfs per logical k"""
-    return _rules.dense_variant(M, K, N, has_res, halfs=2)
-
-
-def conv_variant(case):
-    """the same for a k x k case that is not a pointwise launch (k > 1 or stride > 1)"""
-    return _rules.case_variant(case, halfs=2)

@@ -1,7 +1,7 @@
-"""The shape table of tests/_f16_gemm_cases.py against the C dispatcher's dry run (vip_conv2d_kernel_name: nothing is launched, the
-library loads without a device - tests/test_abi.py): every row selects the kernel it is in the table for, under default dispatch, each
-switch of the fp16 build sits where the table says, the existing operator cases of tests/test_gpu_ops.py select what they were written
-for, and every GEMM-like launch of the ensemble step (profiles/r04_fast_shapes_with_floors.log) runs on an instantiation that some
+"""The shape table of tests/_f16_gemm_cases.py against the C dispatcher's dry run (vip_conv2d_kernel_name / vip_conv2d_kernel_variant:
+the plan of the launch without the launch, the library loads without a device - tests/test_abi.py): every row selects the kernel and
+the instantiation it is in the table for, under default dispatch, each switch of the fp16 build sits where the table says, the
+existing operator cases of tests/test_gpu_ops.py select what they were written for, and every GEMM-like launch of the ensemble step (profiles/r04_fast_shapes_with_floors.log) runs on an instantiation that some
 operator test compares with the oracle."""
 import os
 import re
@@ -13,7 +13,6 @@ import vipcup_amd  # noqa: F401
 from vipcup_amd import ops
 
 from tests import _f16_gemm_cases as T
-from tests import _gemm_rules as rules
 from tests import test_gpu_ops as G
 
 # the dispatch switches that are read once per process or per call: the table is for the default of each
@@ -43,13 +42,30 @@ def conv_desc(case):
     return T.conv_desc(case, _ldw(k, k, Cin // groups, Cout // groups, groups))
 
 
+def dense_variant(M, K, N, epi="none"):
+    """the instantiation and tile grid the dispatcher plans for an fp16 Dense [M, K] x [K, N] with that epilogue family"""
+    d, res = dense_desc(M, K, N, epi)
+    return ops.conv_kernel_variant(d, res)
+
+
+def conv_variant(case, gated=False):
+    """the same for a CONV_CASES tuple"""
+    d, res = conv_desc(case)
+    return ops.conv_kernel_variant(d, res, has_gate=gated)
+
+
+def pointwise_epilogue(act, use_res):
+    """an epilogue the pointwise kernels carry: an activation or a residual, not both (that one is conv_igemm_kernel's)"""
+    return not (act and use_res)
+
+
 @pytest.mark.parametrize("M,K,N,epi,kernel,variant,what", T.DENSE_CASES, ids=T.DENSE_IDS)
 def test_dense_row_selects_its_kernel(M, K, N, epi, kernel, variant, what):
     d, res = dense_desc(M, K, N, epi)
     assert d.ldw == K
     assert ops.conv_kernel_name(d, res) == kernel, what
-    assert T.dense_variant(M, K, N, epi) == variant, what
-    assert rules.kernel_of(variant) == kernel
+    assert ops.conv_kernel_variant(d, res) == variant, what
+    assert T.same_kernel(ops.conv_kernel_name(d, res), ops.conv_kernel_variant(d, res))
 
 
 @pytest.mark.parametrize("B,K,N,res,kernel,variant,what", T.GATED_CASES, ids=T.GATED_IDS)
@@ -58,8 +74,8 @@ def test_gated_row_selects_its_kernel(B, K, N, res, kernel, variant, what):
     d, _ = conv_desc(case)
     assert d.Ho * d.Wo == 49 and 256 // 49 >= 5          # a 256-pixel tile spans six images
     assert ops.conv_kernel_name(d, res, has_gate=True) == kernel, what
-    assert T.conv_variant(case, gated=True) == variant, what
-    assert rules.kernel_of(variant) == kernel
+    assert ops.conv_kernel_variant(d, res, has_gate=True) == variant, what
+    assert T.same_kernel(ops.conv_kernel_name(d, res, has_gate=True), ops.conv_kernel_variant(d, res, has_gate=True))
     if K >= 768:                                         # the deep-K loop is the gate's alone: without one the shape leaves this kernel
         assert ops.conv_kernel_name(d, res) != kernel
 
@@ -68,8 +84,8 @@ def test_gated_row_selects_its_kernel(B, K, N, res, kernel, variant, what):
 def test_conv_row_selects_its_kernel(case, kernel, variant, what):
     d, res = conv_desc(case)
     assert ops.conv_kernel_name(d, res) == kernel, what
-    assert T.conv_variant(case) == variant, what
-    assert rules.kernel_of(variant) == kernel
+    assert ops.conv_kernel_variant(d, res) == variant, what
+    assert T.same_kernel(ops.conv_kernel_name(d, res), ops.conv_kernel_variant(d, res))
 
 
 def test_grouped_strided_row_is_selected_by_row_count():
@@ -88,7 +104,7 @@ def test_dense_boundaries(below, above):
     for M, K, N, kernel in (below, above):
         d, _ = dense_desc(M, K, N, "none")
         assert ops.conv_kernel_name(d, False) == kernel, (M, K, N)
-        assert rules.kernel_of(T.dense_variant(M, K, N)) == kernel, (M, K, N)
+        assert T.same_kernel(kernel, ops.conv_kernel_variant(d, False)), (M, K, N)
     assert below[3] != above[3] and sum(a != b for a, b in zip(below[:3], above[:3])) == 1     # one switch, one step
 
 
@@ -110,7 +126,7 @@ def test_conv_igemm_tile_shapes_are_reached_by_existing_cases(case, variant, sou
         assert (case[0], case[3], case[4]) in G.DENSE_SHAPES and case[9:] == ("gelu", True)      # test_dense's epilogue
     d, res = conv_desc(case)
     assert ops.conv_kernel_name(d, res) == "conv_igemm_kernel"
-    assert T.conv_variant(case) == variant
+    assert ops.conv_kernel_variant(d, res) == variant
 
 
 # ---- the intent of the existing operator cases, pinned here because test_conv2d is re-run under VIP_PWK_CONV=1 ----
@@ -128,11 +144,11 @@ def test_pointwise_stream_cases_select_pw_gemm_and_reach_every_k_step():
     for case in G.PW_CASES:
         c = _pw_case(case)
         d, res = conv_desc(c)
-        if rules.pointwise_mode(c[9], None, c[10]):
+        if pointwise_epilogue(c[9], c[10]):
             assert ops.conv_kernel_name(d, res) == "pw_gemm_kernel", case
-            seen.add((rules.instantiation(T.conv_variant(c)), res))
+            seen.add((T.instantiation(ops.conv_kernel_variant(d, res)), res))
         else:
-            assert ops.conv_kernel_name(d, res) == "conv_igemm_kernel" and T.conv_variant(c) == "conv_igemm<64,128>", case
+            assert ops.conv_kernel_name(d, res) == "conv_igemm_kernel" and ops.conv_kernel_variant(d, res) == "conv_igemm<64,128>", case
             other.append(case)
     assert {v for v, _ in seen} == {f"pw_gemm<KS={ks}>" for ks in (1, 2, 3, 4, 6, 8)}
     assert {v for v, res in seen if res} >= {"pw_gemm<KS=2>", "pw_gemm<KS=4>", "pw_gemm<KS=8>"}       # the residual epilogue, PRE and not
@@ -145,7 +161,7 @@ def test_few_rows_cases_select_rows_gemm():
             d = T.dense_desc(M, K, N, "none", _ldw(1, 1, K, N, 1))[0]
             d.act_pre = ops._act(act)
             assert ops.conv_kernel_name(d, False) == "rows_gemm_kernel", (M, K, N, act)
-            assert rules.dense_variant(M, K, N, act=act) == "rows_gemm"
+            assert ops.conv_kernel_variant(d, False) == "rows_gemm"
 
 
 def _gated_existing(c):
@@ -158,7 +174,7 @@ def test_gated_cases_select_pwk_direct():
         case = _gated_existing(c)
         d, res = conv_desc(case)
         assert ops.conv_kernel_name(d, res, has_gate=True) == "pwk_direct_kernel", c
-        assert T.conv_variant(case, gated=True).endswith("gated> PT=1"), c      # all four: fewer than 256 workgroups
+        assert ops.conv_kernel_variant(d, res, has_gate=True).endswith("gated> PT=1"), c      # all four: fewer than 256 workgroups
 
 
 # ---- coverage ----
@@ -166,17 +182,17 @@ def test_gated_cases_select_pwk_direct():
 def covered():
     """the instantiations some operator test compares with the oracle under default dispatch: the rows of the table and the existing case
     lists whose intent the tests above pin"""
-    seen = {rules.instantiation(v) for *_, v, _ in T.DENSE_CASES} | {v for *_, v, _ in T.GATED_CASES} | {v for _, _, v, _ in T.CONV_F16_CASES}
+    seen = {T.instantiation(v) for *_, v, _ in T.DENSE_CASES} | {v for *_, v, _ in T.GATED_CASES} | {v for _, _, v, _ in T.CONV_F16_CASES}
     seen |= {v for _, v, _ in T.IGEMM_ROWS}
-    seen |= {rules.instantiation(T.conv_variant(_pw_case(c))) for c in G.PW_CASES if rules.pointwise_mode(c[3], None, c[4])}
-    seen |= {rules.dense_variant(M, K, N) for M, K, N in G.FEW_ROWS_SHAPES}
-    seen |= {T.conv_variant(_gated_existing(c), gated=True) for c in G.GATED_CASES}
+    seen |= {T.instantiation(conv_variant(_pw_case(c))) for c in G.PW_CASES if pointwise_epilogue(c[3], c[4])}
+    seen |= {dense_variant(M, K, N) for M, K, N in G.FEW_ROWS_SHAPES}
+    seen |= {conv_variant(_gated_existing(c), gated=True) for c in G.GATED_CASES}
     return seen
 
 
 def test_table_covers_every_instantiation_it_names():
     assert covered() >= T.INSTANTIATIONS
-    own = {rules.instantiation(v) for *_, v, _ in T.DENSE_CASES} | {v for *_, v, _ in T.GATED_CASES} | {v for _, _, v, _ in T.CONV_F16_CASES}
+    own = {T.instantiation(v) for *_, v, _ in T.DENSE_CASES} | {v for *_, v, _ in T.GATED_CASES} | {v for _, _, v, _ in T.CONV_F16_CASES}
     # what had no operator-level oracle test before this table
     assert own >= {"pwk_direct<1> PT=4", "pwk_direct<2> PT=4", "pwk_direct<1,gated> PT=4", "pwk_direct<2,gated> PT=4", "pwk_gemm<2,2>",
                    "gemm8p<basic>", "gemm8p<pipe>", "im2col<1>", "im2col<2>", "conv_igemm<128,128>", "conv_igemm<64,128>"}
@@ -206,8 +222,9 @@ def log_launches():
 
 
 def test_every_launch_of_the_ensemble_step_runs_a_tested_instantiation():
-    """The profile lists the launches of one ensemble step at batch 256 with their kernel and shape.  Each must map, by the rules, to the
-    kernel the profile names and to an instantiation `covered()` holds.  Grid sizes are exempt: the tile counts of the ensemble's maps
+    """The profile lists the launches of one ensemble step at batch 256 with their kernel and shape.  Each must map, by the dry run of a
+    descriptor built from the line (a k x k line: M images of k x k pixels with one output pixel each, the line's stride and groups), to
+    the kernel the profile names and to an instantiation `covered()` holds.  Grid sizes are exempt: the tile counts of the ensemble's maps
     (up to 3 211 264 rows) are not reproduced - the table takes the smallest grid that selects each instantiation and exercises its
     edges (a last tile with one row, ragged channel tiles, a grid that is no multiple of the 8 XCDs) - so variants are compared without
     their `m x n` suffix."""
@@ -217,12 +234,11 @@ def test_every_launch_of_the_ensemble_step_runs_a_tested_instantiation():
     assert sum(1 for l in launches if l[7]) >= 20
     seen, missing = covered(), []
     for kernel, M, N, K, k, s, g, gated, res, act in launches:
-        if (k, s, g) == (1, 1, 1):
-            v = rules.dense_variant(M, K, N, res, T.HALFS, gated, act)
-        else:
-            assert K % (k * k) == 0 and N % g == 0
-            v = rules.conv_variant_of(M, k * k, K // (k * k), N // g, T.HALFS, rules.pointwise_mode(act, None, res), gated)
-        assert rules.kernel_of(v) == kernel, (kernel, M, N, K, k, s, g, gated, res, act, v)
-        if rules.instantiation(v) not in seen:
-            missing.append((rules.instantiation(v), M, N, K, k, s, g))
+        assert K % (k * k) == 0 and N % g == 0
+        d, _ = conv_desc((M, k, k, K // (k * k) * g, N, k, s, (0, 0, 0, 0), g, act, res))
+        assert d.B * d.Ho * d.Wo == M and d.kh * d.kw * d.Cin // d.groups == K
+        v = ops.conv_kernel_variant(d, res, has_gate=gated)
+        assert ops.conv_kernel_name(d, res, has_gate=gated) == kernel and T.same_kernel(kernel, v), (kernel, M, N, K, k, s, g, gated, res, act, v)
+        if T.instantiation(v) not in seen:
+            missing.append((T.instantiation(v), M, N, K, k, s, g))
     assert not missing, missing

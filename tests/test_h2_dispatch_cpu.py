@@ -1,6 +1,6 @@
-"""The shape table of tests/_h2_gemm_cases.py against the C dispatcher's dry run (vip_conv2d_kernel_name_h2: nothing is launched, the
-library loads without a device - tests/test_abi.py): every row selects the kernel it is in the table for, under default dispatch, and
-each switch of the packed build (thresholds on 2 K) sits where the table says."""
+"""The shape table of tests/_h2_gemm_cases.py against the C dispatcher's dry run (vip_conv2d_kernel_name_h2 / _variant_h2: the plan of the
+launch without the launch, the library loads without a device - tests/test_abi.py): every row selects the kernel and the instantiation
+it is in the table for, under default dispatch, and each switch of the packed build (thresholds on 2 K) sits where the table says."""
 import pytest
 import torch
 
@@ -40,14 +40,14 @@ def test_dense_row_selects_its_kernel(M, K, N, epi, kernel, variant, what):
     d, res = dense_desc(M, K, N, epi)
     assert d.ldw == 2 * K
     assert ops.conv_kernel_name_h2(d, res) == kernel, what
-    assert T.dense_variant(M, K, N, res) == variant, what
+    assert ops.conv_kernel_variant_h2(d, res) == variant, what
 
 
 @pytest.mark.parametrize("case,kernel,variant,what", T.CONV_H2_CASES, ids=T.CONV_H2_IDS)
 def test_conv_row_selects_its_kernel(case, kernel, variant, what):
     d, res = conv_desc(case)
     assert ops.conv_kernel_name_h2(d, res) == kernel, what
-    assert T.conv_variant(case) == variant, what
+    assert ops.conv_kernel_variant_h2(d, res) == variant, what
 
 
 @pytest.mark.parametrize("below,above", T.DENSE_BOUNDARIES, ids=lambda p: "x".join(str(v) for v in p[:3]))
@@ -55,7 +55,7 @@ def test_dense_boundaries(below, above):
     for M, K, N, kernel in (below, above):
         d, _ = dense_desc(M, K, N, "none")
         assert ops.conv_kernel_name_h2(d, False) == kernel, (M, K, N)
-        assert T.dense_variant(M, K, N).startswith(kernel.replace("_kernel", "")), (M, K, N)
+        assert ops.conv_kernel_variant_h2(d, False).startswith(kernel.replace("_kernel", "")), (M, K, N)
 
 
 def test_conv_im2col_boundary():
@@ -75,4 +75,5 @@ def test_table_covers_every_instantiation_it_names():
                     "conv_igemm<128,128>"}
     big = [(M, v) for M, K, N, e, k, v, w in T.DENSE_CASES if M >= 1 << 19]
     assert len(big) == 1 and big[0][1] == "pw_gemm<KS=8> 2 x 192"           # the one large case: the 156 KB slice
-    assert T.dense_variant(big[0][0] - (1 << 19) + 65536, 128, 384) == "pw_gemm<KS=8> 3 x 128"     # what 72 KB would give
+    d, _ = dense_desc(big[0][0] - (1 << 19) + 65536, 128, 384, "none")
+    assert ops.conv_kernel_variant_h2(d, False) == "pw_gemm<KS=8> 3 x 128"                          # what 72 KB would give

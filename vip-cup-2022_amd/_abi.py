@@ -146,6 +146,7 @@ SIGNATURES = {
     "vip_conv2d_nhwc_h2": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _f, _vp, _vp]),
     "vip_conv2d_gated_nhwc_h2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _f, _vp, _vp]),
     "vip_conv2d_kernel_name_h2": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
+    "vip_conv2d_kernel_variant_h2": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "vip_dwconv2d_nhwc_h2": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _vp]),
     "vip_mlp_fused_supported_h2": (_i, [_i] * 4),
     "vip_mlp_fused_plan_h2": (_i, [_i] * 4 + [C.POINTER(_i)] * 2),
@@ -175,6 +176,7 @@ SIGNATURES = {
     "vip_cam_compose_f32": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "vip_cam_overlay_u8": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     "vip_conv2d_kernel_name": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
+    "vip_conv2d_kernel_variant": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_workspace_bytes": (_sz, [_i, C.POINTER(C.c_int64), _i]),
     "vip_microbench_copy": (_i, [_vp, _vp, _sz, _vp]),
     "vip_microbench_copy_variant": (_i, [_vp, _vp, _sz, _i, _vp]),

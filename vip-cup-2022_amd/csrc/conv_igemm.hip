@@ -80,6 +80,38 @@ struct ConvArgs {
     float ln_eps;
 };
 
+// What one call launches.  plan() (below the kernels) fills it from the arguments alone - host code, no HIP call, so a dry run
+// (vip_conv2d_kernel_name / _variant) is plan() without launch() - and launch() maps it to the instantiation.
+enum Family { PW_GEMM, ROWS_GEMM, GEMM8P, PWX, PWK_DIRECT, PWK_GEMM, IM2COL, CONV_IGEMM };
+struct Plan {
+    Family family;
+    int mode;                           // epilogue the pointwise kernels carry: act_pre (0..4), 5 residual, 6 residual + ReLU; -1: none of these
+    int ng, pt, wn, ks, ksc, bm, bn;    // template arguments, those the family has
+    bool gated, hilo, ln, xsplit, pipe;
+    bool pf2;                           // PWK_DIRECT: the VIP_PWK_PF2 experiment (pwk_direct2_kernel)
+    int m_blocks, n_blocks;             // -> ConvArgs (0 for the kernels that do not read them)
+    int n_chunks, nb_ch, lds_stride;    // PW_GEMM: channel chunks (grid y), channels per chunk, LDS row stride in bytes
+};
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a plan's template argument back as a compile-time constant
+template <int... Vs, class F>
+int with_const(int v, F&& f) {
+    int st = VIP_ERR_UNSUPPORTED;
+    if (!((v == Vs && ((st = f(std::integral_constant<int, Vs>{})), true)) || ...)) vip_set_error("vip_conv2d_nhwc_f16: no instantiation for %d", v);
+    return st;
+}
+
+// CU count of the device (256 where it cannot be asked): caps the persistent grids of pw_gemm_kernel and gemm8p_kernel
+inline int device_cus() {
+    static const int cus = [] {
+        hipDeviceProp_t pr;
+        int dev = 0;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+                   ? pr.multiProcessorCount : 256;
+    }();
+    return cus;
+}
+
 // ---- H2 epilogue core: 8 consecutive channels of one pixel (two accumulator quads) -> activation -> (+ residual) -> post -> packed
 // store.  `off` = byte offset of the channel group in y, `roff` in the residual (OOB2 for masked lanes).
 template <int ACT, bool RES, int POST>      // POST: 0 none, 1 ReLU, 2 run-time a.act_post
@@ -616,38 +648,11 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
     }
 }
 
-template <int KS, int PT, bool HILO = false>
-int launch_pw(const ConvArgs& a, int mode, hipStream_t s) {
-    if constexpr (!HILO) {
-        if (a.w_lo) return launch_pw<KS, PT, true>(a, mode, s);
-    }
+template <int KS, int PT, bool HILO>
+int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
     constexpr bool PRE = KS <= 3;
-    // two workgroups per CU.  H2: a packed weight slice is twice as large, so the same budget cuts N into more channel chunks and
-    // every chunk re-reads the activations; with >= 512K rows that traffic costs more than the second resident workgroup gains
-    // (M=2.5M N=384 K=96: 1.71 -> 1.23 ms), below that the shorter launch prefers the two workgroups (M=160K N=512 K=128:
-    // 0.16 vs 0.20 ms) - profiles/r04_ab_pw_h2_lds.log.  VIP_PW_H2_LDS_KB overrides.
-    static const int h2_lds_kb = getenv("VIP_PW_H2_LDS_KB") ? atoi(getenv("VIP_PW_H2_LDS_KB")) : 0;
-    const int LDS_MAX = (H2 ? (h2_lds_kb ? h2_lds_kb : (a.M >= (1 << 19) ? 156 : 72)) : 72) * 1024;
-    // row stride in 16-byte chunks == 2 (mod 4), i.e. 32 (mod 64) bytes: ds_read_b128 is serviced in the lane groups
-    // {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... over 64 banks, and with the fragment pattern (lane&15 = row, lane>>4 =
-    // chunk) that stride puts each group's 16 chunks on 16 distinct 16-byte slots (an ODD chunk stride does not: 46 %
-    // conflict cycles measured)
-    int s16 = KS * 4 * (HILO ? 2 : 1);
-    while ((s16 & 3) != 2) ++s16;
-    const int stride = s16 * 16;
-    const int cout64 = (a.Cout_g + 63) & ~63;
-    const int max_rows = (LDS_MAX / (stride + 4)) & ~63;
-    const int n_chunks = (cout64 + max_rows - 1) / max_rows;
-    const int nb_ch = (((cout64 / 64 + n_chunks - 1) / n_chunks)) * 64;
     const int n_tiles = (a.M + 64 * PT - 1) / (64 * PT);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
-    int gx = (2 * n_cu + n_chunks - 1) / n_chunks;
+    int gx = (2 * device_cus() + p.n_chunks - 1) / p.n_chunks;      // two workgroups per CU
     if (gx > n_tiles) gx = n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
@@ -655,23 +660,9 @@ int launch_pw(const ConvArgs& a, int mode, hipStream_t s) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO>), dim3((unsigned)gx, (unsigned)n_chunks), dim3(256),
-                       (size_t)nb_ch * (stride + 4), s, a, nb_ch, stride, n_tiles, mode);
+    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
+                       (size_t)p.nb_ch * (p.lds_stride + 4), s, a, p.nb_ch, p.lds_stride, n_tiles, p.mode);
     return vip_launch_status("vip_conv2d_nhwc_f16(pw)");
-}
-
-template <int PT>
-int launch_pw_k(const ConvArgs& a, int mode, hipStream_t s) {
-    const int ks = H2 ? 2 * ((a.K + 63) >> 6) : (a.K + 31) >> 5;     // H2: whole 64-half chunks (hi and lo planes of 32 logical k)
-    switch (ks) {
-        case 1: return launch_pw<1, PT>(a, mode, s);
-        case 2: return launch_pw<2, PT>(a, mode, s);
-        case 3: return launch_pw<3, PT>(a, mode, s);
-        case 4: return launch_pw<4, PT>(a, mode, s);
-        case 5:
-        case 6: return launch_pw<6, PT>(a, mode, s);
-        default: return launch_pw<8, PT>(a, mode, s);
-    }
 }
 
 // ---- pointwise (1x1, stride 1) / dense layers, any K: activations direct to registers, weights through LDS ----
@@ -686,7 +677,7 @@ int launch_pw_k(const ConvArgs& a, int mode, hipStream_t s) {
 // chip idle (7x7 and 13x13 maps with narrow outputs: 98 workgroups for M = 12 544, N = 208) - more, smaller workgroups.
 template <int NG, bool GATED, int PT = 4>
 __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode) {
-    constexpr int NB = 64 * NG, ROWB = 160;                  // LDS row: 64 halfs + 32 B pad (stride = 32 mod 64: launch_pw)
+    constexpr int NB = 64 * NG, ROWB = 160;                  // LDS row: 64 halfs + 32 B pad (stride = 32 mod 64: plan_pw)
     constexpr int STAGE = NB * ROWB;
     constexpr int W_IT = NB / 32;                            // 16-byte weight chunks staged per thread per k-chunk
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
@@ -1200,22 +1191,11 @@ __global__ __launch_bounds__(256, 2) void pwx_ln_kernel(ConvArgs a, int mode) {
     pwx_body<KSC, PT, true>(a, mode);
 }
 
-template <int KSC, int PT>
-int launch_pwx(const ConvArgs& a0, int mode, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + 64 * PT - 1) / (64 * PT);
-    a.n_blocks = 1;
-    hipLaunchKernelGGL((pwx_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
-    return vip_launch_status("vip_conv2d_nhwc_f16(pwx)");
-}
-
-template <int KSC, int PT>
-int launch_pwx_ln(const ConvArgs& a0, int mode, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + 64 * PT - 1) / (64 * PT);
-    a.n_blocks = 1;
-    hipLaunchKernelGGL((pwx_ln_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
-    return vip_launch_status("vip_ln_gemm_bias_act_f16");
+template <int KSC, int PT, bool LN>
+int launch_pwx(const ConvArgs& a, int mode, hipStream_t s) {
+    if constexpr (LN) hipLaunchKernelGGL((pwx_ln_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
+    else hipLaunchKernelGGL((pwx_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
+    return vip_launch_status(LN ? "vip_ln_gemm_bias_act_f16" : "vip_conv2d_nhwc_f16(pwx)");
 }
 
 #if VIP_BUILD_EXPERIMENTS
@@ -1398,7 +1378,7 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
     // 4 x WN waves: wave (wm, wn) owns pixels 64 wm .. +63 and channels (64 NG) wn .. of the 256 x (64 NG WN) block tile.
     // WN = 2 halves the L2 traffic of the activations (each activation image feeds two waves) at the same number of
     // resident waves per CU (one 8-wave workgroup instead of two 4-wave ones).
-    constexpr int PT = 4, NB = 64 * NG, NBLK = NB * WN, ROWB = 160;   // LDS row: 64 halfs + 32 B pad (32 mod 64: launch_pw)
+    constexpr int PT = 4, NB = 64 * NG, NBLK = NB * WN, ROWB = 160;   // LDS row: 64 halfs + 32 B pad (32 mod 64: plan_pw)
     constexpr int NTHR = 256 * WN;
     constexpr int STAGE = NBLK * ROWB;
     constexpr int W_IT = NBLK * 8 / NTHR;                    // 16-byte weight chunks staged per thread per k-chunk (4)
@@ -1627,66 +1607,30 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
     if constexpr (NG > 1) epi(std::integral_constant<int, 1>{});
 }
 
-template <int NG, int PT>
-void launch_pwk_direct_pt(ConvArgs& a, int mode, hipStream_t s) {
-    a.m_blocks = (a.M + 64 * PT - 1) / (64 * PT);
-    const dim3 grid((unsigned)(a.m_blocks * a.n_blocks));
-    if (a.gate) hipLaunchKernelGGL((pwk_direct_kernel<NG, true, PT>), grid, dim3(256), 0, s, a, mode);
-    else hipLaunchKernelGGL((pwk_direct_kernel<NG, false, PT>), grid, dim3(256), 0, s, a, mode);
-}
-
 template <int NG>
-int launch_pwk_direct(const ConvArgs& a0, int mode, hipStream_t s) {
-    ConvArgs a = a0;
-    a.n_blocks = (a.Cout_g + 64 * NG - 1) / (64 * NG);
-    // fewer 256-pixel workgroups than CUs (7x7 / 13x13 maps with narrow outputs): 64-pixel tiles instead - measured 48 -> 29 us on
-    // M = 12 544, N = 208, K = 1 248 (98 -> 392 workgroups), 35 -> 28 us on 43 264 x 128 x 768; 128-pixel tiles in the band up to
-    // 2 x CUs measured no gain and are not instantiated (tools/bench_pwk_fill.py, profiles/r02_pwk_small_tiles_ab.log)
-    static const int fill = getenv("VIP_PWK_FILL") ? atoi(getenv("VIP_PWK_FILL")) : 256;
-    const long wg256 = (long)((a.M + 255) / 256) * a.n_blocks;
-    if (wg256 < fill) launch_pwk_direct_pt<NG, 1>(a, mode, s);
+int launch_pwk_direct(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, a, p.mode); };
+    if (p.pt == 1) p.gated ? go(pwk_direct_kernel<NG, true, 1>) : go(pwk_direct_kernel<NG, false, 1>);
 #if VIP_BUILD_EXPERIMENTS
-    else if (!a.gate && getenv("VIP_PWK_PF2") && atoi(getenv("VIP_PWK_PF2"))) {     // the two-chunks-ahead experiment (read per call)
-        a.m_blocks = (a.M + 127) / 128;
-        hipLaunchKernelGGL((pwk_direct2_kernel<NG>), dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, a, mode);
-    }
+    else if (p.pf2) go(pwk_direct2_kernel<NG>);
 #endif
-    else launch_pwk_direct_pt<NG, 4>(a, mode, s);
+    else p.gated ? go(pwk_direct_kernel<NG, true, 4>) : go(pwk_direct_kernel<NG, false, 4>);
     return vip_launch_status("vip_conv2d_nhwc_f16(pwk-direct)");
 }
 
-template <int NG, int WN>
-int launch_pwk(const ConvArgs& a0, int mode, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + 255) / 256;
-    a.n_blocks = (a.Cout_g + 64 * NG * WN - 1) / (64 * NG * WN);
+// IM2COL: the k x k form, one grid plane per group (the pointwise form is ungrouped)
+template <int NG, int WN, bool IM2COL>
+int launch_pwk(const ConvArgs& a, int mode, int groups, hipStream_t s) {
     constexpr size_t smem = (2 * 64 * NG * WN + 4 * 64) * 160;     // 2 weight stages + 4 activation images
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pwk_gemm_kernel<NG, WN, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_set = true;
-    }
-    const dim3 grid((unsigned)(a.m_blocks * a.n_blocks));
-    hipLaunchKernelGGL((pwk_gemm_kernel<NG, WN, false>), grid, dim3(256 * WN), smem, s, a, mode);
-    return vip_launch_status("vip_conv2d_nhwc_f16(pwk)");
-}
-
-template <int NG>
-int launch_pwk_conv(const ConvArgs& a0, int mode, int groups, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + 255) / 256;
-    a.n_blocks = (a.Cout_g + 64 * NG - 1) / (64 * NG);
-    constexpr size_t smem = (2 * 64 * NG + 4 * 64) * 160;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pwk_gemm_kernel<NG, 1, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pwk_gemm_kernel<NG, WN, IM2COL>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr_set = true;
     }
     const dim3 grid((unsigned)(a.m_blocks * a.n_blocks), (unsigned)groups);
-    hipLaunchKernelGGL((pwk_gemm_kernel<NG, 1, true>), grid, dim3(256), smem, s, a, mode);
-    return vip_launch_status("vip_conv2d_nhwc_f16(pwk-im2col)");
+    hipLaunchKernelGGL((pwk_gemm_kernel<NG, WN, IM2COL>), grid, dim3(256 * WN), smem, s, a, mode);
+    return vip_launch_status(IM2COL ? "vip_conv2d_nhwc_f16(pwk-im2col)" : "vip_conv2d_nhwc_f16(pwk)");
 }
 
 #include "gemm8p.hpp"
@@ -1824,11 +1768,14 @@ __global__ __launch_bounds__(256) void rows_gemm_kernel(ConvArgs a) {
     }
 }
 
+template <bool XSPLIT>
+int launch_rows(const ConvArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(rows_gemm_kernel<XSPLIT>, dim3((unsigned)((a.Cout_g + 15) / 16), (unsigned)((a.M + 63) / 64)), dim3(256), 0, s, a);
+    return vip_launch_status("vip_conv2d_nhwc_f16(rows)");
+}
+
 template <int BM, int BN>
-int launch(const ConvArgs& a0, int groups, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + BM - 1) / BM;
-    a.n_blocks = (a.Cout_g + BN - 1) / BN;
+int launch_igemm(const ConvArgs& a, int groups, hipStream_t s) {
     const int nk = (a.K + 63) >> 6;
     const size_t smem = (nk == 1 ? 1 : 2) * (BM + BN) * 128;  // a single k-tile needs no second stage
     static bool attr_set = false;
@@ -1844,21 +1791,208 @@ int launch(const ConvArgs& a0, int groups, hipStream_t s) {
 
 }  // namespace
 
-// vip_conv2d_kernel_name(): the selection below runs with g_dry set, records the kernel it would launch and returns
-static thread_local bool g_dry = false;
-static thread_local const char* g_pick = "";
-#define VIP_PICK(name, call)          \
-    do {                              \
-        if (g_dry) {                  \
-            g_pick = (name);          \
-            return VIP_OK;            \
-        }                             \
-        return (call);                \
-    } while (0)
+// ---- selection: which kernel, which template arguments, which tile grid.  Host code alone - every threshold and every selection
+// switch of the environment is read here (static: once per process; VIP_G8P_MINK, VIP_PWX, VIP_PWK_PF2 and VIP_LN_GEMM_ALL per call:
+// their tests set them mid-process), and the selection's VIP_ERR_UNSUPPORTED exits are here (those of the argument checks stay in front).
+static void plan_blocks(Plan& p, const ConvArgs& a, int bm, int bn) {
+    p.m_blocks = (a.M + bm - 1) / bm;
+    p.n_blocks = (a.Cout_g + bn - 1) / bn;
+}
 
-static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
-                       const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
-                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
+static int plan_pw(Plan& p, const ConvArgs& a) {
+    p.family = PW_GEMM; p.pt = 4; p.hilo = a.w_lo != nullptr;
+    const int ks = H2 ? 2 * ((a.K + 63) >> 6) : (a.K + 31) >> 5;     // H2: whole 64-half chunks (hi and lo planes of 32 logical k)
+    p.ks = ks <= 4 ? ks : ks <= 6 ? 6 : 8;
+    // two workgroups per CU.  H2: a packed weight slice is twice as large, so the same budget cuts N into more channel chunks and
+    // every chunk re-reads the activations; with >= 512K rows that traffic costs more than the second resident workgroup gains
+    // (M=2.5M N=384 K=96: 1.71 -> 1.23 ms), below that the shorter launch prefers the two workgroups (M=160K N=512 K=128:
+    // 0.16 vs 0.20 ms) - profiles/r04_ab_pw_h2_lds.log.  VIP_PW_H2_LDS_KB overrides.
+    static const int h2_lds_kb = getenv("VIP_PW_H2_LDS_KB") ? atoi(getenv("VIP_PW_H2_LDS_KB")) : 0;
+    const int LDS_MAX = (H2 ? (h2_lds_kb ? h2_lds_kb : (a.M >= (1 << 19) ? 156 : 72)) : 72) * 1024;
+    // row stride in 16-byte chunks == 2 (mod 4), i.e. 32 (mod 64) bytes: ds_read_b128 is serviced in the lane groups
+    // {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... over 64 banks, and with the fragment pattern (lane&15 = row, lane>>4 =
+    // chunk) that stride puts each group's 16 chunks on 16 distinct 16-byte slots (an ODD chunk stride does not: 46 %
+    // conflict cycles measured)
+    int s16 = p.ks * 4 * (p.hilo ? 2 : 1);
+    while ((s16 & 3) != 2) ++s16;
+    p.lds_stride = s16 * 16;
+    const int cout64 = (a.Cout_g + 63) & ~63;
+    const int max_rows = (LDS_MAX / (p.lds_stride + 4)) & ~63;
+    p.n_chunks = (cout64 + max_rows - 1) / max_rows;
+    p.nb_ch = (((cout64 / 64 + p.n_chunks - 1) / p.n_chunks)) * 64;
+    return VIP_OK;
+}
+
+static int plan_pwx(Plan& p, const ConvArgs& a, int ksc, int pt, bool ln) {
+    p.family = PWX; p.ksc = ksc; p.pt = pt; p.ln = ln;
+    p.m_blocks = (a.M + 64 * pt - 1) / (64 * pt); p.n_blocks = 1;
+    return VIP_OK;
+}
+
+static int plan_pwk_direct(Plan& p, const ConvArgs& a) {
+    p.family = PWK_DIRECT; p.ng = a.Cout_g <= 64 ? 1 : 2; p.gated = a.gate != nullptr;
+    // fewer 256-pixel workgroups than CUs (7x7 / 13x13 maps with narrow outputs): 64-pixel tiles instead - measured 48 -> 29 us on
+    // M = 12 544, N = 208, K = 1 248 (98 -> 392 workgroups), 35 -> 28 us on 43 264 x 128 x 768; 128-pixel tiles in the band up to
+    // 2 x CUs measured no gain and are not instantiated (tools/bench_pwk_fill.py, profiles/r02_pwk_small_tiles_ab.log)
+    static const int fill = getenv("VIP_PWK_FILL") ? atoi(getenv("VIP_PWK_FILL")) : 256;
+    const long wg256 = (long)((a.M + 255) / 256) * ((a.Cout_g + 64 * p.ng - 1) / (64 * p.ng));
+    p.pt = wg256 < fill ? 1 : 4;
+#if VIP_BUILD_EXPERIMENTS
+    if (p.pt == 4 && !a.gate && getenv("VIP_PWK_PF2") && atoi(getenv("VIP_PWK_PF2"))) {     // the two-chunks-ahead experiment (read per call)
+        p.pf2 = true; p.pt = 2;       // pwk_direct2_kernel's 128-pixel block tile
+    }
+#endif
+    plan_blocks(p, a, 64 * p.pt, 64 * p.ng);
+    return VIP_OK;
+}
+
+static int plan_pwk(Plan& p, const ConvArgs& a, int ng, int wn) {
+    p.family = PWK_GEMM; p.ng = ng; p.wn = wn;
+    plan_blocks(p, a, 256, 64 * ng * wn);
+    return VIP_OK;
+}
+
+static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* out) {
+    Plan& p = *out = Plan{};
+    const long M = a.M;
+    const int cin_g = d->Cin / d->groups, cout_g = a.Cout_g;
+    const bool residual = a.res, gate = a.gate, w_lo = a.w_lo;
+    // epilogue variants the pointwise kernels carry: act_pre alone, or residual (+ post-ReLU) with no act_pre
+    int mode = -1;
+    if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
+    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
+    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
+    p.mode = mode;
+#if !VIP_GEMM_H2
+    if (a.ln_g) {     // vip_ln_gemm_bias_act_f16: the one kernel with the LayerNorm prologue, no fall-back (a missing kernel is an error)
+        VIP_REQUIRE(mode >= 0 && a.ln_b && !w_lo && !gate && !a.y_lo_off && !x_split && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 &&
+                        d->sw == 1 && d->pt == 0 && d->pl == 0 && d->Ho == d->H && d->Wo == d->W && d->cin_off == 0 &&
+                        vip_ln_gemm_supported((int)M, a.K, cout_g, d->act_pre) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K,
+                    VIP_ERR_UNSUPPORTED,
+                    "vip_ln_gemm_bias_act_f16: M=%ld K=%d N=%d act=%d/%d%s not taken (vip_ln_gemm_supported; (activation) or "
+                    "(residual [+ReLU]) epilogue)", M, a.K, cout_g, d->act_pre, d->act_post, residual ? " +res" : "");
+        const int ksc = (a.K + 63) >> 6;
+        return plan_pwx(p, a, ksc <= 2 ? 2 : ksc <= 3 ? 3 : ksc <= 4 ? 4 : 6, 2, true);
+    }
+#endif
+    // HBM-bound shapes (short K): a smaller M tile -> 24-48 KB LDS and half the accumulators -> 3-5 workgroups per
+    // CU in flight instead of 2, which is what hides the load -> MFMA -> store latency chain of a 1-4 k-tile block.
+    // (Tried and measured SLOWER on these shapes: a two-deep register prefetch (+40 VGPRs), an LDS-transposed
+    // "fully coalesced" epilogue, and a persistent tile loop that prefetches the next tile under the epilogue
+    // (+60 VGPRs): all three trade resident workgroups for in-workgroup overlap, and residency wins.)
+    const bool short_k = a.K <= 256;
+    static const int pw_mode = getenv("VIP_PW") ? atoi(getenv("VIP_PW")) : 3;
+    if (pw_mode && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->pl == 0 &&
+        d->Ho == d->H && d->Wo == d->W) {
+        if (w_lo) {     // hi + lo weights: the streaming kernel is the one that carries them (any M)
+            VIP_REQUIRE(mode >= 0 && short_k && !gate && !a.y_lo_off, VIP_ERR_UNSUPPORTED,
+                        "vip_conv2d_hilo_nhwc_f16: 1x1 stride-1 ungrouped, K <= 256, (activation) or (residual [+ReLU]) epilogue");
+            return plan_pw(p, a);
+        }
+        if (M <= 256 && !residual && !gate && d->act_post == VIP_ACT_NONE && d->ldy % 4 == 0 && d->cout_off % 4 == 0 &&
+            a.x_span_bytes < 0xFFFF0000L - 2L * a.K && 2L * cout_g * d->ldw < 0xFFFF0000L - 2L * a.K) {
+            p.family = ROWS_GEMM; p.xsplit = x_split;
+            return VIP_OK;
+        }
+        VIP_REQUIRE(!a.y_lo_off && !x_split, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: at most 256 rows, N %% 4 == 0");
+        if (mode >= 0 && (pw_mode & 1) && short_k && M >= 65536 && !gate) return plan_pw(p, a);
+        // deep K, wide N: the LDS-DMA kernel (gemm8p.hpp).  VIP_G8P_MINK: smallest K it takes (0 = never).  1024: in isolation it
+        // wins from K = 256 up (+6..+27 %), but it owns a CU (128 KB of LDS, 8 waves x 256 VGPRs, persistent) and the ensemble step
+        // runs three member streams - with the K = 256-768 layers on it the STEP was 1.5-2 % slower (58.2 ms vs 57.1-57.4,
+        // alternating runs on one box, profiles/r02_gemm8p_mink_streams_ab.log) and a single stream gained nothing either.
+        const char* g8_env = getenv("VIP_G8P_MINK");     // read per call: the kernel's own tests lower it
+        const int g8_min_k = g8_env ? atoi(g8_env) : 1024;
+        if (mode >= 0 && g8_min_k > 0 && !gate && a.K >= g8_min_k && gemm8p_eligible(a) && cout_g % 256 == 0 &&
+            (long)((M + 255) / 256) * (cout_g / 256) >= 128) {
+            p.family = GEMM8P; p.pipe = a.K % 128 == 0;
+            plan_blocks(p, a, 256, 256);
+            return VIP_OK;
+        }
+        if (mode >= 0 && (pw_mode & 2) && a.x_span_bytes < 0xFFFFFFF0L) {
+            // (a 64 x 256 wave tile at one wave per SIMD - NG = 4 - measured 15-40 % slower than NG = 2 at two)
+            static const int xl_min_k = getenv("VIP_PWK_XLK") ? atoi(getenv("VIP_PWK_XLK")) : 768;
+            // (gated convolutions: only the direct kernel carries the gate pipeline - their deep-K cases are small launches)
+            // short K, wide N: the activation-resident kernel (pwx_kernel) - an EXPERIMENT, off unless VIP_PWX=1 (read per call: its tests
+            // set it).  Measured per shape against pwk_direct_kernel (profiles/r04_pwx_vs_pwk_direct.log): a wash on the fp16 storage
+            // (sum of ten ensemble shapes 566 vs 564 us) and 7-35 % slower on the packed storage, where K = 256 needs 128 fragment
+            // registers, leaves 16 pixels per wave and makes every 64-pixel workgroup stream all of W out of L2.  The K <= 256 layers are
+            // not bound by the fill / drain this kernel removes: their GELU / residual epilogues issue 7 VALU instructions per MFMA.
+            const char* pwx_env = getenv("VIP_PWX");
+            const int pwx_on = pwx_env ? atoi(pwx_env) : 0;
+            if (pwx_on && !gate && cout_g >= 256 && a.K <= (H2 ? 512 : 256) && a.K > 64 && M >= 16384 && a.x_span_bytes < 0xFFFF0000L - 2L * a.K) {
+                const int ksc = (a.K + 63) >> 6;
+                if (H2) {
+                    if (ksc <= 4) return plan_pwx(p, a, 4, 2, false);
+                    return plan_pwx(p, a, ksc <= 6 ? 6 : 8, 1, false);      // (32 pixels per wave spill at 96 fragment registers)
+                }
+                return plan_pwx(p, a, ksc <= 2 ? 2 : ksc <= 3 ? 3 : 4, 2, false);
+            }
+            if ((a.K < xl_min_k || gate) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K) return plan_pwk_direct(p, a);
+            VIP_REQUIRE(!gate, VIP_ERR_UNSUPPORTED, "vip_conv2d_gated_nhwc_f16: input tensor too large (4 GB - 2K)");
+            if (cout_g <= 64) return plan_pwk(p, a, 1, 1);
+            // 256 x 256 block tiles (8 waves): 5 % on deep-K layers whose N is a multiple of 256; slower whenever the last
+            // 256-channel tile is half empty (N = 384: 258 -> 346 us) or K is short
+            static const int wn2_min_k = getenv("VIP_PWK_WN2K") ? atoi(getenv("VIP_PWK_WN2K")) : 1024;
+            if (cout_g % 256 == 0 && a.K >= wn2_min_k && (long)((M + 255) / 256) * (cout_g / 256) >= 256) return plan_pwk(p, a, 2, 2);
+            return plan_pwk(p, a, 2, 1);
+        }
+    }
+    {   // k x k convolutions on the pointwise kernel with im2col staging (64 px x 128 ch wave tiles, half the LDS fragment
+        // reads per MFMA of the 64 x 64 tiles below): stems (Cin <= 16: 277 vs 385 us on the EfficientNet stems) and every
+        // layer with at least 32 K pixels - measured per shape on the ensemble after the MFMA-priority change: +3..+25 %
+        // (ResNeSt's grouped 3x3: 585 -> 726, 721 -> 853 TF), except the 7 x 7-pixel stages (M = 12 544: 637 -> 497 TF),
+        // which keep the tile kernel.  VIP_PWK_CONV: 1 = every eligible conv (tests), -1 = stems only.
+        static const int im2col_all = getenv("VIP_PWK_CONV") ? atoi(getenv("VIP_PWK_CONV")) : 0;
+        if ((cin_g <= 16 || im2col_all > 0 || (im2col_all == 0 && M >= 32768)) && mode >= 0 && !gate && a.x_span_bytes < 0xFFFFFFF0L && d->H < 30000 &&
+            d->W < 30000 && d->pt < 16 && d->pl < 16) {
+            p.family = IM2COL; p.ng = cout_g <= 64 ? 1 : 2;
+            plan_blocks(p, a, 256, 64 * p.ng);
+            return VIP_OK;
+        }
+    }
+    VIP_REQUIRE(!w_lo, VIP_ERR_UNSUPPORTED, "vip_conv2d_hilo_nhwc_f16: only 1x1 stride-1 ungrouped convolutions with K <= 256");
+    VIP_REQUIRE(!gate, VIP_ERR_UNSUPPORTED,
+                "vip_conv2d_gated_nhwc_f16: only 1x1 stride-1 ungrouped convolutions with (activation) or (residual [+ReLU]) "
+                "epilogues take a gate; apply vip_scale_add_act_f16 first");
+    p.family = CONV_IGEMM; p.bm = short_k ? 64 : 128; p.bn = cout_g <= 64 ? 64 : 128;
+    plan_blocks(p, a, p.bm, p.bn);
+    return VIP_OK;
+}
+
+// ---- launch: the plan's instantiation.  What is read here depends on the device or changes nothing in the selection: the CU count that
+// caps the persistent grids, VIP_G8P_PERSIST, the once-per-kernel dynamic-LDS attributes.
+static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s) {
+    a.m_blocks = p.m_blocks; a.n_blocks = p.n_blocks;
+    switch (p.family) {
+        case PW_GEMM:
+            return with_const<1, 2, 3, 4, 6, 8>(p.ks, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                return p.hilo ? launch_pw<KS, 4, true>(a, p, s) : launch_pw<KS, 4, false>(a, p, s);
+            });
+        case ROWS_GEMM: return p.xsplit ? launch_rows<true>(a, s) : launch_rows<false>(a, s);
+        case GEMM8P: return launch_gemm8p(a, p.mode, p.pipe, s);
+        case PWX:
+#if !VIP_GEMM_H2
+            if (p.ln) return with_const<2, 3, 4, 6>(p.ksc, [&](auto ksc) { return launch_pwx<decltype(ksc)::value, 2, true>(a, p.mode, s); });
+#endif
+            if (p.pt == 2) return with_const<2, 3, 4>(p.ksc, [&](auto ksc) { return launch_pwx<decltype(ksc)::value, 2, false>(a, p.mode, s); });
+            return with_const<6, 8>(p.ksc, [&](auto ksc) { return launch_pwx<decltype(ksc)::value, 1, false>(a, p.mode, s); });
+        case PWK_DIRECT: return p.ng == 1 ? launch_pwk_direct<1>(a, p, s) : launch_pwk_direct<2>(a, p, s);
+        case PWK_GEMM:
+            if (p.ng == 1) return launch_pwk<1, 1, false>(a, p.mode, groups, s);
+            return p.wn == 1 ? launch_pwk<2, 1, false>(a, p.mode, groups, s) : launch_pwk<2, 2, false>(a, p.mode, groups, s);
+        case IM2COL: return p.ng == 1 ? launch_pwk<1, 1, true>(a, p.mode, groups, s) : launch_pwk<2, 1, true>(a, p.mode, groups, s);
+        case CONV_IGEMM:
+            if (p.bn == 64) return p.bm == 64 ? launch_igemm<64, 64>(a, groups, s) : launch_igemm<128, 64>(a, groups, s);
+            return p.bm == 64 ? launch_igemm<64, 128>(a, groups, s) : launch_igemm<128, 128>(a, groups, s);
+    }
+    return VIP_ERR_UNSUPPORTED;
+}
+
+// the argument checks, the kernel arguments and the plan of one call
+static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
+                       const vip_conv_desc* d, const void* w_lo, bool x_split, float out_scale, int* status, const float* ln_g,
+                       const float* ln_b, float ln_eps, ConvArgs* args, Plan* p) {
     VIP_REQUIRE(x && w && y && d, VIP_ERR_BAD_ARG, "vip_conv2d_nhwc_f16: null pointer");
     VIP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kh > 0 && d->kw > 0 &&
                     d->sh > 0 && d->sw > 0 && d->Ho > 0 && d->Wo > 0 && d->groups > 0 && d->pt >= 0 && d->pl >= 0,
@@ -1883,7 +2017,7 @@ static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void
     const long M = (long)d->B * d->Ho * d->Wo;
     VIP_REQUIRE(M < (1L << 31) - 256, VIP_ERR_UNSUPPORTED, "vip_conv2d_nhwc_f16: B*Ho*Wo too large");
 
-    ConvArgs a;
+    ConvArgs& a = *args;
     a.x = (const f16*)x; a.w = (const f16*)w; a.bias = bias; a.res = (const f16*)residual; a.y = (f16*)y;
     a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo;
     // the INPUT side in halfs (H2: twice the logical channels - see the head of this file), the output side in logical channels
@@ -1909,117 +2043,49 @@ static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void
     a.gate_hw = d->Ho * d->Wo;
     a.y_lo_off = y_lo_off;
     a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
-    hipStream_t s = (hipStream_t)stream;
-#if !VIP_GEMM_H2
-    if (ln_g) {     // vip_ln_gemm_bias_act_f16: the one kernel with the LayerNorm prologue, no fall-back (a missing kernel is an error)
-        int mode = -1;
-        if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
-        VIP_REQUIRE(mode >= 0 && ln_b && !w_lo && !gate && !y_lo_off && !x_split && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 &&
-                        d->sw == 1 && d->pt == 0 && d->pl == 0 && d->Ho == d->H && d->Wo == d->W && d->cin_off == 0 &&
-                        vip_ln_gemm_supported((int)M, a.K, cout_g, d->act_pre) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K,
-                    VIP_ERR_UNSUPPORTED,
-                    "vip_ln_gemm_bias_act_f16: M=%ld K=%d N=%d act=%d/%d%s not taken (vip_ln_gemm_supported; (activation) or "
-                    "(residual [+ReLU]) epilogue)", M, a.K, cout_g, d->act_pre, d->act_post, residual ? " +res" : "");
-        const int ksc = (a.K + 63) >> 6;
-        if (ksc <= 2) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<2, 2>(a, mode, s)));
-        if (ksc <= 3) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<3, 2>(a, mode, s)));
-        if (ksc <= 4) VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<4, 2>(a, mode, s)));
-        VIP_PICK("pwx_ln_kernel", (launch_pwx_ln<6, 2>(a, mode, s)));
+    return plan(a, d, x_split, p);
+}
+
+static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
+                       const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
+                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
+    ConvArgs a;
+    Plan p;
+    const int st = conv2d_plan(x, gate, y_lo_off, w, bias, residual, y, d, w_lo, x_split, out_scale, status, ln_g, ln_b, ln_eps, &a, &p);
+    return st != VIP_OK ? st : launch(p, a, d->groups, (hipStream_t)stream);
+}
+
+// vip_conv2d_kernel_name[_h2] / vip_conv2d_kernel_variant[_h2]: a dry run - the checks and the plan of the call the flags describe, and
+// no launch.  The name is the kernel family (profile labels), the variant the instantiation and its tile grid.
+static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* out,
+                        size_t cap) {
+    VIP_REQUIRE(d && out && cap > 0, VIP_ERR_BAD_ARG, "%s: null pointer", who);
+    static const char dummy[16] = {0};     // non-null stand-ins: nothing is dereferenced or launched in a dry run
+    ConvArgs a;
+    Plan p;
+    const int st = conv2d_plan(dummy, has_gate ? dummy : nullptr, 0, dummy, nullptr, has_residual ? dummy : nullptr, const_cast<char*>(dummy), d,
+                               has_w_lo ? dummy : nullptr, false, 1.f, nullptr, nullptr, nullptr, 0.f, &a, &p);
+    if (st != VIP_OK) return st;
+    static const char* const kernel[] = {"pw_gemm_kernel",    "rows_gemm_kernel", "gemm8p_kernel",           "pwx_kernel",
+                                         "pwk_direct_kernel", "pwk_gemm_kernel",  "pwk_gemm_kernel(im2col)", "conv_igemm_kernel"};
+    if (!variant) {
+        snprintf(out, cap, "%s", p.family == PWX && p.ln ? "pwx_ln_kernel" : kernel[p.family]);
+        return VIP_OK;
     }
-#endif
-    // HBM-bound shapes (short K): a smaller M tile -> 24-48 KB LDS and half the accumulators -> 3-5 workgroups per
-    // CU in flight instead of 2, which is what hides the load -> MFMA -> store latency chain of a 1-4 k-tile block.
-    // (Tried and measured SLOWER on these shapes: a two-deep register prefetch (+40 VGPRs), an LDS-transposed
-    // "fully coalesced" epilogue, and a persistent tile loop that prefetches the next tile under the epilogue
-    // (+60 VGPRs): all three trade resident workgroups for in-workgroup overlap, and residency wins.)
-    const bool short_k = a.K <= 256;
-    static const int pw_mode = getenv("VIP_PW") ? atoi(getenv("VIP_PW")) : 3;
-    if (pw_mode && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->pl == 0 &&
-        d->Ho == d->H && d->Wo == d->W) {
-        // epilogue variants the pointwise kernels carry: act_pre alone, or residual (+ post-ReLU) with no act_pre
-        int mode = -1;
-        if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
-        if (w_lo) {     // hi + lo weights: the streaming kernel is the one that carries them (any M)
-            VIP_REQUIRE(mode >= 0 && short_k && !gate && !y_lo_off, VIP_ERR_UNSUPPORTED,
-                        "vip_conv2d_hilo_nhwc_f16: 1x1 stride-1 ungrouped, K <= 256, (activation) or (residual [+ReLU]) epilogue");
-            VIP_PICK("pw_gemm_kernel", launch_pw_k<4>(a, mode, s));
-        }
-        if (M <= 256 && !residual && !gate && d->act_post == VIP_ACT_NONE && d->ldy % 4 == 0 && d->cout_off % 4 == 0 &&
-            a.x_span_bytes < 0xFFFF0000L - 2L * a.K && 2L * cout_g * d->ldw < 0xFFFF0000L - 2L * a.K) {
-            if (g_dry) { g_pick = "rows_gemm_kernel"; return VIP_OK; }
-            if (x_split) hipLaunchKernelGGL(rows_gemm_kernel<true>, dim3((unsigned)((cout_g + 15) / 16), (unsigned)((M + 63) / 64)), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(rows_gemm_kernel<false>, dim3((unsigned)((cout_g + 15) / 16), (unsigned)((M + 63) / 64)), dim3(256), 0, s, a);
-            return vip_launch_status("vip_conv2d_nhwc_f16(rows)");
-        }
-        VIP_REQUIRE(!y_lo_off && !x_split, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: at most 256 rows, N %% 4 == 0");
-        if (mode >= 0 && (pw_mode & 1) && short_k && M >= 65536 && !gate) VIP_PICK("pw_gemm_kernel", launch_pw_k<4>(a, mode, s));
-        // deep K, wide N: the LDS-DMA kernel (gemm8p.hpp).  VIP_G8P_MINK: smallest K it takes (0 = never).  1024: in isolation it
-        // wins from K = 256 up (+6..+27 %), but it owns a CU (128 KB of LDS, 8 waves x 256 VGPRs, persistent) and the ensemble step
-        // runs three member streams - with the K = 256-768 layers on it the STEP was 1.5-2 % slower (58.2 ms vs 57.1-57.4,
-        // alternating runs on one box, profiles/r02_gemm8p_mink_streams_ab.log) and a single stream gained nothing either.
-        const char* g8_env = getenv("VIP_G8P_MINK");     // read per call: the kernel's own tests lower it
-        const int g8_min_k = g8_env ? atoi(g8_env) : 1024;
-        if (mode >= 0 && g8_min_k > 0 && !gate && a.K >= g8_min_k && gemm8p_eligible(a) && cout_g % 256 == 0 &&
-            (long)((M + 255) / 256) * (cout_g / 256) >= 128)
-            VIP_PICK("gemm8p_kernel", launch_gemm8p(a, mode, s));
-        if (mode >= 0 && (pw_mode & 2) && a.x_span_bytes < 0xFFFFFFF0L) {
-            // (a 64 x 256 wave tile at one wave per SIMD - NG = 4 - measured 15-40 % slower than NG = 2 at two)
-            static const int xl_min_k = getenv("VIP_PWK_XLK") ? atoi(getenv("VIP_PWK_XLK")) : 768;
-            // (gated convolutions: only the direct kernel carries the gate pipeline - their deep-K cases are small launches)
-            // short K, wide N: the activation-resident kernel (pwx_kernel) - an EXPERIMENT, off unless VIP_PWX=1 (read per call: its tests
-            // set it).  Measured per shape against pwk_direct_kernel (profiles/r04_pwx_vs_pwk_direct.log): a wash on the fp16 storage
-            // (sum of ten ensemble shapes 566 vs 564 us) and 7-35 % slower on the packed storage, where K = 256 needs 128 fragment
-            // registers, leaves 16 pixels per wave and makes every 64-pixel workgroup stream all of W out of L2.  The K <= 256 layers are
-            // not bound by the fill / drain this kernel removes: their GELU / residual epilogues issue 7 VALU instructions per MFMA.
-            const char* pwx_env = getenv("VIP_PWX");
-            const int pwx_on = pwx_env ? atoi(pwx_env) : 0;
-            if (pwx_on && !gate && cout_g >= 256 && a.K <= (H2 ? 512 : 256) && a.K > 64 && M >= 16384 && a.x_span_bytes < 0xFFFF0000L - 2L * a.K) {
-                const int ksc = (a.K + 63) >> 6;
-                if (H2) {
-                    if (ksc <= 4) VIP_PICK("pwx_kernel", (launch_pwx<4, 2>(a, mode, s)));
-                    if (ksc <= 6) VIP_PICK("pwx_kernel", (launch_pwx<6, 1>(a, mode, s)));      // (32 pixels per wave spill at 96 fragment registers)
-                    VIP_PICK("pwx_kernel", (launch_pwx<8, 1>(a, mode, s)));
-                } else {
-                    if (ksc <= 2) VIP_PICK("pwx_kernel", (launch_pwx<2, 2>(a, mode, s)));
-                    if (ksc <= 3) VIP_PICK("pwx_kernel", (launch_pwx<3, 2>(a, mode, s)));
-                    VIP_PICK("pwx_kernel", (launch_pwx<4, 2>(a, mode, s)));
-                }
-            }
-            if ((a.K < xl_min_k || gate) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K)
-                VIP_PICK("pwk_direct_kernel", cout_g <= 64 ? launch_pwk_direct<1>(a, mode, s) : launch_pwk_direct<2>(a, mode, s));
-            VIP_REQUIRE(!gate, VIP_ERR_UNSUPPORTED, "vip_conv2d_gated_nhwc_f16: input tensor too large (4 GB - 2K)");
-            if (cout_g <= 64) VIP_PICK("pwk_gemm_kernel", (launch_pwk<1, 1>(a, mode, s)));
-            // 256 x 256 block tiles (8 waves): 5 % on deep-K layers whose N is a multiple of 256; slower whenever the last
-            // 256-channel tile is half empty (N = 384: 258 -> 346 us) or K is short
-            static const int wn2_min_k = getenv("VIP_PWK_WN2K") ? atoi(getenv("VIP_PWK_WN2K")) : 1024;
-            if (cout_g % 256 == 0 && a.K >= wn2_min_k && (long)((M + 255) / 256) * (cout_g / 256) >= 256) VIP_PICK("pwk_gemm_kernel", (launch_pwk<2, 2>(a, mode, s)));
-            VIP_PICK("pwk_gemm_kernel", (launch_pwk<2, 1>(a, mode, s)));
-        }
+    switch (p.family) {
+        case PW_GEMM: snprintf(out, cap, "pw_gemm<KS=%d%s> %d x %d", p.ks, p.hilo ? ",hilo" : "", p.n_chunks, p.nb_ch); break;
+        case ROWS_GEMM: snprintf(out, cap, "rows_gemm%s", p.xsplit ? "<xsplit>" : ""); break;
+        case GEMM8P: snprintf(out, cap, "gemm8p<%s> %d x %d", p.pipe ? "pipe" : "basic", p.m_blocks, p.n_blocks); break;
+        case PWX: snprintf(out, cap, "%s<%d,%d>", p.ln ? "pwx_ln" : "pwx", p.ksc, p.pt); break;
+        case PWK_DIRECT:
+            if (p.pf2) snprintf(out, cap, "pwk_direct2<%d>", p.ng);
+            else snprintf(out, cap, "pwk_direct<%d%s> PT=%d", p.ng, p.gated ? ",gated" : "", p.pt);
+            break;
+        case PWK_GEMM: snprintf(out, cap, "pwk_gemm<%d,%d> %d x %d", p.ng, p.wn, p.m_blocks, p.n_blocks); break;
+        case IM2COL: snprintf(out, cap, "im2col<%d>", p.ng); break;
+        case CONV_IGEMM: snprintf(out, cap, "conv_igemm<%d,%d>", p.bm, p.bn); break;
     }
-    {   // k x k convolutions on the pointwise kernel with im2col staging (64 px x 128 ch wave tiles, half the LDS fragment
-        // reads per MFMA of the 64 x 64 tiles below): stems (Cin <= 16: 277 vs 385 us on the EfficientNet stems) and every
-        // layer with at least 32 K pixels - measured per shape on the ensemble after the MFMA-priority change: +3..+25 %
-        // (ResNeSt's grouped 3x3: 585 -> 726, 721 -> 853 TF), except the 7 x 7-pixel stages (M = 12 544: 637 -> 497 TF),
-        // which keep the tile kernel.  VIP_PWK_CONV: 1 = every eligible conv (tests), -1 = stems only.
-        int mode = -1;
-        if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
-        else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
-        static const int im2col_all = getenv("VIP_PWK_CONV") ? atoi(getenv("VIP_PWK_CONV")) : 0;
-        if ((cin_g <= 16 || im2col_all > 0 || (im2col_all == 0 && M >= 32768)) && mode >= 0 && !gate && a.x_span_bytes < 0xFFFFFFF0L && d->H < 30000 &&
-            d->W < 30000 && d->pt < 16 && d->pl < 16)
-            VIP_PICK("pwk_gemm_kernel(im2col)", cout_g <= 64 ? launch_pwk_conv<1>(a, mode, d->groups, s) : launch_pwk_conv<2>(a, mode, d->groups, s));
-    }
-    VIP_REQUIRE(!w_lo, VIP_ERR_UNSUPPORTED, "vip_conv2d_hilo_nhwc_f16: only 1x1 stride-1 ungrouped convolutions with K <= 256");
-    VIP_REQUIRE(!gate, VIP_ERR_UNSUPPORTED,
-                "vip_conv2d_gated_nhwc_f16: only 1x1 stride-1 ungrouped convolutions with (activation) or (residual [+ReLU]) "
-                "epilogues take a gate; apply vip_scale_add_act_f16 first");
-    if (cout_g <= 64) VIP_PICK("conv_igemm_kernel", short_k ? (launch<64, 64>(a, d->groups, s)) : (launch<128, 64>(a, d->groups, s)));
-    VIP_PICK("conv_igemm_kernel", short_k ? (launch<64, 128>(a, d->groups, s)) : (launch<128, 128>(a, d->groups, s)));
+    return VIP_OK;
 }
 
 #if VIP_GEMM_H2
@@ -2044,15 +2110,11 @@ extern "C" int vip_conv2d_gated_nhwc_h2(const void* x, const void* gate, const v
 }
 
 extern "C" int vip_conv2d_kernel_name_h2(const vip_conv_desc* d, int has_residual, char* name, size_t cap) {
-    VIP_REQUIRE(d && name && cap > 0, VIP_ERR_BAD_ARG, "vip_conv2d_kernel_name_h2: null pointer");
-    static const char dummy[16] = {0};     // non-null stand-ins: nothing is dereferenced or launched in a dry run
-    g_dry = true;
-    g_pick = "";
-    const int st = conv2d_impl(dummy, nullptr, 0, dummy, nullptr, has_residual ? dummy : nullptr, const_cast<char*>(dummy), d, nullptr);
-    g_dry = false;
-    if (st != VIP_OK) return st;
-    snprintf(name, cap, "%s", g_pick);
-    return VIP_OK;
+    return kernel_query("vip_conv2d_kernel_name_h2", false, d, has_residual, 0, 0, name, cap);
+}
+
+extern "C" int vip_conv2d_kernel_variant_h2(const vip_conv_desc* d, int has_residual, char* variant, size_t cap) {
+    return kernel_query("vip_conv2d_kernel_variant_h2", true, d, has_residual, 0, 0, variant, cap);
 }
 #else
 extern "C" int vip_conv2d_nhwc_f16(const void* x, const void* w, const float* bias, const void* residual, void* y,
@@ -2076,25 +2138,27 @@ extern "C" int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const v
 
 extern "C" int vip_conv2d_kernel_name(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* name,
                                       size_t cap) {
-    VIP_REQUIRE(d && name && cap > 0, VIP_ERR_BAD_ARG, "vip_conv2d_kernel_name: null pointer");
-    static const char dummy[16] = {0};     // non-null stand-ins: nothing is dereferenced or launched in a dry run
-    g_dry = true;
-    g_pick = "";
-    const int st = conv2d_impl(dummy, has_gate ? dummy : nullptr, 0, dummy, nullptr, has_residual ? dummy : nullptr,
-                               const_cast<char*>(dummy), d, nullptr, has_w_lo ? dummy : nullptr);
-    g_dry = false;
-    if (st != VIP_OK) return st;
-    snprintf(name, cap, "%s", g_pick);
-    return VIP_OK;
+    return kernel_query("vip_conv2d_kernel_name", false, d, has_residual, has_gate, has_w_lo, name, cap);
+}
+
+extern "C" int vip_conv2d_kernel_variant(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* variant,
+                                         size_t cap) {
+    return kernel_query("vip_conv2d_kernel_variant", true, d, has_residual, has_gate, has_w_lo, variant, cap);
+}
+
+// the descriptor of a plain GEMM [M, K] x [K, N]: M images of one pixel, a 1 x 1 ungrouped convolution
+static vip_conv_desc gemm_desc(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int act_pre, int act_post) {
+    vip_conv_desc d;
+    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
+    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = ldc; d.cout_off = 0; d.ldr = ldr;
+    d.res_off = 0; d.ldw = ldw; d.act_pre = act_pre; d.act_post = act_post;
+    return d;
 }
 
 extern "C" int vip_gemm_bias_act_f16(const void* A, const void* W, const float* bias, const void* residual,
                                      void* C, int M, int N, int K, int lda, int ldw, int ldc, int ldr,
                                      int act_pre, int act_post, void* stream) {
-    vip_conv_desc d;
-    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
-    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = ldc; d.cout_off = 0; d.ldr = ldr;
-    d.res_off = 0; d.ldw = ldw; d.act_pre = act_pre; d.act_post = act_post;
+    const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, ldc, ldr, act_pre, act_post);
     return vip_conv2d_nhwc_f16(A, W, bias, residual, C, &d, stream);
 }
 
@@ -2124,20 +2188,14 @@ extern "C" int vip_ln_gemm_bias_act_f16(const void* A, const float* ln_gamma, co
                                         int ldc, int ldr, int act_pre, int act_post, void* stream) {
     VIP_REQUIRE(ln_gamma && ln_beta, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: null LayerNorm parameters");
     VIP_REQUIRE(ln_eps > 0.f, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: eps must be positive");
-    vip_conv_desc d;
-    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
-    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = ldc; d.cout_off = 0; d.ldr = ldr;
-    d.res_off = 0; d.ldw = ldw; d.act_pre = act_pre; d.act_post = act_post;
+    const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, ldc, ldr, act_pre, act_post);
     return conv2d_impl(A, nullptr, 0, W, bias, residual, C, &d, stream, nullptr, false, 1.f, nullptr, ln_gamma, ln_beta, ln_eps);
 }
 
 extern "C" int vip_gemm_split_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda,
                                   int ldw, int act, void* stream) {
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: M=%d (1..256 rows)", M);
-    vip_conv_desc d;
-    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
-    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = lda; d.cin_off = 0; d.ldy = 2 * N; d.cout_off = 0; d.ldr = 0;
-    d.res_off = 0; d.ldw = ldw; d.act_pre = act; d.act_post = VIP_ACT_NONE;
+    const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, 2 * N, 0, act, VIP_ACT_NONE);
     return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream);
 }
 
@@ -2145,10 +2203,7 @@ extern "C" int vip_gemm_split2_f16(const void* A, const void* W, const float* bi
                                    void* stream) {
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split2_f16: M=%d (1..256 rows)", M);
     VIP_REQUIRE(K % 8 == 0, VIP_ERR_ALIGNMENT, "vip_gemm_split2_f16: K must be a multiple of 8");
-    vip_conv_desc d;
-    d.B = M; d.H = 1; d.W = 1; d.Cin = K; d.Cout = N; d.kh = d.kw = 1; d.sh = d.sw = 1; d.pt = d.pl = 0;
-    d.Ho = d.Wo = 1; d.groups = 1; d.ldx = 2 * K; d.cin_off = 0; d.ldy = 2 * N; d.cout_off = 0; d.ldr = 0;
-    d.res_off = 0; d.ldw = ldw; d.act_pre = act; d.act_post = VIP_ACT_NONE;
+    const vip_conv_desc d = gemm_desc(M, N, K, 2 * K, ldw, 2 * N, 0, act, VIP_ACT_NONE);
     return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream, nullptr, true);
 }
 #endif  // VIP_GEMM_H2

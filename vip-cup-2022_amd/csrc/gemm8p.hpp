@@ -353,10 +353,8 @@ inline bool gemm8p_eligible(const ConvArgs& a) {
     return a.K % 64 == 0 && a.K >= 128 && a.x_span_bytes < 0x7FFF0000L && 2L * a.Cout_g * a.ldw < 0x7FFF0000L;
 }
 
-inline int launch_gemm8p(const ConvArgs& a0, int mode, hipStream_t s) {
-    ConvArgs a = a0;
-    a.m_blocks = (a.M + 255) / 256;
-    a.n_blocks = (a.Cout_g + 255) / 256;
+// pipe: gemm8p_kernel<true>, the schedule that needs K % 128 == 0
+inline int launch_gemm8p(const ConvArgs& a, int mode, bool pipe, hipStream_t s) {
     constexpr size_t smem = 8 * G8_SLOT;
     static bool attr_set = false;
     if (!attr_set) {
@@ -366,15 +364,10 @@ inline int launch_gemm8p(const ConvArgs& a0, int mode, hipStream_t s) {
     }
     // one 128 KiB workgroup per CU; VIP_G8P_PERSIST=0 launches one workgroup per tile instead (no fill / drain overlap)
     static const int persist = getenv("VIP_G8P_PERSIST") ? atoi(getenv("VIP_G8P_PERSIST")) : 1;
-    static const int cus = [] {
-        hipDeviceProp_t pr;
-        int dev = 0;
-        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-                   ? pr.multiProcessorCount : 256;
-    }();
+    const int cus = device_cus();
     const int tiles = a.m_blocks * a.n_blocks;
     const dim3 grid((unsigned)(persist ? (tiles < cus ? tiles : cus) : tiles));
-    if (a.K % 128 == 0) hipLaunchKernelGGL((gemm8p_kernel<true>), grid, dim3(512), smem, s, a, mode);
+    if (pipe) hipLaunchKernelGGL((gemm8p_kernel<true>), grid, dim3(512), smem, s, a, mode);
     else hipLaunchKernelGGL((gemm8p_kernel<false>), grid, dim3(512), smem, s, a, mode);
     return vip_launch_status("vip_conv2d_nhwc_f16(gemm8p)");
 }

@@ -245,7 +245,7 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
 }
 
 // LDS row stride for `chunks` 16-byte chunks: == 32 (mod 64) bytes, conflict-free for the fragment read pattern under
-// the ds_read_b128 lane grouping (see launch_pw in conv_igemm.hip)
+// the ds_read_b128 lane grouping (see plan_pw in conv_igemm.hip)
 static int mlp_stride(int chunks) {
     while ((chunks & 3) != 2) ++chunks;
     return chunks * 16;

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp_h2_kernel(MlpH2Args a) {
 }
 
 // LDS row stride for `chunks` 16-byte chunks: == 32 (mod 64) bytes, conflict-free for the fragment read pattern under the ds_read_b128
-// lane grouping (launch_pw in conv_igemm.hip)
+// lane grouping (plan_pw in conv_igemm.hip)
 int mlp_h2_stride(int chunks) {
     while ((chunks & 3) != 2) ++chunks;
     return chunks * 16;

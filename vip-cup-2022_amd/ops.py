@@ -529,19 +529,31 @@ def make_dense_weight(kernel_io: torch.Tensor, bias: Optional[torch.Tensor], dev
     return make_conv_weight(kernel_io.reshape(1, 1, *kernel_io.shape), bias, 1, device, None, pad_cout_to)
 
 
+def _conv_dry_run(query, d: "_abi.ConvDesc", *flags) -> Optional[str]:
+    buf = C.create_string_buffer(64)
+    return buf.value.decode() if query(C.byref(d), *map(int, flags), buf, 64) == 0 else None
+
+
 def conv_kernel_name(d: "_abi.ConvDesc", has_residual: bool, has_gate: bool = False, has_w_lo: bool = False) -> Optional[str]:
     """The kernel vip_conv2d_nhwc_f16 (/ _gated_ / _hilo_) launches for this descriptor - asked of the C dispatcher
     itself (a dry run of the selection, vip_conv2d_kernel_name); None when the combination is not supported."""
-    buf = C.create_string_buffer(64)
-    st = _abi.lib().vip_conv2d_kernel_name(C.byref(d), int(has_residual), int(has_gate), int(has_w_lo), buf, 64)
-    return buf.value.decode() if st == 0 else None
+    return _conv_dry_run(_abi.lib().vip_conv2d_kernel_name, d, has_residual, has_gate, has_w_lo)
 
 
 def conv_kernel_name_h2(d: "_abi.ConvDesc", has_residual: bool) -> Optional[str]:
     """the kernel vip_conv2d_nhwc_h2 launches for this descriptor (a dry run of the C dispatcher)"""
-    buf = C.create_string_buffer(64)
-    st = _abi.lib().vip_conv2d_kernel_name_h2(C.byref(d), int(has_residual), buf, 64)
-    return buf.value.decode() if st == 0 else None
+    return _conv_dry_run(_abi.lib().vip_conv2d_kernel_name_h2, d, has_residual)
+
+
+def conv_kernel_variant(d: "_abi.ConvDesc", has_residual: bool, has_gate: bool = False, has_w_lo: bool = False) -> Optional[str]:
+    """The same dry run down to the instantiation and its tile grid ("pwk_gemm<2,2> 65 x 4", "pwk_direct<2,gated> PT=4", "im2col<2>":
+    vip_conv2d_kernel_variant); None when the combination is not supported."""
+    return _conv_dry_run(_abi.lib().vip_conv2d_kernel_variant, d, has_residual, has_gate, has_w_lo)
+
+
+def conv_kernel_variant_h2(d: "_abi.ConvDesc", has_residual: bool) -> Optional[str]:
+    """the instantiation vip_conv2d_nhwc_h2 launches for this descriptor (vip_conv2d_kernel_variant_h2)"""
+    return _conv_dry_run(_abi.lib().vip_conv2d_kernel_variant_h2, d, has_residual)
 
 
 # Dry runs of the persistent launches (nothing is launched; each launcher calls the function its query calls).  A plan is
