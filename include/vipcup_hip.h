@@ -33,7 +33,8 @@ typedef enum vip_status {
     VIP_ERR_UNSUPPORTED = -3,  /* shape outside what the kernel family implements    */
     VIP_ERR_LAUNCH = -4,       /* hipGetLastError() != hipSuccess after the launch   */
     VIP_ERR_JPEG = -5,         /* stream is not a baseline JPEG this decoder accepts */
-    VIP_ERR_PNG = -6           /* stream is not a PNG this decoder accepts           */
+    VIP_ERR_PNG = -6,          /* stream is not a PNG this decoder accepts           */
+    VIP_ERR_WEBP = -7          /* stream is not a WebP this decoder accepts          */
 } vip_status;
 
 /* activation codes shared by every epilogue */
@@ -674,6 +675,58 @@ int vip_png_inflate_h(const uint8_t* const* png_h, const size_t* len_h, int n, v
  * (png_set_scale_16).  Adam7 passes are scattered to their pixel positions.  rgb_u8 [n][maxH][maxW][3]; pixels beyond an
  * image's size are left untouched. */
 int vip_png_unfilter_rgb_u8(uint8_t* filtered, const vip_png_desc* desc, int n, uint8_t* rgb_u8, int maxH, int maxW,
+                            void* stream);
+
+/* Lossless WebP (RIFF container, VP8L bitstream): the host decodes everything that is serial (prefix codes, LZ77, colour
+ * cache, the transforms' sub-images), the GPU undoes the transforms and writes 8-bit RGB.  Same output as
+ * vip_jpeg_idct_rgb_u8.  Lossy (VP8) and animated files are refused. */
+#define VIP_WEBP_PREDICTOR 0
+#define VIP_WEBP_CROSS_COLOR 1
+#define VIP_WEBP_SUBTRACT_GREEN 2
+#define VIP_WEBP_COLOR_INDEXING 3
+/* vip_webp_desc.stats: what the host decoder met in the stream (coverage word for the tests) */
+#define VIP_WEBP_STAT_CACHE 1         /* a colour cache was used                    */
+#define VIP_WEBP_STAT_META 2          /* a meta prefix image was used               */
+#define VIP_WEBP_STAT_SIMPLE 4        /* a simple prefix code was read              */
+#define VIP_WEBP_STAT_MAX_SYMBOL 8    /* a normal code with max_symbol was read     */
+#define VIP_WEBP_STAT_REP16 16        /* code-length repeat codes 16, 17, 18        */
+#define VIP_WEBP_STAT_REP17 32
+#define VIP_WEBP_STAT_REP18 64
+#define VIP_WEBP_STAT_PLANE 128       /* a backward reference with a plane code (<= 120) */
+#define VIP_WEBP_STAT_LINEAR 256      /* a backward reference with a linear distance     */
+typedef struct vip_webp_desc {
+    int32_t width, height;            /* image size                                                          */
+    int32_t has_alpha;                /* the header's alpha hint (alpha is dropped either way)               */
+    int32_t coded_width;              /* width of the entropy-coded main image: < width when colour indexing
+                                         bundles 2, 4 or 8 pixels per coded pixel                            */
+    int32_t n_transforms;             /* 0..4                                                                */
+    int32_t stats;                    /* VIP_WEBP_STAT_* bits, filled by vip_webp_entropy_h                  */
+    int32_t type[4];                  /* per transform, in the order read: VIP_WEBP_*                        */
+    int32_t bits[4];                  /* block size bits (predictor, cross-colour) / pixel bundling bits     */
+    int32_t xsize[4];                 /* the image width the transform works at                              */
+    int64_t stream_off;               /* byte offset of the image's words in the batch buffer                */
+    int64_t data_off[4];              /* sub-image / 256-entry table of the transform, relative to stream_off */
+    int64_t argb_off;                 /* the main image's 32-bit ARGB words, relative to stream_off; width * height
+                                         words are reserved (coded_width * height are written by the host)   */
+} vip_webp_desc;
+
+/* Host: walk the RIFF container (VP8L, or VP8X followed by VP8L), read the VP8L header and fill width, height and
+ * has_alpha (everything else zero); *stream_bytes_h = an upper bound of the image's share of the batch buffer:
+ * width * height words for the main image, ceil(w/4) * ceil(h/4) words for each of a predictor and a cross-colour
+ * sub-image, 256 words of palette.  VIP_MAX_JPEG_PIXELS applies as for PNG: larger -> VIP_ERR_WEBP. */
+int vip_webp_probe_h(const uint8_t* webp_h, size_t len, vip_webp_desc* desc_h, size_t* stream_bytes_h);
+
+/* Host, multithreaded: decode the VP8L streams of n WebP files - transform headers and their sub-images, colour cache,
+ * meta prefix image, prefix codes, LZ77 - and write per image the still-transformed ARGB words and the transforms' data
+ * back to back in stream_h (each image takes its probe bound); the palette is delta-decoded and zero-padded to 256
+ * entries.  No transform is undone.  Errors name the image ("webp image K: ..."). */
+int vip_webp_entropy_h(const uint8_t* const* webp_h, const size_t* len_h, int n, vip_webp_desc* desc_h, uint8_t* stream_h,
+                       size_t stream_cap, size_t* stream_used_h, int threads);
+
+/* Device: undo the transforms in the reverse of the order read, IN PLACE in `words` (a device copy of what
+ * vip_webp_entropy_h produced), drop alpha and write rgb_u8 [n][maxH][maxW][3]; pixels beyond an image's size are left
+ * untouched and an all-zero descriptor writes nothing.  A palette index past the table is transparent black. */
+int vip_webp_inverse_rgb_u8(uint8_t* words, const vip_webp_desc* desc, int n, uint8_t* rgb_u8, int maxH, int maxW,
                             void* stream);
 
 /* Host: the 1025x2 coefficient table of TensorFlow's legacy bicubic kernel (Keys a = -0.5). */

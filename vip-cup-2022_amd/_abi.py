@@ -41,6 +41,13 @@ class PngDesc(C.Structure):
                 ("palette", (C.c_uint8 * 3) * 256)]
 
 
+class WebpDesc(C.Structure):
+    """mirror of vip_webp_desc (include/vipcup_hip.h)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("has_alpha", C.c_int32), ("coded_width", C.c_int32),
+                ("n_transforms", C.c_int32), ("stats", C.c_int32), ("type", C.c_int32 * 4), ("bits", C.c_int32 * 4),
+                ("xsize", C.c_int32 * 4), ("stream_off", C.c_int64), ("data_off", C.c_int64 * 4), ("argb_off", C.c_int64)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/vipcup_hip.h declares
@@ -111,6 +118,9 @@ SIGNATURES = {
     "vip_png_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_png_inflate_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_png_unfilter_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
+    "vip_webp_probe_h": (_i, [_vp, _sz, _vp, _vp]),
+    "vip_webp_entropy_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
+    "vip_webp_inverse_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
     "vip_bicubic_table_f32": (_i, [_vp]),
     "vip_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tile_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),

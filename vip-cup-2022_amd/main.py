@@ -25,7 +25,8 @@
 
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
 155-164); the output CSV has columns ``filename,logit`` with logit in {0.0, 1.0} = (ensemble mean > 0.487)
-(main.py:143-145,225).  ``--scores-out`` additionally writes the continuous ensemble mean (the reference keeps
+(main.py:143-145,225).  The files may be JPEG, PNG or lossless WebP in any mix; the format is picked from each file's first
+bytes (lossy and animated WebP are refused).  ``--scores-out`` additionally writes the continuous ensemble mean (the reference keeps
 it only in memory).  The ensemble manifest is ``ckpts/ckpts.json`` ([name, [H,W], idx],
 main.py:171-198); members whose graph is not built yet are reported and skipped only under ``--allow-missing``.
 ``--heatmaps DIR`` additionally writes, per input file, the ensemble's Grad-CAM evidence map (``<name>.npy``: fp32 in [0, 1] at the

@@ -31,7 +31,7 @@ def bicubic_table(device) -> torch.Tensor:
     return _TABLE_DEV[key]
 
 
-# per image, JPEG and PNG (csrc/png_host.cpp reads the same variable); the task's images are 200 x 200
+# per image, JPEG, PNG and WebP (csrc/png_host.cpp and csrc/webp_host.cpp read the same variable); the task's images are 200 x 200
 MAX_JPEG_PIXELS = int(os.environ.get("VIP_MAX_JPEG_PIXELS", str(64 << 20)))
 
 
@@ -276,12 +276,24 @@ class PngStage:
         return len(self.desc)
 
 
-class MixedStage:
-    """``host_decode`` of a batch that holds PNGs: the PNG subset inflated, the JPEG subset (if any) entropy-decoded,
-    and where each image of the batch sits in them."""
+class WebpStage:
+    """What ``entropy_decode_webps`` returns: ``desc`` (ctypes array of WebpDesc) and the batch's still-transformed ARGB
+    words with the transforms' data (uint8 numpy array, or a page-locked torch tensor; 4-byte aligned)."""
 
-    def __init__(self, n, png_idx, png, jpeg_idx, jpeg):
+    def __init__(self, desc, stream):
+        self.desc, self.stream = desc, stream
+
+    def __len__(self):
+        return len(self.desc)
+
+
+class MixedStage:
+    """``host_decode`` of a batch that is not all JPEG and not all WebP: the PNG subset (if any) inflated, the JPEG subset
+    (if any) entropy-decoded, the WebP subset (if any) entropy-decoded, and where each image of the batch sits in them."""
+
+    def __init__(self, n, png_idx, png, jpeg_idx, jpeg, webp_idx=(), webp=None):
         self.n, self.png_idx, self.png, self.jpeg_idx, self.jpeg = n, png_idx, png, jpeg_idx, jpeg
+        self.webp_idx, self.webp = webp_idx, webp
 
     def __len__(self):
         return self.n
@@ -290,7 +302,7 @@ class MixedStage:
 def _remap_index(msg: str, index: Optional[Sequence[int]]) -> str:
     if index is None:
         return msg
-    return re.sub(r"png image (\d+)", lambda m: f"png image {index[int(m.group(1))]}", msg)
+    return re.sub(r"(png|webp) image (\d+)", lambda m: f"{m.group(1)} image {index[int(m.group(2))]}", msg)
 
 
 def inflate_pngs(pngs: Sequence[bytes], threads: int = 0, pinned: bool = False,
@@ -359,41 +371,116 @@ def decode_png_stage(staged: PngStage, device="cuda") -> DecodedBatch:
     return DecodedBatch(rgb, sizes, sizes_host)
 
 
+def entropy_decode_webps(webps: Sequence[bytes], threads: int = 0, pinned: bool = False,
+                         index: Optional[Sequence[int]] = None) -> WebpStage:
+    """Host stage of the lossless WebP path, the twin of ``inflate_pngs``: container walk + everything serial in the VP8L
+    streams (prefix codes, LZ77, colour cache, the transforms' sub-images; C++ threads, the GIL is released inside the
+    ctypes call).  ``index``: the batch position of every WebP, used in error messages.  Raises VipError (naming the
+    image) for a lossy or animated file, a damaged stream, or a size beyond VIP_MAX_JPEG_PIXELS."""
+    lib = _abi.lib()
+    n = len(webps)
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in webps]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in webps])
+    desc = (_abi.WebpDesc * n)()
+    total = 0
+    tmp = _abi.WebpDesc()
+    need = C.c_size_t(0)
+    for i in range(n):
+        where = i if index is None else index[i]
+        st = lib.vip_webp_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
+        if st != 0:
+            raise _abi.VipError(f"webp image {where}: vip_webp_probe_h failed with vip_status {st}: "
+                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
+        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"webp image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+        total += need.value
+    size = total + 4                                  # whole words, and never empty
+    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
+    stream = stream_t.numpy() if pinned else np.empty((size // 4,), dtype=np.uint32).view(np.uint8)
+    used = C.c_size_t(0)
+    st = lib.vip_webp_entropy_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
+    if st != 0:
+        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
+        raise _abi.VipError(f"vip_webp_entropy_h failed with vip_status {st}: {msg}")
+    return WebpStage(desc, stream_t if pinned else stream)
+
+
+def _webp_into(stage: WebpStage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
+    """Launch the inverse-transform kernel for the WebPs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
+    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
+    full = (_abi.WebpDesc * n)()                      # the other rows get all-zero descriptors: nothing written
+    for k, i in enumerate(slots):
+        full[i] = stage.desc[k]
+    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
+    if isinstance(stage.stream, torch.Tensor):
+        stream_d = stage.stream.to(device, non_blocking=True)
+    else:
+        stream_d = torch.from_numpy(stage.stream).to(device)
+    _launch("vip_webp_inverse_rgb_u8", _p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW)
+
+
+def decode_webp_stage(staged: WebpStage, device="cuda") -> DecodedBatch:
+    """Device half of the lossless WebP path, the twin of ``decode_png_stage``: ``staged`` = ``entropy_decode_webps(...)``.
+    Undoes the VP8L transforms (predictor, cross-colour, subtract-green, colour indexing) in the reverse of the order
+    read and drops alpha: the RGB of libwebp's decoder, bit for bit."""
+    n = len(staged.desc)
+    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
+    maxH = max(h for h, _ in sizes_host)
+    maxW = max(w for _, w in sizes_host)
+    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
+    _webp_into(staged, range(n), n, rgb, device)
+    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
+    return DecodedBatch(rgb, sizes, sizes_host)
+
+
 def image_format(raw: bytes, i: int = 0) -> str:
-    """"jpeg" or "png", from the magic bytes (not the file name); anything else raises VipError naming image ``i``."""
+    """"jpeg", "png" or "webp", from the magic bytes (not the file name); anything else raises VipError naming image ``i``."""
     if raw[:2] == b"\xff\xd8":
         return "jpeg"
     if raw[:8] == PNG_SIGNATURE:
         return "png"
-    raise _abi.VipError(f"image {i}: neither a JPEG (FF D8) nor a PNG (89 50 4E 47 0D 0A 1A 0A) signature")
+    if raw[:4] == b"RIFF" and raw[8:12] == b"WEBP":
+        return "webp"
+    raise _abi.VipError(f"image {i}: neither a JPEG (FF D8), a PNG (89 50 4E 47 0D 0A 1A 0A) nor a WebP (RIFF....WEBP) signature")
 
 
 def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False):
     """Host stage of ``decode_images``: picks the format of every image by its magic bytes.  An all-JPEG batch returns
-    exactly what ``entropy_decode`` returns (same calls, same buffers); a batch with PNGs returns a ``MixedStage``."""
+    exactly what ``entropy_decode`` returns (same calls, same buffers), an all-WebP batch a ``WebpStage``; anything else
+    returns a ``MixedStage``.  Lossy and animated WebPs are refused here, before any launch."""
     kinds = [image_format(r, i) for i, r in enumerate(raws)]
-    if "png" not in kinds:
+    if "png" not in kinds and "webp" not in kinds:
         return entropy_decode(raws, threads, pinned)
+    if all(k == "webp" for k in kinds):
+        return entropy_decode_webps(raws, threads, pinned)
     png_idx = [i for i, k in enumerate(kinds) if k == "png"]
     jpeg_idx = [i for i, k in enumerate(kinds) if k == "jpeg"]
-    png = inflate_pngs([raws[i] for i in png_idx], threads, pinned, index=png_idx)
+    webp_idx = [i for i, k in enumerate(kinds) if k == "webp"]
+    png = inflate_pngs([raws[i] for i in png_idx], threads, pinned, index=png_idx) if png_idx else None
     jpeg = entropy_decode([raws[i] for i in jpeg_idx], threads, pinned) if jpeg_idx else None
-    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg)
+    webp = entropy_decode_webps([raws[i] for i in webp_idx], threads, pinned, index=webp_idx) if webp_idx else None
+    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg, webp_idx, webp)
 
 
 def decode_staged(staged, device="cuda") -> DecodedBatch:
-    """Device half of ``decode_images``: ``staged`` = ``host_decode(...)`` (or ``entropy_decode`` / ``inflate_pngs``).  In a
-    mixed batch the PNG kernel writes straight into the batch's pixels and the JPEG subset, decoded as ``decode_entropy``
-    does, is copied into its rows."""
+    """Device half of ``decode_images``: ``staged`` = ``host_decode(...)`` (or ``entropy_decode`` / ``inflate_pngs`` /
+    ``entropy_decode_webps``).  In a mixed batch the PNG and WebP kernels write straight into the batch's pixels and the
+    JPEG subset, decoded as ``decode_entropy`` does, is copied into its rows."""
     if isinstance(staged, tuple):
         return decode_entropy(staged, device)
     if isinstance(staged, PngStage):
         return decode_png_stage(staged, device)
+    if isinstance(staged, WebpStage):
+        return decode_webp_stage(staged, device)
     n = staged.n
     sizes_host: List[Tuple[int, int]] = [(0, 0)] * n
-    for k, i in enumerate(staged.png_idx):
-        d = staged.png.desc[k]
-        sizes_host[i] = (int(d.height), int(d.width))
+    for idx, sub in ((staged.png_idx, staged.png), (staged.webp_idx, staged.webp)):
+        for k, i in enumerate(idx):
+            d = sub.desc[k]
+            sizes_host[i] = (int(d.height), int(d.width))
     jb = None
     if staged.jpeg is not None:
         jb = decode_entropy(staged.jpeg, device)
@@ -402,7 +489,10 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
     maxH = max(h for h, _ in sizes_host)
     maxW = max(w for _, w in sizes_host)
     rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    _png_into(staged.png, staged.png_idx, n, rgb, device)
+    if staged.png is not None:
+        _png_into(staged.png, staged.png_idx, n, rgb, device)
+    if staged.webp is not None:
+        _webp_into(staged.webp, staged.webp_idx, n, rgb, device)
     if jb is not None:
         rows = torch.tensor(staged.jpeg_idx, dtype=torch.long, device=device)
         rgb[rows, :jb.rgb.shape[1], :jb.rgb.shape[2]] = jb.rgb
@@ -411,8 +501,8 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
 
 
 def decode_images(raws: Sequence[bytes], device="cuda", threads: int = 0) -> DecodedBatch:
-    """``build_decoder(ext=...)`` for a batch of JPEG and / or PNG byte strings (dataset/dataset.py:22-30), the format
-    of each image picked from its content."""
+    """``build_decoder(ext=...)`` for a batch of JPEG, PNG and / or lossless WebP byte strings (dataset/dataset.py:22-30),
+    the format of each image picked from its content."""
     return decode_staged(host_decode(raws, threads), device)
 
 
