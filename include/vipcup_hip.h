@@ -729,6 +729,114 @@ int vip_webp_entropy_h(const uint8_t* const* webp_h, const size_t* len_h, int n,
 int vip_webp_inverse_rgb_u8(uint8_t* words, const vip_webp_desc* desc, int n, uint8_t* rgb_u8, int maxH, int maxW,
                             void* stream);
 
+/* Lossy WebP (RIFF container, a VP8 key frame, RFC 6386): the host reads everything the boolean decoder carries - frame
+ * header, per-macroblock modes, residual tokens - and dequantises; the GPU predicts, adds the residuals, runs the in-loop
+ * filter, upsamples the chroma planes ("fancy" 9-3-3-1) and converts to 8-bit RGB: libwebp's decoder, bit for bit.  Alpha
+ * (an ALPH chunk) is dropped.  Opt-in: vip_webp_probe_h / vip_webp_entropy_h keep refusing a `VP8 ` chunk. */
+/* vip_vp8_desc.stats: what the host decoder met in the stream (coverage word for the tests) */
+#define VIP_VP8_STAT_SEGMENTS (1ll << 0)        /* segmentation enabled                                   */
+#define VIP_VP8_STAT_MAP_UPDATE (1ll << 1)      /* a segment map was read                                 */
+#define VIP_VP8_STAT_SEG_DELTA (1ll << 2)       /* segment data in delta mode                             */
+#define VIP_VP8_STAT_SIMPLE_FILTER (1ll << 3)
+#define VIP_VP8_STAT_NORMAL_FILTER (1ll << 4)
+#define VIP_VP8_STAT_SHARPNESS (1ll << 5)       /* sharpness > 0 with a filter on                         */
+#define VIP_VP8_STAT_LEVEL0_MB (1ll << 6)       /* a macroblock at filter level 0 in a filtered frame     */
+#define VIP_VP8_STAT_LF_DELTA (1ll << 7)        /* loop-filter deltas enabled                             */
+#define VIP_VP8_STAT_PARTS2 (1ll << 8)          /* 2, 4, 8 token partitions                               */
+#define VIP_VP8_STAT_PARTS4 (1ll << 9)
+#define VIP_VP8_STAT_PARTS8 (1ll << 10)
+#define VIP_VP8_STAT_BPRED (1ll << 11)          /* a macroblock with 16 sub-block modes                   */
+#define VIP_VP8_STAT_BMODE0 (1ll << 12)         /* .. << 21: one bit per sub-block mode (VIP_VP8_B_*)     */
+#define VIP_VP8_STAT_YMODE0 (1ll << 22)         /* .. << 25: one bit per 16x16 mode (DC, TM, V, H)        */
+#define VIP_VP8_STAT_UVMODE0 (1ll << 26)        /* .. << 29: one bit per chroma mode (DC, TM, V, H)       */
+#define VIP_VP8_STAT_SKIP (1ll << 30)           /* a macroblock with its skip flag set                    */
+#define VIP_VP8_STAT_PROBA_UPDATE (1ll << 31)   /* a coefficient probability update was read              */
+#define VIP_VP8_STAT_CAT6 (1ll << 32)           /* a token of the largest category                        */
+#define VIP_VP8_STAT_Y2_AC (1ll << 33)          /* a Y2 block with more than its DC                       */
+#define VIP_VP8_STAT_DC_ONLY (1ll << 34)        /* a coded block with only its DC                         */
+#define VIP_VP8_STAT_FULL_BLOCK (1ll << 35)     /* a coded block with AC coefficients                     */
+#define VIP_VP8_STAT_ALL ((1ll << 36) - 1)
+/* modes, in libwebp's numbering; DC, TM, V, H double as the 16x16 and chroma modes */
+#define VIP_VP8_B_DC 0
+#define VIP_VP8_B_TM 1
+#define VIP_VP8_B_VE 2
+#define VIP_VP8_B_HE 3
+#define VIP_VP8_B_RD 4
+#define VIP_VP8_B_VR 5
+#define VIP_VP8_B_LD 6
+#define VIP_VP8_B_VL 7
+#define VIP_VP8_B_HD 8
+#define VIP_VP8_B_HU 9
+#define VIP_VP8_B_PRED 4                        /* vip_vp8_mb.ymode of a macroblock with sub-block modes   */
+/* one macroblock, everything resolved on the host.  Coded blocks are numbered Y 0..15 (raster), U 16..19, V 20..23,
+ * Y2 24; their 16 dequantised int16 coefficients (raster order) lie back to back, in that order, from block coef_idx of
+ * the image's coefficient area.  A luma block of a 16x16-predicted macroblock takes its DC from the inverse WHT of Y2
+ * (when Y2 is coded) and its stored [0] is 0. */
+typedef struct vip_vp8_mb {
+    uint8_t ymode;                    /* VIP_VP8_B_DC / TM / VE / HE for 16x16 prediction, VIP_VP8_B_PRED             */
+    uint8_t uvmode;                   /* VIP_VP8_B_DC / TM / VE / HE                                                  */
+    uint8_t flevel;                   /* loop filter level 0..63, 0 = not filtered                                    */
+    uint8_t ilevel;                   /* interior limit                                                               */
+    uint8_t hev;                      /* high edge variance threshold                                                 */
+    uint8_t inner;                    /* 1: the inner edges are filtered too                                          */
+    uint8_t segment, skip;            /* as read (not used by the device)                                             */
+    uint8_t bmodes[16];               /* sub-block modes of a VIP_VP8_B_PRED macroblock                               */
+    uint32_t nz;                      /* bit b: block b is coded (25 bits)                                            */
+    uint32_t dc_only;                 /* bit b: only [0] of coded block b is non-zero                                 */
+    uint32_t coef_idx;                /* first coded block of the macroblock, in blocks of 16 coefficients            */
+    uint32_t reserved;
+} vip_vp8_mb;
+typedef struct vip_vp8_desc {
+    int32_t width, height;            /* image size                                                                   */
+    int32_t mb_w, mb_h;               /* in macroblocks                                                               */
+    int32_t has_alpha;                /* the VP8X alpha flag (alpha is dropped either way)                            */
+    int32_t filter_type;              /* 0 none, 1 simple, 2 normal                                                   */
+    int64_t stats;                    /* VIP_VP8_STAT_* bits, filled by vip_vp8_entropy_h                             */
+    int64_t stream_off;               /* byte offset of the image's data in the batch buffer (8-byte aligned)         */
+    int64_t mb_off;                   /* mb_w * mb_h vip_vp8_mb records, relative to stream_off                       */
+    int64_t coef_off;                 /* the coded blocks' int16 coefficients, relative to stream_off                 */
+    int64_t coef_blocks;              /* how many blocks of 16 coefficients                                           */
+    int64_t plane_off;                /* byte offset of the image's Y / U / V planes in the device scratch buffer:
+                                         mb_w * mb_h * 384 bytes, Y [16 mb_h][16 mb_w] then U and V [8 mb_h][8 mb_w]  */
+} vip_vp8_desc;
+
+/* Host: walk the RIFF container (a `VP8 ` chunk, alone or behind VP8X; ALPH, ICCP, EXIF, XMP and unknown chunks are
+ * skipped), read the frame tag and the key-frame start code and fill width, height, mb_w, mb_h and has_alpha (everything
+ * else zero); *stream_bytes_h = an upper bound of the image's share of the batch buffer (every block of every macroblock
+ * coded).  Refused with VIP_ERR_WEBP: animation, an inter frame, a frame not shown, profile > 3, a first partition past
+ * the chunk, a VP8X canvas that differs from the frame, zero sizes, sizes beyond VIP_MAX_JPEG_PIXELS; a VP8L file too
+ * (that is vip_webp_probe_h's). */
+int vip_vp8_probe_h(const uint8_t* webp_h, size_t len, vip_vp8_desc* desc_h, size_t* stream_bytes_h);
+
+/* Host, multithreaded (images over up to `threads` workers): decode the frame header, the macroblock modes and the
+ * residual tokens of n lossy WebP files, dequantise as libwebp does, and write per image the macroblock records and the
+ * coded blocks' coefficients back to back in stream_h (8-byte aligned; only what is used: *stream_used_h <= the sum of
+ * the probe bounds, and the same bytes whatever `threads` is).  plane_off is filled for a scratch buffer that holds the
+ * batch's planes back to back (vip_vp8_scratch_bytes).  Errors name the image ("webp image K: ..."). */
+int vip_vp8_entropy_h(const uint8_t* const* webp_h, const size_t* len_h, int n, vip_vp8_desc* desc_h, uint8_t* stream_h,
+                      size_t stream_cap, size_t* stream_used_h, int threads);
+
+/* Host: *bytes_h = the size of the device scratch buffer the descriptors' planes need (at least 16). */
+int vip_vp8_scratch_bytes(const vip_vp8_desc* desc_h, int n, size_t* bytes_h);
+
+/* Device: from a device copy of what vip_vp8_entropy_h produced (stream, stream_bytes of it) reconstruct every image -
+ * intra prediction + inverse WHT / DCT into the planes in `scratch`, then the in-loop filter in place, then chroma
+ * upsampling and YUV -> RGB - and write rgb_u8 [n][maxH][maxW][3], cropped to the image's size; pixels beyond it are
+ * left untouched and an all-zero descriptor writes nothing.  A descriptor whose records or planes do not fit
+ * stream_bytes / scratch_bytes is skipped. */
+int vip_vp8_reconstruct_rgb_u8(const uint8_t* stream_d, size_t stream_bytes, const vip_vp8_desc* desc, int n, uint8_t* scratch,
+                               size_t scratch_bytes, uint8_t* rgb_u8, int maxH, int maxW, void* stream);
+
+/* The same with a choice of stages, for measurements (tools/bench_webp_lossy.py): reconstruction and filter are one
+ * launch, the output another; a stage left out leaves the planes in `scratch` as the call found them. */
+#define VIP_VP8_STAGE_RECON 1
+#define VIP_VP8_STAGE_FILTER 2
+#define VIP_VP8_STAGE_OUTPUT 4
+#define VIP_VP8_STAGE_LDS_PLANES 8    /* with RECON: images of up to 13 x 13 macroblocks keep their planes in LDS until the end */
+int vip_vp8_default_stages(void);      /* the mask vip_vp8_reconstruct_rgb_u8 runs */
+int vip_vp8_reconstruct_stages_rgb_u8(const uint8_t* stream_d, size_t stream_bytes, const vip_vp8_desc* desc, int n, uint8_t* scratch,
+                                      size_t scratch_bytes, uint8_t* rgb_u8, int maxH, int maxW, int stages, void* stream);
+
 /* Host: the 1025x2 coefficient table of TensorFlow's legacy bicubic kernel (Keys a = -0.5). */
 int vip_bicubic_table_f32(float* table_h);
 

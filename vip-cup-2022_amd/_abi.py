@@ -48,6 +48,20 @@ class WebpDesc(C.Structure):
                 ("xsize", C.c_int32 * 4), ("stream_off", C.c_int64), ("data_off", C.c_int64 * 4), ("argb_off", C.c_int64)]
 
 
+class Vp8Mb(C.Structure):
+    """mirror of vip_vp8_mb (include/vipcup_hip.h)"""
+    _fields_ = [("ymode", C.c_uint8), ("uvmode", C.c_uint8), ("flevel", C.c_uint8), ("ilevel", C.c_uint8), ("hev", C.c_uint8),
+                ("inner", C.c_uint8), ("segment", C.c_uint8), ("skip", C.c_uint8), ("bmodes", C.c_uint8 * 16), ("nz", C.c_uint32),
+                ("dc_only", C.c_uint32), ("coef_idx", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Vp8Desc(C.Structure):
+    """mirror of vip_vp8_desc (include/vipcup_hip.h)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mb_w", C.c_int32), ("mb_h", C.c_int32), ("has_alpha", C.c_int32),
+                ("filter_type", C.c_int32), ("stats", C.c_int64), ("stream_off", C.c_int64), ("mb_off", C.c_int64),
+                ("coef_off", C.c_int64), ("coef_blocks", C.c_int64), ("plane_off", C.c_int64)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/vipcup_hip.h declares
@@ -121,6 +135,12 @@ SIGNATURES = {
     "vip_webp_probe_h": (_i, [_vp, _sz, _vp, _vp]),
     "vip_webp_entropy_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
     "vip_webp_inverse_rgb_u8": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp]),
+    "vip_vp8_probe_h": (_i, [_vp, _sz, _vp, _vp]),
+    "vip_vp8_entropy_h": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _i]),
+    "vip_vp8_scratch_bytes": (_i, [_vp, _i, _vp]),
+    "vip_vp8_reconstruct_rgb_u8": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _vp]),
+    "vip_vp8_default_stages": (_i, []),
+    "vip_vp8_reconstruct_stages_rgb_u8": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _i, _vp]),
     "vip_bicubic_table_f32": (_i, [_vp]),
     "vip_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tile_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),

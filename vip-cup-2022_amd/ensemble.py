@@ -189,8 +189,9 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
                 batch_size: int = REF_BATCH, rank: int = 0, world: int = 1, dist=None,
                 scorer: Optional[Callable] = None, tta: int = 1, tta_seed: int = 0,
                 shard: str = "images", costs: Optional[Sequence[float]] = None,
-                batch_scorer: Optional[Callable] = None) -> np.ndarray:
+                batch_scorer: Optional[Callable] = None, lossy_webp: Optional[bool] = None) -> np.ndarray:
     """Score images [0, n_images) with every member; returns ``[M, n_images]`` fp32 probabilities on every rank.
+    ``lossy_webp``: the lossy WebP switch of ``pipeline.host_decode`` (None: the ``VIP_WEBP_LOSSY`` knob).
 
     ``jpegs_for(lo, hi)`` returns the JPEG / PNG byte strings of images lo..hi-1 (read lazily, per batch).
     ``members`` = [(spec, model)] with ``spec.input_hw`` and ``model.predict(x) -> [n, C]``.
@@ -218,7 +219,7 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
         if scorer is not None:
             return raws
         from . import pipeline
-        return pipeline.host_decode(raws, pinned=True)
+        return pipeline.host_decode(raws, pinned=True, lossy_webp=lossy_webp)
 
     # read-ahead (the overlap the reference gets from tf.data's prefetch, dataset/dataset.py:101): while the GPU scores batch i the
     # host stage of batch i+2 runs on a worker thread, and the DEVICE half of batch i+1 (H2D of the coefficients, IDCT, colour) is
@@ -406,14 +407,14 @@ class MemberStreams:
             main.wait_event(done)
 
 
-def measure_costs(members, raws: Sequence[bytes], dist=None, rank: int = 0) -> List[float]:
+def measure_costs(members, raws: Sequence[bytes], dist=None, rank: int = 0, lossy_webp: Optional[bool] = None) -> List[float]:
     """ms per image of every member on a sample batch (JPEG / PNG byte strings), timed on rank 0 (a serial pass, the one
     ``MemberStreams._calibrate`` makes) and broadcast so that every rank derives the SAME hybrid ShardPlan.  Set-up traffic
     (one float per member), not part of the per-image data path."""
     from . import pipeline
     costs = torch.zeros((len(members),), dtype=torch.float64, device="cuda")
     if rank == 0:
-        batch = pipeline.decode_images(list(raws))
+        batch = pipeline.decode_images(list(raws), lossy_webp=lossy_webp)
         inputs = member_inputs(batch, members)
         ms = MemberStreams(2)
         ms._calibrate(members, inputs)          # warm-up: first-launch costs (module load, attribute calls)

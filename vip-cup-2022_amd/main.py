@@ -1,6 +1,6 @@
 """Drop-in CLI for the reference entry point (main.py:151-235):
 
-    python3 vip-cup-2022_amd/main.py <input.csv> <output.csv> [--scores-out scores.csv] [--synthetic]
+    python3 vip-cup-2022_amd/main.py <input.csv> <output.csv> [--scores-out scores.csv] [--synthetic] [--webp-lossy]
                                      [--heatmaps DIR [--heatmap-format npy|png] [--heatmap-members]]
                                      [--stress-jpeg Q[,Q...] --stress-out FILE.csv [--stress-subsampling 420|444]]
                                      [--stress-resize P[,P...] --stress-out FILE.csv [--stress-resize-filter bilinear|bicubic|lanczos]]
@@ -26,7 +26,8 @@
 Same contract: the input CSV has a ``filename`` column with paths relative to the CSV's directory (main.py:77-79,
 155-164); the output CSV has columns ``filename,logit`` with logit in {0.0, 1.0} = (ensemble mean > 0.487)
 (main.py:143-145,225).  The files may be JPEG, PNG or lossless WebP in any mix; the format is picked from each file's first
-bytes (lossy and animated WebP are refused).  ``--scores-out`` additionally writes the continuous ensemble mean (the reference keeps
+bytes (animated WebP is refused, and so is lossy WebP unless ``--webp-lossy`` or ``VIP_WEBP_LOSSY=1`` turns its decoder on: VP8 key
+frames, libwebp's pixels bit for bit; off by default).  ``--scores-out`` additionally writes the continuous ensemble mean (the reference keeps
 it only in memory).  The ensemble manifest is ``ckpts/ckpts.json`` ([name, [H,W], idx],
 main.py:171-198); members whose graph is not built yet are reported and skipped only under ``--allow-missing``.
 ``--heatmaps DIR`` additionally writes, per input file, the ensemble's Grad-CAM evidence map (``<name>.npy``: fp32 in [0, 1] at the
@@ -511,6 +512,9 @@ def main(argv=None):
     ap.add_argument("--scores-out", default=None)
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--allow-missing", action="store_true")
+    ap.add_argument("--webp-lossy", action="store_true",
+                    help="accept lossy WebP files (VP8 key frames; env VIP_WEBP_LOSSY=1 does the same): token decode on the host, "
+                         "reconstruction on the GPU, libwebp's pixels bit for bit.  Off by default: such files are refused")
     ap.add_argument("--ckpt-cfg", default=os.path.join(HERE, "ckpts", "ckpts.json"))
     ap.add_argument("--batch-size", type=int, default=128)  # main.py:85
     ap.add_argument("--debug", type=int, default=0)         # main.py:82-83: first 100 images
@@ -886,12 +890,14 @@ def main(argv=None):
 
     t0 = time.time()
     costs = None
+    lossy_webp = True if a.webp_lossy else None          # None: the VIP_WEBP_LOSSY knob decides
     if a.shard == "hybrid" and world > 1:
-        costs = ensemble.measure_costs(members, jpegs_for(0, min(len(paths), a.batch_size)), dist, rank)
+        costs = ensemble.measure_costs(members, jpegs_for(0, min(len(paths), a.batch_size)), dist, rank, lossy_webp=lossy_webp)
         if rank == 0:
             print("> HYBRID PLAN:", ensemble.ShardPlan("hybrid", len(members), world, costs).describe())
     per_model = ensemble.score_files(jpegs_for, len(paths), members, a.batch_size, rank, world, dist,
-                                     tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer)
+                                     tta=a.tta, tta_seed=a.tta_seed, shard=a.shard, costs=costs, batch_scorer=batch_scorer,
+                                     lossy_webp=lossy_webp)
     uniq, score, decision = ensemble.aggregate(names, per_model)
     stressed = None
     if stress_run:                                      # the one extra collective of a stress run: every rank's [V, M, n_local] rows

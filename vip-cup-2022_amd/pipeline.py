@@ -287,13 +287,27 @@ class WebpStage:
         return len(self.desc)
 
 
+class Vp8Stage:
+    """What ``entropy_decode_vp8s`` returns: ``desc`` (ctypes array of Vp8Desc), the batch's macroblock records and dequantised
+    coefficients (uint8 numpy array, or a page-locked torch tensor; 8-byte aligned, only what the images used) and
+    ``scratch_bytes``, the size of the device buffer their Y / U / V planes need."""
+
+    def __init__(self, desc, stream, scratch_bytes):
+        self.desc, self.stream, self.scratch_bytes = desc, stream, scratch_bytes
+
+    def __len__(self):
+        return len(self.desc)
+
+
 class MixedStage:
     """``host_decode`` of a batch that is not all JPEG and not all WebP: the PNG subset (if any) inflated, the JPEG subset
-    (if any) entropy-decoded, the WebP subset (if any) entropy-decoded, and where each image of the batch sits in them."""
+    (if any) entropy-decoded, the lossless WebP subset (if any) entropy-decoded, the lossy WebP subset (only with the
+    ``lossy_webp`` switch on) token-decoded, and where each image of the batch sits in them."""
 
-    def __init__(self, n, png_idx, png, jpeg_idx, jpeg, webp_idx=(), webp=None):
+    def __init__(self, n, png_idx, png, jpeg_idx, jpeg, webp_idx=(), webp=None, vp8_idx=(), vp8=None):
         self.n, self.png_idx, self.png, self.jpeg_idx, self.jpeg = n, png_idx, png, jpeg_idx, jpeg
         self.webp_idx, self.webp = webp_idx, webp
+        self.vp8_idx, self.vp8 = vp8_idx, vp8
 
     def __len__(self):
         return self.n
@@ -436,6 +450,98 @@ def decode_webp_stage(staged: WebpStage, device="cuda") -> DecodedBatch:
     return DecodedBatch(rgb, sizes, sizes_host)
 
 
+def lossy_webp_enabled(lossy_webp: Optional[bool] = None) -> bool:
+    """The lossy WebP switch: the keyword when it is given, else the ``VIP_WEBP_LOSSY`` knob (default 0), read per call."""
+    if lossy_webp is not None:
+        return bool(lossy_webp)
+    return os.environ.get("VIP_WEBP_LOSSY", "0") == "1"
+
+
+def webp_is_lossy(raw: bytes) -> bool:
+    """True when the first image chunk of a RIFF / WEBP file is ``VP8 `` (a lossy key frame), from the chunk tags alone.  Anything
+    else - ``VP8L``, animation, a damaged container - is left to the lossless path and its messages."""
+    pos, end = 12, min(len(raw), 8 + int.from_bytes(raw[4:8], "little"))
+    while pos + 8 <= end:
+        tag = raw[pos:pos + 4]
+        if tag == b"VP8 ":
+            return True
+        if tag in (b"VP8L", b"ANIM", b"ANMF"):
+            return False
+        size = int.from_bytes(raw[pos + 4:pos + 8], "little")
+        pos += 8 + size + (size & 1)
+    return False
+
+
+def entropy_decode_vp8s(webps: Sequence[bytes], threads: int = 0, pinned: bool = False,
+                        index: Optional[Sequence[int]] = None) -> Vp8Stage:
+    """Host stage of the lossy WebP path, the twin of ``entropy_decode_webps``: container walk, the VP8 key frame's header,
+    per-macroblock modes and residual tokens (the boolean decoder; C++ threads, the GIL is released inside the ctypes call),
+    dequantised as libwebp does.  ``index``: the batch position of every file, used in error messages.  Raises VipError
+    (naming the image) for an animated file, an inter frame, a damaged stream, or a size beyond VIP_MAX_JPEG_PIXELS."""
+    lib = _abi.lib()
+    n = len(webps)
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in webps]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in webps])
+    desc = (_abi.Vp8Desc * n)()
+    total = 0
+    tmp = _abi.Vp8Desc()
+    need = C.c_size_t(0)
+    for i in range(n):
+        where = i if index is None else index[i]
+        st = lib.vip_vp8_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
+        if st != 0:
+            raise _abi.VipError(f"webp image {where}: vip_vp8_probe_h failed with vip_status {st}: "
+                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
+        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"webp image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+        total += need.value
+    size = (total + 7) // 8 * 8 + 8                   # whole 8-byte words, and never empty
+    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
+    stream = stream_t.numpy() if pinned else np.empty((size // 8,), dtype=np.uint64).view(np.uint8)
+    used = C.c_size_t(0)
+    st = lib.vip_vp8_entropy_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
+    if st != 0:
+        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
+        raise _abi.VipError(f"vip_vp8_entropy_h failed with vip_status {st}: {msg}")
+    scratch = C.c_size_t(0)
+    _abi.check(lib.vip_vp8_scratch_bytes(desc, n, C.byref(scratch)), "vip_vp8_scratch_bytes")
+    keep = max(int(used.value), 8)                    # what was not used is not copied to the device
+    return Vp8Stage(desc, (stream_t if pinned else stream)[:keep], int(scratch.value))
+
+
+def _vp8_into(stage: Vp8Stage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
+    """Launch the reconstruction kernels for the lossy WebPs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
+    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
+    full = (_abi.Vp8Desc * n)()                       # the other rows get all-zero descriptors: nothing written
+    for k, i in enumerate(slots):
+        full[i] = stage.desc[k]
+    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
+    if isinstance(stage.stream, torch.Tensor):
+        stream_d = stage.stream.to(device, non_blocking=True)
+    else:
+        stream_d = torch.from_numpy(stage.stream).to(device)
+    scratch = torch.empty((stage.scratch_bytes,), dtype=torch.uint8, device=device)      # every byte is written before it is read
+    _launch("vip_vp8_reconstruct_rgb_u8", _p(stream_d), stream_d.numel(), _p(desc_d), n, _p(scratch), scratch.numel(), _p(rgb),
+            maxH, maxW)
+
+
+def decode_vp8_stage(staged: Vp8Stage, device="cuda") -> DecodedBatch:
+    """Device half of the lossy WebP path, the twin of ``decode_webp_stage``: ``staged`` = ``entropy_decode_vp8s(...)``.
+    Intra prediction + inverse WHT / DCT, the in-loop filter, fancy chroma upsampling and YUV -> RGB; alpha dropped: the
+    RGB of libwebp's decoder, bit for bit."""
+    n = len(staged.desc)
+    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
+    maxH = max(h for h, _ in sizes_host)
+    maxW = max(w for _, w in sizes_host)
+    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
+    _vp8_into(staged, range(n), n, rgb, device)
+    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
+    return DecodedBatch(rgb, sizes, sizes_host)
+
+
 def image_format(raw: bytes, i: int = 0) -> str:
     """"jpeg", "png" or "webp", from the magic bytes (not the file name); anything else raises VipError naming image ``i``."""
     if raw[:2] == b"\xff\xd8":
@@ -447,22 +553,31 @@ def image_format(raw: bytes, i: int = 0) -> str:
     raise _abi.VipError(f"image {i}: neither a JPEG (FF D8), a PNG (89 50 4E 47 0D 0A 1A 0A) nor a WebP (RIFF....WEBP) signature")
 
 
-def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False):
+def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False, lossy_webp: Optional[bool] = None):
     """Host stage of ``decode_images``: picks the format of every image by its magic bytes.  An all-JPEG batch returns
     exactly what ``entropy_decode`` returns (same calls, same buffers), an all-WebP batch a ``WebpStage``; anything else
-    returns a ``MixedStage``.  Lossy and animated WebPs are refused here, before any launch."""
+    returns a ``MixedStage``.  Animated WebPs are refused here, before any launch, and so are lossy ones unless the switch
+    is on (``lossy_webp``; ``None``: the ``VIP_WEBP_LOSSY`` knob, default 0): then the WebPs are split by their chunk tags, an
+    all-lossy batch returns a ``Vp8Stage`` and a ``MixedStage`` carries the lossy subset as ``vp8``.  With the switch off
+    the calls made are exactly those made before the switch existed."""
     kinds = [image_format(r, i) for i, r in enumerate(raws)]
     if "png" not in kinds and "webp" not in kinds:
         return entropy_decode(raws, threads, pinned)
+    if lossy_webp_enabled(lossy_webp):
+        kinds = ["vp8" if k == "webp" and webp_is_lossy(r) else k for k, r in zip(kinds, raws)]
+        if all(k == "vp8" for k in kinds):
+            return entropy_decode_vp8s(raws, threads, pinned)
     if all(k == "webp" for k in kinds):
         return entropy_decode_webps(raws, threads, pinned)
     png_idx = [i for i, k in enumerate(kinds) if k == "png"]
     jpeg_idx = [i for i, k in enumerate(kinds) if k == "jpeg"]
     webp_idx = [i for i, k in enumerate(kinds) if k == "webp"]
+    vp8_idx = [i for i, k in enumerate(kinds) if k == "vp8"]
     png = inflate_pngs([raws[i] for i in png_idx], threads, pinned, index=png_idx) if png_idx else None
     jpeg = entropy_decode([raws[i] for i in jpeg_idx], threads, pinned) if jpeg_idx else None
     webp = entropy_decode_webps([raws[i] for i in webp_idx], threads, pinned, index=webp_idx) if webp_idx else None
-    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg, webp_idx, webp)
+    vp8 = entropy_decode_vp8s([raws[i] for i in vp8_idx], threads, pinned, index=vp8_idx) if vp8_idx else None
+    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg, webp_idx, webp, vp8_idx, vp8)
 
 
 def decode_staged(staged, device="cuda") -> DecodedBatch:
@@ -475,9 +590,11 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
         return decode_png_stage(staged, device)
     if isinstance(staged, WebpStage):
         return decode_webp_stage(staged, device)
+    if isinstance(staged, Vp8Stage):
+        return decode_vp8_stage(staged, device)
     n = staged.n
     sizes_host: List[Tuple[int, int]] = [(0, 0)] * n
-    for idx, sub in ((staged.png_idx, staged.png), (staged.webp_idx, staged.webp)):
+    for idx, sub in ((staged.png_idx, staged.png), (staged.webp_idx, staged.webp), (staged.vp8_idx, staged.vp8)):
         for k, i in enumerate(idx):
             d = sub.desc[k]
             sizes_host[i] = (int(d.height), int(d.width))
@@ -493,6 +610,8 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
         _png_into(staged.png, staged.png_idx, n, rgb, device)
     if staged.webp is not None:
         _webp_into(staged.webp, staged.webp_idx, n, rgb, device)
+    if staged.vp8 is not None:
+        _vp8_into(staged.vp8, staged.vp8_idx, n, rgb, device)
     if jb is not None:
         rows = torch.tensor(staged.jpeg_idx, dtype=torch.long, device=device)
         rgb[rows, :jb.rgb.shape[1], :jb.rgb.shape[2]] = jb.rgb
@@ -500,10 +619,10 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
     return DecodedBatch(rgb, sizes, sizes_host)
 
 
-def decode_images(raws: Sequence[bytes], device="cuda", threads: int = 0) -> DecodedBatch:
+def decode_images(raws: Sequence[bytes], device="cuda", threads: int = 0, lossy_webp: Optional[bool] = None) -> DecodedBatch:
     """``build_decoder(ext=...)`` for a batch of JPEG, PNG and / or lossless WebP byte strings (dataset/dataset.py:22-30),
-    the format of each image picked from its content."""
-    return decode_staged(host_decode(raws, threads), device)
+    the format of each image picked from its content; with the ``lossy_webp`` switch on (see ``host_decode``) lossy WebP too."""
+    return decode_staged(host_decode(raws, threads, lossy_webp=lossy_webp), device)
 
 
 def decode_jpegs(jpegs: Sequence[bytes], device="cuda", threads: int = 0) -> DecodedBatch:
