@@ -837,6 +837,62 @@ int vip_vp8_default_stages(void);      /* the mask vip_vp8_reconstruct_rgb_u8 ru
 int vip_vp8_reconstruct_stages_rgb_u8(const uint8_t* stream_d, size_t stream_bytes, const vip_vp8_desc* desc, int n, uint8_t* scratch,
                                       size_t scratch_bytes, uint8_t* rgb_u8, int maxH, int maxW, int stages, void* stream);
 
+/* Lossy WebP re-save (the stress test's `w<Q>` step): the project's own VP8 key-frame encoder up to the entropy coder,
+ * which is lossless and skipped - forward colour conversion, mode decision, forward transforms and quantisation on the
+ * GPU, then the decoder's own in-loop filter and RGB output.  The decisions are the project's, not libwebp's; the result
+ * is a valid key frame: written out as a file (tests/_vp8.py does that), libwebp decodes it to the same pixels, bit for bit.
+ * The rules, all integer and deterministic:
+ *  - RGB -> YUV 4:2:0 as libwebp's plain integer path: Y = (16839 R + 33059 G + 6420 B + (16 << 16) + 32768) >> 16; with
+ *    R, G, B summed over a 2 x 2 block, U = clip8((-9719 R - 19081 G + 28800 B + (128 << 18) + (1 << 17)) >> 18) and
+ *    V = clip8((28800 R - 24116 G - 4684 B + (128 << 18) + (1 << 17)) >> 18).  The last column and row are replicated for odd
+ *    sizes and out to the macroblock grid.
+ *  - One quantiser index for the frame, base_q = clamp(int(127 (1 - l^(1/3))), 0, 127) with c = quality / 100 and
+ *    l = 2 c / 3 below c = 0.75, 2 c - 1 from there (libwebp's quality curve, float64 on the host); no segments, no deltas;
+ *    the six steps as a decoder derives them from base_q.
+ *  - level = sign(c) min(2047, (|c| + ((3 q) >> 3)) / q); the decoder sees level * q.
+ *  - Forward 4 x 4 DCT and WHT in the published integer forms of VP8 encoders.
+ *  - Chroma: of DC, TM, VE, HE the mode with the smallest sum of squared errors between source and prediction over U and V
+ *    together, ties to the first in that order.
+ *  - Luma: S16 = the smallest prediction SSE of the four 16 x 16 modes (ties as for chroma).  Sub-blocks in raster order take
+ *    the best of the ten modes by prediction SSE, ties to the lowest VIP_VP8_B_* number, and are transformed, quantised and
+ *    reconstructed in place before the next one predicts; S4 = the sum of their SSEs.  Sub-block modes are used when
+ *    S4 + i4_bias < S16, i4_bias = (k * q * q) >> 4 with q the luma AC step (k: DESIGN.md).  A 16 x 16 macroblock sends its
+ *    sixteen luma DCs through the forward WHT as Y2.
+ *  - A macroblock without a non-zero level is skipped.
+ *  - Normal loop filter, sharpness 0, one level = clamp((a * base_q + b) >> 4, 0, 63) (a, b: DESIGN.md), no deltas. */
+typedef struct vip_vp8_enc_params {
+    int32_t quality, base_q;
+    int32_t y1[2], y2[2], uv[2];      /* [0] DC step, [1] AC step                                                      */
+    int32_t filter_level;             /* the frame header's level; 0: no filter                                        */
+    int32_t flevel, ilevel, hev;      /* what every macroblock record gets                                             */
+    int32_t i4_bias;
+    int32_t reserved;
+    uint32_t y1_inv[2], y2_inv[2], uv_inv[2];   /* ceil(2^32 / step): (x * inv) >> 32 == x / step for 0 <= x < 65536  */
+} vip_vp8_enc_params;
+
+/* Host: the numbers above for `quality` (1..100). */
+int vip_vp8_encode_params_h(int quality, vip_vp8_enc_params* params_h);
+
+/* Host: the descriptors of n images re-saved as lossy WebP, sizes_hw_h int32 [n][2] = (h, w), in the layout
+ * vip_vp8_entropy_h produces, every macroblock with room for 25 coded blocks (coef_idx = 25 * macroblock index), stream_off and coef_off
+ * 16-byte aligned; filter_type
+ * from `quality`.  *stream_bytes_h / *scratch_bytes_h = the sizes of the device buffers they address.  Sizes beyond
+ * VIP_MAX_JPEG_PIXELS are refused. */
+int vip_vp8_encode_layout_h(const int32_t* sizes_hw_h, int n, int quality, vip_vp8_desc* desc_h, size_t* stream_bytes_h,
+                            size_t* scratch_bytes_h);
+
+/* Device: encode rgb_u8 [n][maxH][maxW][3] (image i at its descriptor's size, a device copy of vip_vp8_encode_layout_h's)
+ * at `quality`: per image the macroblock records and the dequantised coefficients of the coded blocks into stream_d (coded
+ * blocks back to back from block coef_idx), the quantised levels into levels_d (int16 [macroblock][25][16], raster order,
+ * macroblocks of the batch back to back in image order - for tests) and the unfiltered reconstruction into the planes in
+ * `scratch`.  vip_vp8_reconstruct_stages_rgb_u8 with VIP_VP8_STAGE_FILTER | VIP_VP8_STAGE_OUTPUT then gives the pixels of
+ * the re-saved file.  No atomics: the output does not depend on the batch around an image; every byte of an image's share
+ * of stream_d's coefficient area and of levels_d is written.  A descriptor that does not fit the buffers or the slots is
+ * skipped.  Null pointers, a quality outside 1..100 and slots beyond VIP_MAX_JPEG_PIXELS are refused before any HIP call. */
+int vip_vp8_encode_rgb_u8(const uint8_t* rgb_u8, const vip_vp8_desc* desc, int n, int maxH, int maxW, int quality, uint8_t* stream_d,
+                          size_t stream_bytes, int16_t* levels_d, size_t levels_elems, uint8_t* scratch, size_t scratch_bytes,
+                          void* stream);
+
 /* Host: the 1025x2 coefficient table of TensorFlow's legacy bicubic kernel (Keys a = -0.5). */
 int vip_bicubic_table_f32(float* table_h);
 

@@ -62,6 +62,13 @@ class Vp8Desc(C.Structure):
                 ("coef_off", C.c_int64), ("coef_blocks", C.c_int64), ("plane_off", C.c_int64)]
 
 
+class Vp8EncParams(C.Structure):
+    """mirror of vip_vp8_enc_params (include/vipcup_hip.h)"""
+    _fields_ = [("quality", C.c_int32), ("base_q", C.c_int32), ("y1", C.c_int32 * 2), ("y2", C.c_int32 * 2), ("uv", C.c_int32 * 2),
+                ("filter_level", C.c_int32), ("flevel", C.c_int32), ("ilevel", C.c_int32), ("hev", C.c_int32), ("i4_bias", C.c_int32),
+                ("reserved", C.c_int32), ("y1_inv", C.c_uint32 * 2), ("y2_inv", C.c_uint32 * 2), ("uv_inv", C.c_uint32 * 2)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/vipcup_hip.h declares
@@ -141,6 +148,9 @@ SIGNATURES = {
     "vip_vp8_reconstruct_rgb_u8": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _vp]),
     "vip_vp8_default_stages": (_i, []),
     "vip_vp8_reconstruct_stages_rgb_u8": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _i, _vp]),
+    "vip_vp8_encode_params_h": (_i, [_i, _vp]),
+    "vip_vp8_encode_layout_h": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "vip_vp8_encode_rgb_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "vip_bicubic_table_f32": (_i, [_vp]),
     "vip_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "vip_tile_resize_bicubic_norm_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),

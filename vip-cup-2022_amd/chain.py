@@ -20,10 +20,11 @@ label's ranges, in that canonical spelling only, matched against the whole token
     tone         ac<PP>  acl<PP>                        cutoff percent 00..49 (acl: one curve from the luma)
                  eq
                  clahe<TT>                              ten times the clip limit, 10..99
+    WebP re-save w<Q>                                   quality 1..100 (lossy WebP)
 
 ``parse_chain`` returns ``(kind, arg)`` per step: ``kind`` names the ``pipeline`` function (``recompress``, ``rescale``, ``blur``,
 ``median``, ``flip``, ``crop``, ``rotate``, ``gray``, ``bgr``, ``hue``, ``saturation``, ``contrast``, ``brightness``, ``gamma``,
-``sharpen``) or, for the noise steps, the kind of ``pipeline.noise`` (``gaussian``, ``mono``, ``speckle``, ``impulse``) and, for the tone
+``sharpen``, ``webp_recompress``) or, for the noise steps, the kind of ``pipeline.noise`` (``gaussian``, ``mono``, ``speckle``, ``impulse``) and, for the tone
 steps, the mode of ``pipeline.tone`` (``autocontrast``, ``autocontrast_luma``, ``equalize``, ``clahe``); ``arg`` is that function's
 argument in the user's units (None for ``gray``, ``bgr`` and ``equalize``)."""
 import re
@@ -68,6 +69,7 @@ STEPS = {row.kind: row for row in (
     Step("acl", 2, False, "autocontrast_luma", 0, 49, None, 1, "--stress-autocontrast-luma", "autocontrast_lumas", "asc", "tone"),
     Step("eq", None, False, "equalize", None, None, None, None, "--stress-equalize", "equalize", None, "tone"),
     Step("clahe", 2, False, "clahe", 10, 99, None, 10, "--stress-clahe", "clahes", "asc", "tone"),
+    Step("w", 0, False, "webp_recompress", 1, 100, None, 1, "--stress-webp", "webps", "desc", "recompression"),
 )}
 STEP_FLAGS = {kind: row.flag for kind, row in STEPS.items()}
 NOISE_STEPS = tuple(kind for kind, row in STEPS.items() if row.family == "noise")
@@ -116,7 +118,7 @@ def parse_step(token: str) -> Tuple[str, object]:
         return kind, step_arg(kind, -v if m.group(1) else v)
     raise ValueError(f"chain step {token!r}: expected a single-variant stress label in its canonical spelling and range (q<Q>, r<P>, "
                      "b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, con<PPP>, "
-                     "bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, clahe<TT>)")
+                     "bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, clahe<TT>, w<Q>)")
 
 
 def parse_chain(text: str) -> List[Tuple[str, object]]:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "vipcup_hip.h"
+#include "vp8_params.hpp"
 #include "vp8_tables.hpp"
 
 void vip_set_error(const char* fmt, ...);
@@ -202,9 +203,8 @@ struct Bool {
 
 // ---- frame header ------------------------------------------------------------------------------------------
 
-struct Quant {
-    int y1[2], y2[2], uv[2];
-};
+using vp8_params::clipi;
+using vp8_params::Quant;
 
 struct Header {
     int use_segment = 0, update_map = 0, absolute_delta = 1;
@@ -217,8 +217,6 @@ struct Header {
     int use_skip = 0, skip_p = 0;
     uint8_t flevel[4][2], ilevel[4][2], hev[4][2];
 };
-
-int clipi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
 
 int read_frame_header(Bool& br, Header& H, int64_t* stats, Err& e) {
     br.get(1);                                               // colour space
@@ -269,14 +267,7 @@ int read_frame_header(Bool& br, Header& H, int64_t* stats, Err& e) {
     for (int s = 0; s < 4; ++s) {
         int q = base_q;
         if (H.use_segment) q = H.seg_quant[s] + (H.absolute_delta ? 0 : base_q);
-        Quant& m = H.q[s];
-        m.y1[0] = DC_TABLE[clipi(q + dq[0], 127)];
-        m.y1[1] = AC_TABLE[clipi(q, 127)];
-        m.y2[0] = DC_TABLE[clipi(q + dq[1], 127)] * 2;
-        m.y2[1] = (AC_TABLE[clipi(q + dq[2], 127)] * 101581) >> 16;
-        if (m.y2[1] < 8) m.y2[1] = 8;
-        m.uv[0] = DC_TABLE[clipi(q + dq[3], 117)];
-        m.uv[1] = AC_TABLE[clipi(q + dq[4], 127)];
+        vp8_params::quant_steps(q, dq, H.q[s]);
     }
     br.get(1);                                               // refresh_entropy_probs: meaningless in a single frame
     for (int t = 0; t < 4; ++t)
@@ -304,20 +295,7 @@ int read_frame_header(Bool& br, Header& H, int64_t* stats, Err& e) {
                 level += H.ref_lf_delta[0];
                 if (i4) level += H.mode_lf_delta[0];
             }
-            level = clipi(level, 63);
-            int il = 0, hv = 0;
-            if (level > 0) {
-                il = level;
-                if (H.sharpness > 0) {
-                    il >>= H.sharpness > 4 ? 2 : 1;
-                    if (il > 9 - H.sharpness) il = 9 - H.sharpness;
-                }
-                if (il < 1) il = 1;
-                hv = level >= 40 ? 2 : level >= 15 ? 1 : 0;
-            }
-            H.flevel[s][i4] = (uint8_t)(H.filter_type ? level : 0);
-            H.ilevel[s][i4] = (uint8_t)il;
-            H.hev[s][i4] = (uint8_t)hv;
+            vp8_params::filter_strength(level, H.sharpness, H.filter_type, H.flevel[s][i4], H.ilevel[s][i4], H.hev[s][i4]);
         }
     }
     return VIP_OK;

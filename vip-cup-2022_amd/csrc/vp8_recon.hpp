@@ -156,11 +156,10 @@ VP8_HD void vp8_edges4(const Vp8Planes& P, int mx, int my, int bx, int by, int e
 #define VP8_AVG3(a, b, c) (((a) + 2 * (b) + (c) + 2) >> 2)
 #define VP8_AVG2(a, b) (((a) + (b) + 1) >> 1)
 
-// row k of the 4x4 prediction of one sub-block
-VP8_HD void vp8_pred4_row(int mode, const int e[13], int k, int out[4]) {
+// the 4x4 prediction of one sub-block, d[x + 4 y]
+VP8_HD void vp8_pred4_block(int mode, const int e[13], int d[16]) {
     const int X = e[0], A = e[1], B = e[2], C = e[3], D = e[4], E = e[5], F = e[6], G = e[7], H = e[8];
     const int I = e[9], J = e[10], K = e[11], L = e[12];
-    int d[16];
 #define DST(x, y) d[(x) + (y) * 4]
     switch (mode) {
         case VIP_VP8_B_DC: {
@@ -257,6 +256,12 @@ VP8_HD void vp8_pred4_row(int mode, const int e[13], int k, int out[4]) {
             break;
     }
 #undef DST
+}
+
+// row k of the 4x4 prediction of one sub-block
+VP8_HD void vp8_pred4_row(int mode, const int e[13], int k, int out[4]) {
+    int d[16];
+    vp8_pred4_block(mode, e, d);
     for (int x = 0; x < 4; ++x) out[x] = d[k * 4 + x];
 }
 

@@ -498,7 +498,7 @@ def stress_labels(*args, **keywords) -> List[str]:
     ``stress_batch``'s keywords in ``stress_batch``'s order, less the batch, the members, ``after_fork``, ``subsampling``,
     ``resize_filter`` and ``blur_radius``; the remaining options are accepted and change no label.
     ``q<Q>`` for every quality as given, then every single-variant label of ``stress_variants`` (spelled by ``chain.step_label``: the
-    grammar is in ``chain``'s docstring; ``scales`` and ``crops`` largest first, every other list ascending by signed value, ``h``
+    grammar is in ``chain``'s docstring; ``scales``, ``crops`` and ``webps`` largest first, every other list ascending by signed value, ``h``
     before ``v``), each followed by its ``_q<Q>`` labels, and last the ``chains`` in the order given, each under its own text
     (``r50+shp080+q75``) and never followed by ``_q<Q>`` labels."""
     spec = _LABEL_SIGNATURE.bind(*args, **keywords).arguments
@@ -513,7 +513,8 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
                  mono_noises: Sequence[float] = (), speckles: Sequence[int] = (), impulses: Sequence[float] = (), noise_seed: int = 0,
                  noise_keys=None, sharpens: Sequence[int] = (), sharpen_sigma: float = 1.0, sharpen_radius: Optional[int] = None,
                  sharpen_threshold: int = 0, chains: Sequence[str] = (), autocontrasts: Sequence[int] = (),
-                 autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8):
+                 autocontrast_lumas: Sequence[int] = (), equalize: bool = False, clahes: Sequence[float] = (), clahe_grid: int = 8,
+                 webps: Sequence[int] = ()):
     """Stress test of one batch: ``_score_batch`` on the batch as it is - the same inputs, streams and calls, so row 0 is bit for bit what a
     plain run returns - and then on perturbed copies of the decoded pixels, each image at its own size, before any member's resize.
     ``staged`` as for ``_score_batch``; it is decoded once.
@@ -537,7 +538,8 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
         ``sharpen_threshold``, one launch per variant
       ``autocontrasts`` / ``autocontrast_lumas`` (integer cutoff percents 0..49), ``equalize``, ``clahes`` (clip limits 1.0..9.9;
         ``clahe_grid`` tiles per axis): ``pipeline.tone``, a curve measured from each image's own histogram, nothing returns to the host
-    Every list but ``scales`` and ``crops`` is taken ascending; no list is de-duplicated.
+      ``webps`` (qualities 1..100, largest first): ``pipeline.webp_recompress``, the image as a lossy WebP save gives it back
+    Every list but ``scales``, ``crops`` and ``webps`` is taken ascending; no list is de-duplicated.
     Last the ``chains`` (chain texts, ``pipeline.parse_chain``: ``"r50+shp080+q75"``; scored in the order given): the decoded batch goes
     through each chain's steps left to right (``pipeline.apply_chain`` with this call's options, ``noise_seed`` and ``noise_keys``) and
     the result is scored ONCE, exactly as the chain is written: ``qualities`` do not multiply chain rows, a chain that should end in a

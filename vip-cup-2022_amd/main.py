@@ -17,6 +17,7 @@
                                      [--stress-sharpen-threshold T]                                                          (--stress-out FILE.csv)
                                      [--stress-autocontrast C[,C...]] [--stress-autocontrast-luma C[,C...]] [--stress-equalize]
                                      [--stress-clahe L[,L...]] [--stress-clahe-grid G]                                       (--stress-out FILE.csv)
+                                     [--stress-webp Q[,Q...] --stress-out FILE.csv]
                                      [--stress-chain STEP+STEP[+STEP...][,CHAIN...]]                                         (--stress-out FILE.csv)
                                      [--tiles-out FILE.csv [--tile-size 200] [--tile-stride S] [--tile-max 256] [--tile-agg mean|max]]
                                      [--occlusion DIR [--occlusion-grid 8] [--occlusion-window 2] [--occlusion-fill mean|gray]
@@ -103,12 +104,19 @@ three launches - histograms, tables, pixels - and nothing returns to the host.  
 ``ac``, ``acl``, ``eq``, ``clahe``, each list ascending, unsaved and - with ``--stress-jpeg`` - re-saved (``<label>_q<Q>``); a value listed twice is
 refused.  ``stress.json`` then lists ``autocontrast_cutoffs``, ``autocontrast_luma_cutoffs``, ``equalize``, ``clahe_limits`` and ``clahe_grid``
 under ``settings``.
+``--stress-webp 90,75,50 --stress-out stress.csv`` is the lossy WebP re-save - what CDNs and messengers transcode uploads to; the
+reference has none: the decoded image at its own size goes through the project's own VP8 key-frame encoder on the GPU (libwebp's colour
+conversion and quality curve; 4 x 4 transforms, 16 x 16 and 4 x 4 intra prediction chosen by prediction error, the in-loop filter, 4:2:0
+chroma with the fancy upsampler; include/vipcup_hip.h states the rules) and comes back as libwebp would decode the file, bit for bit.
+Qualities are integers in 1..100, highest first; a value listed twice is refused.  The rows ``w<Q>`` follow the tone rows, unsaved and -
+with ``--stress-jpeg`` - re-saved as JPEG (``w<Q>_q<Q'>``).  The refusals are those of ``--stress-jpeg``.  ``stress.json`` then lists
+``webp_qualities`` under ``settings`` (also when only a chain holds a ``w`` step).
 ``--stress-chain r50+shp080+q75,q90+crop95+q75 --stress-out stress.csv`` scores every image after a SEQUENCE of perturbations, as files
 are laundered in practice (downscale, sharpen, re-save; a second JPEG on a shifted block grid).  A chain is 2..8 steps joined by ``+``;
 up to 16 chains, separated by commas, keep the order given; a chain listed twice is refused.  A step is exactly a single-variant label
 of the flags above in its canonical spelling and range, matched against the whole token: ``q<Q>``, ``r<P>``, ``b<TT>``, ``m3``, ``m5``,
 ``fliph``, ``flipv``, ``crop<PP>``, ``rot<TTT>``, ``rotm<TTT>``, ``gray``, ``bgr``, ``hue<DDD>``, ``huem<DDD>``, ``sat<PPP>``, ``con<PPP>``, ``bri<PP>``,
-``brim<PP>``, ``gam<PPP>``, ``n<TTT>``, ``nm<TTT>``, ``spk<PP>``, ``imp<TTT>``, ``shp<PPP>``, ``ac<PP>``, ``acl<PP>``, ``eq``, ``clahe<TT>``; a one-step chain is refused with the name of the
+``brim<PP>``, ``gam<PPP>``, ``n<TTT>``, ``nm<TTT>``, ``spk<PP>``, ``imp<TTT>``, ``shp<PPP>``, ``ac<PP>``, ``acl<PP>``, ``eq``, ``clahe<TT>``, ``w<Q>``; a one-step chain is refused with the name of the
 flag that gives that row; the ``r`` percents of a chain must multiply to 10..400 %.  The steps run left to right on the decoded image
 at its own size, each with the options of its family's flags (``--stress-subsampling`` for ``q``, ``--stress-resize-filter`` for ``r``,
 ``--stress-blur-radius`` for ``b``, ``--stress-crop-origin`` for ``crop``, ``--stress-rotate-fill`` for ``rot``, ``--stress-sharpen-sigma`` /
@@ -242,6 +250,7 @@ _LISTS = {kind: _List(*row) for kind, row in {
     "autocontrast": (r"\d{1,2}", ONCE, "integer cutoff percents in 0..49", "autocontrast_cutoffs"),
     "autocontrast_luma": (r"\d{1,2}", ONCE, "integer cutoff percents in 0..49", "autocontrast_luma_cutoffs"),
     "clahe": (_TENTHS, ONCE, "clip limits in 1.0..9.9 with at most one fractional digit", "clahe_limits"),
+    "webp_recompress": (None, ONCE, "integer qualities in 1..100", "webp_qualities"),
 }.items()}
 # An option flag: its keyword of ``stress_batch``, the step kind whose flag it is read after (and written after, in the settings), the kinds
 # it governs - it is accepted with the flag of one of them or with a chain that holds one -, the refusal otherwise, its integer range
@@ -381,6 +390,8 @@ def _write_stress(a, names, members, per_model, stressed, spec, mode):
     rows = [row for kind, row in grammar.STEPS.items() if kind != "recompress"]
     # a family with one of its flags given writes all its lists (empty ones too) and options; sharpening also with a shp step in a chain
     present = {row.family for row in rows if row.keyword in spec} | ({"sharpening"} if "sharpen" in in_chain else set())
+    if "webp_recompress" in in_chain:                   # the WebP re-save shares its family with --stress-jpeg, whose settings stand above
+        present.add("recompression")
     for row in rows:
         if row.family in present:
             if row.kind in _LISTS:
@@ -672,6 +683,11 @@ def main(argv=None):
     ap.add_argument("--stress-clahe-grid", type=int, default=None, metavar="G",
                     help="tiles per axis of --stress-clahe (1..16, default 8; fewer on an axis shorter than 16 G pixels, a tile is at "
                          "least 16 pixels wide); needs --stress-clahe or a --stress-chain with a clahe step")
+    ap.add_argument("--stress-webp", default=None, metavar="Q[,Q...]",
+                    help="lossy WebP stress test: also score every image as it comes back from a lossy WebP save at each quality (integers "
+                         "in 1..100; highest first; a value listed twice is refused) - the project's own VP8 key-frame encoder on the GPU, "
+                         "decoded as libwebp decodes the file -, unsaved and - with --stress-jpeg - re-saved as JPEG at every quality; needs "
+                         "--stress-out, whose table gains the labels w<Q>, w<Q>_q<Q'> after the tone rows")
     ap.add_argument("--stress-chain", default=None, metavar="STEP+STEP[+STEP...][,CHAIN...]",
                     help="stress chains: also score every image after a SEQUENCE of perturbations, e.g. r50+shp080+q75 (downscale, "
                          "sharpen, re-save: what a messenger does) or q90+crop95+q75 (double compression on a shifted block grid).  A "
@@ -679,7 +695,7 @@ def main(argv=None):
                          "twice is refused.  A step is a single-variant label of the other stress flags in its canonical spelling: q<Q>, "
                          "r<P>, b<TT>, m3, m5, fliph, flipv, crop<PP>, rot<TTT>, rotm<TTT>, gray, bgr, hue<DDD>, huem<DDD>, sat<PPP>, "
                          "con<PPP>, bri<PP>, brim<PP>, gam<PPP>, n<TTT>, nm<TTT>, spk<PP>, imp<TTT>, shp<PPP>, ac<PP>, acl<PP>, eq, "
-                         "clahe<TT>; it takes the options of its "
+                         "clahe<TT>, w<Q>; it takes the options of its "
                          "family's flags (--stress-subsampling, --stress-resize-filter, --stress-blur-radius, --stress-crop-origin, "
                          "--stress-rotate-fill, --stress-sharpen-sigma / -radius / -threshold, --stress-noise-seed, --stress-clahe-grid), which "
                          "are accepted "

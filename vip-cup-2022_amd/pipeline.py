@@ -708,6 +708,62 @@ def recompress(batch: DecodedBatch, quality: int, subsampling: str = "4:2:0") ->
     return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
 
 
+class WebpEncoded:
+    """What ``webp_encode`` leaves on the device: ``desc`` (ctypes array of Vp8Desc, host) and ``desc_d``, ``stream`` (uint8: per image
+    the macroblock records and the dequantised coefficients, the layout of ``entropy_decode_vp8s``), ``levels`` (int16 ``[macroblocks
+    of the batch, 25, 16]``, raster order), ``scratch`` (uint8: the planes before the loop filter) and ``params`` (Vp8EncParams)."""
+
+    def __init__(self, desc, desc_d, stream, levels, scratch, params):
+        self.desc, self.desc_d, self.stream, self.levels, self.scratch, self.params = desc, desc_d, stream, levels, scratch, params
+
+
+def webp_encode_params(quality: int) -> "_abi.Vp8EncParams":
+    """Host: what ``quality`` (1..100) stands for in the lossy WebP re-save - quantiser index, steps, loop-filter level, mode bias"""
+    params = _abi.Vp8EncParams()
+    _abi.check(_abi.lib().vip_vp8_encode_params_h(_int_arg("quality", quality, 1, 100), C.byref(params)), "vip_vp8_encode_params_h")
+    return params
+
+
+def webp_encode(batch: DecodedBatch, quality: int) -> WebpEncoded:
+    """The encoder half of ``webp_recompress``: one launch (``vip_vp8_encode_rgb_u8``) that leaves the batch's macroblock records,
+    coefficients, levels and unfiltered planes on the device.  Argument checks run before any launch."""
+    quality = _int_arg("quality", quality, 1, 100)
+    if not isinstance(batch, DecodedBatch):
+        raise ValueError(f"webp_encode: expected a DecodedBatch, got {type(batch).__name__}")
+    n, maxH, maxW, _ = batch.rgb.shape
+    device = batch.rgb.device
+    lib = _abi.lib()
+    sizes = np.ascontiguousarray(np.array(batch.sizes_host, dtype=np.int32).reshape(n, 2))
+    desc = (_abi.Vp8Desc * n)()
+    stream_bytes, scratch_bytes = C.c_size_t(0), C.c_size_t(0)
+    _abi.check(lib.vip_vp8_encode_layout_h(sizes.ctypes.data_as(C.c_void_p), n, quality, desc, C.byref(stream_bytes), C.byref(scratch_bytes)),
+               "vip_vp8_encode_layout_h")
+    params = webp_encode_params(quality)
+    desc_d = torch.from_numpy(np.frombuffer(bytes(desc), dtype=np.uint8).copy()).to(device)
+    stream = torch.empty((stream_bytes.value,), dtype=torch.uint8, device=device)
+    scratch = torch.empty((scratch_bytes.value,), dtype=torch.uint8, device=device)
+    levels = torch.empty((sum(d.mb_w * d.mb_h for d in desc), 25, 16), dtype=torch.int16, device=device)
+    src = batch.rgb if batch.rgb.is_contiguous() else batch.rgb.contiguous()
+    _launch("vip_vp8_encode_rgb_u8", _p(src), _p(desc_d), n, maxH, maxW, quality, _p(stream), stream.numel(), _p(levels), levels.numel(),
+            _p(scratch), scratch.numel())
+    return WebpEncoded(desc, desc_d, stream, levels, scratch, params)
+
+
+def webp_recompress(batch: DecodedBatch, quality: int) -> DecodedBatch:
+    """The batch as it would come back from a lossy WebP save at ``quality`` (1..100) and a load, each image re-saved at its own size:
+    what a CDN or a messenger does to an upload today.  The encoder is the project's own (include/vipcup_hip.h states its rules: libwebp's
+    colour conversion and quality curve, mode decision by prediction error, no segments) and stops in front of the entropy coder, which
+    is lossless; the decoder half is the lossy WebP input path's loop filter and RGB output, unchanged.  The pixels are those libwebp
+    decodes from the file these decisions make, bit for bit.  Returns a new batch of the same sizes; ``batch`` is not touched.  Runs on
+    the current stream; only the descriptors come from the host."""
+    enc = webp_encode(batch, quality)
+    n, maxH, maxW, _ = batch.rgb.shape
+    rgb = torch.zeros_like(batch.rgb)
+    _launch("vip_vp8_reconstruct_stages_rgb_u8", _p(enc.stream), enc.stream.numel(), _p(enc.desc_d), n, _p(enc.scratch), enc.scratch.numel(),
+            _p(rgb), maxH, maxW, 2 | 4)                 # VIP_VP8_STAGE_FILTER | VIP_VP8_STAGE_OUTPUT: the reconstruction stands already
+    return DecodedBatch(rgb, batch.sizes, list(batch.sizes_host))
+
+
 RESAMPLE_FILTERS = {"bilinear": 0, "bicubic": 1, "lanczos": 2}      # VIP_RESAMPLE_* (include/vipcup_hip.h)
 _RESAMPLE_TABLES: Dict[Tuple[int, int, str], Tuple[np.ndarray, np.ndarray, int]] = {}
 _RESAMPLE_TILE: List[int] = []
@@ -1493,6 +1549,8 @@ def apply_step(batch: DecodedBatch, kind: str, arg, options, mean: Optional[torc
         return tone(batch, kind, arg, options["clahe_grid"])
     if kind == "recompress":
         return recompress(batch, arg, options["subsampling"])
+    if kind == "webp_recompress":
+        return webp_recompress(batch, arg)
     if kind == "rescale":
         return rescale(batch, arg, options["resize_filter"])
     if kind == "blur":
