@@ -1027,6 +1027,10 @@ int vip_conv2d_gated_nhwc_h2(const void* x, const void* gate, const void* w, con
  * gamma / beta, depthwise filters, head matrices, relative-position table) and fp32 head outputs as there */
 int vip_dwconv2d_nhwc_h2(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride,
                          int pt, int pl, int Ho, int Wo, int act, int* status, void* stream);
+/* Dry run of the stride-1 register-tiled launch vip_dwconv2d_nhwc_h2 makes (dwconv_tile_h2_kernel), as vip_dwconv2d_tile_plan: returns
+ * the tile groups a channel block's workgroups walk (0: that kernel does not take the call), *workgroups = gridDim.x, geom[4] =
+ * {4-channel chunks per block, tiles per block, channel blocks (gridDim.y), workgroup cap}.  Pure host arithmetic: no device is needed. */
+long vip_dwconv2d_tile_plan_h2(int B, int H, int W, int C, int k, int stride, int pt, int pl, int Ho, int Wo, int* workgroups, int* geom);
 /* Stride-1 k = 3 / 5 / 7 DepthwiseConv2D on the packed storage, staged through LDS (dwconv_lds_h2.hip) - the Keras DepthwiseConv2D of
  * tfimm's ConvNeXtBlock (/root/reference/models/tfimm/architectures/convnext.py:200-229) and of the MBConv blocks in strict mode.
  * w_quad: the filter QUAD-MAJOR, fp32 [C/4][k*k][4] (vip_dw_filter_quad_major converts the [k*k][C] layout of vip_dwconv2d_nhwc_h2).

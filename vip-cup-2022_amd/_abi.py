@@ -188,6 +188,7 @@ SIGNATURES = {
     "vip_conv2d_kernel_name_h2": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "vip_conv2d_kernel_variant_h2": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "vip_dwconv2d_nhwc_h2": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _vp]),
+    "vip_dwconv2d_tile_plan_h2": (C.c_long, [_i] * 10 + [C.POINTER(_i)] * 2),
     "vip_mlp_fused_supported_h2": (_i, [_i] * 4),
     "vip_mlp_fused_plan_h2": (_i, [_i] * 4 + [C.POINTER(_i)] * 2),
     "vip_mlp_fused_h2": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp] + [_i] * 9 + [_vp, _vp]),

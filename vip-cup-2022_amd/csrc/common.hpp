@@ -51,6 +51,8 @@ long vip_dwconv_tiled_plan(int B, int H, int W, int C, int k, int Ho, int Wo, in
 // the same on the packed STRICT storage (dwconv.hip); returns 1 when the shape is not handled there
 int vip_dwconv_tiled_h2(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k, int pt, int pl, int Ho,
                         int Wo, int act, int* status, hipStream_t s);
+// dry run of that launch: tile groups (0: shape not handled), *workgroups = blocks per channel block, geom[4] optional
+long vip_dwconv_tiled_plan_h2(int B, int H, int W, int C, int k, int Ho, int Wo, int* workgroups, int* geom);
 // attention cores of the packed STRICT storage on the matrix cores (attn_h2.hip); return 1 when the configuration is not built there
 int vip_window_attn_h2_mfma(const void* qkv, const void* q_global, const float* bias_table, void* out, int B, int Hp, int Wp, int C, int heads,
                             int ws, int nq, float scale, int* status, hipStream_t s);

@@ -374,22 +374,43 @@ __global__ __launch_bounds__(256, 2) void dwconv_tile_h2_kernel(const char* __re
     if (bad && status) *status = VIP_H2_OVERFLOW;
 }
 
+// Launch geometry of dwconv_tile_h2_kernel for T x TW register tiles, the one place it is computed: launch_tile_h2 and the dry run
+// vip_dwconv2d_tile_plan_h2() read it.  Pure arithmetic: the workgroup cap is sized for 256 CUs.
+struct DwTileH2Plan {
+    int cb;                  // 4-channel chunks per block
+    int tiles_x, tiles_y;
+    long n_tiles;
+    int tiles_per_block;
+    int gyc;                 // channel blocks: gridDim.y
+    long groups;             // tile groups: the work units of a channel block
+    long gx_cap;
+    long gx;                 // gridDim.x
+};
+
+template <int T, int TW>
+DwTileH2Plan tile_plan_h2(int B, int Ho, int Wo, int C) {
+    DwTileH2Plan p;
+    const int C4 = C / 4;
+    p.cb = C4 < 32 ? C4 : 32;                                    // 4-channel chunks per block: <= 128 channels
+    if (C4 % 24 == 0 && C4 % 32 != 0) p.cb = 24;                  // ConvNeXt widths 96/192/384/768
+    p.tiles_x = (Wo + TW - 1) / TW;
+    p.tiles_y = (Ho + T - 1) / T;
+    p.n_tiles = (long)B * p.tiles_x * p.tiles_y;
+    p.tiles_per_block = 256 / p.cb;
+    p.gyc = (C4 + p.cb - 1) / p.cb;
+    p.groups = (p.n_tiles + p.tiles_per_block - 1) / p.tiles_per_block;
+    p.gx_cap = (256L * VIP_DW_BLOCKS_PER_CU + p.gyc - 1) / p.gyc;
+    p.gx = p.groups > p.gx_cap ? p.gx_cap : p.groups;
+    return p;
+}
+
 template <int K, int T, int TW, bool WHOLE>
 int launch_tile_h2(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int pt, int pl, int Ho, int Wo,
                    int act, int* status, hipStream_t s) {
-    const int C4 = C / 4;
-    int cb = C4 < 32 ? C4 : 32;                                  // 4-channel chunks per block: <= 128 channels
-    if (C4 % 24 == 0 && C4 % 32 != 0) cb = 24;                    // ConvNeXt widths 96/192/384/768
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + T - 1) / T;
-    const long n_tiles = (long)B * tiles_x * tiles_y;
-    const int tiles_per_block = 256 / cb;
-    const int gyc = (C4 + cb - 1) / cb;
-    long gx = (n_tiles + tiles_per_block - 1) / tiles_per_block;
-    const long gx_cap = (256L * VIP_DW_BLOCKS_PER_CU + gyc - 1) / gyc;
-    if (gx > gx_cap) gx = gx_cap;
-    const size_t smem = (size_t)K * K * cb * 4 * sizeof(float);
-    hipLaunchKernelGGL((dwconv_tile_h2_kernel<K, T, TW, WHOLE>), dim3((unsigned)gx, (unsigned)gyc), dim3(256), smem, s, (const char*)x, w,
-                       bias, (char*)y, B, H, W, C, pt, pl, Ho, Wo, act, cb, tiles_x, tiles_y, n_tiles, 4L * B * H * W * C, status);
+    const DwTileH2Plan p = tile_plan_h2<T, TW>(B, Ho, Wo, C);
+    const size_t smem = (size_t)K * K * p.cb * 4 * sizeof(float);
+    hipLaunchKernelGGL((dwconv_tile_h2_kernel<K, T, TW, WHOLE>), dim3((unsigned)p.gx, (unsigned)p.gyc), dim3(256), smem, s, (const char*)x,
+                       w, bias, (char*)y, B, H, W, C, pt, pl, Ho, Wo, act, p.cb, p.tiles_x, p.tiles_y, p.n_tiles, 4L * B * H * W * C, status);
     return vip_launch_status("vip_dwconv2d_nhwc_h2(tile)");
 }
 
@@ -514,6 +535,25 @@ long vip_dwconv_tiled_plan(int B, int H, int W, int C, int k, int Ho, int Wo, in
     if (k == 3) p = tile_plan<2, 4>(B, Ho, Wo, C, pooled != 0);          // the register tiles of vip_dwconv_tiled
     else if (k == 5) p = tile_plan<2, 2>(B, Ho, Wo, C, pooled != 0);
     else if (k == 7) p = tile_plan<2, 4>(B, Ho, Wo, C, pooled != 0);
+    else return 0;
+    if (workgroups) *workgroups = (int)p.gx;
+    if (geom) {
+        geom[0] = p.cb;
+        geom[1] = p.tiles_per_block;
+        geom[2] = p.gyc;
+        geom[3] = (int)p.gx_cap;
+    }
+    return p.groups;
+}
+
+// dry run of launch_tile_h2, as vip_dwconv_tiled_plan: tile groups, the blocks per channel block that walk them, and optionally
+// geom[4] = {cb (4-channel chunks), tiles per block, channel blocks, block cap}; 0 when vip_dwconv_tiled_h2 does not take the shape
+long vip_dwconv_tiled_plan_h2(int B, int H, int W, int C, int k, int Ho, int Wo, int* workgroups, int* geom) {
+    if (4L * B * H * W * C >= 0xFFFFFFE0L || C % 8 != 0) return 0;
+    DwTileH2Plan p;
+    if (k == 3) p = tile_plan_h2<2, 4>(B, Ho, Wo, C);                     // the register tiles of vip_dwconv_tiled_h2
+    else if (k == 5) p = tile_plan_h2<2, 2>(B, Ho, Wo, C);
+    else if (k == 7) p = tile_plan_h2<2, 4>(B, Ho, Wo, C);
     else return 0;
     if (workgroups) *workgroups = (int)p.gx;
     if (geom) {

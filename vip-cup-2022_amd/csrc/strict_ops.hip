@@ -820,13 +820,21 @@ extern "C" int vip_layernorm_h2(const void* x, const float* gamma, const float* 
                                 void* stream) {
     return layernorm_impl<SH2, 8>("vip_layernorm_h2", x, gamma, beta, y, rows, C, eps, status, stream);
 }
+// stride 1: the register-tiled kernel of dwconv.hip (the fp16 path's scheme; VIP_DW_H2_TILE=0: the plain kernel below).  The LDS-staged
+// kernel takes a quad-major filter and has its own entry point, vip_dwconv2d_s1_h2 (dwconv_lds_h2.hip)
+static bool dw_h2_tiled(int B, int H, int W, int C, int stride, int pt, int pl, int Ho, int Wo) {
+    static const bool tiled = !(getenv("VIP_DW_H2_TILE") && atoi(getenv("VIP_DW_H2_TILE")) == 0);
+    return tiled && stride == 1 && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && Ho > 0 && Wo > 0 && pt >= 0 && pl >= 0 &&
+           (long)(Ho - 1) - pt < H && (long)(Wo - 1) - pl < W;
+}
+extern "C" long vip_dwconv2d_tile_plan_h2(int B, int H, int W, int C, int k, int stride, int pt, int pl, int Ho, int Wo, int* workgroups,
+                                          int* geom) {
+    if (!dw_h2_tiled(B, H, W, C, stride, pt, pl, Ho, Wo)) return 0;
+    return vip_dwconv_tiled_plan_h2(B, H, W, C, k, Ho, Wo, workgroups, geom);
+}
 extern "C" int vip_dwconv2d_nhwc_h2(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k, int stride,
                                     int pt, int pl, int Ho, int Wo, int act, int* status, void* stream) {
-    // stride 1: the register-tiled kernel of dwconv.hip (the fp16 path's scheme; VIP_DW_H2_TILE=0: the plain kernel below).  The LDS-staged
-    // kernel takes a quad-major filter and has its own entry point, vip_dwconv2d_s1_h2 (dwconv_lds_h2.hip)
-    static const bool tiled = !(getenv("VIP_DW_H2_TILE") && atoi(getenv("VIP_DW_H2_TILE")) == 0);
-    if (tiled && stride == 1 && x && w && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && Ho > 0 && Wo > 0 && pt >= 0 && pl >= 0 &&
-        (unsigned)act <= 4u && (long)(Ho - 1) - pt < H && (long)(Wo - 1) - pl < W) {
+    if (x && w && y && (unsigned)act <= 4u && dw_h2_tiled(B, H, W, C, stride, pt, pl, Ho, Wo)) {
         const int st = vip_dwconv_tiled_h2(x, w, bias, y, B, H, W, C, k, pt, pl, Ho, Wo, act, status, (hipStream_t)stream);
         if (st != 1) return st;
     }

@@ -567,13 +567,17 @@ def mlp_plan(M: int, C_: int, hidden: int, packed: bool = False, act="gelu"):
     return (n, wg.value, rows.value) if n > 0 else None
 
 
-def dwconv_tile_plan(B: int, H: int, W: int, Cc: int, k: int, pad=None, pooled: bool = False):
+def dwconv_tile_plan(B: int, H: int, W: int, Cc: int, k: int, pad=None, pooled: bool = False, packed: bool = False):
     """``(tile groups, workgroups per channel block, {cb, tiles_per_block, channel_blocks, cap})`` of the fp16 stride-1 depthwise
-    launch (``pooled``: the pooling form ``dwconv2d_se`` uses).  Host arithmetic only: works without a GPU."""
+    launch (``pooled``: the pooling form ``dwconv2d_se`` uses; ``packed``: the tile kernel of the strict storage, ``cb`` in 4-channel
+    chunks - what ``dwconv2d`` launches where the LDS-staged kernel does not take the call).  Host arithmetic only: works without a GPU."""
     pad = (k // 2,) * 4 if pad is None else pad
     Ho, Wo = _out_hw(H, W, k, k, 1, 1, pad)
     wg, geom = C.c_int(0), (C.c_int * 4)()
-    n = _abi.lib().vip_dwconv2d_tile_plan(B, H, W, Cc, k, 1, Ho, Wo, int(pooled), C.byref(wg), geom)
+    if packed:
+        n = 0 if pooled else _abi.lib().vip_dwconv2d_tile_plan_h2(B, H, W, Cc, k, 1, pad[0], pad[2], Ho, Wo, C.byref(wg), geom)
+    else:
+        n = _abi.lib().vip_dwconv2d_tile_plan(B, H, W, Cc, k, 1, Ho, Wo, int(pooled), C.byref(wg), geom)
     return (n, wg.value, dict(zip(("cb", "tiles_per_block", "channel_blocks", "cap"), geom))) if n > 0 else None
 
 
