@@ -105,6 +105,22 @@ int vip_conv2d_gated_nhwc_f16(const void* x, const void* gate, const void* w, co
 int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const void* w_lo, const float* bias, const void* residual,
                              void* y, const vip_conv_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Block-final 1x1 convolution of a squeeze-excite bottleneck with the block tail in its epilogue:
+ *   y[m, n] = act_post( (conv(x)[m, n] + bias[n]) * g[image(m), n] + residual[m, n] ),   g = hi + lo of out_gate
+ * out_gate [B][2][Cout] fp16 is the split gate of vip_se_gate_f16 / vip_gemm_split_f16.  The layer is linear, so the gate's
+ * pooled input mean_hw(conv(x)) = W mean_hw(x) + b can be formed from x BEFORE this launch (reduce weights folded with W): the
+ * un-gated map is never written, and the pooling read and the vip_scale_add_act_f16 launch go (ResNet-RS `SE`,
+ * resnet_rs_model.py:145-183,262-280).  The multiply is fp32 on the accumulators, before the residual add and the single fp16
+ * rounding of the store.  w_lo: the second weight term (vip_conv2d_hilo_nhwc_f16) or NULL.  act_pre none, act_post none / ReLU,
+ * ungrouped, cout_off = 0, and only where the same call with a residual selects pw_gemm_kernel or pwk_direct_kernel - the
+ * selection is that call's own; everything else returns VIP_ERR_UNSUPPORTED and the caller runs conv + vip_scale_add_act_f16.
+ * vip_conv2d_out_gated_variant: the dry run - VIP_OK and the instantiation ("pwk_direct<2> PT=4 ogate") where the call is taken.
+ * ------------------------------------------------------------------------------------------ */
+int vip_conv2d_out_gated_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
+                                  const void* residual, void* y, const vip_conv_desc* d, void* stream);
+int vip_conv2d_out_gated_variant(const vip_conv_desc* d, int has_w_lo, char* variant, size_t cap);
+
 /* Dense / 1x1 convenience wrapper: C[M,N] = act_post(act_pre(A[M,K] @ W[N,K]^T + bias) + residual).
  * Replaces tf.keras.layers.Dense (gcvit/layers/attention.py:25,33, feature.py:20-22;
  * tfimm/layers/transformers.py:192-205; all classifier heads). */
@@ -142,6 +158,11 @@ int vip_gemm_split_f16(const void* A, const void* W, const float* bias, void* C,
  * rounding error is the same for every pixel the gate later scales, so it is not averaged away.  M <= 256, N % 4 == 0, K % 8 == 0. */
 int vip_gemm_split2_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int ldw, int act,
                         void* stream);
+/* vip_gemm_split2_f16 with two-term weights: v = act((A_hi + A_lo) @ W^T + A_hi @ W_lo^T + bias), W_lo = fp16(W32 - W) in the layout
+ * of W.  For a first squeeze-excite layer that is the PRODUCT of two layers (the reduce layer folded with the linear layer in front of
+ * the pool, see vip_conv2d_out_gated_nhwc_f16): its elements are not fp16 values. */
+int vip_gemm_split2_hilo_f16(const void* A, const void* W, const void* W_lo, const float* bias, void* C, int M, int N, int K, int ldw,
+                             int act, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused two-layer MLP:  y[M,C] = W2 . act(W1 . LN(x) + b1) + b2 (+ residual), hidden tensor never written to memory.
@@ -180,6 +201,11 @@ int vip_mlp_fused_f16(const void* x, const float* ln_gamma, const float* ln_beta
 int vip_se_gate_f16(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* gate,
                     int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2,
                     int split, void* stream);
+/* The same with a two-term first matrix, w1_lo = fp16(W32 - w1) in the layout of w1, joined with it in fp32 (~22-bit weights): for a
+ * reduce layer folded with the linear layer in front of the pool (see vip_conv2d_out_gated_nhwc_f16). */
+int vip_se_gate_hilo_f16(const void* x, const void* w1, const void* w1_lo, const float* b1, const void* w2, const float* b2, void* gate,
+                         int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2, int split,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Depthwise Conv2D k x k (+bias)(+act).  Replaces tf.keras.layers.DepthwiseConv2D:

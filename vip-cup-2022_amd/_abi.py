@@ -78,6 +78,8 @@ SIGNATURES = {
     "vip_conv2d_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_conv2d_gated_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_conv2d_hilo_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
+    "vip_conv2d_out_gated_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
+    "vip_conv2d_out_gated_variant": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "vip_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "vip_ln_gemm_supported": (_i, [_i, _i, _i, _i]),
     "vip_ln_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 4 + [_i] * 9 + [_vp]),
@@ -85,8 +87,10 @@ SIGNATURES = {
     "vip_mlp_fused_plan": (_i, [_i] * 4 + [C.POINTER(_i)] * 2),
     "vip_mlp_fused_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 6 + [_i] * 9 + [_vp]),
     "vip_se_gate_f16": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
+    "vip_se_gate_hilo_f16": (_i, [_vp] * 7 + [_i] * 11 + [_vp]),
     "vip_gemm_split_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "vip_gemm_split2_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
+    "vip_gemm_split2_hilo_f16": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 5 + [_vp]),
     "vip_dwconv2d_nhwc_f16": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_vp]),
     "vip_dwconv2d_pool_parts": (_i, [_i] * 8),
     "vip_dwconv2d_tile_plan": (C.c_long, [_i] * 9 + [C.POINTER(_i)] * 2),

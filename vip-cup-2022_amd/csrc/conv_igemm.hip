@@ -73,6 +73,10 @@ struct ConvArgs {
     const f16* gate;   // optional per-image input-channel gate [B][2][K] (hi, lo planes of a squeeze-excite scale, folded into the load); pwk only
     int y_lo_off;      // rows kernel: != 0 -> also write fp16(v - fp16(v)) this many halfs after each output (split gate)
     int gate_hw;       // pixels per image (image index of pixel m = m / gate_hw)
+    const f16* ogate;  // optional per-image OUTPUT-channel gate [B][2][Cout] (hi, lo planes), applied to the accumulators in the epilogue
+                       // (modes 7 / 8 of pw_gemm_kernel and pwk_direct_kernel; image index from gate_hw)
+    int ogate_elems;   // halfs in ogate (buffer descriptor)
+    unsigned hw_magic; // min(2^32 / gate_hw, 2^32 - 1): m / gate_hw = umulhi(m, hw_magic), + 1 when the remainder reaches gate_hw
     float out_scale;   // H2: 1 / (power-of-two scale folded into the weights AND the bias), applied to the accumulators
     int* status;       // H2: device word raised to VIP_H2_OVERFLOW when an output does not fit the fp16 range (may be NULL)
     const float* ln_g; // pwx_ln_kernel: LayerNorm scale / shift [K] fp32 over the input row, applied to the activation fragments (else NULL)
@@ -85,7 +89,8 @@ struct ConvArgs {
 enum Family { PW_GEMM, ROWS_GEMM, GEMM8P, PWX, PWK_DIRECT, PWK_GEMM, IM2COL, CONV_IGEMM };
 struct Plan {
     Family family;
-    int mode;                           // epilogue the pointwise kernels carry: act_pre (0..4), 5 residual, 6 residual + ReLU; -1: none of these
+    int mode;                           // epilogue the pointwise kernels carry: act_pre (0..4), 5 residual, 6 residual + ReLU, 7 / 8 = 5 / 6
+                                        // with the output gate (a.ogate); -1: none of these
     int ng, pt, wn, ks, ksc, bm, bn;    // template arguments, those the family has
     bool gated, hilo, ln, xsplit, pipe;
     bool pf2;                           // PWK_DIRECT: the VIP_PWK_PF2 experiment (pwk_direct2_kernel)
@@ -455,10 +460,49 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
 //   * waves never synchronise after the weight staging, so one wave's epilogue (VALU + stores) overlaps the
 //     others' loads and MFMAs.
 // epilogue of the streaming kernel: the bias is already in the accumulators (it was the MFMA C operand), the
-// activation runs two values per VALU slot, and residual / post-ReLU code exists only in the variants that use it
-template <int PT, int ACT, bool RES, bool POST_RELU>
+// activation runs two values per VALU slot, and residual / post-ReLU / output-gate code exists only in the variants that use it.
+// OGATE: out = post(acc * g[image(m), n] + res) - the squeeze-excite multiply of a block tail whose gate was computed from the layer's
+// INPUT (the layer is linear, so mean_hw(y) = W mean_hw(x) + b).  g = hi + lo of the split gate [B][2][Cout] (exact in fp32), the
+// multiply is fp32 on the accumulators (bias included), before the residual add and the one fp16 rounding of the store.
+// The gates come out of LDS (stage_out_gate below put the rows of the tile's few images there, joined to fp32): fetched from memory per
+// pixel they were two more 16-byte loads and sixteen conversions next to every residual load (ResNet-RS stage 1: 193 -> 178 us).
+struct GateLds {
+    const float* g;     // [images][stride] fp32, image img0 first, channel n0 first
+    int img0, stride, n0;
+};
+
+// m / gate_hw without a division (hw_magic = min(2^32 / gate_hw, 2^32 - 1): the estimate is at most one short)
+__device__ __forceinline__ unsigned image_of(const ConvArgs& a, unsigned m) {
+    unsigned img = __umulhi(m, a.hw_magic);
+    if (m - img * (unsigned)a.gate_hw >= (unsigned)a.gate_hw) ++img;
+    return img;
+}
+
+// rows [m_first, m_first + rows) of the output, channels [n0, n0 + nch): g[img - img0][n - n0] = hi + lo for their images, written by
+// `nthreads` threads (a wave or the workgroup; the caller synchronises them) -> the first image.  Channels past Cout read as zero.
+__device__ __forceinline__ int stage_out_gate(const ConvArgs& a, float* g_lds, int stride, int m_first, int rows, int n0, int nch, int t,
+                                              int nthreads) {
+    const __amdgpu_buffer_rsrc_t rb_g = __builtin_amdgcn_make_buffer_rsrc((void*)a.ogate, 0, (unsigned)a.ogate_elems * 2u, 0x00020000);
+    const int img0 = (int)image_of(a, (unsigned)min(m_first, a.M - 1)), img1 = (int)image_of(a, (unsigned)min(m_first + rows - 1, a.M - 1));
+    const int q = nch >> 2;                                  // 4-channel groups per image
+    for (int i = t; i < (img1 - img0 + 1) * q; i += nthreads) {
+        const int im = i / q, c = (i - im * q) * 4, n = n0 + c;
+        const unsigned off = n < a.Cout_g ? ((unsigned)(img0 + im) * 2u * (unsigned)a.Cout_g + (unsigned)n) * 2u : 0xFFFFFFF0u;
+        typedef __attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned u32x2;
+        const u32x2 hv = __builtin_amdgcn_raw_buffer_load_b64(rb_g, off, 0, 0);
+        const u32x2 lv = __builtin_amdgcn_raw_buffer_load_b64(rb_g, n < a.Cout_g ? off + (unsigned)a.Cout_g * 2u : 0xFFFFFFF0u, 0, 0);
+        const f16x4 hh = __builtin_bit_cast(f16x4, hv), ll = __builtin_bit_cast(f16x4, lv);
+        f32x4 gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = (float)hh[j] + (float)ll[j];
+        *reinterpret_cast<f32x4*>(g_lds + im * stride + c) = gv;
+    }
+    return img0;
+}
+
+template <int PT, int ACT, bool RES, bool POST_RELU, bool OGATE = false>
 __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][4], int m_base, int n_first,
-                                            const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y) {
+                                            const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y, GateLds gl = GateLds{}) {
     constexpr unsigned OOB = 0xFFFFFFF0u;
     if constexpr (H2) {
 #pragma unroll
@@ -475,22 +519,34 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
         }
         return;
     }
+    static_assert(!(OGATE && H2), "the output gate is carried by the fp16-storage build only");
 #pragma unroll
     for (int p = 0; p < PT; ++p) {
         const int m = m_base + p * 16;
+        int g_row = 0;           // the pixel's image row in the staged gates (rows past M: the first one, their stores are dropped)
+        if constexpr (OGATE) g_row = m < a.M ? ((int)image_of(a, (unsigned)m) - gl.img0) * gl.stride - gl.n0 : -gl.n0;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int n = n_first + h * 32;
             const bool ok = (m < a.M) & (n < a.Cout_g);
             U4H8 r;
+            f32x4 g0, g1;
             if constexpr (RES)
                 r.u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
                                                     rb_res, ok ? ((unsigned)m * (unsigned)a.ldr + (unsigned)(a.res_off + n)) * 2u : OOB, 0, 0));
+            if constexpr (OGATE) {      // (n is inside the staged channel range for every lane: the range is whole 64-channel tiles)
+                g0 = *reinterpret_cast<const f32x4*>(gl.g + g_row + n);
+                g1 = *reinterpret_cast<const f32x4*>(gl.g + g_row + n + 4);
+            }
             U4H8 o;
 #pragma unroll
             for (int j = 0; j < 8; j += 2) {
                 const f32x4 av = acc[p][h * 2 + (j >> 2)];
                 f32x2 t = vip_act2<ACT>((f32x2){av[j & 3], av[(j & 3) + 1]});
+                if constexpr (OGATE) {
+                    const f32x4 gq = j < 4 ? g0 : g1;
+                    t = t * (f32x2){gq[j & 3], gq[(j & 3) + 1]};
+                }
                 if constexpr (RES) t = t + (f32x2){(float)r.e[j], (float)r.e[j + 1]};
                 if constexpr (POST_RELU) t = (f32x2){fmaxf(t.x, 0.f), fmaxf(t.y, 0.f)};
                 o.e[j] = (f16)t.x;
@@ -503,10 +559,13 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
     }
 }
 
-// mode = act_pre (0..4) without residual, 5 = residual, 6 = residual + post-ReLU (both with act_pre none)
+// mode = act_pre (0..4) without residual, 5 = residual, 6 = residual + post-ReLU (both with act_pre none), 7 / 8 = 5 / 6 with the
+// output gate (fp16 storage only)
 // HILO: the LDS row of a channel holds its fp16 weights followed by their low halves (w_lo); every activation fragment is
 // multiplied by both, so the layer computes with ~22-bit weights.  These layers are HBM-bound, the second MFMA is free.
-template <int KS, int PT, bool PRE, bool HILO>
+// OG: the instantiations of the output-gated epilogue (modes 7 / 8, nothing else) - kernels of their own, so that the gate's registers
+// (two more 16-byte loads per 8 channels, live next to the prefetched tile) cost the un-gated layers nothing.
+template <int KS, int PT, bool PRE, bool HILO, bool OG = false>
 __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, int lds_stride, int n_tiles, int mode) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -515,6 +574,9 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
     const int nch = min(nb_ch, ((a.Cout_g - n_chunk0) + 63) & ~63);   // channels computed by this block (x64)
     constexpr unsigned OOB = 0xFFFFFFF0u;
     float* bias_lds = reinterpret_cast<float*>(smem + nb_ch * lds_stride);
+    // OG: each wave keeps the gate rows of its 64 pixels' images (at most OG_IMAGES: conv2d_plan) behind the bias, [image][nb_ch] fp32
+    constexpr int OG_IMAGES = 4;
+    float* g_lds = bias_lds + nb_ch + (tid >> 6) * (OG_IMAGES * nb_ch);
 
     {   // stage the weight slice: LDS row j <-> channel n_chunk0 + (j & ~63) + perm(j & 63) (fragment order)
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
@@ -574,6 +636,16 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
             // is all out-of-range offsets: no memory traffic)
             load_x(tile + gridDim.x, xn);
         }
+        GateLds gl{};
+        if constexpr (OG) {     // wave-local: LDS operations of one wave complete in order, the fences keep the compiler to it
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int img0 = stage_out_gate(a, g_lds, nb_ch, __builtin_amdgcn_readfirstlane(m0), 16 * PT, n_chunk0, nch, lane, 64);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            gl = GateLds{g_lds, img0, nb_ch, n_chunk0};
+        }
         for (int sub = 0; sub < nch; sub += 64) {
             f32x4 acc[PT][4];
             const char* ws = wl + sub * lds_stride;
@@ -627,6 +699,10 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
                 }
             }
             const int m_base = m0 + l15, n_first = n_chunk0 + sub + lq * 8;
+            if constexpr (OG) {
+                if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+                else pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+            } else
             switch (mode) {
                 case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
                 case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
@@ -648,20 +724,24 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
     }
 }
 
-template <int KS, int PT, bool HILO>
+// LDS of the output-gated streaming kernel's gate rows: 4 waves x OG_IMAGES images x nb_ch fp32
+constexpr size_t pw_og_lds(int nb_ch) { return (size_t)4 * 4 * nb_ch * 4; }
+
+template <int KS, int PT, bool HILO, bool OG = false>
 int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
-    constexpr bool PRE = KS <= 3;
+    // (the gated epilogue holds two more 16-byte loads per 8 channels: at KS = 3 it does not fit next to a prefetched tile without scratch)
+    constexpr bool PRE = OG ? KS <= 2 : KS <= 3;
     const int n_tiles = (a.M + 64 * PT - 1) / (64 * PT);
     int gx = (2 * device_cus() + p.n_chunks - 1) / p.n_chunks;      // two workgroups per CU
     if (gx > n_tiles) gx = n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO, OG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
-                       (size_t)p.nb_ch * (p.lds_stride + 4), s, a, p.nb_ch, p.lds_stride, n_tiles, p.mode);
+    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO, OG>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
+                       (size_t)p.nb_ch * (p.lds_stride + 4) + (OG ? pw_og_lds(p.nb_ch) : 0), s, a, p.nb_ch, p.lds_stride, n_tiles, p.mode);
     return vip_launch_status("vip_conv2d_nhwc_f16(pw)");
 }
 
@@ -904,6 +984,17 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode
     asm volatile("" : "+v"(m_base), "+v"(n_lane));
     // (not a loop over g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be
     // indexed dynamically, i.e. live in scratch)
+    GateLds gl{};
+#if !VIP_GEMM_H2
+    if constexpr (!GATED) {
+        if (mode >= 7) {    // output gate: the weight stages are free after the loop's last barrier - the gate rows of the block's images go there
+            float* g_lds = reinterpret_cast<float*>(smem);
+            const int img0 = stage_out_gate(a, g_lds, NB, mb * (64 * PT), 64 * PT, n0, NB, (int)threadIdx.x, 256);
+            __syncthreads();
+            gl = GateLds{g_lds, img0, NB, n0};
+        }
+    }
+#endif
     auto epi = [&](auto gtag) {
         constexpr int G_ = decltype(gtag)::value;
         const int n_first = n_lane + G_ * 64;
@@ -914,6 +1005,11 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode
             case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
             case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
             case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
+#if !VIP_GEMM_H2
+            // output gate: the instantiations without the INPUT gate alone (plan() sends no other one here in modes 7 / 8)
+            case 7: if constexpr (!GATED) pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl); break;
+            case 8: if constexpr (!GATED) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl); break;
+#endif
             default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
         }
     };
@@ -1642,7 +1738,9 @@ int launch_pwk(const ConvArgs& a, int mode, int groups, hipStream_t s) {
 // waves whose partial sums meet in LDS once, and (N/16) x (M/64) workgroups run side by side.
 // XSPLIT: the rows are [M][2][K] - a hi and a lo fp16 plane (what gap_kernel / this kernel write with y_lo_off) - and every weight
 // fragment meets both: the vector keeps ~22 bits through the squeeze-excite / ECA / split-attention chains.
-template <bool XSPLIT>
+// WLO (with XSPLIT, fp16 storage): two-term weights - a.w_lo, fp16(W32 - w) in the layout of w, meets the hi plane of the rows (the
+// product of the two lo terms is below the fp32 sum's own rounding)
+template <bool XSPLIT, bool WLO = false>
 __global__ __launch_bounds__(256) void rows_gemm_kernel(ConvArgs a) {
     // workgroup = (16 channels, 64 rows): blockIdx.y = row quarter; its 4 waves split K and meet in LDS.  (One workgroup
     // per channel slab streaming ALL rows was bound by a single CU's L2 bandwidth: 1 MB of activations per workgroup.)
@@ -1699,6 +1797,24 @@ __global__ __launch_bounds__(256) void rows_gemm_kernel(ConvArgs a) {
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int p = 0; p < 4; ++p) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u].h, xf[u][p].h, acc[p], 0, 0, 0);
+            if constexpr (WLO) {
+                const __amdgpu_buffer_rsrc_t rwl = __builtin_amdgcn_make_buffer_rsrc(
+                    (void*)a.w_lo, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool ok = (ks0 + u < ks_hi) & ((ks0 + u) * 32 + lq * 8 < a.K);
+                    wf[u].u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rwl, ok ? w_off + (ks0 + u) * 64 : OOB, 0, 0));
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u].h, xf[u][p].h, acc[p], 0, 0, 0);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {       // the weights' first term again, for the rows' lo plane
+                    const bool ok = (ks0 + u < ks_hi) & ((ks0 + u) * 32 + lq * 8 < a.K);
+                    wf[u].u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? w_off + (ks0 + u) * 64 : OOB, 0, 0));
+                }
+            }
             if constexpr (XSPLIT) {     // the lo plane: K halfs further in the same row
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -1768,9 +1884,9 @@ __global__ __launch_bounds__(256) void rows_gemm_kernel(ConvArgs a) {
     }
 }
 
-template <bool XSPLIT>
+template <bool XSPLIT, bool WLO = false>
 int launch_rows(const ConvArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(rows_gemm_kernel<XSPLIT>, dim3((unsigned)((a.Cout_g + 15) / 16), (unsigned)((a.M + 63) / 64)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((rows_gemm_kernel<XSPLIT, WLO>), dim3((unsigned)((a.Cout_g + 15) / 16), (unsigned)((a.M + 63) / 64)), dim3(256), 0, s, a);
     return vip_launch_status("vip_conv2d_nhwc_f16(rows)");
 }
 
@@ -1884,6 +2000,13 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
     static const int pw_mode = getenv("VIP_PW") ? atoi(getenv("VIP_PW")) : 3;
     if (pw_mode && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->pl == 0 &&
         d->Ho == d->H && d->Wo == d->W) {
+        if (w_lo && x_split) {      // vip_gemm_split2_hilo_f16: a few split rows against two-term weights
+            VIP_REQUIRE(!H2 && M <= 256 && !residual && !gate && a.y_lo_off && d->act_post == VIP_ACT_NONE && d->ldy % 4 == 0 &&
+                            d->cout_off % 4 == 0 && a.x_span_bytes < 0xFFFF0000L - 2L * a.K && 2L * cout_g * d->ldw < 0xFFFF0000L - 2L * a.K,
+                        VIP_ERR_UNSUPPORTED, "vip_gemm_split2_hilo_f16: at most 256 rows, N %% 4 == 0");
+            p.family = ROWS_GEMM; p.xsplit = true; p.hilo = true;
+            return VIP_OK;
+        }
         if (w_lo) {     // hi + lo weights: the streaming kernel is the one that carries them (any M)
             VIP_REQUIRE(mode >= 0 && short_k && !gate && !a.y_lo_off, VIP_ERR_UNSUPPORTED,
                         "vip_conv2d_hilo_nhwc_f16: 1x1 stride-1 ungrouped, K <= 256, (activation) or (residual [+ReLU]) epilogue");
@@ -1967,9 +2090,15 @@ static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s) {
         case PW_GEMM:
             return with_const<1, 2, 3, 4, 6, 8>(p.ks, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value;
+                if constexpr (!H2 && KS <= 4)       // (K > 128: the gated epilogue would spill - conv2d_plan declines)
+                    if (p.mode >= 7) return p.hilo ? launch_pw<KS, 4, true, true>(a, p, s) : launch_pw<KS, 4, false, true>(a, p, s);
+                if (p.mode >= 7) return (int)VIP_ERR_UNSUPPORTED;
                 return p.hilo ? launch_pw<KS, 4, true>(a, p, s) : launch_pw<KS, 4, false>(a, p, s);
             });
-        case ROWS_GEMM: return p.xsplit ? launch_rows<true>(a, s) : launch_rows<false>(a, s);
+        case ROWS_GEMM:
+            if constexpr (!H2)
+                if (p.hilo) return launch_rows<true, true>(a, s);
+            return p.xsplit ? launch_rows<true>(a, s) : launch_rows<false>(a, s);
         case GEMM8P: return launch_gemm8p(a, p.mode, p.pipe, s);
         case PWX:
 #if !VIP_GEMM_H2
@@ -1992,7 +2121,7 @@ static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s) {
 // the argument checks, the kernel arguments and the plan of one call
 static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
                        const vip_conv_desc* d, const void* w_lo, bool x_split, float out_scale, int* status, const float* ln_g,
-                       const float* ln_b, float ln_eps, ConvArgs* args, Plan* p) {
+                       const float* ln_b, float ln_eps, ConvArgs* args, Plan* p, const void* out_gate = nullptr) {
     VIP_REQUIRE(x && w && y && d, VIP_ERR_BAD_ARG, "vip_conv2d_nhwc_f16: null pointer");
     VIP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kh > 0 && d->kw > 0 &&
                     d->sh > 0 && d->sw > 0 && d->Ho > 0 && d->Wo > 0 && d->groups > 0 && d->pt >= 0 && d->pl >= 0,
@@ -2043,28 +2172,52 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
     a.gate_hw = d->Ho * d->Wo;
     a.y_lo_off = y_lo_off;
     a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
-    return plan(a, d, x_split, p);
+    a.ogate = (const f16*)out_gate;
+    a.ogate_elems = 0;
+    a.hw_magic = a.gate_hw > 1 ? (unsigned)((1L << 32) / a.gate_hw) : 0xFFFFFFFFu;
+    if (!out_gate) return plan(a, d, x_split, p);
+    // Output gate: the selection is the residual call's own (the plan below does not see the gate); only the two kernel families that
+    // serve the block-final 1x1 layers carry the gated epilogue, everything else declines and the caller runs its two launches.
+    VIP_REQUIRE(!H2 && residual && !gate && !y_lo_off && !x_split && !ln_g && d->groups == 1 && d->cout_off == 0 && d->act_pre == VIP_ACT_NONE &&
+                    (d->act_post == VIP_ACT_NONE || d->act_post == VIP_ACT_RELU) && 4L * d->B * d->Cout < 0xFFFFFFF0L,
+                VIP_ERR_UNSUPPORTED, "vip_conv2d_out_gated_nhwc_f16: ungrouped, residual [+ReLU] epilogue, no input gate, cout_off = 0");
+    a.ogate_elems = 2 * d->B * d->Cout;
+    const int st = plan(a, d, x_split, p);
+    if (st != VIP_OK) return st;
+    // (pw_gemm_kernel up to K = 128: with six or eight k-steps of activation fragments resident the gated epilogue goes to scratch.
+    // The gate rows of a tile's images are staged in LDS: a wave's 64 pixels may span four images there - maps of 32 pixels and more -
+    // next to a weight slice that still leaves room for two workgroups per CU; the direct kernel has its 256 pixels' images in the
+    // weight stages, 80 of them.)
+    const bool pw_ok = p->family == PW_GEMM && p->ks <= 4 && 63 / a.gate_hw + 2 <= 4 &&
+                       (size_t)p->nb_ch * (p->lds_stride + 4) + pw_og_lds(p->nb_ch) <= 80 * 1024;
+    const bool pwk_ok = p->family == PWK_DIRECT && !p->gated && !p->pf2 && (64 * p->pt - 1) / a.gate_hw + 2 <= 80;
+    VIP_REQUIRE((p->mode == 5 || p->mode == 6) && (pw_ok || pwk_ok), VIP_ERR_UNSUPPORTED,
+                "vip_conv2d_out_gated_nhwc_f16: this shape's kernel carries no output gate (pw_gemm_kernel up to K = 128 and "
+                "pwk_direct_kernel do)");
+    p->mode += 2;
+    return VIP_OK;
 }
 
 static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
                        const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
-                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
+                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
+                       const void* out_gate = nullptr) {
     ConvArgs a;
     Plan p;
-    const int st = conv2d_plan(x, gate, y_lo_off, w, bias, residual, y, d, w_lo, x_split, out_scale, status, ln_g, ln_b, ln_eps, &a, &p);
+    const int st = conv2d_plan(x, gate, y_lo_off, w, bias, residual, y, d, w_lo, x_split, out_scale, status, ln_g, ln_b, ln_eps, &a, &p, out_gate);
     return st != VIP_OK ? st : launch(p, a, d->groups, (hipStream_t)stream);
 }
 
 // vip_conv2d_kernel_name[_h2] / vip_conv2d_kernel_variant[_h2]: a dry run - the checks and the plan of the call the flags describe, and
 // no launch.  The name is the kernel family (profile labels), the variant the instantiation and its tile grid.
 static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* out,
-                        size_t cap) {
+                        size_t cap, bool out_gate = false) {
     VIP_REQUIRE(d && out && cap > 0, VIP_ERR_BAD_ARG, "%s: null pointer", who);
     static const char dummy[16] = {0};     // non-null stand-ins: nothing is dereferenced or launched in a dry run
     ConvArgs a;
     Plan p;
     const int st = conv2d_plan(dummy, has_gate ? dummy : nullptr, 0, dummy, nullptr, has_residual ? dummy : nullptr, const_cast<char*>(dummy), d,
-                               has_w_lo ? dummy : nullptr, false, 1.f, nullptr, nullptr, nullptr, 0.f, &a, &p);
+                               has_w_lo ? dummy : nullptr, false, 1.f, nullptr, nullptr, nullptr, 0.f, &a, &p, out_gate ? dummy : nullptr);
     if (st != VIP_OK) return st;
     static const char* const kernel[] = {"pw_gemm_kernel",    "rows_gemm_kernel", "gemm8p_kernel",           "pwx_kernel",
                                          "pwk_direct_kernel", "pwk_gemm_kernel",  "pwk_gemm_kernel(im2col)", "conv_igemm_kernel"};
@@ -2073,13 +2226,13 @@ static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, i
         return VIP_OK;
     }
     switch (p.family) {
-        case PW_GEMM: snprintf(out, cap, "pw_gemm<KS=%d%s> %d x %d", p.ks, p.hilo ? ",hilo" : "", p.n_chunks, p.nb_ch); break;
+        case PW_GEMM: snprintf(out, cap, "pw_gemm<KS=%d%s> %d x %d%s", p.ks, p.hilo ? ",hilo" : "", p.n_chunks, p.nb_ch, p.mode >= 7 ? " ogate" : ""); break;
         case ROWS_GEMM: snprintf(out, cap, "rows_gemm%s", p.xsplit ? "<xsplit>" : ""); break;
         case GEMM8P: snprintf(out, cap, "gemm8p<%s> %d x %d", p.pipe ? "pipe" : "basic", p.m_blocks, p.n_blocks); break;
         case PWX: snprintf(out, cap, "%s<%d,%d>", p.ln ? "pwx_ln" : "pwx", p.ksc, p.pt); break;
         case PWK_DIRECT:
             if (p.pf2) snprintf(out, cap, "pwk_direct2<%d>", p.ng);
-            else snprintf(out, cap, "pwk_direct<%d%s> PT=%d", p.ng, p.gated ? ",gated" : "", p.pt);
+            else snprintf(out, cap, "pwk_direct<%d%s> PT=%d%s", p.ng, p.gated ? ",gated" : "", p.pt, p.mode >= 7 ? " ogate" : "");
             break;
         case PWK_GEMM: snprintf(out, cap, "pwk_gemm<%d,%d> %d x %d", p.ng, p.wn, p.m_blocks, p.n_blocks); break;
         case IM2COL: snprintf(out, cap, "im2col<%d>", p.ng); break;
@@ -2134,6 +2287,20 @@ extern "C" int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const v
                                         const void* residual, void* y, const vip_conv_desc* d, void* stream) {
     VIP_REQUIRE(w_lo, VIP_ERR_BAD_ARG, "vip_conv2d_hilo_nhwc_f16: null w_lo");
     return conv2d_impl(x, nullptr, 0, w_hi, bias, residual, y, d, stream, w_lo);
+}
+
+/* y = act_post(conv(x) * g + residual), g = hi + lo of out_gate [B][2][Cout] fp16 (vip_se_gate_f16 with split): the squeeze-excite
+ * multiply, the shortcut add and the block's ReLU in the epilogue of the block-final 1x1 layer.  w_lo: the layer's second weight term
+ * or NULL.  Only where the same call with a residual selects pw_gemm_kernel or pwk_direct_kernel; VIP_ERR_UNSUPPORTED otherwise. */
+extern "C" int vip_conv2d_out_gated_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
+                                             const void* residual, void* y, const vip_conv_desc* d, void* stream) {
+    VIP_REQUIRE(out_gate && residual, VIP_ERR_BAD_ARG, "vip_conv2d_out_gated_nhwc_f16: null gate or residual");
+    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream, w_lo, false, 1.f, nullptr, nullptr, nullptr, 0.f, out_gate);
+}
+
+/* dry run of vip_conv2d_out_gated_nhwc_f16: VIP_OK and the instantiation ("pw_gemm<KS=2,hilo> 1 x 256 ogate") where the call is taken */
+extern "C" int vip_conv2d_out_gated_variant(const vip_conv_desc* d, int has_w_lo, char* variant, size_t cap) {
+    return kernel_query("vip_conv2d_out_gated_variant", true, d, 1, 0, has_w_lo, variant, cap, true);
 }
 
 extern "C" int vip_conv2d_kernel_name(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* name,
@@ -2197,6 +2364,15 @@ extern "C" int vip_gemm_split_f16(const void* A, const void* W, const float* bia
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: M=%d (1..256 rows)", M);
     const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, 2 * N, 0, act, VIP_ACT_NONE);
     return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream);
+}
+
+extern "C" int vip_gemm_split2_hilo_f16(const void* A, const void* W, const void* W_lo, const float* bias, void* C, int M, int N, int K,
+                                        int ldw, int act, void* stream) {
+    VIP_REQUIRE(W_lo, VIP_ERR_BAD_ARG, "vip_gemm_split2_hilo_f16: null W_lo");
+    VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split2_hilo_f16: M=%d (1..256 rows)", M);
+    VIP_REQUIRE(K % 8 == 0, VIP_ERR_ALIGNMENT, "vip_gemm_split2_hilo_f16: K must be a multiple of 8");
+    const vip_conv_desc d = gemm_desc(M, N, K, 2 * K, ldw, 2 * N, 0, act, VIP_ACT_NONE);
+    return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream, W_lo, true);
 }
 
 extern "C" int vip_gemm_split2_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int ldw, int act,

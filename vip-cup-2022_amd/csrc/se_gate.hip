@@ -18,6 +18,7 @@ namespace {
 struct SeArgs {
     const f16* x;
     const f16* w1;
+    const f16* w1_lo;    // W1LO: the second term of w1, fp16(W32 - w1) in w1's layout (a folded reduce layer: vip_se_gate_hilo_f16)
     const float* b1;
     const f16* w2;
     const float* b2;
@@ -36,7 +37,9 @@ struct SeArgs {
 
 constexpr int SE_THREADS = 512;
 
-template <bool H2S>
+// W1LO: the first matrix comes as two fp16 terms (w1 + w1_lo, ~22 bits), joined in fp32 before the multiply.  For a reduce layer that
+// is the PRODUCT of two layers (ops.se_fold): its elements are not fp16 values, and their rounding would be the gate's largest error.
+template <bool H2S, bool W1LO = false>
 __global__ __launch_bounds__(SE_THREADS) void se_gate_kernel(SeArgs a) {
     constexpr int ES = H2S ? 2 : 1;                      // halfs per element
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -126,6 +129,12 @@ __global__ __launch_bounds__(SE_THREADS) void se_gate_kernel(SeArgs a) {
             for (int u = 0; u < 4; ++u) {
                 const int r = r0 + u < a.Cr ? r0 + u : a.Cr - 1;
                 ld8(a.w1 + (long)r * a.ldw1, c8 * 8, w[u]);               // (ldw in halfs in both storages)
+                if constexpr (W1LO) {
+                    float wl[8];
+                    ld8(a.w1_lo + (long)r * a.ldw1, c8 * 8, wl);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) w[u][j] += wl[j];
+                }
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -174,9 +183,8 @@ __global__ __launch_bounds__(SE_THREADS) void se_gate_kernel(SeArgs a) {
 
 }  // namespace
 
-extern "C" int vip_se_gate_f16(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* gate,
-                               int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2,
-                               int split, void* stream) {
+static int se_gate_f16(const void* x, const void* w1, const void* w1_lo, const float* b1, const void* w2, const float* b2, void* gate,
+                       int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2, int split, void* stream) {
     VIP_REQUIRE(x && w1 && w2 && gate, VIP_ERR_BAD_ARG, "vip_se_gate_f16: null pointer");
     VIP_REQUIRE(B > 0 && HW > 0 && C > 0 && Cr > 0 && Cout > 0, VIP_ERR_BAD_ARG, "vip_se_gate_f16: non-positive dimension");
     VIP_REQUIRE((unsigned)act1 <= 4u && (unsigned)act2 <= 4u, VIP_ERR_BAD_ARG, "vip_se_gate_f16: unknown activation code");
@@ -192,8 +200,24 @@ extern "C" int vip_se_gate_f16(const void* x, const void* w1, const float* b1, c
     a.act1 = act1; a.act2 = act2; a.split = split ? 1 : 0;
     a.part = nullptr; a.parts = 0;
     a.s1 = a.s2 = 1.f; a.status = nullptr;
-    hipLaunchKernelGGL(se_gate_kernel<false>, dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
+    a.w1_lo = (const f16*)w1_lo;
+    if (w1_lo) hipLaunchKernelGGL((se_gate_kernel<false, true>), dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(se_gate_kernel<false>, dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
     return vip_launch_status("vip_se_gate_f16");
+}
+
+extern "C" int vip_se_gate_f16(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* gate,
+                               int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2,
+                               int split, void* stream) {
+    return se_gate_f16(x, w1, nullptr, b1, w2, b2, gate, B, HW, C, ldx, Cr, ldw1, Cout, ldw2, act1, act2, split, stream);
+}
+
+/* vip_se_gate_f16 with a two-term first matrix: w1_lo = fp16(W32 - w1) in the layout of w1 (same ldw1). */
+extern "C" int vip_se_gate_hilo_f16(const void* x, const void* w1, const void* w1_lo, const float* b1, const void* w2, const float* b2,
+                                    void* gate, int B, int HW, int C, int ldx, int Cr, int ldw1, int Cout, int ldw2, int act1, int act2,
+                                    int split, void* stream) {
+    VIP_REQUIRE(w1_lo, VIP_ERR_BAD_ARG, "vip_se_gate_hilo_f16: null w1_lo");
+    return se_gate_f16(x, w1, w1_lo, b1, w2, b2, gate, B, HW, C, ldx, Cr, ldw1, Cout, ldw2, act1, act2, split, stream);
 }
 
 /* The same chain on the packed STRICT storage: x [B][HW][ldx] and gate [B][Cout] packed (hi, lo) pairs (counts in ELEMENTS), w1 / w2
@@ -214,7 +238,7 @@ extern "C" int vip_se_gate_h2(const void* x, const void* w1, const float* b1, fl
     a.x = (const f16*)x; a.w1 = (const f16*)w1; a.b1 = b1; a.w2 = (const f16*)w2; a.b2 = b2; a.gate = (f16*)gate;
     a.HW = HW; a.C = C; a.ldx = ldx; a.Cr = Cr; a.ldw1 = ldw1; a.Co = Cout; a.ldw2 = ldw2; a.ldg = Cout;
     a.act1 = act1; a.act2 = act2; a.split = 0;
-    a.part = nullptr; a.parts = 0;
+    a.part = nullptr; a.parts = 0; a.w1_lo = nullptr;
     a.s1 = s1; a.s2 = s2; a.status = status;
     hipLaunchKernelGGL(se_gate_kernel<true>, dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
     return vip_launch_status("vip_se_gate_h2");
@@ -237,7 +261,7 @@ extern "C" int vip_se_gate_pooled_h2(const float* partials, int parts, const voi
     a.x = nullptr; a.w1 = (const f16*)w1; a.b1 = b1; a.w2 = (const f16*)w2; a.b2 = b2; a.gate = (f16*)gate;
     a.HW = HW; a.C = C; a.ldx = C; a.Cr = Cr; a.ldw1 = ldw1; a.Co = Cout; a.ldw2 = ldw2; a.ldg = Cout;
     a.act1 = act1; a.act2 = act2; a.split = 0;
-    a.part = partials; a.parts = parts;
+    a.part = partials; a.parts = parts; a.w1_lo = nullptr;
     a.s1 = s1; a.s2 = s2; a.status = status;
     hipLaunchKernelGGL(se_gate_kernel<true>, dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
     return vip_launch_status("vip_se_gate_pooled_h2");
@@ -259,7 +283,7 @@ extern "C" int vip_se_gate_pooled_f16(const float* partials, int parts, const vo
     a.x = nullptr; a.w1 = (const f16*)w1; a.b1 = b1; a.w2 = (const f16*)w2; a.b2 = b2; a.gate = (f16*)gate;
     a.HW = HW; a.C = C; a.ldx = C; a.Cr = Cr; a.ldw1 = ldw1; a.Co = Cout; a.ldw2 = ldw2; a.ldg = split ? 2 * Cout : Cout;
     a.act1 = act1; a.act2 = act2; a.split = split ? 1 : 0;
-    a.part = partials; a.parts = parts;
+    a.part = partials; a.parts = parts; a.w1_lo = nullptr;
     a.s1 = a.s2 = 1.f; a.status = nullptr;
     hipLaunchKernelGGL(se_gate_kernel<false>, dim3(B), dim3(SE_THREADS), smem, (hipStream_t)stream, a);
     return vip_launch_status("vip_se_gate_pooled_f16");

@@ -38,6 +38,7 @@ _MLP_H2_FUSED = _env_flag("VIP_MLP_H2_FUSED", True)            # packed strict: 
 _SE_H2_FUSED = _env_flag("VIP_SE_H2_FUSED", True)              # packed strict: se_gate as one launch (vip_se_gate_h2)
 _H2_GATED = _env_flag("VIP_H2_GATED", True)                    # packed strict: the gate folded into the GEMM's activation operand
 _DW_H2_LDS = _env_int("VIP_DW_H2_LDS", 3)                      # smallest k the LDS-staged strict depthwise kernel takes (0: never)
+_SE_TAIL = _env_flag("VIP_SE_TAIL", True)                      # squeeze-excite block tails: gate from the final 1x1 layer's input, tail in its epilogue
 _DW_SE_FUSED = _env_flag("VIP_DW_SE_POOL", True)               # dwconv2d_se: the depthwise kernel leaves the pool's partial sums
 _GCVIT_BLOCK_FUSED = _env_flag("VIP_GCVIT_BLOCK_FUSED", True)  # gcvit_attn_block as one launch
 # the 14 x 14-window form of the fused block (C = 256, 8 heads: csrc/gcvit_block14.hip) is correct and NOT faster than the four launches
@@ -275,6 +276,7 @@ class ConvWeight:
     exact: Optional["ConvWeight"] = None  # calibration only (exact_weights()): [w | fp16(W32 - w)] along K, the uncorrected bias
     w_bf3: Optional[torch.Tensor] = None  # f32 mode: the fp32 weights as three bf16 planes [3, cout, ldwp] (w = p0 + p1 + p2 exactly)
     h2_scale: float = 0.0                 # packed strict mode (> 0): ``w`` holds fp16 (hi, lo) pairs of W * h2_scale, ``bias`` = b * h2_scale
+    fold: Optional[tuple] = None          # se_fold(): (what it was made from, the squeeze-excite reduce layer folded with this layer)
 
     @property
     def cin(self):
@@ -699,6 +701,85 @@ def conv2d(x: torch.Tensor, cw: ConvWeight, stride=1, pad=(0, 0, 0, 0), act=None
     return out
 
 
+def se_tail_folded(c3: ConvWeight, se_r: ConvWeight, se_e: ConvWeight) -> bool:
+    """Whether a squeeze-excite block tail ``scale_add_act(y, se_gate(y), shortcut)``, ``y = conv2d(z, c3)``, runs in its folded form:
+    gate from ``z`` with ``se_fold(c3, se_r)``, then ``conv2d_out_gated``.  The fp16 storage only, and never inside ``calibration()`` /
+    ``unfused()`` / ``exact_weights()``: there every layer is its own launch and sees its own input."""
+    return bool(_SE_TAIL and not (_UNFUSED or _CALIB or _EXACT) and c3.kind == se_r.kind == se_e.kind == "f16" and _pointwise(c3)
+                and _pointwise(se_r) and _pointwise(se_e) and se_r.cin == c3.cout and se_e.cin == se_r.cout and se_e.cout == c3.cout)
+
+
+def _fold_tag(c3: ConvWeight, se_r: ConvWeight) -> list:
+    """what a fold was made from: the reduce layer and the two bias tensors with their write counters (the weights never change)"""
+    return [se_r] + [v for b in (c3.bias, se_r.bias) for v in (b, None if b is None else b._version)]
+
+
+def se_fold(c3: ConvWeight, se_r: ConvWeight) -> ConvWeight:
+    """The reduce layer of a squeeze-excite block folded with the linear 1x1 layer ``c3`` in front of the pool:
+    ``Wr . mean_hw(W3 z + b3) + br = (Wr W3) . mean_hw(z) + (Wr b3 + br)`` -> the ConvWeight ``[r, f]`` that ``se_gate`` applies to the
+    pooled INPUT of ``c3`` (a quarter of the channels of its output, and a matrix four times smaller).  Folded in fp64 from the tensors
+    the layers multiply by - ``c3.w`` plus its second term ``w_lo`` where it has one, the fp32 biases as they are NOW.  The product's
+    elements are not fp16 values and one rounding of them would be the gate's largest error (4e-5 where ``se_gate`` itself is held to
+    2e-5), so the fold carries TWO terms, ``w = fp16(W)`` and ``w_lo = fp16(W - w)``, which ``se_gate`` joins in fp32.  Built on first
+    use and kept on ``c3``; built again when a bias tensor was replaced or written to (bias calibration does the former)."""
+    tag = _fold_tag(c3, se_r)
+    f = c3.fold
+    if f is not None and all(a is b or (type(a) is int and type(b) is int and a == b) for a, b in zip(f[0], tag)):
+        return f[1]
+    k, c = c3.cin, c3.cout
+    w3 = c3.w[:, :k].detach().cpu().double()
+    if c3.w_lo is not None:
+        w3 = w3 + c3.w_lo[:, :k].detach().cpu().double()
+    wr = se_r.w[:, :c].detach().cpu().double()
+    wf = (wr @ w3).float()                                                    # [r, f]
+    bf = torch.zeros(se_r.cout, dtype=torch.float64)
+    if c3.bias is not None:
+        bf = bf + wr @ c3.bias.detach().cpu().double()
+    if se_r.bias is not None:
+        bf = bf + se_r.bias.detach().cpu().double()
+    dev = c3.w.device
+    hi = wf.to(torch.float16)
+    folded = ConvWeight(w=hi.to(dev).contiguous(), bias=bf.float().to(dev).contiguous(), kh=1, kw=1, cin_g=k, cout=se_r.cout, groups=1,
+                        alg_cin_g=k, w_lo=(wf - hi.float()).to(torch.float16).to(dev).contiguous())
+    c3.fold = (tag, folded)
+    return folded
+
+
+def out_gate_variant(d: "_abi.ConvDesc", has_w_lo: bool = False) -> Optional[str]:
+    """The instantiation vip_conv2d_out_gated_nhwc_f16 launches for this descriptor ("pw_gemm<KS=2,hilo> 1 x 256 ogate": a dry run of
+    the C dispatcher, vip_conv2d_out_gated_variant) - the one the same call with a residual selects; None where it is not taken."""
+    return _conv_dry_run(_abi.lib().vip_conv2d_out_gated_variant, d, has_w_lo)
+
+
+def _out_gate_desc(x, cw: ConvWeight, gate, residual, act_post):
+    """the descriptor of the one-launch form of ``conv2d_out_gated``, or None where the call takes the two launches"""
+    if not (_SE_TAIL and not (_UNFUSED or _CALIB or _EXACT) and x.dtype == torch.float16 and x.is_cuda and x.dim() == 4 and x.is_contiguous()
+            and cw.kind == "f16" and _pointwise(cw) and x.shape[3] == cw.cin and residual is not None and residual.dtype == torch.float16
+            and residual.is_contiguous() and residual.shape == (*x.shape[:3], cw.cout) and gate.dtype == torch.float16
+            and gate.is_contiguous() and gate.shape == (x.shape[0], 2, cw.cout) and act_post in (None, "none", "linear", "relu")):
+        return None
+    B, H, W, ldx = x.shape
+    d = _abi.ConvDesc(B=B, H=H, W=W, Cin=cw.cin, Cout=cw.cout, kh=1, kw=1, sh=1, sw=1, pt=0, pl=0, Ho=H, Wo=W, groups=1, ldx=ldx, cin_off=0,
+                      ldy=cw.cout, cout_off=0, ldr=cw.cout, res_off=0, ldw=cw.ldw, act_pre=0, act_post=_act(act_post))
+    return d if out_gate_variant(d, cw.w_lo is not None) is not None else None
+
+
+def conv2d_out_gated(x: torch.Tensor, cw: ConvWeight, gate: torch.Tensor, residual: torch.Tensor, act_post=None) -> torch.Tensor:
+    """``act_post(conv2d(x, cw) * gate + residual)`` for a 1x1 layer without activation and a split gate ``[B, 2, cw.cout]`` that does
+    not depend on the layer's output (``se_fold``): ONE launch where the C ABI takes the shape (``out_gate_variant``: the gate multiply,
+    the residual add and the ReLU run on the fp32 accumulators, the un-gated map is never stored), otherwise ``conv2d`` then
+    ``scale_add_act`` - there the un-gated map is rounded to fp16 in between."""
+    d = _out_gate_desc(x, cw, gate, residual, act_post)
+    if d is None:
+        return scale_add_act(conv2d(x, cw), gate, residual, act_post)
+    out = torch.empty((*x.shape[:3], cw.cout), dtype=torch.float16, device=x.device)
+    has_lo = cw.w_lo is not None
+    _launch("vip_conv2d_out_gated_nhwc_f16", _p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(gate), _p(residual), _p(out), C.byref(d),
+            prof=lambda: _conv_prof(conv_kernel_name(d, True, False, has_lo) or "unsupported", d, cw, residual, 2.0, 2.0,
+                                    f" ogate res act_post={act_post}"))
+    return out
+
+
 _H2_SPAN_MAX = 0xFFFFFFE0       # the C kernels address every tensor through 32-bit buffer offsets
 
 
@@ -888,8 +969,12 @@ def se_gate(x: torch.Tensor, fc1: ConvWeight, fc2: ConvWeight, act1, act2="sigmo
         g = dense_split(dense_split(global_avgpool(x, split=True), fc1, act=act1), fc2, act=act2)
         return g if split else g[:, 0].contiguous()
     out = torch.empty((B, 2, fc2.cout) if split else (B, fc2.cout), dtype=torch.float16, device=x.device)
-    _launch("vip_se_gate_f16", _p(x), _p(fc1.w), _p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(out), B, H * W, Cc, Cc, fc1.cout, fc1.ldw,
-            fc2.cout, fc2.ldw, _act(act1), _act(act2), int(split))
+    tail = (_p(fc1.bias), _p(fc2.w), _p(fc2.bias), _p(out), B, H * W, Cc, Cc, fc1.cout, fc1.ldw, fc2.cout, fc2.ldw, _act(act1), _act(act2),
+            int(split))
+    if fc1.w_lo is not None:        # a two-term first layer (se_fold)
+        _launch("vip_se_gate_hilo_f16", _p(x), _p(fc1.w), _p(fc1.w_lo), *tail)
+    else:
+        _launch("vip_se_gate_f16", _p(x), _p(fc1.w), *tail)
     return out
 
 
@@ -905,11 +990,15 @@ def dense_split(x: torch.Tensor, cw: ConvWeight, act=None) -> torch.Tensor:
     if _EXACT and cw.exact is not None:
         x, cw, _ = _exact_operands(x, cw)
     M, K = x.shape[0], x.shape[-1]
+    if cw.w_lo is not None and not split_in:
+        raise _abi.VipError("dense_split: two-term weights take split rows [M, 2, K] only (vip_gemm_split2_hilo_f16)")
     out = torch.empty((M, 2, cw.cout), dtype=torch.float16, device=x.device)
     for m0 in range(0, M, 256):       # the C entry points take at most 256 rows (a batch of pooled vectors)
         m1 = min(M, m0 + 256)
         head = (_p(x[m0:m1]), _p(cw.w), _p(cw.bias), _p(out[m0:m1]), m1 - m0, cw.cout, K)
-        if split_in:
+        if cw.w_lo is not None:
+            _launch("vip_gemm_split2_hilo_f16", _p(x[m0:m1]), _p(cw.w), _p(cw.w_lo), *head[2:], cw.ldw, _act(act))
+        elif split_in:
             _launch("vip_gemm_split2_f16", *head, cw.ldw, _act(act))
         else:
             _launch("vip_gemm_split_f16", *head, K, cw.ldw, _act(act))

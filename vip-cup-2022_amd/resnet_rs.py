@@ -4,7 +4,9 @@ meaning (``depth``, ``se_ratio``, ``classes``, ``first_strides``, ``bn_epsilon``
 
 Every Conv2D+BatchNormalization(+Activation) group of the reference is ONE implicit-GEMM launch (BN is
 folded into the weights at load time, kecam model_surgery.py:407-421); the SE excite multiply, the
-residual Add and the block's output activation are one fused elementwise launch.
+residual Add and the block's output activation run in the epilogue of the block's last convolution,
+whose gate is computed from that convolution's INPUT (``ops.se_fold``; one elementwise launch after
+it on the strict storages and while calibrating).
 """
 from typing import Dict, List
 
@@ -107,6 +109,17 @@ class ResNetRS(CamMixin):
                 self.blocks.append(blk)
         self.head_w = p["predictions/kernel"].t().contiguous().to(device=device, dtype=torch.float32)
         self.head_b = p["predictions/bias"].to(device=device, dtype=torch.float32)
+        if not ops.KEEP_ROUNDING_ERROR:        # (a model built for bias calibration is prepared after it: zoo.construct)
+            self.prepare()
+
+    def prepare(self):
+        """Build the folded squeeze-excite reduce layers (ops.se_fold) NOW - after construction and again after bias calibration, which
+        replaces the biases they are made from - rather than inside the first forward pass: that pass is the one the ensemble times to
+        spread its members over streams, and host work in it would be booked as the member's cost."""
+        if self.has_se:
+            for blk in self.blocks:
+                if ops.se_tail_folded(blk["c3"], blk["se_r"], blk["se_e"]):
+                    ops.se_fold(blk["c3"], blk["se_r"])
 
     # resnet_rs_model.py:186-282
     def _bottleneck(self, x, blk):
@@ -122,6 +135,12 @@ class ResNetRS(CamMixin):
                 shortcut = ops.conv2d(x, blk["proj"], stride=s)
         y = ops.conv2d(x, blk["c1"], act=self.act)
         y = ops.conv2d(y, blk["c2"], stride=s, pad=(1, 1, 1, 1) if s == 1 else fixed_padding(3), act=self.act)
+        if self.has_se and ops.se_tail_folded(blk["c3"], blk["se_r"], blk["se_e"]):
+            # conv_3 is linear, so the pooled input of the gate is W3 . mean_hw(y) + b3: the gate comes from conv_3's INPUT (a quarter
+            # of the channels) through the folded reduce layer, and conv_3 finishes the block in its epilogue - its un-gated output,
+            # the pooling read of it and the elementwise launch are gone
+            scale = ops.se_gate(y, ops.se_fold(blk["c3"], blk["se_r"]), blk["se_e"], "relu", "sigmoid")
+            return ops.conv2d_out_gated(y, blk["c3"], scale, shortcut, self.act)
         y = ops.conv2d(y, blk["c3"])
         scale = None
         if self.has_se:

@@ -165,6 +165,8 @@ def construct(spec: MemberSpec, params, bias_calibration: bool = True, precision
         model.precision = "fast"
         batch = calibration_batch if calibration_batch is not None else pipeline.calibration_batch()
         calibrate(model, batch.resized(spec.input_hw, spec.input_hw))
+        if hasattr(model, "prepare"):      # what a model derives from its calibrated biases (ResNet-RS: the folded squeeze-excite layers)
+            model.prepare()
         torch.cuda.synchronize()
         return model
 
