@@ -120,6 +120,15 @@ int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const void* w_lo, 
 int vip_conv2d_out_gated_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
                                   const void* residual, void* y, const vip_conv_desc* d, void* stream);
 int vip_conv2d_out_gated_variant(const vip_conv_desc* d, int has_w_lo, char* variant, size_t cap);
+/* The two-output form: also y2[m, n] = act2(y[m, n]), from the ROUNDED y by the expression of vip_scale_add_act_f16's second output, so
+ * y2 is bit for bit what that launch gives on y.  The tail of an ECA-NFNet block (nfnets.py:116-168): deep_4 is linear, its ECA gate is
+ * formed from its pooled INPUT, and the next block reads act(x) - the un-gated map, the pool over it and the elementwise launch go.
+ * y2: the shape, span and leading dimension of y.  act2: VIP_ACT_SILU (anything else VIP_ERR_UNSUPPORTED).  Kernels of their own
+ * (pw_gemm_kernel<.., OG, Y2>, pwk_direct_kernel<.., OG2>); the selection and what declines are the one-output call's.
+ * vip_conv2d_out_gated2_variant: the dry run - the one-output variant with " y2" behind it. */
+int vip_conv2d_out_gated2_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
+                                   const void* residual, void* y, void* y2, int act2, const vip_conv_desc* d, void* stream);
+int vip_conv2d_out_gated2_variant(const vip_conv_desc* d, int has_w_lo, int act2, char* variant, size_t cap);
 
 /* Dense / 1x1 convenience wrapper: C[M,N] = act_post(act_pre(A[M,K] @ W[N,K]^T + bias) + residual).
  * Replaces tf.keras.layers.Dense (gcvit/layers/attention.py:25,33, feature.py:20-22;

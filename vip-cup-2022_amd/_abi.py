@@ -80,6 +80,8 @@ SIGNATURES = {
     "vip_conv2d_hilo_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_conv2d_out_gated_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
     "vip_conv2d_out_gated_variant": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
+    "vip_conv2d_out_gated2_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(ConvDesc), _vp]),
+    "vip_conv2d_out_gated2_variant": (_i, [C.POINTER(ConvDesc), _i, _i, C.c_char_p, _sz]),
     "vip_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _vp, _vp] + [_i] * 9 + [_vp]),
     "vip_ln_gemm_supported": (_i, [_i, _i, _i, _i]),
     "vip_ln_gemm_bias_act_f16": (_i, [_vp, _vp, _vp, _f] + [_vp] * 4 + [_i] * 9 + [_vp]),

@@ -22,6 +22,7 @@
 // kecam common_layers.py:190-248; tfimm convnext.py:260-267,320-327) and every Dense layer.
 #include "common.hpp"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 // VIP_GEMM_H2 = 1 (conv_h2.hip includes this file a second time): the same kernels for the packed STRICT storage of common.hpp -
@@ -82,6 +83,11 @@ struct ConvArgs {
     const float* ln_g; // pwx_ln_kernel: LayerNorm scale / shift [K] fp32 over the input row, applied to the activation fragments (else NULL)
     const float* ln_b;
     float ln_eps;
+};
+
+// the arguments of the two-output instantiations of the output-gated epilogue (pw_gemm_kernel<.., OG, Y2>, pwk_direct_kernel<.., OG2>)
+struct ConvArgs2 : ConvArgs {
+    f16* y2;           // second output act2(y): the shape, span and leading dimension of y
 };
 
 // What one call launches.  plan() (below the kernels) fills it from the arguments alone - host code, no HIP call, so a dry run
@@ -500,9 +506,13 @@ __device__ __forceinline__ int stage_out_gate(const ConvArgs& a, float* g_lds, i
     return img0;
 }
 
-template <int PT, int ACT, bool RES, bool POST_RELU, bool OGATE = false>
+// Y2 (with OGATE): a second output y2 = fp16(silu(float(y))) from the ROUNDED y, to rb_y2 at y's offsets - the expression of
+// scale_add_act_kernel's second output (pointwise.hip), so y2 is bit for bit what that launch computes from y (the next block's act(x)
+// of an ECA-NFNet block tail).
+template <int PT, int ACT, bool RES, bool POST_RELU, bool OGATE = false, bool Y2 = false>
 __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][4], int m_base, int n_first,
-                                            const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y, GateLds gl = GateLds{}) {
+                                            const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y, GateLds gl = GateLds{},
+                                            const __amdgpu_buffer_rsrc_t* rb_y2 = nullptr) {
     constexpr unsigned OOB = 0xFFFFFFF0u;
     if constexpr (H2) {
 #pragma unroll
@@ -520,6 +530,7 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
         return;
     }
     static_assert(!(OGATE && H2), "the output gate is carried by the fp16-storage build only");
+    static_assert(OGATE || !Y2, "the second output belongs to the output-gated epilogue");
 #pragma unroll
     for (int p = 0; p < PT; ++p) {
         const int m = m_base + p * 16;
@@ -555,6 +566,14 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
             __builtin_amdgcn_raw_buffer_store_b128(
                 __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o.u), rb_y,
                 ok ? ((unsigned)m * (unsigned)a.ldy + (unsigned)(a.cout_off + n)) * 2u : OOB, 0, 0);      // (unsigned: spans < 4 GiB, m * ld * 2 may pass 2^31)
+            if constexpr (Y2) {
+                U4H8 o2;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o2.e[j] = (f16)vip_act((float)o.e[j], VIP_ACT_SILU);
+                __builtin_amdgcn_raw_buffer_store_b128(
+                    __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o2.u), *rb_y2,
+                    ok ? ((unsigned)m * (unsigned)a.ldy + (unsigned)(a.cout_off + n)) * 2u : OOB, 0, 0);
+            }
         }
     }
 }
@@ -565,8 +584,12 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
 // multiplied by both, so the layer computes with ~22-bit weights.  These layers are HBM-bound, the second MFMA is free.
 // OG: the instantiations of the output-gated epilogue (modes 7 / 8, nothing else) - kernels of their own, so that the gate's registers
 // (two more 16-byte loads per 8 channels, live next to the prefetched tile) cost the un-gated layers nothing.
-template <int KS, int PT, bool PRE, bool HILO, bool OG = false>
-__global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, int lds_stride, int n_tiles, int mode) {
+// Y2 (with OG): the two-output form of the gated epilogue (vip_conv2d_out_gated2_nhwc_f16) - kernels of their own again, and the one
+// argument they add (a.y2: ConvArgs2) is theirs alone, so the other instantiations keep their arguments, registers and code.
+template <int KS, int PT, bool PRE, bool HILO, bool OG = false, bool Y2 = false>
+__global__ __launch_bounds__(256, 2) void pw_gemm_kernel(std::conditional_t<Y2, ConvArgs2, ConvArgs> a, int nb_ch, int lds_stride, int n_tiles,
+                                                         int mode) {
+    static_assert(OG || !Y2, "the second output belongs to the output-gated instantiations");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
@@ -699,7 +722,11 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(ConvArgs a, int nb_ch, 
                 }
             }
             const int m_base = m0 + l15, n_first = n_chunk0 + sub + lq * 8;
-            if constexpr (OG) {
+            if constexpr (Y2) {
+                const __amdgpu_buffer_rsrc_t rb_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, (unsigned)a.y_span_bytes, 0x00020000);
+                if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+                else pw_epilogue<PT, VIP_ACT_NONE, true, false, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+            } else if constexpr (OG) {
                 if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
                 else pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
             } else
@@ -745,6 +772,27 @@ int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
     return vip_launch_status("vip_conv2d_nhwc_f16(pw)");
 }
 
+// the two-output form of the output-gated launch: the grid, the LDS and the prefetch rule of launch_pw<.., OG = true>
+template <int KS, int PT, bool HILO>
+int launch_pw_og2(const ConvArgs& a, const Plan& p, f16* y2, hipStream_t s) {
+    constexpr bool PRE = KS <= 2;
+    const int n_tiles = (a.M + 64 * PT - 1) / (64 * PT);
+    int gx = (2 * device_cus() + p.n_chunks - 1) / p.n_chunks;
+    if (gx > n_tiles) gx = n_tiles;
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO, true, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    ConvArgs2 a2;
+    static_cast<ConvArgs&>(a2) = a;
+    a2.y2 = y2;
+    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO, true, true>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
+                       (size_t)p.nb_ch * (p.lds_stride + 4) + pw_og_lds(p.nb_ch), s, a2, p.nb_ch, p.lds_stride, n_tiles, p.mode);
+    return vip_launch_status("vip_conv2d_out_gated2_nhwc_f16(pw)");
+}
+
 // ---- pointwise (1x1, stride 1) / dense layers, any K: activations direct to registers, weights through LDS ----
 // Same operand routing as the streaming kernel, for K too large to keep the weight slice resident: the block's
 // [64*NG channels] x 64-k weight chunk is double-buffered in LDS (shared by the 4 waves, one barrier per chunk);
@@ -755,8 +803,12 @@ int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
 // one barrier per chunk).  2-5 % faster than the LDS-staged form for K < 768, 5-10 % slower beyond (bench_gemm.py).
 // PT = 16-pixel tiles per wave: 4 (256-pixel block tile) by default; 2 / 1 for layers whose 256-pixel grid would leave most of the
 // chip idle (7x7 and 13x13 maps with narrow outputs: 98 workgroups for M = 12 544, N = 208) - more, smaller workgroups.
-template <int NG, bool GATED, int PT = 4>
-__global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode) {
+// OG2: the output-gated epilogue with the second output and nothing else (vip_conv2d_out_gated2_nhwc_f16: modes 7 / 8, a.y2 the second
+// output's base with the span and leading dimension of y) - kernels of their own with an argument of their own (ConvArgs2): the shared
+// kernel's loop sits at the register limit, and it keeps its arguments, registers and code.
+template <int NG, bool GATED, int PT = 4, bool OG2 = false>
+__global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<OG2, ConvArgs2, ConvArgs> a, int mode) {
+    static_assert(!(OG2 && (GATED || H2)), "the second output: fp16 storage, no input gate");
     constexpr int NB = 64 * NG, ROWB = 160;                  // LDS row: 64 halfs + 32 B pad (stride = 32 mod 64: plan_pw)
     constexpr int STAGE = NB * ROWB;
     constexpr int W_IT = NB / 32;                            // 16-byte weight chunks staged per thread per k-chunk
@@ -998,6 +1050,14 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(ConvArgs a, int mode
     auto epi = [&](auto gtag) {
         constexpr int G_ = decltype(gtag)::value;
         const int n_first = n_lane + G_ * 64;
+#if !VIP_GEMM_H2
+        if constexpr (OG2) {
+            const __amdgpu_buffer_rsrc_t rb_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, (unsigned)a.y_span_bytes, 0x00020000);
+            if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+            else pw_epilogue<PT, VIP_ACT_NONE, true, false, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+            return;
+        }
+#endif
         switch (mode) {
             case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
             case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
@@ -1714,6 +1774,19 @@ int launch_pwk_direct(const ConvArgs& a, const Plan& p, hipStream_t s) {
     return vip_launch_status("vip_conv2d_nhwc_f16(pwk-direct)");
 }
 
+#if !VIP_GEMM_H2
+template <int NG>
+int launch_pwk_direct_og2(const ConvArgs& a, const Plan& p, f16* y2, hipStream_t s) {
+    ConvArgs2 a2;
+    static_cast<ConvArgs&>(a2) = a;
+    a2.y2 = y2;
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, a2, p.mode); };
+    if (p.pt == 1) go(pwk_direct_kernel<NG, false, 1, true>);
+    else go(pwk_direct_kernel<NG, false, 4, true>);
+    return vip_launch_status("vip_conv2d_out_gated2_nhwc_f16(pwk-direct)");
+}
+#endif
+
 // IM2COL: the k x k form, one grid plane per group (the pointwise form is ungrouped)
 template <int NG, int WN, bool IM2COL>
 int launch_pwk(const ConvArgs& a, int mode, int groups, hipStream_t s) {
@@ -2084,8 +2157,21 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
 
 // ---- launch: the plan's instantiation.  What is read here depends on the device or changes nothing in the selection: the CU count that
 // caps the persistent grids, VIP_G8P_PERSIST, the once-per-kernel dynamic-LDS attributes.
-static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s) {
+// y2: the second output of vip_conv2d_out_gated2_nhwc_f16 (modes 7 / 8 alone: the two-output instantiations), else NULL
+static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s, f16* y2 = nullptr) {
     a.m_blocks = p.m_blocks; a.n_blocks = p.n_blocks;
+#if !VIP_GEMM_H2
+    if (y2) {
+        if (p.mode < 7) return (int)VIP_ERR_UNSUPPORTED;
+        if (p.family == PW_GEMM)
+            return with_const<1, 2, 3, 4>(p.ks, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                return p.hilo ? launch_pw_og2<KS, 4, true>(a, p, y2, s) : launch_pw_og2<KS, 4, false>(a, p, y2, s);
+            });
+        if (p.family == PWK_DIRECT) return p.ng == 1 ? launch_pwk_direct_og2<1>(a, p, y2, s) : launch_pwk_direct_og2<2>(a, p, y2, s);
+        return (int)VIP_ERR_UNSUPPORTED;
+    }
+#endif
     switch (p.family) {
         case PW_GEMM:
             return with_const<1, 2, 3, 4, 6, 8>(p.ks, [&](auto ks) {
@@ -2201,11 +2287,11 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
 static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
                        const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
                        int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
-                       const void* out_gate = nullptr) {
+                       const void* out_gate = nullptr, void* y2 = nullptr) {
     ConvArgs a;
     Plan p;
     const int st = conv2d_plan(x, gate, y_lo_off, w, bias, residual, y, d, w_lo, x_split, out_scale, status, ln_g, ln_b, ln_eps, &a, &p, out_gate);
-    return st != VIP_OK ? st : launch(p, a, d->groups, (hipStream_t)stream);
+    return st != VIP_OK ? st : launch(p, a, d->groups, (hipStream_t)stream, (f16*)y2);
 }
 
 // vip_conv2d_kernel_name[_h2] / vip_conv2d_kernel_variant[_h2]: a dry run - the checks and the plan of the call the flags describe, and
@@ -2301,6 +2387,26 @@ extern "C" int vip_conv2d_out_gated_nhwc_f16(const void* x, const void* w, const
 /* dry run of vip_conv2d_out_gated_nhwc_f16: VIP_OK and the instantiation ("pw_gemm<KS=2,hilo> 1 x 256 ogate") where the call is taken */
 extern "C" int vip_conv2d_out_gated_variant(const vip_conv_desc* d, int has_w_lo, char* variant, size_t cap) {
     return kernel_query("vip_conv2d_out_gated_variant", true, d, 1, 0, has_w_lo, variant, cap, true);
+}
+
+/* The same with a second output y2 = act2(y), computed from the ROUNDED y by the expression of vip_scale_add_act_f16's second output (bit
+ * for bit what that launch gives on y): the tail of an ECA-NFNet block, whose next block reads act(x).  y2: the shape, span and leading
+ * dimension of y.  act2: VIP_ACT_SILU is what is built; the selection and what declines are those of the one-output call. */
+extern "C" int vip_conv2d_out_gated2_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
+                                              const void* residual, void* y, void* y2, int act2, const vip_conv_desc* d, void* stream) {
+    VIP_REQUIRE(out_gate && residual && y2, VIP_ERR_BAD_ARG, "vip_conv2d_out_gated2_nhwc_f16: null gate, residual or second output");
+    VIP_REQUIRE(act2 == VIP_ACT_SILU, VIP_ERR_UNSUPPORTED, "vip_conv2d_out_gated2_nhwc_f16: act2=%d (the second output is built for SiLU)", act2);
+    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream, w_lo, false, 1.f, nullptr, nullptr, nullptr, 0.f, out_gate, y2);
+}
+
+/* dry run of vip_conv2d_out_gated2_nhwc_f16: the one-output call's selection with " y2" behind it ("pwk_direct<2> PT=4 ogate y2") */
+extern "C" int vip_conv2d_out_gated2_variant(const vip_conv_desc* d, int has_w_lo, int act2, char* variant, size_t cap) {
+    VIP_REQUIRE(act2 == VIP_ACT_SILU, VIP_ERR_UNSUPPORTED, "vip_conv2d_out_gated2_variant: act2=%d (the second output is built for SiLU)", act2);
+    const int st = kernel_query("vip_conv2d_out_gated2_variant", true, d, 1, 0, has_w_lo, variant, cap, true);
+    if (st != VIP_OK) return st;
+    const size_t n = strlen(variant);
+    if (n + 4 <= cap) memcpy(variant + n, " y2", 4);
+    return VIP_OK;
 }
 
 extern "C" int vip_conv2d_kernel_name(const vip_conv_desc* d, int has_residual, int has_gate, int has_w_lo, char* name,

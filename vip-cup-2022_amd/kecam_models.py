@@ -443,6 +443,16 @@ class NormFreeNet(_Base):
             pre_beta = betas[-1]
         self.post = mk("post_")
         self.head_w, self.head_b = _head(p, dev)
+        if not ops.KEEP_ROUNDING_ERROR:        # (a model built for bias calibration is prepared after it: zoo.construct)
+            self.prepare()
+
+    def prepare(self):
+        """Build the ECA layers folded with deep_4 (ops.se_fold) NOW - after construction and again after bias calibration, which
+        replaces the biases they are made from - never inside a forward pass: the first one is what the ensemble times to spread its
+        members over streams, and host work in it would be booked as this member's cost."""
+        for blk in self.blocks:
+            if ops.eca_tail_folded(blk["d4"], blk["eca"]):
+                ops.se_fold(blk["d4"], blk["eca"])
 
     def features(self, x, collect=None):
         assert x.shape[-1] == 8
@@ -451,8 +461,13 @@ class NormFreeNet(_Base):
         y = ops.conv2d(x, self.stem[0], stride=fs, pad=PAD1, act=act)          # stem (:182-191)
         y = ops.conv2d(y, self.stem[1], pad=PAD1, act=act)
         y = ops.conv2d(y, self.stem[2], pad=PAD1, act=act)
-        y = ops.conv2d(y, self.stem[3], stride=2, pad=PAD1)
-        pre = ops.scale_add_act(y, None, None, act)                            # act(x); beta folded into the convs
+        if self.blocks[0]["sc"] is not None and ops.eca_tail_folded(self.blocks[0]["d4"], self.blocks[0]["eca"]):
+            # the first block has a shortcut conv, so only act(stem) is ever read: the activation goes into the stem's epilogue (one
+            # rounding of silu(acc) instead of two, and no elementwise pass over the map)
+            y = pre = ops.conv2d(y, self.stem[3], stride=2, pad=PAD1, act=act)
+        else:
+            y = ops.conv2d(y, self.stem[3], stride=2, pad=PAD1)
+            pre = ops.scale_add_act(y, None, None, act)                        # act(x); beta folded into the convs
         for bi, blk in enumerate(self.blocks):                                 # block (:116-168)
             s = blk["stride"]
             if blk["sc"] is not None:
@@ -464,12 +479,23 @@ class NormFreeNet(_Base):
             d = ops.conv2d(pre, blk["d1"], act=act)
             d = ops.conv2d(d, blk["d2"], stride=s, pad=PAD1, act=act)
             d = ops.conv2d(d, blk["d3"], pad=PAD1, act=act)
-            d = ops.conv2d(d, blk["d4"])
-            a = ops.dense_split(ops.global_avgpool(d, split=True), blk["eca"], act="sigmoid")   # pooled vector and gate: hi/lo planes
-            if bi + 1 < len(self.blocks):      # the next block's act(x) is a second output of this launch
-                y, pre = ops.scale_add_act(d, a, sc, None, act2=act)
+            more = bi + 1 < len(self.blocks)   # the next block's act(x) is a second output of the tail's launch
+            if ops.eca_tail_folded(blk["d4"], blk["eca"]):
+                # deep_4 is linear, so the gate's pooled input is W4 . mean_hw(z) + b4: the gate comes from deep_4's INPUT (a quarter of
+                # the channels) through the ECA matrix folded with deep_4, and deep_4 finishes the block in its epilogue - its un-gated
+                # output, the pooling read of it and the elementwise launch are gone
+                a = ops.dense_split(ops.global_avgpool(d, split=True), ops.se_fold(blk["d4"], blk["eca"]), act="sigmoid")
+                if more:
+                    y, pre = ops.conv2d_out_gated(d, blk["d4"], a, sc, None, act2=act)
+                else:
+                    y = ops.conv2d_out_gated(d, blk["d4"], a, sc, None)
             else:
-                y = ops.scale_add_act(d, a, sc, None)
+                d = ops.conv2d(d, blk["d4"])
+                a = ops.dense_split(ops.global_avgpool(d, split=True), blk["eca"], act="sigmoid")   # pooled vector and gate: hi/lo planes
+                if more:
+                    y, pre = ops.scale_add_act(d, a, sc, None, act2=act)
+                else:
+                    y = ops.scale_add_act(d, a, sc, None)
             if collect is not None and blk["last"]:
                 collect.append(y)
         return ops.conv2d(y, self.post, act=act)

@@ -38,7 +38,7 @@ _MLP_H2_FUSED = _env_flag("VIP_MLP_H2_FUSED", True)            # packed strict: 
 _SE_H2_FUSED = _env_flag("VIP_SE_H2_FUSED", True)              # packed strict: se_gate as one launch (vip_se_gate_h2)
 _H2_GATED = _env_flag("VIP_H2_GATED", True)                    # packed strict: the gate folded into the GEMM's activation operand
 _DW_H2_LDS = _env_int("VIP_DW_H2_LDS", 3)                      # smallest k the LDS-staged strict depthwise kernel takes (0: never)
-_SE_TAIL = _env_flag("VIP_SE_TAIL", True)                      # squeeze-excite block tails: gate from the final 1x1 layer's input, tail in its epilogue
+_SE_TAIL = _env_flag("VIP_SE_TAIL", True)                      # squeeze-excite / ECA block tails (ResNet-RS, ECA-NFNet): gate from the final 1x1 layer's input, tail in its epilogue
 _DW_SE_FUSED = _env_flag("VIP_DW_SE_POOL", True)               # dwconv2d_se: the depthwise kernel leaves the pool's partial sums
 _GCVIT_BLOCK_FUSED = _env_flag("VIP_GCVIT_BLOCK_FUSED", True)  # gcvit_attn_block as one launch
 # the 14 x 14-window form of the fused block (C = 256, 8 heads: csrc/gcvit_block14.hip) is correct and NOT faster than the four launches
@@ -709,6 +709,14 @@ def se_tail_folded(c3: ConvWeight, se_r: ConvWeight, se_e: ConvWeight) -> bool:
                 and _pointwise(se_r) and _pointwise(se_e) and se_r.cin == c3.cout and se_e.cin == se_r.cout and se_e.cout == c3.cout)
 
 
+def eca_tail_folded(d4: ConvWeight, eca: ConvWeight) -> bool:
+    """Whether an ECA-NFNet block tail ``scale_add_act(d, gate(d), shortcut, act2=)``, ``d = conv2d(z, d4)``, runs in its folded form: the
+    one-layer gate from the pooled ``z`` through ``se_fold(d4, eca)``, then ``conv2d_out_gated(..., act2=)``.  The exclusions of
+    ``se_tail_folded``: the fp16 storage only, never inside ``calibration()`` / ``unfused()`` / ``exact_weights()``."""
+    return bool(_SE_TAIL and not (_UNFUSED or _CALIB or _EXACT) and d4.kind == eca.kind == "f16" and _pointwise(d4) and _pointwise(eca)
+                and eca.cin == d4.cout and eca.cout == d4.cout)
+
+
 def _fold_tag(c3: ConvWeight, se_r: ConvWeight) -> list:
     """what a fold was made from: the reduce layer and the two bias tensors with their write counters (the weights never change)"""
     return [se_r] + [v for b in (c3.bias, se_r.bias) for v in (b, None if b is None else b._version)]
@@ -751,6 +759,12 @@ def out_gate_variant(d: "_abi.ConvDesc", has_w_lo: bool = False) -> Optional[str
     return _conv_dry_run(_abi.lib().vip_conv2d_out_gated_variant, d, has_w_lo)
 
 
+def out_gate2_variant(d: "_abi.ConvDesc", has_w_lo: bool = False, act2="silu") -> Optional[str]:
+    """The instantiation of the two-output form (vip_conv2d_out_gated2_nhwc_f16, "pwk_direct<2> PT=4 ogate y2": the dry run
+    vip_conv2d_out_gated2_variant) - the one-output call's selection; None where it is not taken (any ``act2`` but SiLU included)."""
+    return _conv_dry_run(_abi.lib().vip_conv2d_out_gated2_variant, d, has_w_lo, _act(act2))
+
+
 def _out_gate_desc(x, cw: ConvWeight, gate, residual, act_post):
     """the descriptor of the one-launch form of ``conv2d_out_gated``, or None where the call takes the two launches"""
     if not (_SE_TAIL and not (_UNFUSED or _CALIB or _EXACT) and x.dtype == torch.float16 and x.is_cuda and x.dim() == 4 and x.is_contiguous()
@@ -764,16 +778,27 @@ def _out_gate_desc(x, cw: ConvWeight, gate, residual, act_post):
     return d if out_gate_variant(d, cw.w_lo is not None) is not None else None
 
 
-def conv2d_out_gated(x: torch.Tensor, cw: ConvWeight, gate: torch.Tensor, residual: torch.Tensor, act_post=None) -> torch.Tensor:
+def conv2d_out_gated(x: torch.Tensor, cw: ConvWeight, gate: torch.Tensor, residual: torch.Tensor, act_post=None, act2=None):
     """``act_post(conv2d(x, cw) * gate + residual)`` for a 1x1 layer without activation and a split gate ``[B, 2, cw.cout]`` that does
     not depend on the layer's output (``se_fold``): ONE launch where the C ABI takes the shape (``out_gate_variant``: the gate multiply,
     the residual add and the ReLU run on the fp32 accumulators, the un-gated map is never stored), otherwise ``conv2d`` then
-    ``scale_add_act`` - there the un-gated map is rounded to fp16 in between."""
+    ``scale_add_act`` - there the un-gated map is rounded to fp16 in between.
+    With ``act2`` returns ``(y, act2(y))`` as ``scale_add_act`` does - the second output from the rounded ``y``, from the same launch
+    where ``act2`` is SiLU (``out_gate2_variant``)."""
     d = _out_gate_desc(x, cw, gate, residual, act_post)
+    if d is not None and act2 is not None and out_gate2_variant(d, cw.w_lo is not None, act2) is None:
+        d = None
     if d is None:
-        return scale_add_act(conv2d(x, cw), gate, residual, act_post)
+        return scale_add_act(conv2d(x, cw), gate, residual, act_post, act2=act2)
     out = torch.empty((*x.shape[:3], cw.cout), dtype=torch.float16, device=x.device)
     has_lo = cw.w_lo is not None
+    if act2 is not None:
+        out2 = torch.empty_like(out)
+        _launch("vip_conv2d_out_gated2_nhwc_f16", _p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(gate), _p(residual), _p(out), _p(out2),
+                _act(act2), C.byref(d),
+                prof=lambda: _conv_prof(conv_kernel_name(d, True, False, has_lo) or "unsupported", d, cw, residual, 2.0, 2.0,
+                                        f" ogate res act_post={act_post} act2={act2}"))
+        return out, out2
     _launch("vip_conv2d_out_gated_nhwc_f16", _p(x), _p(cw.w), _p(cw.w_lo), _p(cw.bias), _p(gate), _p(residual), _p(out), C.byref(d),
             prof=lambda: _conv_prof(conv_kernel_name(d, True, False, has_lo) or "unsupported", d, cw, residual, 2.0, 2.0,
                                     f" ogate res act_post={act_post}"))
