@@ -157,7 +157,10 @@ __global__ __launch_bounds__(256) void slayernorm_kernel(const void* __restrict_
     }
     sum = wave_reduce_sum(sum);
     const float mean = sum / (float)C;
-    float sq = 0.f;
+    // `mean` carries the rounding of a sum of C uncentred values: on a row with mean 100 and spread 0.25 that alone is 5e-5 of the
+    // output.  The centred values d are small, so their sum is accurate: dm = sum(d) / C is the error of `mean`, the output is centred
+    // once more by it, and sum((d - dm)^2) = sum(d^2) - C dm^2 - one more value in the second reduction, no third one.
+    float rs = 0.f, sq = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         const int c4 = lane + i * 64;
@@ -165,12 +168,15 @@ __global__ __launch_bounds__(256) void slayernorm_kernel(const void* __restrict_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float d = v[i][j] - mean;
+                rs += d;
                 sq += d * d;
             }
         }
     }
+    rs = wave_reduce_sum(rs);
     sq = wave_reduce_sum(sq);
-    const float rstd = 1.0f / sqrtf(sq / (float)C + eps);
+    const float dm = rs / (float)C;
+    const float rstd = 1.0f / sqrtf(fmaxf(sq / (float)C - dm * dm, 0.f) + eps);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         const int c4 = lane + i * 64;
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(256) void slayernorm_kernel(const void* __restrict_
             const f32x4 g = ld4(gamma + c4 * 4), bb = ld4(beta + c4 * 4);
             f32x4 o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + bb[j];
+            for (int j = 0; j < 4; ++j) o[j] = ((v[i][j] - mean) - dm) * rstd * g[j] + bb[j];
             S::st(y, (long)row * C + c4 * 4, o, status);
         }
     }
@@ -214,19 +220,22 @@ __global__ __launch_bounds__(256) void h2_layernorm_kernel(const char* __restric
     }
     sum = group_allreduce_sum(sum, lpr);
     const float mean = sum / (float)C;
-    float sq = 0.f;
+    float rs = 0.f, sq = 0.f;             // centred once more by dm, the rounding error of `mean` (slayernorm_kernel)
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         if (sub + i * lpr < C8) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float d = v[i][j] - mean;
+                rs += d;
                 sq += d * d;
             }
         }
     }
+    rs = group_allreduce_sum(rs, lpr);
     sq = group_allreduce_sum(sq, lpr);
-    const float rstd = 1.0f / sqrtf(sq / (float)C + eps);
+    const float dm = rs / (float)C;
+    const float rstd = 1.0f / sqrtf(fmaxf(sq / (float)C - dm * dm, 0.f) + eps);
     bool bad = false;
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
@@ -236,8 +245,8 @@ __global__ __launch_bounds__(256) void h2_layernorm_kernel(const char* __restric
             const f32x4 g0 = ld4(gamma + c8 * 8), g1 = ld4(gamma + c8 * 8 + 4), b0 = ld4(beta + c8 * 8), b1 = ld4(beta + c8 * 8 + 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                o[j] = (v[i][j] - mean) * rstd * g0[j] + b0[j];
-                o[4 + j] = (v[i][4 + j] - mean) * rstd * g1[j] + b1[j];
+                o[j] = ((v[i][j] - mean) - dm) * rstd * g0[j] + b0[j];
+                o[4 + j] = ((v[i][4 + j] - mean) - dm) * rstd * g1[j] + b1[j];
             }
             U4H8 oh, ol;
             h2_split8(o, oh, ol);
