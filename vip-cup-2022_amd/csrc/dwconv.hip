@@ -119,20 +119,33 @@ __global__ __launch_bounds__(256, 2) void dwconv_tile_kernel(const f16* __restri
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[i][j][q] = (f32x2){0.f, 0.f};
 
-    const unsigned xoff0 = (unsigned)((((long)b * H * W) * C + c0) * 2);
-    auto load_row = [&](int iy, uint4 (&raw)[PW]) {
-        const int gy = oy0 - pt + iy;
-        const bool row_ok = (unsigned)gy < (unsigned)H;
+    // Addressing is set up once per tile: which of the PW patch columns are inside the image (a lane mask each) and the byte offset
+    // of the patch's first row and column (mod 2^32: the offset of every pixel inside the image is below x_bytes < 2^32).  A row then
+    // costs one add for its base and, per load, one add of the wave-uniform column offset and one select against the out-of-range
+    // value - no multiply, no branch.  The column offset stays in the VECTOR offset: with the column in the instruction's scalar
+    // offset the vector offset would have to be in range by itself, and the base of a patch that starts left of the image is
+    // "negative" (a huge unsigned) in the first row of the first image, though its valid columns are not.
+    const unsigned row_bytes = (unsigned)W * (unsigned)C * 2u;
+    bool col_ok[PW];
+#pragma unroll
+    for (int q = 0; q < PW; ++q) col_ok[q] = (unsigned)(ox0 - pl + q) < (unsigned)W;
+    int row_gy = oy0 - pt;                                   // image row of the next load_row
+    unsigned row_off = (unsigned)((((long)b * H * W) * C + c0) * 2) + (unsigned)(row_gy * W + ox0 - pl) * ((unsigned)C * 2u);
+    asm volatile("" : "+v"(row_off));     // opaque: hipcc otherwise folds the column offsets into PW bases of their own, PW VGPRs too many
+    auto load_row = [&](uint4 (&raw)[PW]) {
+        const bool row_ok = (unsigned)row_gy < (unsigned)H;
 #pragma unroll
         for (int q = 0; q < PW; ++q) {
-            const int gx = ox0 - pl + q;
-            const bool ok = row_ok & ((unsigned)gx < (unsigned)W);
-            const unsigned off = ok ? xoff0 + (unsigned)((gy * W + gx) * C * 2) : 0xFFFFFFF0u;
+            const unsigned off = (row_ok & col_ok[q]) ? row_off + (unsigned)q * ((unsigned)C * 2u) : 0xFFFFFFF0u;
             raw[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
         }
+        ++row_gy;
+        row_off += row_bytes;
+        __builtin_amdgcn_sched_barrier(0);       // rows are requested in the order they are consumed: the first FMAs wait for one row
     };
     // multiply-accumulate one converted input row into the output rows it feeds
-    auto mac_row = [&](int iy, const uint4 (&rawrow)[PW]) {
+    // (oy_lo .. oy_hi - 1: the output rows it feeds, literal at every call, so the loop over them carries no test)
+    auto mac_row = [&](int iy, const uint4 (&rawrow)[PW], int oy_lo, int oy_hi) {
         f32x2 xr[PW][4];
 #pragma unroll
         for (int q = 0; q < PW; ++q) {
@@ -147,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void dwconv_tile_kernel(const f16* __restri
 #pragma unroll
         for (int oy = 0; oy < T; ++oy) {
             const int r = iy - oy;                 // wave-uniform
-            if (r < 0 || r >= K) continue;
+            if (oy < oy_lo || oy >= oy_hi) continue;
             // weights of tap (r, s+1) are fetched from LDS before the FMAs of tap (r, s)
             const float* wrow = wl + (r * K) * (cb_chunks * 8);
             float4 w0 = *reinterpret_cast<const float4*>(wrow);
@@ -172,22 +185,33 @@ __global__ __launch_bounds__(256, 2) void dwconv_tile_kernel(const f16* __restri
         // cannot cover a memory round trip, P x PW loads in flight per lane can
         uint4 raw[P][PW];
 #pragma unroll
-        for (int iy = 0; iy < P; ++iy) load_row(iy, raw[iy]);
+        for (int iy = 0; iy < P; ++iy) load_row(raw[iy]);
 #pragma unroll
-        for (int iy = 0; iy < P; ++iy) mac_row(iy, raw[iy]);
+        for (int iy = 0; iy < P; ++iy) mac_row(iy, raw[iy], iy - K + 1 > 0 ? iy - K + 1 : 0, iy + 1 < T ? iy + 1 : T);
     } else {
-        uint4 raw[PW];
-        load_row(0, raw);
+        // Rows 1 .. K-1 feed both output rows and are walked in pairs, alternating between two buffers, so that the prefetched
+        // row is never copied and the pair loop carries no test; row 0 (first output row only) and row K (second only) are peeled.
+        static_assert(T == 2 && K % 2 == 1, "row 0, (K - 1) / 2 pairs of full rows, row K");
+        uint4 even[PW], odd[PW];
+        load_row(even);
+        load_row(odd);
+        mac_row(0, even, 0, 1);
         // NOT unrolled (unrolling makes hipcc hoist every load and spill); the NEXT row's loads are issued before the
         // current row is converted and multiplied, so their latency hides under ~400 VALU instructions
 #pragma unroll 1
-        for (int iy = 0; iy < P; ++iy) {
-            uint4 nxt[PW];
-            load_row(iy + 1 < P ? iy + 1 : iy, nxt);
-            mac_row(iy, raw);
-#pragma unroll
-            for (int q = 0; q < PW; ++q) raw[q] = nxt[q];
+        for (int iy = 1; iy < K; iy += 2) {
+            int row = iy;
+            asm volatile("" : "+s"(row));                 // opaque: tap addresses come from the row, not from PW strength-reduced bases
+            load_row(even);
+            mac_row(row, odd, 0, T);
+            __builtin_amdgcn_sched_barrier(0);            // no load into a buffer ahead of its conversion: that would take 40 VGPRs more
+            load_row(odd);
+            mac_row(row + 1, even, 0, T);
+            __builtin_amdgcn_sched_barrier(0);
         }
+        int last = K;
+        asm volatile("" : "+s"(last));                    // opaque: the last row's tap addresses are not computed (and kept) ahead of the loop
+        mac_row(last, odd, 1, T);
     }
 
     float bv[8];     // loaded per tile (L1-resident): keeping it across the tile loop costs 8 VGPRs of a full budget
