@@ -1216,6 +1216,27 @@ int vip_cam_compose_f32(const float* const* maps_h, const int* grid_h_h, const i
 int vip_cam_overlay_u8(const uint8_t* rgb_u8, const uint8_t* map_u8, const uint8_t* table_u8, float alpha, int n, int maxH,
                        int maxW, uint8_t* out_u8, void* stream);
 
+/* ---- HorNet global-local filter (csrc/global_filter.hip) ------------------------------------------------------------------------
+ * Everything between the two LayerNorms of kecam hornet/hornet.py:53-81 `global_local_filter` in one launch, on the three storages
+ * (_f16: fp16, _s32: fp32, _h2: packed (hi, lo) pairs with the status word of the other packed producers).  x, y [B][H][W][S],
+ * half = S / 2; w3 [3][3][half] and g [H][W][half] are fp32 parameters:
+ *   y[b,h,w,2i]   = sum_{dy,dx in -1..1} w3[dy+1][dx+1][i] * x[b,h+dy,w+dx,i]               (DepthwiseConv2D 3x3, SAME, no bias;
+ *                                                                                             pixels outside the map count as zero)
+ *   y[b,h,w,2i+1] = sum_{a<H, c<W} g[a][c][i] * x[b,(h-a) mod H,(w-c) mod W,half+i]
+ * The second line is irfft2(rfft2(x[..., half+i]) * Wc[..., i], s=(H,W)) with g = irfft2(Wc, s=(H,W)) (numpy / pocketfft semantics:
+ * the imaginary parts of the k = 0 column, and of the Nyquist column for even W, do not reach the output) - the `ComplexDense`
+ * weight as a circular depthwise filter, built on the host in float64.  Channels 2i / 2i+1 are the reference's concat on a new last
+ * axis + reshape.  fp32 products and sums in an order fixed by (H, W), one rounding on the store; no atomics: bit-reproducible and
+ * independent of the batch.  The whole map is held in LDS: 2 <= H, W <= 16 and S % 16 == 0, anything else is VIP_ERR_UNSUPPORTED.
+ * W = 14 / 12 / 7 / 6 (the maps of 224 and 200 pixel inputs) run register-blocked, the other widths a generic form. */
+int vip_global_local_filter_supported(int H, int W, int S);
+/* dry run: workgroups per image (0: unsupported); *block_channels = channels of S one workgroup owns, *lds_bytes = its LDS */
+int vip_global_local_filter_plan(int H, int W, int S, int* block_channels, int* lds_bytes);
+int vip_global_local_filter_nhwc_f16(const void* x, const float* w3, const float* g, void* y, int B, int H, int W, int S, void* stream);
+int vip_global_local_filter_nhwc_s32(const float* x, const float* w3, const float* g, float* y, int B, int H, int W, int S, void* stream);
+int vip_global_local_filter_nhwc_h2(const void* x, const float* w3, const float* g, void* y, int B, int H, int W, int S, int* status,
+                                    void* stream);
+
 /* Which kernel vip_conv2d_nhwc_f16 / _gated_ / _hilo_ would launch for this descriptor ("pw_gemm_kernel",
  * "pwk_direct_kernel", "pwk_gemm_kernel", "pwk_gemm_kernel(im2col)", "rows_gemm_kernel", "conv_igemm_kernel"):
  * the dispatcher itself in a dry run, nothing is launched.  Used to label profiler records (bench.py roofline). */

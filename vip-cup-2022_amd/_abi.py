@@ -222,6 +222,12 @@ SIGNATURES = {
     "vip_cam_h2": (_i, [_vp, _vp, _vp, _f] + [_vp] * 5 + [_i] * 4 + [C.c_long, _i, _i, _i, _vp]),
     "vip_cam_compose_f32": (_i, [_vp] * 5 + [_i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "vip_cam_overlay_u8": (_i, [_vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
+    # HorNet global-local filter: csrc/global_filter.hip
+    "vip_global_local_filter_supported": (_i, [_i, _i, _i]),
+    "vip_global_local_filter_plan": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "vip_global_local_filter_nhwc_f16": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    "vip_global_local_filter_nhwc_s32": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    "vip_global_local_filter_nhwc_h2": (_i, [_vp] * 4 + [_i] * 4 + [_vp, _vp]),
     "vip_conv2d_kernel_name": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_conv2d_kernel_variant": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_workspace_bytes": (_sz, [_i, C.POINTER(C.c_int64), _i]),

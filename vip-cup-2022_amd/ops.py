@@ -182,6 +182,7 @@ _KIND_OPS = {
     "mhsa_fwd": (_ALL_KINDS, True),
     "dwconv2d_nhwc": (_ALL_KINDS, True),
     "window_attn_fwd": (_ALL_KINDS, True),
+    "global_local_filter_nhwc": (_ALL_KINDS, True),
     "cam": ({"f16": "f32", "s32": "s32", "h2": "h2"}, False),
     "scale_add_act": (_STRICT_KINDS, True),
     "radix_combine": (_STRICT_KINDS, True),
@@ -1550,6 +1551,46 @@ def radix_combine(x, scale, radix: int = 2):
     else:
         _launch_kind("radix_combine", kind, _p(x), _p(scale), _p(out), B, H * W, Cc, radix)
     return out
+
+
+def global_local_filter(x, w3: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """HorNet ``global_local_filter`` between its two LayerNorms (kecam hornet.py:56-79) as one launch: x ``[B,H,W,S]``; channels
+    ``[:S/2]`` through the 3x3 depthwise filter ``w3 [3,3,S/2]`` (zero padded, no bias), channels ``[S/2:]`` through the circular
+    whole-map filter ``g [H,W,S/2]`` (``make_global_filter_weight``: rfft2 -> complex weight -> irfft2), interleaved channel by channel."""
+    kind = _kind(x, "global_local_filter.x")
+    B, H, W, S = x.shape
+    _chk32(w3, "global_local_filter.w3")
+    _chk32(g, "global_local_filter.g")
+    if tuple(w3.shape) != (3, 3, S // 2) or tuple(g.shape) != (H, W, S // 2):
+        raise _abi.VipError(f"global_local_filter: x {tuple(x.shape)} needs w3 (3, 3, {S // 2}) and g ({H}, {W}, {S // 2}), "
+                            f"got {tuple(w3.shape)} and {tuple(g.shape)}")
+    out = torch.empty_like(x)
+    _launch_kind("global_local_filter_nhwc", kind, _p(x), _p(w3), _p(g), _p(out), B, H, W, S,
+                 prof=lambda: ("global_local_filter_kernel", 2.0 * B * H * W * (S // 2) * (H * W + 9), 2.0 * x.numel() * x.element_size()))
+    return out
+
+
+def global_filter_plan(H: int, W: int, S: int):
+    """dry run of ``global_local_filter``: (workgroups per image, channels of S per workgroup, LDS bytes), None when unsupported"""
+    bc, lds = C.c_int(0), C.c_int(0)
+    n = _abi.lib().vip_global_local_filter_plan(H, W, S, C.byref(bc), C.byref(lds))
+    return (n, bc.value, lds.value) if n > 0 else None
+
+
+def make_global_filter_weight(complex_weight: torch.Tensor, H: int, W: int, device="cuda", name: str = "complex_weight") -> torch.Tensor:
+    """kecam ``ComplexDense`` weight ``[2, H, W // 2 + 1, half]`` (real, imaginary: hornet.py:34-42) -> the real circular filter
+    ``g = irfft2(wr + j wi, s=(H, W))`` as fp32 ``[H, W, half]``, computed in float64 on the host:
+    ``irfft2(rfft2(x) * Wc, s=(H, W))`` is the circular convolution of x with g.  ``irfft2`` is the numpy / pocketfft real inverse, which
+    the reference's comments equate tf.signal.irfft2d to (hornet.py:69-70): the imaginary parts of the k = 0 column, and of the
+    Nyquist column for even W, do not reach g.  A weight stored for another map size is refused - resizing it is the training side's
+    ``load_resized_weights`` (hornet.py:44-50)."""
+    cw = complex_weight.detach()
+    if cw.dim() != 4 or cw.shape[0] != 2 or tuple(cw.shape[1:3]) != (H, W // 2 + 1):
+        raise ValueError(f"{name}: stored for a map of {tuple(cw.shape[1:3])} (H, W // 2 + 1) frequencies, shape {tuple(cw.shape)}; "
+                         f"this model's map is {H} x {W} and needs ({H}, {W // 2 + 1}) - resize the filter when the checkpoint is exported")
+    wc = torch.complex(cw[0].to("cpu", torch.float64), cw[1].to("cpu", torch.float64))
+    g = torch.fft.irfft2(wc, s=(H, W), dim=(0, 1))
+    return g.to(torch.float32).contiguous().to(device)
 
 
 def make_dw_weight(depthwise_kernel_hwc1: torch.Tensor, scale: Optional[torch.Tensor] = None, device="cuda") -> torch.Tensor:

@@ -67,6 +67,14 @@ MEMBERS: Dict[str, MemberSpec] = {
     "hornet_base": MemberSpec("hornet_base", "HorNetBase-200x200", 200, 1028,
                               lambda seed: hornet.synth_params(hornet.CONFIGS["hornet_base"], seed),
                               lambda p, **kw: hornet.HorNet(p, **hornet.CONFIGS["hornet_base"], **kw), "hornet_ref", 11.6),
+    # the global-filter variants (hornet.py:183-185, :204-207): built for the manifest's resolution - a ComplexDense weight has the
+    # size of its stack's map (12 x 12 and 6 x 6 at 200 pixels, 14 x 14 and 7 x 7 at 224)
+    "hornet_base_gf": MemberSpec("hornet_base_gf", "HorNetBaseGF-200x200", 200, 1034,
+                                 lambda seed: hornet.synth_params(hornet.CONFIGS["hornet_base_gf"], seed, input_hw=200),
+                                 lambda p, **kw: hornet.HorNet(p, **hornet.CONFIGS["hornet_base_gf"], input_hw=200, **kw), "hornet_ref", 11.70),
+    "hornet_tiny_gf": MemberSpec("hornet_tiny_gf", "HorNetTinyGF-224x224", 224, 1035,
+                                 lambda seed: hornet.synth_params(hornet.CONFIGS["hornet_tiny_gf"], seed, input_hw=224),
+                                 lambda p, **kw: hornet.HorNet(p, **hornet.CONFIGS["hornet_tiny_gf"], input_hw=224, **kw), "hornet_ref", 4.06),
     "gcvit_base": MemberSpec("gcvit_base", "GCViTBase-224x224", 224, 1022,
                              lambda seed: gcvit.synth_params(gcvit.NAME2CONFIG["gcvit_base"], seed),
                              lambda p, **kw: gcvit.GCViT(p, **gcvit.NAME2CONFIG["gcvit_base"], **kw), "gcvit_ref", 14.3, "head"),
