@@ -10,15 +10,17 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <atomic>
-#include <thread>
 #include <vector>
 
+#include "host_batch.hpp"
 #include "vipcup_hip.h"
 
 void vip_set_error(const char* fmt, ...);
 
 namespace {
+
+// what decode_image and decode_scans, which run on worker threads, report into; parse runs on the calling thread only
+using Err = host_batch::Err<VIP_ERR_JPEG>;
 
 const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -361,14 +363,12 @@ inline int decode_sym(BitReader& br, const HuffTable& t) {
 
 // Progressive (and multi-scan sequential) decoding: every scan refines the same coefficient arrays.
 // Follows jdphuff.c (decode_mcu_DC_first / DC_refine / AC_first / AC_refine).
-int decode_scans(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
+int decode_scans(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef, Err& e) {
     for (const Scan& sc : P.scans) {
         for (int i = 0; i < sc.ns; ++i) {
             const bool need_dc = sc.ss == 0 && sc.ah == 0, need_ac = sc.se > 0;
-            if ((need_dc && !sc.dc[sc.td[i]].present) || (need_ac && !sc.ac[sc.ta[i]].present)) {
-                vip_set_error("jpeg: scan uses a Huffman table that was not defined");
-                return VIP_ERR_JPEG;
-            }
+            if ((need_dc && !sc.dc[sc.td[i]].present) || (need_ac && !sc.ac[sc.ta[i]].present))
+                return fail(e, "jpeg: scan uses a Huffman table that was not defined");
         }
         BitReader br;
         br.p = sc.data;
@@ -519,10 +519,8 @@ int decode_scans(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
                         for (int by = 0; by < P.comp[c].v; ++by)
                             for (int bx = 0; bx < P.comp[c].h; ++bx) {
                                 const long brow = (long)my * P.comp[c].v + by, bcol = (long)mx * P.comp[c].h + bx;
-                                if (block(i, coef + D.coef_off[c] + (brow * D.blocks_w[c] + bcol) * 64) != 0) {
-                                    vip_set_error("jpeg: corrupt Huffman code in a progressive scan");
-                                    return VIP_ERR_JPEG;
-                                }
+                                if (block(i, coef + D.coef_off[c] + (brow * D.blocks_w[c] + bcol) * 64) != 0)
+                                    return fail(e, "jpeg: corrupt Huffman code in a progressive scan");
                             }
                     }
                     if (sc.restart_interval) --to_restart;
@@ -534,10 +532,8 @@ int decode_scans(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
             for (int y = 0; y < bh; ++y)
                 for (int x = 0; x < bw; ++x) {
                     restart_if_due();
-                    if (block(0, coef + D.coef_off[c] + ((long)y * D.blocks_w[c] + x) * 64) != 0) {
-                        vip_set_error("jpeg: corrupt Huffman code in a progressive scan");
-                        return VIP_ERR_JPEG;
-                    }
+                    if (block(0, coef + D.coef_off[c] + ((long)y * D.blocks_w[c] + x) * 64) != 0)
+                        return fail(e, "jpeg: corrupt Huffman code in a progressive scan");
                     if (sc.restart_interval) --to_restart;
                 }
         }
@@ -545,20 +541,15 @@ int decode_scans(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
     return VIP_OK;
 }
 
-int decode_image(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
+int decode_image(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef, Err& e) {
     if (!P.scans.empty()) {
         for (int c = 0; c < P.ncomp; ++c)
-            if (!P.qt_present[P.comp[c].tq]) {
-                vip_set_error("jpeg: missing quantisation table");
-                return VIP_ERR_JPEG;
-            }
-        return decode_scans(P, D, coef);
+            if (!P.qt_present[P.comp[c].tq]) return fail(e, "jpeg: missing quantisation table");
+        return decode_scans(P, D, coef, e);
     }
     for (int c = 0; c < P.ncomp; ++c) {
-        if (!P.qt_present[P.comp[c].tq] || !P.dc[P.comp[c].td].present || !P.ac[P.comp[c].ta].present) {
-            vip_set_error("jpeg: missing quantisation / Huffman table");
-            return VIP_ERR_JPEG;
-        }
+        if (!P.qt_present[P.comp[c].tq] || !P.dc[P.comp[c].td].present || !P.ac[P.comp[c].ta].present)
+            return fail(e, "jpeg: missing quantisation / Huffman table");
     }
     BitReader br;
     br.p = P.scan;
@@ -586,20 +577,14 @@ int decode_image(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
                         int16_t* blk = coef + D.coef_off[c] + (brow * D.blocks_w[c] + bcol) * 64;
                         br.refill();
                         int s = decode_sym(br, tdc);
-                        if (s < 0 || s > 11) {
-                            vip_set_error("jpeg: corrupt DC code");
-                            return VIP_ERR_JPEG;
-                        }
+                        if (s < 0 || s > 11) return fail(e, "jpeg: corrupt DC code");
                         br.refill();
                         pred[c] += extend(br.get(s), s);
                         blk[0] = (int16_t)pred[c];
                         for (int k = 1; k < 64;) {
                             br.refill();
                             const int rs = decode_sym(br, tac);
-                            if (rs < 0) {
-                                vip_set_error("jpeg: corrupt AC code");
-                                return VIP_ERR_JPEG;
-                            }
+                            if (rs < 0) return fail(e, "jpeg: corrupt AC code");
                             const int r = rs >> 4, sz = rs & 15;
                             if (sz == 0) {
                                 if (r != 15) break;  // EOB
@@ -607,10 +592,7 @@ int decode_image(const Parsed& P, const vip_jpeg_desc& D, int16_t* coef) {
                                 continue;
                             }
                             k += r;
-                            if (k > 63) {
-                                vip_set_error("jpeg: AC run past the end of the block");
-                                return VIP_ERR_JPEG;
-                            }
+                            if (k > 63) return fail(e, "jpeg: AC run past the end of the block");
                             blk[ZIGZAG[k]] = (int16_t)extend(br.get(sz), sz);
                             ++k;
                         }
@@ -664,21 +646,7 @@ extern "C" int vip_jpeg_entropy_decode_h(const uint8_t* const* jpeg_h, const siz
     // pass 2: entropy decoding, one image at a time per worker
     if (threads < 1) threads = 1;
     if (threads > n) threads = n > 0 ? n : 1;
-    std::atomic<int> next(0), status(VIP_OK);
-    auto work = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n || status.load() != VIP_OK) return;
-            const int st = decode_image(parsed[i], desc_h[i], coef_h);
-            if (st != VIP_OK) status.store(st);
-        }
-    };
-    if (threads == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(work);
-        for (auto& t : pool) t.join();
-    }
-    return status.load();
+    const auto failed = host_batch::run<Err>(n, threads, [&](int i, Err& e) { return decode_image(parsed[i], desc_h[i], coef_h, e); });
+    if (failed.status != VIP_OK) vip_set_error("%s", failed.err.msg);
+    return failed.status;
 }

@@ -6,35 +6,21 @@
 //
 // Ancillary chunks (gAMA, iCCP, sRGB, tRNS, tEXt, APNG acTL / fcTL / fdAT, ...) are skipped: only the default image
 // is decoded, without colour management; tRNS does not matter for channels=3 (alpha is dropped).
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <mutex>
-#include <thread>
 #include <vector>
 
+#include "host_batch.hpp"
 #include "vipcup_hip.h"
 
 void vip_set_error(const char* fmt, ...);
 
 namespace {
 
-// error text of one image, formatted where the failure is found (a worker thread) and reported by the calling thread
-struct Err {
-    char msg[256] = "";
-};
-
-int fail(Err& e, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(e.msg, sizeof(e.msg), fmt, ap);
-    va_end(ap);
-    return VIP_ERR_PNG;
-}
+using Err = host_batch::Err<VIP_ERR_PNG>;
 
 const uint8_t SIGNATURE[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
 
@@ -500,33 +486,9 @@ extern "C" int vip_png_inflate_h(const uint8_t* const* png_h, const size_t* len_
     // pass 2: CRCs + inflate, one image at a time per worker
     if (threads < 1) threads = 1;
     if (threads > n) threads = n > 0 ? n : 1;
-    std::atomic<int> next(0), status(VIP_OK);
-    std::mutex mu;
-    int bad = -1;
-    Err first;
-    auto work = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n || status.load() != VIP_OK) return;
-            Err e;
-            const int st = inflate_image(png_h[i], len_h[i], desc_h[i], stream_h + desc_h[i].stream_off, bytes[i], e);
-            if (st != VIP_OK) {
-                std::lock_guard<std::mutex> g(mu);
-                if (bad < 0 || i < bad) {
-                    bad = i;
-                    first = e;
-                }
-                status.store(st);
-            }
-        }
-    };
-    if (threads == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(work);
-        for (auto& t : pool) t.join();
-    }
-    if (status.load() != VIP_OK) vip_set_error("png image %d: %s", bad, first.msg);
-    return status.load();
+    const auto failed = host_batch::run<Err>(n, threads, [&](int i, Err& e) {
+        return inflate_image(png_h[i], len_h[i], desc_h[i], stream_h + desc_h[i].stream_off, bytes[i], e);
+    });
+    if (failed.status != VIP_OK) vip_set_error("png image %d: %s", failed.index, failed.err.msg);
+    return failed.status;
 }

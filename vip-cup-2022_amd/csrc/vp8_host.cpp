@@ -9,17 +9,13 @@
 // Reads past the end of a partition follow libwebp: the boolean decoder takes one zero byte past the end and then flags
 // the partition as exhausted, which is an error once the macroblock is done.  Plain C++, no HIP: tests/fuzz/vp8_fuzz.cpp
 // compiles this file alone.
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
-#include <mutex>
-#include <thread>
 #include <vector>
 
+#include "host_batch.hpp"
 #include "vipcup_hip.h"
 #include "vp8_params.hpp"
 #include "vp8_tables.hpp"
@@ -30,17 +26,7 @@ namespace {
 
 using namespace vp8_tables;
 
-struct Err {
-    char msg[256] = "";
-};
-
-int fail(Err& e, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(e.msg, sizeof(e.msg), fmt, ap);
-    va_end(ap);
-    return VIP_ERR_WEBP;
-}
+using Err = host_batch::Err<VIP_ERR_WEBP>;
 
 uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint32_t le24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
@@ -576,36 +562,12 @@ extern "C" int vip_vp8_entropy_h(const uint8_t* const* webp_h, const size_t* len
     if (threads < 1) threads = 1;
     if (threads > 16) threads = 16;
     if (threads > n) threads = n;
-    std::atomic<int> next(0), status(VIP_OK);
-    std::mutex mu;
-    int bad = -1;
-    Err first;
-    auto work = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n || status.load() != VIP_OK) return;
-            Err e;
-            const int st = decode_image(webp_h[i], len_h[i], &desc_h[i], images[(size_t)i], e);
-            if (st != VIP_OK) {
-                std::lock_guard<std::mutex> g(mu);
-                if (bad < 0 || i < bad) {
-                    bad = i;
-                    first = e;
-                }
-                status.store(st);
-            }
-        }
-    };
-    if (threads == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(work);
-        for (auto& t : pool) t.join();
-    }
-    if (status.load() != VIP_OK) {
-        vip_set_error("webp image %d: %s", bad, first.msg);
-        return status.load();
+    const auto failed = host_batch::run<Err>(n, threads, [&](int i, Err& e) {
+        return decode_image(webp_h[i], len_h[i], &desc_h[i], images[(size_t)i], e);
+    });
+    if (failed.status != VIP_OK) {
+        vip_set_error("webp image %d: %s", failed.index, failed.err.msg);
+        return failed.status;
     }
     // pass 3: pack what was used, in image order - the offsets serially, the copies on the workers again (a fresh buffer's
     // pages are first touched here, and one thread touching them all costs more than the decode)
@@ -622,29 +584,18 @@ extern "C" int vip_vp8_entropy_h(const uint8_t* const* webp_h, const size_t* len
         off += align8((size_t)D.coef_off + coef_bytes);
         plane += (size_t)D.mb_w * D.mb_h * 384;
     }
-    next.store(0);
-    auto pack = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n) return;
-            const Image& I = images[(size_t)i];
-            const vip_vp8_desc& D = desc_h[i];
-            uint8_t* out = stream_h + D.stream_off;
-            const size_t mb_bytes = I.mbs.size() * sizeof(vip_vp8_mb), coef_bytes = I.coefs.size() * sizeof(int16_t);
-            memcpy(out, I.mbs.data(), mb_bytes);
-            memset(out + mb_bytes, 0, (size_t)D.coef_off - mb_bytes);
-            if (coef_bytes) memcpy(out + D.coef_off, I.coefs.data(), coef_bytes);
-            const size_t end = (size_t)D.coef_off + coef_bytes;
-            memset(out + end, 0, align8(end) - end);
-        }
-    };
-    if (threads == 1) {
-        pack();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(pack);
-        for (auto& t : pool) t.join();
-    }
+    host_batch::run<Err>(n, threads, [&](int i, Err&) {
+        const Image& I = images[(size_t)i];
+        const vip_vp8_desc& D = desc_h[i];
+        uint8_t* out = stream_h + D.stream_off;
+        const size_t mb_bytes = I.mbs.size() * sizeof(vip_vp8_mb), coef_bytes = I.coefs.size() * sizeof(int16_t);
+        memcpy(out, I.mbs.data(), mb_bytes);
+        memset(out + mb_bytes, 0, (size_t)D.coef_off - mb_bytes);
+        if (coef_bytes) memcpy(out + D.coef_off, I.coefs.data(), coef_bytes);
+        const size_t end = (size_t)D.coef_off + coef_bytes;
+        memset(out + end, 0, align8(end) - end);
+        return VIP_OK;
+    });
     if (stream_used_h) *stream_used_h = off;
     return VIP_OK;
 }

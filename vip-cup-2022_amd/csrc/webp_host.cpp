@@ -8,35 +8,21 @@
 // Lossy WebP (a `VP8 ` chunk) and animation (the VP8X animation flag, ANIM / ANMF chunks) are refused.  Every read is
 // bounded by the VP8L chunk: running past its end is an error.  Recursion is two levels deep at most (the main image,
 // then one sub-image), and prefix-code groups are allocated one by one as they are read.
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <vector>
 
+#include "host_batch.hpp"
 #include "vipcup_hip.h"
 
 void vip_set_error(const char* fmt, ...);
 
 namespace {
 
-struct Err {
-    char msg[256] = "";
-};
-
-int fail(Err& e, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(e.msg, sizeof(e.msg), fmt, ap);
-    va_end(ap);
-    return VIP_ERR_WEBP;
-}
+using Err = host_batch::Err<VIP_ERR_WEBP>;
 
 uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint32_t le24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
@@ -551,33 +537,9 @@ extern "C" int vip_webp_entropy_h(const uint8_t* const* webp_h, const size_t* le
     // pass 2: the entropy decode, one image at a time per worker
     if (threads < 1) threads = 1;
     if (threads > n) threads = n;
-    std::atomic<int> next(0), status(VIP_OK);
-    std::mutex mu;
-    int bad = -1;
-    Err first;
-    auto work = [&]() {
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n || status.load() != VIP_OK) return;
-            Err e;
-            const int st = decode_image(webp_h[i], len_h[i], &desc_h[i], stream_h + desc_h[i].stream_off, bytes[(size_t)i], e);
-            if (st != VIP_OK) {
-                std::lock_guard<std::mutex> g(mu);
-                if (bad < 0 || i < bad) {
-                    bad = i;
-                    first = e;
-                }
-                status.store(st);
-            }
-        }
-    };
-    if (threads == 1) {
-        work();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(work);
-        for (auto& t : pool) t.join();
-    }
-    if (status.load() != VIP_OK) vip_set_error("webp image %d: %s", bad, first.msg);
-    return status.load();
+    const auto failed = host_batch::run<Err>(n, threads, [&](int i, Err& e) {
+        return decode_image(webp_h[i], len_h[i], &desc_h[i], stream_h + desc_h[i].stream_off, bytes[(size_t)i], e);
+    });
+    if (failed.status != VIP_OK) vip_set_error("webp image %d: %s", failed.index, failed.err.msg);
+    return failed.status;
 }

@@ -440,11 +440,7 @@ def _score_batch(staged, members, flags: Optional[np.ndarray] = None, after_fork
     ``flags`` bool [tta, n, 3] (hflip, vflip, gray): one pass per row over augmented copies of the resized batch, mean
     over passes (the mean commutes with the multi->binary map 1 - p0)."""
     from . import pipeline
-    if isinstance(staged, pipeline.DecodedBatch):
-        batch = staged
-    else:
-        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
-            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    batch = pipeline.as_batch(staged)
     hook = [after_fork]
     global _MEMBER_STREAMS
     if _MEMBER_STREAMS is None:
@@ -548,11 +544,7 @@ def stress_batch(staged, members, qualities: Sequence[int], subsampling: str = "
     names of rows 1.. ."""
     spec = dict(locals())                                        # the keywords above by name: the variants' lists and the steps' options
     from . import ops, pipeline
-    if isinstance(staged, pipeline.DecodedBatch):
-        batch = staged
-    else:
-        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
-            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    batch = pipeline.as_batch(staged)
     variants = stress_variants(spec)
     kinds = {kind for _, kind, _ in variants}
     qualities, chains = [int(q) for q in qualities], [str(text) for text in chains]
@@ -664,11 +656,7 @@ def tile_batch(staged, members, tile: int = 200, stride: Optional[int] = None, m
     of its tiles (``ops.tile_aggregate``), NaN for an image without tiles."""
     from . import ops, pipeline
     chunk = pipeline._int_arg("chunk", chunk, 1, 65535)
-    if isinstance(staged, pipeline.DecodedBatch):
-        batch = staged
-    else:
-        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
-            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    batch = pipeline.as_batch(staged)
     plan = pipeline.tile_plan(batch.sizes_host, tile, stride, max_tiles)
     plain = _score_batch(batch, members, None, after_fork=after_fork)
     device = batch.rgb.device
@@ -753,11 +741,7 @@ def occlusion_batch(staged, members, grid: int = 8, window: int = 2, fill: str =
     chunk = pipeline._int_arg("chunk", chunk, 1, 65535)
     if fill not in OCCLUSION_FILLS:
         raise ValueError(f"fill {fill!r}: expected one of {', '.join(OCCLUSION_FILLS)}")
-    if isinstance(staged, pipeline.DecodedBatch):
-        batch = staged
-    else:
-        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
-            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    batch = pipeline.as_batch(staged)
     plan = pipeline.occlusion_plan(batch.sizes_host, grid, window)
     plain = _score_batch(batch, members, None, after_fork=after_fork)
     device = batch.rgb.device
@@ -852,11 +836,7 @@ def explain_batch(staged, members, target="score", out: str = "u8", after_fork=N
     in a single launch (``ops.cam_compose``; ``out`` = ``"u8"`` or ``"f32"``).  A fold ensemble contributes the mean of its folds' maps.
     Raises ``VipError`` when a map is not finite."""
     from . import ops, pipeline
-    if isinstance(staged, pipeline.DecodedBatch):
-        batch = staged
-    else:
-        batch = pipeline.decode_images(staged) if isinstance(staged, (list, tuple)) and len(staged) and \
-            isinstance(staged[0], (bytes, bytearray)) else pipeline.decode_staged(staged)
+    batch = pipeline.as_batch(staged)
     global _MEMBER_STREAMS
     if _MEMBER_STREAMS is None:
         _MEMBER_STREAMS = MemberStreams(default_streams())

@@ -10,7 +10,7 @@ import ctypes as C
 import math
 import os
 import re
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,6 +35,18 @@ def bicubic_table(device) -> torch.Tensor:
 MAX_JPEG_PIXELS = int(os.environ.get("VIP_MAX_JPEG_PIXELS", str(64 << 20)))
 
 
+def _raw_args(raws: Sequence[bytes], threads: int):
+    """What every batched host call takes: the files as arrays of pointers and lengths (and the buffers that keep the pointers good),
+    and the thread count, ``threads`` <= 0 standing for one per CPU up to 16."""
+    if threads <= 0:
+        threads = min(16, os.cpu_count() or 1)
+    n = len(raws)
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in raws]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[len(b) for b in raws])
+    return bufs, ptrs, lens, threads
+
+
 def entropy_decode(jpegs: Sequence[bytes], threads: int = 0, pinned: bool = False):
     """Host stage: list of JPEG byte strings -> (desc array (ctypes), coef int16 numpy array); with ``pinned`` the
     coefficients come back as a page-locked torch tensor instead (torch caches such buffers), so that the H2D copy in
@@ -42,11 +54,7 @@ def entropy_decode(jpegs: Sequence[bytes], threads: int = 0, pinned: bool = Fals
     Raises VipError for streams outside the supported Huffman subset (SOF0/1/2, 8-bit, 1 or 3 components) (the reference raises too: TF)."""
     lib = _abi.lib()
     n = len(jpegs)
-    if threads <= 0:
-        threads = min(16, os.cpu_count() or 1)
-    bufs = [np.frombuffer(b, dtype=np.uint8) for b in jpegs]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in jpegs])
+    bufs, ptrs, lens, threads = _raw_args(jpegs, threads)
     desc = (_abi.JpegDesc * n)()
     total = 0
     tmp = _abi.JpegDesc()
@@ -265,52 +273,87 @@ def occlusion_plan(sizes_host: Sequence[Tuple[int, int]], grid: int = 8, window:
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
-class PngStage:
-    """What ``inflate_pngs`` returns: ``desc`` (ctypes array of PngDesc) and the still-filtered scanlines of the batch
-    (uint8 numpy array, or a page-locked torch tensor), padded to whole 4-byte words (the device kernel reads words)."""
+class HostStage:
+    """What the host stage of a format other than JPEG returns (``FORMATS`` lists them): ``desc`` (ctypes array of the format's
+    descriptor), ``stream`` (what the device half reads: a uint8 numpy array, or a page-locked torch tensor; aligned to the format's
+    word and a whole number of them) and ``scratch_bytes``, the size of the device buffer the format's kernels need besides (0: none)."""
 
-    def __init__(self, desc, stream):
-        self.desc, self.stream = desc, stream
-
-    def __len__(self):
-        return len(self.desc)
-
-
-class WebpStage:
-    """What ``entropy_decode_webps`` returns: ``desc`` (ctypes array of WebpDesc) and the batch's still-transformed ARGB
-    words with the transforms' data (uint8 numpy array, or a page-locked torch tensor; 4-byte aligned)."""
-
-    def __init__(self, desc, stream):
-        self.desc, self.stream = desc, stream
-
-    def __len__(self):
-        return len(self.desc)
-
-
-class Vp8Stage:
-    """What ``entropy_decode_vp8s`` returns: ``desc`` (ctypes array of Vp8Desc), the batch's macroblock records and dequantised
-    coefficients (uint8 numpy array, or a page-locked torch tensor; 8-byte aligned, only what the images used) and
-    ``scratch_bytes``, the size of the device buffer their Y / U / V planes need."""
-
-    def __init__(self, desc, stream, scratch_bytes):
+    def __init__(self, desc, stream, scratch_bytes=0):
         self.desc, self.stream, self.scratch_bytes = desc, stream, scratch_bytes
 
     def __len__(self):
         return len(self.desc)
 
 
+class PngStage(HostStage):
+    """What ``inflate_pngs`` returns: ``desc`` (ctypes array of PngDesc) and the still-filtered scanlines of the batch
+    (uint8 numpy array, or a page-locked torch tensor), padded to whole 4-byte words (the device kernel reads words)."""
+
+
+class WebpStage(HostStage):
+    """What ``entropy_decode_webps`` returns: ``desc`` (ctypes array of WebpDesc) and the batch's still-transformed ARGB
+    words with the transforms' data (uint8 numpy array, or a page-locked torch tensor; 4-byte aligned)."""
+
+
+class Vp8Stage(HostStage):
+    """What ``entropy_decode_vp8s`` returns: ``desc`` (ctypes array of Vp8Desc), the batch's macroblock records and dequantised
+    coefficients (uint8 numpy array, or a page-locked torch tensor; 8-byte aligned, only what the images used) and
+    ``scratch_bytes``, the size of the device buffer their Y / U / V planes need."""
+
+
+class Format(NamedTuple):
+    """One row of ``FORMATS``: all that tells the staged path of one input format from that of another."""
+    word: str                    # what the format's messages call an image: "<word> image K: ..."
+    desc: type                   # its descriptor in _abi
+    probe: str                   # C symbol: one file -> size, and the stream bytes it may need
+    batch: str                   # C symbol: the files of a batch -> descriptors and stream (C++ threads)
+    align: int                   # the stream's word in bytes: the buffer is aligned to it and holds whole words
+    trim: bool                   # the batch call packs the stream: only what it used is kept (and copied to the device)
+    scratch: Optional[str]       # C symbol that sizes the device scratch buffer of the launch, None: the launch takes none
+    launch: str                  # C symbol of the device half
+    stage: type                  # what the host stage returns
+    bare: bool                   # host_decode returns a batch of this format alone as ``stage`` itself, not as a MixedStage of one part
+
+
+# The input formats other than JPEG, by the name ``_batch_kinds`` gives their files and ``MixedStage`` gives its attributes.  A fifth
+# format is a row here, its signature in ``_batch_kinds``, its descriptor in _abi.py and a pair of public one-line bindings below.
+FORMATS: Dict[str, Format] = {
+    "png": Format("png", _abi.PngDesc, "vip_png_probe_h", "vip_png_inflate_h", 4, False, None, "vip_png_unfilter_rgb_u8", PngStage, False),
+    "webp": Format("webp", _abi.WebpDesc, "vip_webp_probe_h", "vip_webp_entropy_h", 4, False, None, "vip_webp_inverse_rgb_u8", WebpStage, True),
+    "vp8": Format("webp", _abi.Vp8Desc, "vip_vp8_probe_h", "vip_vp8_entropy_h", 8, True, "vip_vp8_scratch_bytes",
+                  "vip_vp8_reconstruct_rgb_u8", Vp8Stage, True),
+}
+
+
 class MixedStage:
     """``host_decode`` of a batch that is not all JPEG and not all WebP: the PNG subset (if any) inflated, the JPEG subset
     (if any) entropy-decoded, the lossless WebP subset (if any) entropy-decoded, the lossy WebP subset (only with the
-    ``lossy_webp`` switch on) token-decoded, and where each image of the batch sits in them."""
+    ``lossy_webp`` switch on) token-decoded, and where each image of the batch sits in them: ``jpeg_idx`` / ``jpeg`` and, per row
+    of ``FORMATS``, ``png_idx`` / ``png``, ``webp_idx`` / ``webp``, ``vp8_idx`` / ``vp8`` (the stage is None where the list is empty)."""
 
-    def __init__(self, n, png_idx, png, jpeg_idx, jpeg, webp_idx=(), webp=None, vp8_idx=(), vp8=None):
-        self.n, self.png_idx, self.png, self.jpeg_idx, self.jpeg = n, png_idx, png, jpeg_idx, jpeg
-        self.webp_idx, self.webp = webp_idx, webp
-        self.vp8_idx, self.vp8 = vp8_idx, vp8
+    n: int
+    jpeg_idx: List[int]
+    jpeg: Optional[tuple]
+    png_idx: List[int]
+    png: Optional[PngStage]
+    webp_idx: List[int]
+    webp: Optional[WebpStage]
+    vp8_idx: List[int]
+    vp8: Optional[Vp8Stage]
+
+    def __init__(self, n, where, staged):
+        """``where``, ``staged``: batch positions and stage (or None) by kind, "jpeg" and every key of ``FORMATS``"""
+        self.n = n
+        for kind, idx in where.items():
+            setattr(self, kind + "_idx", idx)
+            setattr(self, kind, staged[kind])
 
     def __len__(self):
         return self.n
+
+    def subsets(self):
+        """(batch positions, stage) of every subset other than the JPEG one that is there, in the order of ``FORMATS``"""
+        return [(getattr(self, kind + "_idx"), getattr(self, kind)) for kind in FORMATS if getattr(self, kind) is not None]
 
 
 def _remap_index(msg: str, index: Optional[Sequence[int]]) -> str:
@@ -319,55 +362,89 @@ def _remap_index(msg: str, index: Optional[Sequence[int]]) -> str:
     return re.sub(r"(png|webp) image (\d+)", lambda m: f"{m.group(1)} image {index[int(m.group(2))]}", msg)
 
 
+def _host_stage(row: Format, raws: Sequence[bytes], threads: int = 0, pinned: bool = False,
+                index: Optional[Sequence[int]] = None) -> HostStage:
+    """The host stage of every format of ``FORMATS``: probe each file (size, pixel cap, stream bytes), allocate the batch's stream -
+    page-locked with ``pinned`` - and fill it with one batched call (C++ threads, the GIL is released inside the ctypes call).
+    ``index``: the batch position of every file, used in error messages."""
+    lib = _abi.lib()
+    n = len(raws)
+    bufs, ptrs, lens, threads = _raw_args(raws, threads)
+    probe = getattr(lib, row.probe)
+    desc = (row.desc * n)()
+    total = 0
+    tmp = row.desc()
+    need = C.c_size_t(0)
+    for i in range(n):
+        where = i if index is None else index[i]
+        st = probe(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
+        if st != 0:
+            raise _abi.VipError(f"{row.word} image {where}: {row.probe} failed with vip_status {st}: "
+                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
+        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
+            raise _abi.VipError(f"{row.word} image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
+        total += need.value
+    # whole words, and one more so that the buffer is never empty.  One rule for all: the lossless WebP path used to add its word without
+    # rounding, and rounds nothing now either, since parse_header in csrc/webp_host.cpp sets *stream_bytes = words * 4
+    size = (total + row.align - 1) // row.align * row.align + row.align
+    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
+    stream = stream_t.numpy() if pinned else np.empty((size // row.align,), dtype=f"u{row.align}").view(np.uint8)
+    used = C.c_size_t(0)
+    st = getattr(lib, row.batch)(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
+    if st != 0:
+        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
+        raise _abi.VipError(f"{row.batch} failed with vip_status {st}: {msg}")
+    scratch = C.c_size_t(0)
+    if row.scratch is not None:
+        _abi.check(getattr(lib, row.scratch)(desc, n, C.byref(scratch)), row.scratch)
+    out = stream_t if pinned else stream
+    if row.trim:
+        out = out[:max(int(used.value), row.align)]       # what was not used is not copied to the device
+    return row.stage(desc, out, int(scratch.value))
+
+
+def _stage_into(stage: HostStage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
+    """Launch the device half of ``stage``'s format for its images, image k writing batch row ``slots[k]`` of ``rgb``."""
+    row = next(r for r in FORMATS.values() if isinstance(stage, r.stage))
+    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
+    full = (row.desc * n)()                           # the other rows get all-zero descriptors: no pass, nothing written
+    for k, i in enumerate(slots):
+        full[i] = stage.desc[k]
+    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
+    if isinstance(stage.stream, torch.Tensor):        # page-locked: asynchronous copy
+        stream_d = stage.stream.to(device, non_blocking=True)
+    else:
+        stream_d = torch.from_numpy(stage.stream).to(device)
+    if row.scratch is None:
+        _launch(row.launch, _p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW)
+    else:
+        scratch = torch.empty((stage.scratch_bytes,), dtype=torch.uint8, device=device)      # every byte is written before it is read
+        _launch(row.launch, _p(stream_d), stream_d.numel(), _p(desc_d), n, _p(scratch), scratch.numel(), _p(rgb), maxH, maxW)
+
+
+def _decoded(sizes_host: List[Tuple[int, int]], device, fill) -> DecodedBatch:
+    """The frame of every device half: zeroed pixels large enough for images of ``sizes_host`` [(h, w)], ``fill(rgb)`` launches what
+    writes them, and the batch is what comes out."""
+    maxH = max(h for h, _ in sizes_host)
+    maxW = max(w for _, w in sizes_host)
+    rgb = torch.zeros((len(sizes_host), maxH, maxW, 3), dtype=torch.uint8, device=device)
+    fill(rgb)
+    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
+    return DecodedBatch(rgb, sizes, sizes_host)
+
+
+def _decode_stage(staged: HostStage, device) -> DecodedBatch:
+    n = len(staged.desc)
+    return _decoded([(int(d.height), int(d.width)) for d in staged.desc], device, lambda rgb: _stage_into(staged, range(n), n, rgb, device))
+
+
 def inflate_pngs(pngs: Sequence[bytes], threads: int = 0, pinned: bool = False,
                  index: Optional[Sequence[int]] = None) -> PngStage:
     """Host stage of the PNG path, the twin of ``entropy_decode``: chunk walk + CRC checks + inflate (C++ threads, the
     GIL is released inside the ctypes call) into the still-filtered scanline stream of the batch.  ``index``: the batch
     position of every PNG, used in error messages.  Raises VipError (naming the image) for a stream that is not a valid
     PNG or whose size exceeds VIP_MAX_JPEG_PIXELS."""
-    lib = _abi.lib()
-    n = len(pngs)
-    if threads <= 0:
-        threads = min(16, os.cpu_count() or 1)
-    bufs = [np.frombuffer(b, dtype=np.uint8) for b in pngs]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in pngs])
-    desc = (_abi.PngDesc * n)()
-    total = 0
-    tmp = _abi.PngDesc()
-    need = C.c_size_t(0)
-    for i in range(n):
-        where = i if index is None else index[i]
-        st = lib.vip_png_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
-        if st != 0:
-            raise _abi.VipError(f"png image {where}: vip_png_probe_h failed with vip_status {st}: "
-                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
-        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
-            raise _abi.VipError(f"png image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
-        total += need.value
-    size = (total + 3) // 4 * 4 + 4                 # whole words, and never empty
-    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
-    stream = stream_t.numpy() if pinned else np.empty((size,), dtype=np.uint8)
-    used = C.c_size_t(0)
-    st = lib.vip_png_inflate_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
-    if st != 0:
-        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
-        raise _abi.VipError(f"vip_png_inflate_h failed with vip_status {st}: {msg}")
-    return PngStage(desc, stream_t if pinned else stream)
-
-
-def _png_into(stage: PngStage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
-    """Launch the unfilter + expand kernel for the PNGs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
-    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
-    full = (_abi.PngDesc * n)()                       # the other rows get all-zero descriptors: no pass, nothing written
-    for k, i in enumerate(slots):
-        full[i] = stage.desc[k]
-    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
-    if isinstance(stage.stream, torch.Tensor):
-        stream_d = stage.stream.to(device, non_blocking=True)
-    else:
-        stream_d = torch.from_numpy(stage.stream).to(device)
-    _launch("vip_png_unfilter_rgb_u8", _p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW)
+    return _host_stage(FORMATS["png"], pngs, threads, pinned, index)
 
 
 def decode_png_stage(staged: PngStage, device="cuda") -> DecodedBatch:
@@ -375,14 +452,7 @@ def decode_png_stage(staged: PngStage, device="cuda") -> DecodedBatch:
     scanline filters and expands to 8-bit RGB like ``tf.image.decode_png(channels=3)`` (dataset/dataset.py:30): gray
     1/2/4 bits by bit replication, palette through PLTE (an index past it is black), alpha dropped (tRNS ignored), 16-bit
     samples reduced to round(v / 257) (libpng ``png_set_scale_16``), Adam7 passes scattered to their pixels."""
-    n = len(staged.desc)
-    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
-    maxH = max(h for h, _ in sizes_host)
-    maxW = max(w for _, w in sizes_host)
-    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    _png_into(staged, range(n), n, rgb, device)
-    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
-    return DecodedBatch(rgb, sizes, sizes_host)
+    return _decode_stage(staged, device)
 
 
 def entropy_decode_webps(webps: Sequence[bytes], threads: int = 0, pinned: bool = False,
@@ -391,63 +461,14 @@ def entropy_decode_webps(webps: Sequence[bytes], threads: int = 0, pinned: bool 
     streams (prefix codes, LZ77, colour cache, the transforms' sub-images; C++ threads, the GIL is released inside the
     ctypes call).  ``index``: the batch position of every WebP, used in error messages.  Raises VipError (naming the
     image) for a lossy or animated file, a damaged stream, or a size beyond VIP_MAX_JPEG_PIXELS."""
-    lib = _abi.lib()
-    n = len(webps)
-    if threads <= 0:
-        threads = min(16, os.cpu_count() or 1)
-    bufs = [np.frombuffer(b, dtype=np.uint8) for b in webps]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in webps])
-    desc = (_abi.WebpDesc * n)()
-    total = 0
-    tmp = _abi.WebpDesc()
-    need = C.c_size_t(0)
-    for i in range(n):
-        where = i if index is None else index[i]
-        st = lib.vip_webp_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
-        if st != 0:
-            raise _abi.VipError(f"webp image {where}: vip_webp_probe_h failed with vip_status {st}: "
-                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
-        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
-            raise _abi.VipError(f"webp image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
-        total += need.value
-    size = total + 4                                  # whole words, and never empty
-    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
-    stream = stream_t.numpy() if pinned else np.empty((size // 4,), dtype=np.uint32).view(np.uint8)
-    used = C.c_size_t(0)
-    st = lib.vip_webp_entropy_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
-    if st != 0:
-        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
-        raise _abi.VipError(f"vip_webp_entropy_h failed with vip_status {st}: {msg}")
-    return WebpStage(desc, stream_t if pinned else stream)
-
-
-def _webp_into(stage: WebpStage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
-    """Launch the inverse-transform kernel for the WebPs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
-    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
-    full = (_abi.WebpDesc * n)()                      # the other rows get all-zero descriptors: nothing written
-    for k, i in enumerate(slots):
-        full[i] = stage.desc[k]
-    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
-    if isinstance(stage.stream, torch.Tensor):
-        stream_d = stage.stream.to(device, non_blocking=True)
-    else:
-        stream_d = torch.from_numpy(stage.stream).to(device)
-    _launch("vip_webp_inverse_rgb_u8", _p(stream_d), _p(desc_d), n, _p(rgb), maxH, maxW)
+    return _host_stage(FORMATS["webp"], webps, threads, pinned, index)
 
 
 def decode_webp_stage(staged: WebpStage, device="cuda") -> DecodedBatch:
     """Device half of the lossless WebP path, the twin of ``decode_png_stage``: ``staged`` = ``entropy_decode_webps(...)``.
     Undoes the VP8L transforms (predictor, cross-colour, subtract-green, colour indexing) in the reverse of the order
     read and drops alpha: the RGB of libwebp's decoder, bit for bit."""
-    n = len(staged.desc)
-    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
-    maxH = max(h for h, _ in sizes_host)
-    maxW = max(w for _, w in sizes_host)
-    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    _webp_into(staged, range(n), n, rgb, device)
-    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
-    return DecodedBatch(rgb, sizes, sizes_host)
+    return _decode_stage(staged, device)
 
 
 def lossy_webp_enabled(lossy_webp: Optional[bool] = None) -> bool:
@@ -478,68 +499,14 @@ def entropy_decode_vp8s(webps: Sequence[bytes], threads: int = 0, pinned: bool =
     per-macroblock modes and residual tokens (the boolean decoder; C++ threads, the GIL is released inside the ctypes call),
     dequantised as libwebp does.  ``index``: the batch position of every file, used in error messages.  Raises VipError
     (naming the image) for an animated file, an inter frame, a damaged stream, or a size beyond VIP_MAX_JPEG_PIXELS."""
-    lib = _abi.lib()
-    n = len(webps)
-    if threads <= 0:
-        threads = min(16, os.cpu_count() or 1)
-    bufs = [np.frombuffer(b, dtype=np.uint8) for b in webps]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in webps])
-    desc = (_abi.Vp8Desc * n)()
-    total = 0
-    tmp = _abi.Vp8Desc()
-    need = C.c_size_t(0)
-    for i in range(n):
-        where = i if index is None else index[i]
-        st = lib.vip_vp8_probe_h(ptrs[i], lens[i], C.byref(tmp), C.byref(need))
-        if st != 0:
-            raise _abi.VipError(f"webp image {where}: vip_vp8_probe_h failed with vip_status {st}: "
-                                f"{lib.vip_last_error().decode('utf-8', 'replace')}")
-        if tmp.width * tmp.height > MAX_JPEG_PIXELS:
-            raise _abi.VipError(f"webp image {where}: {tmp.width}x{tmp.height} exceeds VIP_MAX_JPEG_PIXELS={MAX_JPEG_PIXELS}")
-        total += need.value
-    size = (total + 7) // 8 * 8 + 8                   # whole 8-byte words, and never empty
-    stream_t = torch.empty((size,), dtype=torch.uint8, pin_memory=True) if pinned else None
-    stream = stream_t.numpy() if pinned else np.empty((size // 8,), dtype=np.uint64).view(np.uint8)
-    used = C.c_size_t(0)
-    st = lib.vip_vp8_entropy_h(ptrs, lens, n, desc, stream.ctypes.data_as(C.c_void_p), stream.size, C.byref(used), threads)
-    if st != 0:
-        msg = _remap_index(lib.vip_last_error().decode("utf-8", "replace"), index)
-        raise _abi.VipError(f"vip_vp8_entropy_h failed with vip_status {st}: {msg}")
-    scratch = C.c_size_t(0)
-    _abi.check(lib.vip_vp8_scratch_bytes(desc, n, C.byref(scratch)), "vip_vp8_scratch_bytes")
-    keep = max(int(used.value), 8)                    # what was not used is not copied to the device
-    return Vp8Stage(desc, (stream_t if pinned else stream)[:keep], int(scratch.value))
-
-
-def _vp8_into(stage: Vp8Stage, slots: Sequence[int], n: int, rgb: torch.Tensor, device) -> None:
-    """Launch the reconstruction kernels for the lossy WebPs of ``stage``, image k writing batch row ``slots[k]`` of ``rgb``."""
-    maxH, maxW = int(rgb.shape[1]), int(rgb.shape[2])
-    full = (_abi.Vp8Desc * n)()                       # the other rows get all-zero descriptors: nothing written
-    for k, i in enumerate(slots):
-        full[i] = stage.desc[k]
-    desc_d = torch.from_numpy(np.frombuffer(bytes(full), dtype=np.uint8).copy()).to(device)
-    if isinstance(stage.stream, torch.Tensor):
-        stream_d = stage.stream.to(device, non_blocking=True)
-    else:
-        stream_d = torch.from_numpy(stage.stream).to(device)
-    scratch = torch.empty((stage.scratch_bytes,), dtype=torch.uint8, device=device)      # every byte is written before it is read
-    _launch("vip_vp8_reconstruct_rgb_u8", _p(stream_d), stream_d.numel(), _p(desc_d), n, _p(scratch), scratch.numel(), _p(rgb),
-            maxH, maxW)
+    return _host_stage(FORMATS["vp8"], webps, threads, pinned, index)
 
 
 def decode_vp8_stage(staged: Vp8Stage, device="cuda") -> DecodedBatch:
     """Device half of the lossy WebP path, the twin of ``decode_webp_stage``: ``staged`` = ``entropy_decode_vp8s(...)``.
     Intra prediction + inverse WHT / DCT, the in-loop filter, fancy chroma upsampling and YUV -> RGB; alpha dropped: the
     RGB of libwebp's decoder, bit for bit."""
-    n = len(staged.desc)
-    sizes_host = [(int(d.height), int(d.width)) for d in staged.desc]
-    maxH = max(h for h, _ in sizes_host)
-    maxW = max(w for _, w in sizes_host)
-    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    _vp8_into(staged, range(n), n, rgb, device)
-    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
-    return DecodedBatch(rgb, sizes, sizes_host)
+    return _decode_stage(staged, device)
 
 
 def image_format(raw: bytes, i: int = 0) -> str:
@@ -553,6 +520,15 @@ def image_format(raw: bytes, i: int = 0) -> str:
     raise _abi.VipError(f"image {i}: neither a JPEG (FF D8), a PNG (89 50 4E 47 0D 0A 1A 0A) nor a WebP (RIFF....WEBP) signature")
 
 
+def _batch_kinds(raws: Sequence[bytes], lossy_webp: Optional[bool] = None) -> List[str]:
+    """"jpeg" or the key in ``FORMATS`` of every image of a batch: ``image_format``, and with the lossy WebP switch on (``lossy_webp``;
+    ``None``: the ``VIP_WEBP_LOSSY`` knob) the WebPs split by their chunk tags into "webp" (lossless) and "vp8" (lossy)."""
+    kinds = [image_format(r, i) for i, r in enumerate(raws)]
+    if "webp" in kinds and lossy_webp_enabled(lossy_webp):
+        kinds = ["vp8" if k == "webp" and webp_is_lossy(r) else k for k, r in zip(kinds, raws)]
+    return kinds
+
+
 def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False, lossy_webp: Optional[bool] = None):
     """Host stage of ``decode_images``: picks the format of every image by its magic bytes.  An all-JPEG batch returns
     exactly what ``entropy_decode`` returns (same calls, same buffers), an all-WebP batch a ``WebpStage``; anything else
@@ -560,24 +536,25 @@ def host_decode(raws: Sequence[bytes], threads: int = 0, pinned: bool = False, l
     is on (``lossy_webp``; ``None``: the ``VIP_WEBP_LOSSY`` knob, default 0): then the WebPs are split by their chunk tags, an
     all-lossy batch returns a ``Vp8Stage`` and a ``MixedStage`` carries the lossy subset as ``vp8``.  With the switch off
     the calls made are exactly those made before the switch existed."""
-    kinds = [image_format(r, i) for i, r in enumerate(raws)]
-    if "png" not in kinds and "webp" not in kinds:
+    kinds = _batch_kinds(raws, lossy_webp)
+    if kinds.count("jpeg") == len(kinds):            # the common batch: nothing more is done for it here (this runs beside the launching thread)
         return entropy_decode(raws, threads, pinned)
-    if lossy_webp_enabled(lossy_webp):
-        kinds = ["vp8" if k == "webp" and webp_is_lossy(r) else k for k, r in zip(kinds, raws)]
-        if all(k == "vp8" for k in kinds):
-            return entropy_decode_vp8s(raws, threads, pinned)
-    if all(k == "webp" for k in kinds):
-        return entropy_decode_webps(raws, threads, pinned)
-    png_idx = [i for i, k in enumerate(kinds) if k == "png"]
-    jpeg_idx = [i for i, k in enumerate(kinds) if k == "jpeg"]
-    webp_idx = [i for i, k in enumerate(kinds) if k == "webp"]
-    vp8_idx = [i for i, k in enumerate(kinds) if k == "vp8"]
-    png = inflate_pngs([raws[i] for i in png_idx], threads, pinned, index=png_idx) if png_idx else None
-    jpeg = entropy_decode([raws[i] for i in jpeg_idx], threads, pinned) if jpeg_idx else None
-    webp = entropy_decode_webps([raws[i] for i in webp_idx], threads, pinned, index=webp_idx) if webp_idx else None
-    vp8 = entropy_decode_vp8s([raws[i] for i in vp8_idx], threads, pinned, index=vp8_idx) if vp8_idx else None
-    return MixedStage(len(raws), png_idx, png, jpeg_idx, jpeg, webp_idx, webp, vp8_idx, vp8)
+    for kind, row in FORMATS.items():
+        if row.bare and kinds.count(kind) == len(kinds):
+            return _host_stage(row, raws, threads, pinned)
+    order = list(FORMATS)
+    order.insert(1, "jpeg")          # the subsets are staged in the order they always were: which of two damaged files is reported hangs on it
+    where = {kind: [i for i, k in enumerate(kinds) if k == kind] for kind in order}
+    staged = {}
+    for kind, idx in where.items():
+        sub = [raws[i] for i in idx]
+        if not idx:
+            staged[kind] = None
+        elif kind == "jpeg":
+            staged[kind] = entropy_decode(sub, threads, pinned)
+        else:
+            staged[kind] = _host_stage(FORMATS[kind], sub, threads, pinned, index=idx)
+    return MixedStage(len(raws), where, staged)
 
 
 def decode_staged(staged, device="cuda") -> DecodedBatch:
@@ -586,15 +563,11 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
     JPEG subset, decoded as ``decode_entropy`` does, is copied into its rows."""
     if isinstance(staged, tuple):
         return decode_entropy(staged, device)
-    if isinstance(staged, PngStage):
-        return decode_png_stage(staged, device)
-    if isinstance(staged, WebpStage):
-        return decode_webp_stage(staged, device)
-    if isinstance(staged, Vp8Stage):
-        return decode_vp8_stage(staged, device)
+    if isinstance(staged, HostStage):
+        return _decode_stage(staged, device)
     n = staged.n
     sizes_host: List[Tuple[int, int]] = [(0, 0)] * n
-    for idx, sub in ((staged.png_idx, staged.png), (staged.webp_idx, staged.webp), (staged.vp8_idx, staged.vp8)):
+    for idx, sub in staged.subsets():
         for k, i in enumerate(idx):
             d = sub.desc[k]
             sizes_host[i] = (int(d.height), int(d.width))
@@ -603,20 +576,24 @@ def decode_staged(staged, device="cuda") -> DecodedBatch:
         jb = decode_entropy(staged.jpeg, device)
         for k, i in enumerate(staged.jpeg_idx):
             sizes_host[i] = jb.sizes_host[k]
-    maxH = max(h for h, _ in sizes_host)
-    maxW = max(w for _, w in sizes_host)
-    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    if staged.png is not None:
-        _png_into(staged.png, staged.png_idx, n, rgb, device)
-    if staged.webp is not None:
-        _webp_into(staged.webp, staged.webp_idx, n, rgb, device)
-    if staged.vp8 is not None:
-        _vp8_into(staged.vp8, staged.vp8_idx, n, rgb, device)
-    if jb is not None:
-        rows = torch.tensor(staged.jpeg_idx, dtype=torch.long, device=device)
-        rgb[rows, :jb.rgb.shape[1], :jb.rgb.shape[2]] = jb.rgb
-    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
-    return DecodedBatch(rgb, sizes, sizes_host)
+
+    def fill(rgb):
+        for idx, sub in staged.subsets():
+            _stage_into(sub, idx, n, rgb, device)
+        if jb is not None:
+            rows = torch.tensor(staged.jpeg_idx, dtype=torch.long, device=device)
+            rgb[rows, :jb.rgb.shape[1], :jb.rgb.shape[2]] = jb.rgb
+    return _decoded(sizes_host, device, fill)
+
+
+def as_batch(staged) -> DecodedBatch:
+    """What the scoring entry points accept, as a ``DecodedBatch``: an already decoded batch is returned as it is, the raw byte
+    strings of the images go through ``decode_images`` and a host stage (``host_decode(...)`` and its kin) through ``decode_staged``."""
+    if isinstance(staged, DecodedBatch):
+        return staged
+    if isinstance(staged, (list, tuple)) and len(staged) and isinstance(staged[0], (bytes, bytearray)):
+        return decode_images(staged)
+    return decode_staged(staged)
 
 
 def decode_images(raws: Sequence[bytes], device="cuda", threads: int = 0, lossy_webp: Optional[bool] = None) -> DecodedBatch:
@@ -635,9 +612,6 @@ def decode_entropy(host_stage, device="cuda") -> DecodedBatch:
     while the GPU was busy with the previous batch)."""
     desc, coef = host_stage
     n = len(desc)
-    sizes_host = [(int(d.height), int(d.width)) for d in desc]
-    maxH = max(h for h, _ in sizes_host)
-    maxW = max(w for _, w in sizes_host)
     max_blocks = max(sum(d.blocks_w[c] * d.blocks_h[c] for c in range(d.ncomp)) for d in desc)
     if isinstance(coef, torch.Tensor):     # page-locked tensor from entropy_decode(pinned=True): asynchronous copy, and the
         coef_d = coef.to(device, non_blocking=True)   # caching host allocator keeps the buffer until the copy has run
@@ -646,10 +620,9 @@ def decode_entropy(host_stage, device="cuda") -> DecodedBatch:
     desc_bytes = np.frombuffer(bytes(desc), dtype=np.uint8)
     desc_d = torch.from_numpy(desc_bytes.copy()).to(device)
     planes = torch.empty((coef_d.numel(),), dtype=torch.uint8, device=device)
-    rgb = torch.zeros((n, maxH, maxW, 3), dtype=torch.uint8, device=device)
-    _launch("vip_jpeg_idct_rgb_u8", _p(coef_d), _p(desc_d), n, max_blocks, _p(planes), _p(rgb), maxH, maxW)
-    sizes = torch.tensor(sizes_host, dtype=torch.int32, device=device)
-    return DecodedBatch(rgb, sizes, sizes_host)
+    return _decoded([(int(d.height), int(d.width)) for d in desc], device,
+                    lambda rgb: _launch("vip_jpeg_idct_rgb_u8", _p(coef_d), _p(desc_d), n, max_blocks, _p(planes), _p(rgb),
+                                        int(rgb.shape[1]), int(rgb.shape[2])))
 
 
 SUBSAMPLINGS = {"4:2:0": 420, "420": 420, 420: 420, "4:4:4": 444, "444": 444, 444: 444}
