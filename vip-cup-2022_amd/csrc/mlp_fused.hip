@@ -39,6 +39,14 @@ struct MlpArgs {
     int n_tiles;     // tiles of 512 tokens
 };
 
+// LDS row stride for `chunks` 16-byte chunks: == 32 (mod 64) bytes, conflict-free for the fragment read pattern under
+// the ds_read_b128 lane grouping (see plan_pw in conv_igemm.hip).  The kernels take the strides that depend on C alone
+// from here at compile time (row offsets become instruction immediates), the launchers take all of them from here.
+__host__ __device__ constexpr int mlp_stride(int chunks) {
+    while ((chunks & 3) != 2) ++chunks;
+    return chunks * 16;
+}
+
 // LDS row j of a 32-row group holds channel (j>>4)*4 + ((j&15)>>2)*8 + (j&3): MFMA tiles 2h, 2h+1 then give a lane
 // the channels 8*lq .. 8*lq+7 of the group
 __device__ __forceinline__ int frag_channel(int j) {
@@ -51,9 +59,10 @@ __device__ __forceinline__ int frag_channel(int j) {
 // 32 ks + 8 lq + 0..7 for ks < CK, so a token's C channels sit in 4 lanes (lq = 0..3): in-lane sums + two cross-row
 // exchanges.  Two-pass mean / variance in fp32 and the same expression as layernorm_kernel (pointwise.hip); the
 // normalised row is rounded to fp16 exactly where the separate LayerNorm launch rounded it.
+// gamma / beta: channels 8 i .. 8 i + 7 at g + i * step bytes (step = 32: a plain vector in global memory; the resident
+// kernel keeps them in the pads of its LDS weight image, one group per row)
 template <int CK>
-__device__ __forceinline__ void ln_fragments(U4H8 (&xf)[CK], const float* __restrict__ g, const float* __restrict__ b,
-                                             float eps, int lq) {
+__device__ __forceinline__ void ln_fragments(U4H8 (&xf)[CK], const char* g, const char* b, int step, float eps, int lq) {
     constexpr int C = 32 * CK;
     float v[CK][8];
     float sum = 0.f;
@@ -80,8 +89,9 @@ __device__ __forceinline__ void ln_fragments(U4H8 (&xf)[CK], const float* __rest
     const float rstd = rsqrtf(sq / (float)C + eps);
 #pragma unroll
     for (int ks = 0; ks < CK; ++ks) {
-        const float4 g0 = *reinterpret_cast<const float4*>(g + ks * 32 + lq * 8), g1 = *reinterpret_cast<const float4*>(g + ks * 32 + lq * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(b + ks * 32 + lq * 8), b1 = *reinterpret_cast<const float4*>(b + ks * 32 + lq * 8 + 4);
+        const char *gp = g + (ks * 4 + lq) * step, *bp = b + (ks * 4 + lq) * step;
+        const float4 g0 = *reinterpret_cast<const float4*>(gp), g1 = *reinterpret_cast<const float4*>(gp + 16);
+        const float4 b0 = *reinterpret_cast<const float4*>(bp), b1 = *reinterpret_cast<const float4*>(bp + 16);
         const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
         const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
@@ -92,15 +102,42 @@ __device__ __forceinline__ void ln_fragments(U4H8 (&xf)[CK], const float* __rest
 template <int CK, int ACT, int PT>
 __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
     constexpr int C = 32 * CK, NCT = C / 16, NTHR = 2048 / PT;   // 512 tokens per workgroup: 8 waves x 64 or 16 x 32
+    constexpr int S1 = mlp_stride(C / 8);                        // == a.s1
+    // read each weight fragment one ahead of its MFMAs (8 more registers).  C = 64: 134 against 139 us at GCViT level 0,
+    // every round ahead.  C = 96 (126 registers, still four waves per SIMD): 656 against 666 us in the median at ConvNeXt-T
+    // stage 0, but one round of twelve tied, so by the keep rule of DESIGN.md section 3 it stays as it was
+    constexpr bool AHEAD = CK != 3;
     constexpr unsigned OOB = 0xFFFFFFF0u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* w1s = smem;
-    char* w2s = smem + a.Hd * a.s1;
+    char* w2s = smem + a.Hd * S1;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
 
-    {   // stage both weight matrices and b1 (once per workgroup)
+    // Every row of the two images ends in a 32-byte pad (mlp_stride: the conflict-free stride), eight floats.  The small
+    // vectors live there, so that a tile needs no vector-memory instruction between its x loads and its residual loads:
+    //   W1 row 32 q + i (i < 4): b1[32 q + 8 i ..+7]   - the two C-operand reads of slice q for the lanes with lq = i
+    //   W2 row i: b2[8 i ..+7];  row C/8 + i: gamma[8 i ..+7];  row C/4 + i: beta[8 i ..+7]      (i < C/8)
+    // (a NULL bias is staged as zeros)
+    char* b1p = w1s + 2 * C;
+    char* b2p = w2s + 2 * a.Hd;
+    char* lgp = b2p + (C / 8) * a.s2;
+    char* lbp = lgp + (C / 8) * a.s2;
+    {   // stage both weight matrices and the small vectors (once per workgroup)
+        const __amdgpu_buffer_rsrc_t rb1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b1, 0, a.b1 ? (unsigned)(a.Hd * 4) : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b2, 0, a.b2 ? (unsigned)(C * 4) : 0u, 0x00020000);
+        for (int i = tid; i < a.Hd; i += NTHR)
+            *reinterpret_cast<float*>(b1p + ((i & ~31) + ((i >> 3) & 3)) * S1 + (i & 7) * 4) =
+                __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb1, (unsigned)(i * 4), 0, 0));
+        for (int i = tid; i < C; i += NTHR) {
+            *reinterpret_cast<float*>(b2p + (i >> 3) * a.s2 + (i & 7) * 4) =
+                __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb2, (unsigned)(i * 4), 0, 0));
+            if (a.ln_g) {
+                *reinterpret_cast<float*>(lgp + (i >> 3) * a.s2 + (i & 7) * 4) = a.ln_g[i];
+                *reinterpret_cast<float*>(lbp + (i >> 3) * a.s2 + (i & 7) * 4) = a.ln_b[i];
+            }
+        }
         const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w1, 0, (unsigned)(2L * a.Hd * a.ldw1), 0x00020000);
         const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.w2, 0, (unsigned)(2L * C * a.ldw2), 0x00020000);
         constexpr int cpr1 = CK * 4;
@@ -108,7 +145,7 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
             const int j = i / cpr1, c = i - j * cpr1;
             const uint4 v = __builtin_bit_cast(
                 uint4, __builtin_amdgcn_raw_buffer_load_b128(r1, (unsigned)((frag_channel(j) * a.ldw1 + c * 8) * 2), 0, 0));
-            *reinterpret_cast<uint4*>(w1s + j * a.s1 + c * 16) = v;
+            *reinterpret_cast<uint4*>(w1s + j * S1 + c * 16) = v;
         }
         const int cpr2 = a.Hd >> 3;
         for (int i = tid; i < C * cpr2; i += NTHR) {
@@ -123,10 +160,9 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (unsigned)a.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_bytes : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b1, 0, a.b1 ? (unsigned)(a.Hd * 4) : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b2, 0, a.b2 ? (unsigned)(C * 4) : 0u, 0x00020000);
-    const char* w1l = w1s + l15 * a.s1 + lq * 16;
+    const char* w1l = w1s + l15 * S1 + lq * 16;
     const char* w2l = w2s + l15 * a.s2 + lq * 16;
+    const char* b1l = b1p + lq * S1;
     const int nq = a.Hd >> 5;
 
     for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
@@ -140,13 +176,17 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
                 xf[ks][p].u = __builtin_bit_cast(
                     uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, m < a.M ? (unsigned)((m * a.ldx + ks * 32 + lq * 8) * 2) : OOB, 0, 0));
             }
+        // the tile head's LDS addresses are made from an opaque copy of lq: hipcc otherwise keeps every one of them in a
+        // register of its own across the slice loop, and C = 96 (128 registers, four waves per SIMD) spills
+        int lqh = lq;
+        asm volatile("" : "+v"(lqh));
         if (a.ln_g) {   // workgroup-uniform
 #pragma unroll
             for (int p = 0; p < PT; ++p) {
                 U4H8 col[CK];
 #pragma unroll
                 for (int ks = 0; ks < CK; ++ks) col[ks] = xf[ks][p];
-                ln_fragments<CK>(col, a.ln_g, a.ln_b, a.ln_eps, lq);
+                ln_fragments<CK>(col, lgp, lbp, a.s2, a.ln_eps, lqh);
 #pragma unroll
                 for (int ks = 0; ks < CK; ++ks) xf[ks][p] = col[ks];
             }
@@ -155,32 +195,34 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
         f32x4 acc2[NCT][PT];
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
-            const f32x4 bv = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb2, (unsigned)(((ct >> 1) * 32 + lq * 8 + (ct & 1) * 4) * 4), 0, 0));
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(b2p + ((ct >> 1) * 4 + lqh) * a.s2 + (ct & 1) * 16);
 #pragma unroll
             for (int p = 0; p < PT; ++p) acc2[ct][p] = bv;
         }
 
         // hidden slice q: H^T[32 x 64 tokens] = W1[32q.., :] . X^T + b1
+        U4H8 wf[2];
         auto gemm1 = [&](int q, f32x4 (&acc1)[2][PT]) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                // b1 from global (L1-resident, 4 distinct addresses per wave): LDS is full to the last KB
-                const f32x4 bv = __builtin_bit_cast(
-                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb1, (unsigned)((q * 32 + lq * 8 + t * 4) * 4), 0, 0));
+                // b1 from the pad of W1 row 32 q + lq (4 distinct addresses per wave, rows apart: no bank conflict)
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(b1l + q * 32 * S1 + t * 16);
 #pragma unroll
                 for (int p = 0; p < PT; ++p) acc1[t][p] = bv;
             }
+            // AHEAD: weight fragments are read one ahead of their MFMAs (two register sets): fragment f = 2 ks + t of W1,
+            // then W2's first fragment in front of the activation
+            auto rd1 = [&](int f) { return *reinterpret_cast<const uint4*>(w1l + (q * 32 + (f & 1) * 16) * S1 + (f >> 1) * 64); };
+            if constexpr (AHEAD) wf[0].u = rd1(0);
 #pragma unroll
-            for (int ks = 0; ks < CK; ++ks)
+            for (int f = 0; f < 2 * CK; ++f) {
+                const int ks = f >> 1, t = f & 1, g = f + 1;
+                if constexpr (AHEAD) wf[g & 1].u = g < 2 * CK ? rd1(g) : *reinterpret_cast<const uint4*>(w2l + q * 64);
+                else wf[f & 1].u = rd1(f);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    U4H8 wf;
-                    wf.u = *reinterpret_cast<const uint4*>(w1l + (q * 32 + t * 16) * a.s1 + ks * 64);
-#pragma unroll
-                    for (int p = 0; p < PT; ++p)
-                        acc1[t][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf.h, xf[ks][p].h, acc1[t][p], 0, 0, 0);
-                }
+                for (int p = 0; p < PT; ++p)
+                    acc1[t][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[f & 1].h, xf[ks][p].h, acc1[t][p], 0, 0, 0);
+            }
         };
         // activation; the packed result is the B operand (k = 8*lq + j <-> hidden channel 32q + 8*lq + j)
         auto act_pack = [&](const f32x4 (&acc1)[2][PT], U4H8 (&hf)[PT]) {
@@ -199,11 +241,11 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
         auto gemm2 = [&](int q, const U4H8 (&hf)[PT]) {
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
-                U4H8 wf;
-                wf.u = *reinterpret_cast<const uint4*>(w2l + ct * 16 * a.s2 + q * 64);
+                if constexpr (!AHEAD) wf[ct & 1].u = *reinterpret_cast<const uint4*>(w2l + ct * 16 * a.s2 + q * 64);
+                else if (ct + 1 < NCT) wf[(ct + 1) & 1].u = *reinterpret_cast<const uint4*>(w2l + (ct + 1) * 16 * a.s2 + q * 64);
 #pragma unroll
                 for (int p = 0; p < PT; ++p)
-                    acc2[ct][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf.h, hf[p].h, acc2[ct][p], 0, 0, 0);
+                    acc2[ct][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct & 1].h, hf[p].h, acc2[ct][p], 0, 0, 0);
             }
         };
         // (Issuing slice q+1's first-layer MFMAs before slice q's activation - a two-slice software pipeline - was
@@ -244,13 +286,6 @@ __global__ __launch_bounds__(2048 / PT, 1) void mlp_fused_kernel(MlpArgs a) {
     }
 }
 
-// LDS row stride for `chunks` 16-byte chunks: == 32 (mod 64) bytes, conflict-free for the fragment read pattern under
-// the ds_read_b128 lane grouping (see plan_pw in conv_igemm.hip)
-static int mlp_stride(int chunks) {
-    while ((chunks & 3) != 2) ++chunks;
-    return chunks * 16;
-}
-
 // compute units of the current device (256 when it cannot be asked)
 static int mlp_cu_count() {
     static int n_cu = 0;
@@ -277,7 +312,7 @@ static bool mlp_plan_resident(int C, int M, int Hd, MlpPlan& p) {
     p.s1 = mlp_stride(C / 8);
     p.s2 = mlp_stride(Hd >> 3);
     p.smem = (size_t)Hd * p.s1 + (size_t)C * p.s2;
-    if (p.smem > 160 * 1024) return false;
+    if (p.smem > 160 * 1024 || p.s1 - 2 * C < 32 || p.s2 - 2 * Hd < 32) return false;   // the row pads hold b1, b2, gamma and beta
     p.tile = 512;
     p.n_tiles = (M + 511) / 512;
     const int n_cu = mlp_cu_count();
@@ -285,15 +320,22 @@ static bool mlp_plan_resident(int C, int M, int Hd, MlpPlan& p) {
     return true;
 }
 
-// streamed weights (C = 128 / 192 / 256): 256-token tiles, one workgroup per CU
-static void mlp_plan_stream(int C, int M, MlpPlan& p) {
+// streamed weights (C = 128 / 192 / 256): 256-token tiles, one workgroup per CU.  LDS: the two weight stages, behind them b1 [Hd]
+// and b2 [C] in fp32; false when that does not fit (a hidden width past 24 000 at C = 192)
+static size_t mlp_stream_lds(int C, int Hd) {
+    return 2 * ((size_t)32 * mlp_stride(C / 8) + (size_t)C * mlp_stride(4)) + 4 * ((size_t)Hd + (size_t)C);
+}
+
+static bool mlp_plan_stream(int C, int M, int Hd, MlpPlan& p) {
     p.s1 = mlp_stride(C / 8);
     p.s2 = mlp_stride(4);
-    p.smem = 2 * ((size_t)32 * p.s1 + (size_t)C * p.s2);
+    p.smem = mlp_stream_lds(C, Hd);
+    if (p.smem > 160 * 1024) return false;
     p.tile = 256;
     p.n_tiles = (M + 255) / 256;
     const int n_cu = mlp_cu_count();
     p.grid = p.n_tiles < n_cu ? p.n_tiles : n_cu;
+    return true;
 }
 
 template <int CK>
@@ -317,16 +359,27 @@ int launch_mlp(MlpArgs a, hipStream_t s) {
 
 // ---- C = 128 / 192: the two weight matrices (4C x C and C x 4C) no longer fit in LDS together, so they are STREAMED:
 // per 32-channel hidden slice the workgroup stages W1[32q.., :] and W2[:, 32q..] (24 KB at C = 192) into a
-// double-buffered LDS image (global -> VGPR one slice ahead, ds_write after the slice's math, one barrier per slice)
-// while x (32 tokens per wave, 8 waves) and the y accumulators stay in registers for all 4C/32 slices.  The weights
-// come from L2 (2.3 KB per token at C = 192 against 1.15 KB of HBM traffic); the hidden tensor never exists in memory.
+// double-buffered LDS image, one barrier per slice, while x (32 tokens per wave, 8 waves) and the y accumulators stay in
+// registers for all 4C/32 slices.  The weights come from L2 (2.3 KB per token at C = 192 against 1.15 KB of HBM traffic);
+// the hidden tensor never exists in memory.
+// The slice loop's only vector-memory instructions are the loads of the NEXT slice's weights, issued at the head of the
+// slice into named registers and first waited for after the slice's last MFMA, directly in front of the ds_write into the
+// other stage: both biases are staged once per workgroup into LDS (fp32, behind the two stages) and read from there, so
+// that no later load stands in the in-order vmcnt queue between the prefetch and its use.
+// The staging values are named scalars, not an array: hipcc leaves `uint4 wst[W_IT]` on the stack (48 / 64 bytes of
+// scratch per lane at C = 128 / 192, a second memory round trip per slice).  W_IT = 4 (C = 256, built but not offered by
+// vip_mlp_fused_supported) runs out of registers and may keep scratch.
 template <int CK, int ACT>
 __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
     constexpr int C = 32 * CK, PT = 2, NCT = C / 16, NTHR = 512;
     constexpr int W_IT = C / 64;                    // 16-byte weight chunks staged per thread per slice (8C / 512)
+    static_assert(W_IT >= 1 && W_IT <= 4, "staging registers are named for up to four chunks");
     constexpr unsigned OOB = 0xFFFFFFF0u;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int stage_bytes = 32 * a.s1 + C * a.s2;   // W1 slice [32][s1] then W2 slice [C][s2]
+    constexpr int S1 = mlp_stride(C / 8), S2 = mlp_stride(4);   // == a.s1, a.s2
+    constexpr int stage_bytes = 32 * S1 + C * S2;   // W1 slice [32][S1] then W2 slice [C][S2]
+    float* b1s = reinterpret_cast<float*>(smem + 2 * stage_bytes);   // b1 [Hd] then b2 [C] (zeros for a NULL bias)
+    float* b2s = b1s + a.Hd;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
@@ -334,45 +387,71 @@ __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (unsigned)a.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_bytes : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b1, 0, a.b1 ? (unsigned)(a.Hd * 4) : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b2, 0, a.b2 ? (unsigned)(C * 4) : 0u, 0x00020000);
+    {
+        const __amdgpu_buffer_rsrc_t rb1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b1, 0, a.b1 ? (unsigned)(a.Hd * 4) : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rb2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.b2, 0, a.b2 ? (unsigned)(C * 4) : 0u, 0x00020000);
+        for (int i = tid; i < a.Hd; i += NTHR)
+            b1s[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb1, (unsigned)(i * 4), 0, 0));
+        for (int i = tid; i < C; i += NTHR)
+            b2s[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb2, (unsigned)(i * 4), 0, 0));
+    }
 
     // staging plan of this thread: chunk idx = tid + 512 i; the first 4C chunks are the W1 slice, the rest the W2 slice.
     // Plain pointers (one load instruction per chunk whichever matrix it comes from: a `is_w1 ? load(w1) : load(w2)`
-    // would be two predicated loads with a wait each)
-    const char* w_ptr[W_IT];   // source of slice 0
-    unsigned w_step[W_IT];     // bytes between consecutive slices
-    int w_dst[W_IT];           // byte offset inside a stage
-#pragma unroll
-    for (int i = 0; i < W_IT; ++i) {
+    // would be two predicated loads with a wait each); they RUN: each stands on the slice to be loaded next and is
+    // advanced by its step, or taken back to slice 0 after the last slice
+    const char *wp0 = nullptr, *wp1 = nullptr, *wp2 = nullptr, *wp3 = nullptr;   // source of the next slice
+    unsigned ws0 = 0, ws1 = 0, ws2 = 0, ws3 = 0;                                 // bytes between consecutive slices
+    int wd0 = 0, wd1 = 0, wd2 = 0, wd3 = 0;                                      // byte offset inside a stage
+    auto plan_w = [&](int i, const char*& wp, unsigned& ws, int& wd) {
         const int idx = tid + NTHR * i;
         if (idx < 4 * C) {
             const int row = idx / (C / 8), c = idx - row * (C / 8);
-            w_ptr[i] = reinterpret_cast<const char*>(a.w1) + ((long)frag_channel(row) * a.ldw1 + c * 8) * 2;
-            w_step[i] = (unsigned)(32 * a.ldw1 * 2);
-            w_dst[i] = row * a.s1 + c * 16;
+            wp = reinterpret_cast<const char*>(a.w1) + ((long)frag_channel(row) * a.ldw1 + c * 8) * 2;
+            ws = (unsigned)(32 * a.ldw1 * 2);
+            wd = row * S1 + c * 16;
         } else {
             const int j = idx - 4 * C, row = j >> 2, c = j & 3;
-            w_ptr[i] = reinterpret_cast<const char*>(a.w2) + ((long)frag_channel(row) * a.ldw2 + c * 8) * 2;
-            w_step[i] = 64u;
-            w_dst[i] = 32 * a.s1 + row * a.s2 + c * 16;
+            wp = reinterpret_cast<const char*>(a.w2) + ((long)frag_channel(row) * a.ldw2 + c * 8) * 2;
+            ws = 64u;
+            wd = 32 * S1 + row * S2 + c * 16;
         }
-    }
-    uint4 wst[W_IT];
-    auto load_w = [&](int q) {
-#pragma unroll
-        for (int i = 0; i < W_IT; ++i) wst[i] = *reinterpret_cast<const uint4*>(w_ptr[i] + (size_t)q * w_step[i]);
+    };
+    plan_w(0, wp0, ws0, wd0);
+    if constexpr (W_IT > 1) plan_w(1, wp1, ws1, wd1);
+    if constexpr (W_IT > 2) plan_w(2, wp2, ws2, wd2);
+    if constexpr (W_IT > 3) plan_w(3, wp3, ws3, wd3);
+    const int nq = a.Hd >> 5;
+    uint4 wn0, wn1, wn2, wn3;   // the next slice's chunks, in flight from the head of a slice to its tail
+    int nxt = 0;                // the slice the pointers stand on
+    // issue the loads of slice `nxt`, then move the pointers on
+    auto load_w = [&]() {
+        wn0 = *reinterpret_cast<const uint4*>(wp0);
+        if constexpr (W_IT > 1) wn1 = *reinterpret_cast<const uint4*>(wp1);
+        if constexpr (W_IT > 2) wn2 = *reinterpret_cast<const uint4*>(wp2);
+        if constexpr (W_IT > 3) wn3 = *reinterpret_cast<const uint4*>(wp3);
+        const bool wrap = nxt + 1 >= nq;    // workgroup-uniform
+        auto adv = [&](const char*& wp, unsigned ws) { wp += wrap ? -(long)(ws * (unsigned)nxt) : (long)ws; };
+        adv(wp0, ws0);
+        if constexpr (W_IT > 1) adv(wp1, ws1);
+        if constexpr (W_IT > 2) adv(wp2, ws2);
+        if constexpr (W_IT > 3) adv(wp3, ws3);
+        nxt = wrap ? 0 : nxt + 1;
     };
     auto store_w = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < W_IT; ++i) *reinterpret_cast<uint4*>(smem + buf * stage_bytes + w_dst[i]) = wst[i];
+        char* st = smem + buf * stage_bytes;
+        *reinterpret_cast<uint4*>(st + wd0) = wn0;
+        if constexpr (W_IT > 1) *reinterpret_cast<uint4*>(st + wd1) = wn1;
+        if constexpr (W_IT > 2) *reinterpret_cast<uint4*>(st + wd2) = wn2;
+        if constexpr (W_IT > 3) *reinterpret_cast<uint4*>(st + wd3) = wn3;
     };
 
-    const int nq = a.Hd >> 5;
-    load_w(0);
+    load_w();
     store_w(0);
     __syncthreads();
     int buf = 0;
+    const float* b1l = b1s + lq * 8;
+    const float* b2l = b2s + lq * 8;
 
     for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
         const int m0 = tile * (NTHR / 64 * 16 * PT) + wave * (16 * PT);
@@ -391,44 +470,46 @@ __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
                 U4H8 col[CK];
 #pragma unroll
                 for (int ks = 0; ks < CK; ++ks) col[ks] = xf[ks][p];
-                ln_fragments<CK>(col, a.ln_g, a.ln_b, a.ln_eps, lq);
+                ln_fragments<CK>(col, reinterpret_cast<const char*>(a.ln_g), reinterpret_cast<const char*>(a.ln_b), 32, a.ln_eps, lq);
 #pragma unroll
                 for (int ks = 0; ks < CK; ++ks) xf[ks][p] = col[ks];
             }
         }
+        // y accumulators start at b2 (lane: channels 32*hh + 8*lq + 4*t + 0..3 for tile 2*hh + t)
         f32x4 acc2[NCT][PT];
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
-            const f32x4 bv = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb2, (unsigned)(((ct >> 1) * 32 + lq * 8 + (ct & 1) * 4) * 4), 0, 0));
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(b2l + (ct >> 1) * 32 + (ct & 1) * 4);
 #pragma unroll
             for (int p = 0; p < PT; ++p) acc2[ct][p] = bv;
         }
 
 #pragma unroll 1
         for (int q = 0; q < nq; ++q) {
-            load_w(q + 1 < nq ? q + 1 : 0);          // next slice (slice 0 of the next tile after the last one)
+            load_w();                                // next slice (slice 0 of the next tile after the last one)
             __builtin_amdgcn_sched_barrier(0);
-            const char* w1l = smem + buf * stage_bytes + l15 * a.s1 + lq * 16;
-            const char* w2l = smem + buf * stage_bytes + 32 * a.s1 + l15 * a.s2 + lq * 16;
+            const char* w1l = smem + buf * stage_bytes + l15 * S1 + lq * 16;
+            const char* w2l = w1l + 32 * S1 + l15 * (S2 - S1);
             f32x4 acc1[2][PT];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const f32x4 bv = __builtin_bit_cast(
-                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb1, (unsigned)((q * 32 + lq * 8 + t * 4) * 4), 0, 0));
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(b1l + q * 32 + t * 4);
 #pragma unroll
                 for (int p = 0; p < PT; ++p) acc1[t][p] = bv;
             }
+            // weight fragments are read one ahead of their MFMAs (two registers sets): fragment f = 2 ks + t of W1, then
+            // W2's first fragment in front of the activation
+            U4H8 wf[2];
+            wf[0].u = *reinterpret_cast<const uint4*>(w1l);
 #pragma unroll
-            for (int ks = 0; ks < CK; ++ks)
+            for (int f = 0; f < 2 * CK; ++f) {
+                const int ks = f >> 1, t = f & 1, g = f + 1;
+                wf[g & 1].u = g < 2 * CK ? *reinterpret_cast<const uint4*>(w1l + (g & 1) * 16 * S1 + (g >> 1) * 64)
+                                         : *reinterpret_cast<const uint4*>(w2l);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    U4H8 wf;
-                    wf.u = *reinterpret_cast<const uint4*>(w1l + t * 16 * a.s1 + ks * 64);
-#pragma unroll
-                    for (int p = 0; p < PT; ++p)
-                        acc1[t][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf.h, xf[ks][p].h, acc1[t][p], 0, 0, 0);
-                }
+                for (int p = 0; p < PT; ++p)
+                    acc1[t][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[f & 1].h, xf[ks][p].h, acc1[t][p], 0, 0, 0);
+            }
             U4H8 hf[PT];
 #pragma unroll
             for (int p = 0; p < PT; ++p)
@@ -442,14 +523,13 @@ __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
                     }
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
-                U4H8 wf;
-                wf.u = *reinterpret_cast<const uint4*>(w2l + ct * 16 * a.s2);
+                if (ct + 1 < NCT) wf[(ct + 1) & 1].u = *reinterpret_cast<const uint4*>(w2l + (ct + 1) * 16 * S2);
 #pragma unroll
                 for (int p = 0; p < PT; ++p)
-                    acc2[ct][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf.h, hf[p].h, acc2[ct][p], 0, 0, 0);
+                    acc2[ct][p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct & 1].h, hf[p].h, acc2[ct][p], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            store_w(buf ^ 1);
+            store_w(buf ^ 1);                        // the first wait for the prefetch: after the slice's last MFMA
             __syncthreads();
             buf ^= 1;
         }
@@ -483,7 +563,7 @@ __global__ __launch_bounds__(512, 1) void mlp_stream_kernel(MlpArgs a) {
 template <int CK>
 int launch_mlp_stream(MlpArgs a, hipStream_t s) {
     MlpPlan p;
-    mlp_plan_stream(32 * CK, a.M, p);
+    if (!mlp_plan_stream(32 * CK, a.M, a.Hd, p)) return 1;
     a.s1 = p.s1;
     a.s2 = p.s2;
     a.n_tiles = p.n_tiles;
@@ -501,7 +581,8 @@ int launch_mlp_stream(MlpArgs a, hipStream_t s) {
 
 extern "C" int vip_mlp_fused_supported(int M, int C, int hidden, int act) {
     if (act != VIP_ACT_GELU || hidden % 32 != 0 || hidden <= 0 || M < 8192) return 0;
-    if (C == 192) return 1;   // streamed weights (C = 128 and 256 are wired up too but measured slower than two GEMMs)
+    if (C == 192)             // streamed weights (C = 128 and 256 are wired up too but measured slower than two GEMMs)
+        return mlp_stream_lds(C, hidden) <= 160 * 1024;
     if (C != 64 && C != 96) return 0;
     const long s1 = mlp_stride(C / 8), s2 = mlp_stride(hidden >> 3);      // LDS-resident weights
     return (long)hidden * s1 + (long)C * s2 <= 160 * 1024;
@@ -510,8 +591,9 @@ extern "C" int vip_mlp_fused_supported(int M, int C, int hidden, int act) {
 extern "C" int vip_mlp_fused_plan(int M, int C, int hidden, int act, int* workgroups, int* tile_rows) {
     if (!vip_mlp_fused_supported(M, C, hidden, act)) return 0;
     MlpPlan p;
-    if (C == 192) mlp_plan_stream(C, M, p);
-    else if (!mlp_plan_resident(C, M, hidden, p)) return 0;
+    if (C == 192) {
+        if (!mlp_plan_stream(C, M, hidden, p)) return 0;
+    } else if (!mlp_plan_resident(C, M, hidden, p)) return 0;
     if (workgroups) *workgroups = p.grid;
     if (tile_rows) *tile_rows = p.tile;
     return p.n_tiles;
