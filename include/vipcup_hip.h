@@ -1237,6 +1237,34 @@ int vip_global_local_filter_nhwc_s32(const float* x, const float* w3, const floa
 int vip_global_local_filter_nhwc_h2(const void* x, const float* w3, const float* g, void* y, int B, int H, int W, int S, int* status,
                                     void* stream);
 
+/* ---- Swin Transformer V2 shifted cosine window attention (csrc/swin_attn.hip) -----------------------------------------------------
+ * Everything between the `qkv` Dense and the `output` Dense of kecam swin_transformer_v2.py:164-262 (`shifted_window_attention` with
+ * `window_mhsa_with_pair_wise_positional_embedding`) in one launch on the UNPADDED map, on the three storages (_f16: fp16, _s32: fp32,
+ * _h2: packed (hi, lo) pairs with the status word of the other packed producers).
+ *   qkv [B][H][W][3C], channels (q|k|v, head, 32) - query_bias and value_bias already added by the producing Dense; out [B][H][W][C];
+ *   v_bias fp32 [C] or NULL (the layer has no qv_bias): the value row of a padded token;
+ *   tau fp32 [heads] = exp(min(scale_weight, ln 100)); bias_table fp32 [(2ws-1)^2][heads] = 16 sigmoid(meta MLP of the log-spaced
+ *   offsets), built on the host; ws in 2 .. 8 (the caller clamps it to the map); shift 0 or ws / 2 rounded down.
+ * Hp = ceil(H / ws) ws, Wp likewise.  The token at ROLLED position (Y, X) of window (Y / ws, X / ws) is the map's token at
+ * y = (Y + shift) mod Hp, x = (X + shift) mod Wp; with y >= H or x >= W it is PADDED: key 0, value v_bias, never a query, never stored.
+ * Padded keys are not masked: they take part in the softmax of their window with the logit 0 + table.
+ *   qn = q rsqrt(max(sum q^2, 1e-6)), kn likewise (fp32; a maximum under the root, tf.nn.l2_normalize)
+ *   logit = tau[head] qn.kn + bias_table[(qr - kr + ws - 1)(2ws - 1) + (qc - kc + ws - 1)][head]
+ *           + (shift > 0 and region(q) != region(k) ? -100 : 0)
+ *   region(Y, X) = 3 r(Y, Hp) + r(X, Wp), r(t, L) = [t >= L - ws] + [t >= L - shift]   (rolled, padded coordinates)
+ *   out[b, y, x, head 32 + :] = softmax over the ws^2 keys of the window (logit) . v, at the query's unrolled position.
+ * No atomics: bit-reproducible, independent of the batch.  Anything else (head_dim != 32, ws > 8, another shift): VIP_ERR_UNSUPPORTED. */
+int vip_swin_attn_supported(int C, int heads, int ws, int shift);
+/* dry run on the host, nothing is launched: 1 and *Hp, *Wp (the padded map), *items = B * windows * heads (the work items of a
+ * launch), or 0 when the launch would be refused */
+int vip_swin_attn_plan(int B, int H, int W, int heads, int ws, int shift, int* Hp, int* Wp, int* items);
+int vip_swin_attn_fwd_f16(const void* qkv, const float* v_bias, const float* tau, const float* bias_table, void* out, int B, int H, int W,
+                          int C, int heads, int ws, int shift, void* stream);
+int vip_swin_attn_fwd_s32(const float* qkv, const float* v_bias, const float* tau, const float* bias_table, float* out, int B, int H,
+                          int W, int C, int heads, int ws, int shift, void* stream);
+int vip_swin_attn_fwd_h2(const void* qkv, const float* v_bias, const float* tau, const float* bias_table, void* out, int B, int H, int W,
+                         int C, int heads, int ws, int shift, int* status, void* stream);
+
 /* Which kernel vip_conv2d_nhwc_f16 / _gated_ / _hilo_ would launch for this descriptor ("pw_gemm_kernel",
  * "pwk_direct_kernel", "pwk_gemm_kernel", "pwk_gemm_kernel(im2col)", "rows_gemm_kernel", "conv_igemm_kernel"):
  * the dispatcher itself in a dry run, nothing is launched.  Used to label profiler records (bench.py roofline). */

@@ -228,6 +228,12 @@ SIGNATURES = {
     "vip_global_local_filter_nhwc_f16": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
     "vip_global_local_filter_nhwc_s32": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
     "vip_global_local_filter_nhwc_h2": (_i, [_vp] * 4 + [_i] * 4 + [_vp, _vp]),
+    # Swin V2 shifted cosine window attention: csrc/swin_attn.hip
+    "vip_swin_attn_supported": (_i, [_i] * 4),
+    "vip_swin_attn_plan": (_i, [_i] * 6 + [C.POINTER(_i)] * 3),
+    "vip_swin_attn_fwd_f16": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
+    "vip_swin_attn_fwd_s32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
+    "vip_swin_attn_fwd_h2": (_i, [_vp] * 5 + [_i] * 7 + [_vp, _vp]),
     "vip_conv2d_kernel_name": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_conv2d_kernel_variant": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_workspace_bytes": (_sz, [_i, C.POINTER(C.c_int64), _i]),

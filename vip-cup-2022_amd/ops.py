@@ -183,6 +183,7 @@ _KIND_OPS = {
     "dwconv2d_nhwc": (_ALL_KINDS, True),
     "window_attn_fwd": (_ALL_KINDS, True),
     "global_local_filter_nhwc": (_ALL_KINDS, True),
+    "swin_attn_fwd": (_ALL_KINDS, True),
     "cam": ({"f16": "f32", "s32": "s32", "h2": "h2"}, False),
     "scale_add_act": (_STRICT_KINDS, True),
     "radix_combine": (_STRICT_KINDS, True),
@@ -1591,6 +1592,65 @@ def make_global_filter_weight(complex_weight: torch.Tensor, H: int, W: int, devi
     wc = torch.complex(cw[0].to("cpu", torch.float64), cw[1].to("cpu", torch.float64))
     g = torch.fft.irfft2(wc, s=(H, W), dim=(0, 1))
     return g.to(torch.float32).contiguous().to(device)
+
+
+SWIN_MAX_WS = 8
+
+
+def swin_window_attention(qkv, v_bias, tau, bias_table, heads: int, ws: int, shift: int):
+    """Swin V2 ``shifted_window_attention`` between its ``qkv`` and ``output`` Dense layers (kecam swin_transformer_v2.py:164-262) as
+    one launch on the unpadded map: qkv ``[B,H,W,3C]`` (channels (q|k|v, head, 32), query / value bias already added) -> ``[B,H,W,C]``.
+    ``v_bias`` fp32 ``[C]`` or None: the value of a padded token; ``tau`` fp32 ``[heads]`` (``swin_tau``); ``bias_table`` fp32
+    ``[(2ws-1)^2, heads]`` (``make_swin_bias_table``); ``ws`` the window already clamped to the map, ``shift`` 0 or ``ws // 2``.
+    Pad, roll, partition, mask, reverse, un-roll and crop are addressing inside the kernel (include/vipcup_hip.h has the formulas)."""
+    kind = _kind(qkv, "swin_window_attention.qkv")
+    B, H, W, C3 = qkv.shape
+    Cc = C3 // 3
+    _chk32(tau, "swin_window_attention.tau")
+    _chk32(bias_table, "swin_window_attention.bias_table")
+    if v_bias is not None:
+        _chk32(v_bias, "swin_window_attention.v_bias")
+    if C3 != 3 * Cc or tuple(tau.shape) != (heads,) or tuple(bias_table.shape) != ((2 * ws - 1) ** 2, heads) or \
+            (v_bias is not None and tuple(v_bias.shape) != (Cc,)):
+        raise _abi.VipError(f"swin_window_attention: qkv {tuple(qkv.shape)} with {heads} heads and ws {ws} needs tau ({heads},), bias_table "
+                            f"({(2 * ws - 1) ** 2}, {heads}) and v_bias ({Cc},) or None, got {tuple(tau.shape)}, {tuple(bias_table.shape)}, "
+                            f"{None if v_bias is None else tuple(v_bias.shape)}")
+    out = torch.empty((B, H, W, Cc), dtype=qkv.dtype, device=qkv.device)
+
+    def prof():
+        nwh, N = B * (-(-H // ws)) * (-(-W // ws)) * heads, ws * ws
+        return ("swin_attn_kernel", nwh * 4.0 * N * N * 32, B * H * W * 4.0 * Cc * 2,
+                f"swin attn ws{ws} shift{shift} C={Cc} heads={heads} map={H}x{W}")
+    _launch_kind("swin_attn_fwd", kind, _p(qkv), _p(v_bias), _p(tau), _p(bias_table), _p(out), B, H, W, Cc, heads, ws, shift,
+                 prof=prof if kind == "f16" else None)
+    return out
+
+
+def swin_attn_plan(B: int, H: int, W: int, heads: int, ws: int, shift: int):
+    """dry run of ``swin_window_attention``: (Hp, Wp, work items = B * windows * heads), None when the launch would be refused"""
+    hp, wp, items = C.c_int(0), C.c_int(0), C.c_int(0)
+    ok = _abi.lib().vip_swin_attn_plan(B, H, W, heads, ws, shift, C.byref(hp), C.byref(wp), C.byref(items))
+    return (hp.value, wp.value, items.value) if ok == 1 else None
+
+
+def swin_tau(scale_weight: torch.Tensor, device="cuda") -> torch.Tensor:
+    """kecam ``ExpLogitScale`` (swin_transformer_v2.py:31-51): exp(min(weight, ln 100)) per head, float64 on the host -> fp32 ``[heads]``"""
+    w = scale_weight.detach().to("cpu", torch.float64).reshape(-1)
+    return torch.exp(torch.minimum(w, torch.log(torch.tensor(100.0, dtype=torch.float64)))).to(torch.float32).contiguous().to(device)
+
+
+def make_swin_bias_table(meta1_kernel, meta1_bias, meta2_kernel, ws: int, pos_scale: int = -1, device="cuda") -> torch.Tensor:
+    """The relative-position bias of ``window_mhsa_with_pair_wise_positional_embedding`` (swin_transformer_v2.py:60-108, :187-194) as
+    the table the kernel indexes: fp32 ``[(2ws-1)^2, heads]``, row ``(dr + ws - 1)(2ws - 1) + (dc + ws - 1)`` for the offset (dr, dc) =
+    query - key, ``16 sigmoid(meta_dense_2(relu(meta_dense_1(c))))`` with c = sign(o) log2(1 + |o|) / 3 and o = 8 (dr, dc) /
+    (pos_scale - 1); ``pos_scale`` -1: the window itself.  Input-independent: float64 on the host, once per layer."""
+    ps = float(ws if pos_scale == -1 else pos_scale)
+    r = torch.arange(-ws + 1, ws, dtype=torch.float64)
+    o = torch.stack(torch.meshgrid(r, r, indexing="ij"), -1).reshape(-1, 2) * 8.0 / (ps - 1.0)
+    c = torch.sign(o) * torch.log(1.0 + o.abs()) / (torch.log(torch.tensor(2.0, dtype=torch.float64)) * 3.0)
+    k1, b1, k2 = (t.detach().to("cpu", torch.float64) for t in (meta1_kernel, meta1_bias, meta2_kernel))
+    t = torch.relu(c @ k1 + b1) @ k2
+    return (16.0 * torch.sigmoid(t)).to(torch.float32).contiguous().to(device)
 
 
 def make_dw_weight(depthwise_kernel_hwc1: torch.Tensor, scale: Optional[torch.Tensor] = None, device="cuda") -> torch.Tensor:

@@ -11,7 +11,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import gcvit, hornet, kecam_models as km, resnet_rs, tfimm_models as tm
+from . import gcvit, hornet, kecam_models as km, resnet_rs, swin_v2, tfimm_models as tm
 
 
 @dataclass
@@ -25,7 +25,8 @@ class MemberSpec:
     oracle: str          # module under oracle/ that restates the graph (used by tests / bench cpu leg only)
     gmac_per_image: float  # algorithmic GMAC / image
     head: str = "predictions"  # Keras name of the classifier Dense
-    family: str = ""           # constructor-argument dialect for checkpoint variants (variant_kwargs): filled in below from `oracle`
+    family: str = ""           # constructor-argument dialect for checkpoint variants (variant_kwargs): `oracle` when empty; given
+                               # explicitly by a family that has no module under oracle/ ("swin_v2")
 
 
 MEMBERS: Dict[str, MemberSpec] = {
@@ -75,6 +76,18 @@ MEMBERS: Dict[str, MemberSpec] = {
     "hornet_tiny_gf": MemberSpec("hornet_tiny_gf", "HorNetTinyGF-224x224", 224, 1035,
                                  lambda seed: hornet.synth_params(hornet.CONFIGS["hornet_tiny_gf"], seed, input_hw=224),
                                  lambda p, **kw: hornet.HorNet(p, **hornet.CONFIGS["hornet_tiny_gf"], input_hw=224, **kw), "hornet_ref", 4.06),
+    # Swin Transformer V2 (swin_transformer_v2.py:350-377): built for the manifest's resolution - the clamped window, the shift and the
+    # bias table of every block follow from the stack's map (50, 25, 13, 7 at 200 pixels: stacks 1-3 pad, stack 4 is one 7 x 7
+    # window; 56, 28, 14, 7 at 224).  gmac_per_image = swin_v2.gmac_per_image(cfg, input_hw): per token 16*3*C (stem) + 12 C^2 per
+    # block + 8 C^2 per patch merging, per window and head 2 * ws^4 * 32 on the padded map, C * classes for the head -> 3.969 and 15.607
+    "swin_v2_tiny_window8": MemberSpec("swin_v2_tiny_window8", "SwinTransformerV2Tiny_window8-200x200", 200, 1036,
+        lambda seed: swin_v2.synth_params(swin_v2.CONFIGS["swin_transformer_v2_tiny_window8"], seed, input_hw=200),
+        lambda p, **kw: swin_v2.SwinV2(p, **swin_v2.CONFIGS["swin_transformer_v2_tiny_window8"], input_hw=200, **kw), "",
+        round(swin_v2.gmac_per_image(swin_v2.CONFIGS["swin_transformer_v2_tiny_window8"], 200), 3), family="swin_v2"),
+    "swin_v2_base_window8": MemberSpec("swin_v2_base_window8", "SwinTransformerV2Base_window8-224x224", 224, 1037,
+        lambda seed: swin_v2.synth_params(swin_v2.CONFIGS["swin_transformer_v2_base_window8"], seed, input_hw=224),
+        lambda p, **kw: swin_v2.SwinV2(p, **swin_v2.CONFIGS["swin_transformer_v2_base_window8"], input_hw=224, **kw), "",
+        round(swin_v2.gmac_per_image(swin_v2.CONFIGS["swin_transformer_v2_base_window8"], 224), 3), family="swin_v2"),
     "gcvit_base": MemberSpec("gcvit_base", "GCViTBase-224x224", 224, 1022,
                              lambda seed: gcvit.synth_params(gcvit.NAME2CONFIG["gcvit_base"], seed),
                              lambda p, **kw: gcvit.GCViT(p, **gcvit.NAME2CONFIG["gcvit_base"], **kw), "gcvit_ref", 14.3, "head"),
@@ -394,7 +407,7 @@ def variant_kwargs(spec: MemberSpec, info: dict) -> dict:
     if hw is not None and tuple(hw) != (spec.input_hw, spec.input_hw):
         raise ValueError(f"{spec.ckpt_name}: the checkpoint's model_config was built for {hw[0]}x{hw[1]} inputs, the manifest says "
                          f"{spec.input_hw}x{spec.input_hw}")
-    fam = spec.oracle
+    fam = spec.family or spec.oracle
     classes, act, fs = info.get("classes"), info.get("head_act"), info.get("first_strides")
     if fam == "tfimm_ref":                              # dataclass fields (tfimm_models.variant keeps the ones the graph uses)
         c = info.get("tfimm_cfg") or {}
@@ -404,7 +417,9 @@ def variant_kwargs(spec: MemberSpec, info: dict) -> dict:
         if classes is not None and "nb_classes" not in kw:
             kw["nb_classes"] = classes
         return kw
-    if fs is None and "stem_strides" in info:
+    if fam == "swin_v2":                                # a 4x4 stride-4 patch stem: no first_strides argument, nothing to identify
+        fs = None
+    elif fs is None and "stem_strides" in info:
         # the constructor argument behind the stem convolution's stride: HorNet's stem runs at first_strides * 2 (kecam
         # hornet/hornet.py:144), every other family's at first_strides itself (resnet_rs_model.py:97-104, aotnet.py:326,
         # efficientnet_v2.py:155-156, nfnets.py:182-191)
@@ -415,7 +430,7 @@ def variant_kwargs(spec: MemberSpec, info: dict) -> dict:
             fs = ss // 2
         else:
             fs = ss
-    if fs is None and info.get("n_layers", 0) > 1 and fam != "gcvit_ref":
+    if fs is None and info.get("n_layers", 0) > 1 and fam not in ("gcvit_ref", "swin_v2"):
         raise ValueError(f"{spec.ckpt_name}: the checkpoint's model_config lists {info['n_layers']} layers but no stem convolution with "
                          "strides could be identified - refusing to assume first_strides")
     if classes is not None and classes != 1:
