@@ -16,7 +16,7 @@ from tests import _f16_gemm_cases as T
 from tests import test_gpu_ops as G
 
 # the dispatch switches that are read once per process or per call: the table is for the default of each
-SWITCHES = ("VIP_PW", "VIP_PWX", "VIP_PWK_XLK", "VIP_PWK_WN2K", "VIP_PWK_CONV", "VIP_PWK_FILL", "VIP_PWK_PF2", "VIP_G8P_MINK")
+SWITCHES = ("VIP_PW", "VIP_PWX", "VIP_PWK_XLK", "VIP_PWK_WN2K", "VIP_PWK_CONV", "VIP_PWK_FILL", "VIP_G8P_MINK")
 
 
 @pytest.fixture(autouse=True)

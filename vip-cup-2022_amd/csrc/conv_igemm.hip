@@ -93,13 +93,22 @@ struct ConvArgs2 : ConvArgs {
 // What one call launches.  plan() (below the kernels) fills it from the arguments alone - host code, no HIP call, so a dry run
 // (vip_conv2d_kernel_name / _variant) is plan() without launch() - and launch() maps it to the instantiation.
 enum Family { PW_GEMM, ROWS_GEMM, GEMM8P, PWX, PWK_DIRECT, PWK_GEMM, IM2COL, CONV_IGEMM };
+// The epilogue a pointwise kernel carries (the kernels receive it as an int, pw_epilogue_mode below turns it into an instantiation of
+// pw_epilogue): act_pre alone - the VIP_ACT_* code itself, 0..4 - or a residual with no act_pre, plain or followed by ReLU, and those
+// two again with the output gate (a.ogate; fp16 storage only).  EPI_OTHER: none of these (an activation AND a residual, any other
+// act_post) - conv_igemm_kernel's run-time epilogue.
+enum EpiMode : int {
+    EPI_OTHER = -1,
+    EPI_NONE = VIP_ACT_NONE, EPI_RELU = VIP_ACT_RELU, EPI_SILU = VIP_ACT_SILU, EPI_GELU = VIP_ACT_GELU, EPI_SIGMOID = VIP_ACT_SIGMOID,
+    EPI_RES = 5, EPI_RES_RELU = 6,
+    EPI_OGATE_RES = 7, EPI_OGATE_RES_RELU = 8,
+};
+constexpr bool epi_out_gated(EpiMode m) { return m == EPI_OGATE_RES || m == EPI_OGATE_RES_RELU; }
 struct Plan {
     Family family;
-    int mode;                           // epilogue the pointwise kernels carry: act_pre (0..4), 5 residual, 6 residual + ReLU, 7 / 8 = 5 / 6
-                                        // with the output gate (a.ogate); -1: none of these
+    EpiMode mode;
     int ng, pt, wn, ks, ksc, bm, bn;    // template arguments, those the family has
     bool gated, hilo, ln, xsplit, pipe;
-    bool pf2;                           // PWK_DIRECT: the VIP_PWK_PF2 experiment (pwk_direct2_kernel)
     int m_blocks, n_blocks;             // -> ConvArgs (0 for the kernels that do not read them)
     int n_chunks, nb_ch, lds_stride;    // PW_GEMM: channel chunks (grid y), channels per chunk, LDS row stride in bytes
 };
@@ -270,6 +279,14 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x4 (&acc)[MT][4],
     }
 }
 
+// XCD-aware block remap: hardware deals workgroup ids round-robin to the 8 XCDs, so blocks b and b+8 share an XCD (and its L2); give
+// every XCD a contiguous run of logical tiles so the n-blocks that re-read one activation tile hit the same L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
     constexpr int WAVES_N = BN / 64;
@@ -288,15 +305,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
     const int wave = tid >> 6;
     const int group = blockIdx.z;
 
-    // XCD-aware block remap: blocks b and b+8 share an XCD (and its L2); give every XCD a contiguous
-    // run of logical tiles so the n-blocks that re-read one activation tile hit the same L2.
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mb = bid / a.n_blocks;
     const int nb = bid - mb * a.n_blocks;
     const int m0 = mb * BM;
@@ -578,8 +587,66 @@ __device__ __forceinline__ void pw_epilogue(const ConvArgs& a, f32x4 (&acc)[PT][
     }
 }
 
-// mode = act_pre (0..4) without residual, 5 = residual, 6 = residual + post-ReLU (both with act_pre none), 7 / 8 = 5 / 6 with the
-// output gate (fp16 storage only)
+// The epilogue dispatch of every pointwise kernel: the run-time mode (EpiMode) -> the instantiation of pw_epilogue, for one 64-channel
+// group of accumulators.  What an instantiation does with the two output-gated modes is a compile-time property of it (OG):
+enum OutGateCases {
+    OG_UNKNOWN,     // not cases of their own: like any number that is no mode they take the default (the packed build, and every kernel but
+                    // the two below)
+    OG_IGNORED,     // cases that do nothing: pwk_direct_kernel<.., GATED = true> of the fp16 build (plan() sends no output gate there)
+    OG_CARRIED,     // carried beside the other modes: pwk_direct_kernel<.., GATED = false> (gl: the staged gate rows)
+    OG_ALONE,       // nothing else is carried: the kernels of their own that plan() reaches in these modes alone, pw_gemm_kernel<.., OG>
+                    // and, with Y2, the two-output form pwk_direct_kernel<.., OG2> (rb_y2: the descriptor of a.y2, made by the kernel from
+                    // its own argument - the span of y)
+};
+template <int PT, OutGateCases OG = OG_UNKNOWN, bool Y2 = false, class Args>      // Args: ConvArgs, or ConvArgs2 as the kernel holds it
+__device__ __forceinline__ void pw_epilogue_mode(int mode, const Args& a, f32x4 (&acc)[PT][4], int m_base, int n_first,
+                                                 const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y, GateLds gl = GateLds{},
+                                                 const __amdgpu_buffer_rsrc_t* rb_y2 = nullptr) {
+    static_assert(!(H2 && OG != OG_UNKNOWN), "the output gate is carried by the fp16-storage build only");
+    static_assert(OG == OG_ALONE || !Y2, "the second output belongs to the instantiations that carry the output gate alone");
+    if constexpr (Y2) {
+        if (mode == EPI_OGATE_RES_RELU) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, rb_y2);
+        else pw_epilogue<PT, VIP_ACT_NONE, true, false, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, rb_y2);
+    } else if constexpr (OG == OG_ALONE) {
+        if (mode == EPI_OGATE_RES_RELU) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+        else pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+    } else {
+        switch (mode) {
+            case EPI_RELU: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            case EPI_SILU: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            case EPI_GELU: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            case EPI_SIGMOID: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            case EPI_RES: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            case EPI_RES_RELU: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            // (OG_UNKNOWN: the two labels fall through to the default, i.e. are no cases)
+            case EPI_OGATE_RES:
+                if constexpr (OG != OG_UNKNOWN) {
+                    if constexpr (OG == OG_CARRIED) pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+                    break;
+                }
+                [[fallthrough]];
+            case EPI_OGATE_RES_RELU:
+                if constexpr (OG != OG_UNKNOWN) {
+                    if constexpr (OG == OG_CARRIED) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
+                    break;
+                }
+                [[fallthrough]];
+            default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+        }
+    }
+}
+
+// ... for the NG 64-channel groups of a wave tile (n_lane: the lane's first channel in group 0).  One call per group, not a loop over
+// g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be indexed dynamically,
+// i.e. live in scratch.
+template <int NG, int PT>
+__device__ __forceinline__ void pw_epilogue_groups(int mode, const ConvArgs& a, f32x4 (&acc)[NG][PT][4], int m_base, int n_lane,
+                                                   const __amdgpu_buffer_rsrc_t& rb_res, const __amdgpu_buffer_rsrc_t& rb_y) {
+    static_assert(NG == 1 || NG == 2, "one call per group below");
+    pw_epilogue_mode<PT>(mode, a, acc[0], m_base, n_lane, rb_res, rb_y);
+    if constexpr (NG > 1) pw_epilogue_mode<PT>(mode, a, acc[1], m_base, n_lane + 64, rb_res, rb_y);
+}
+
 // HILO: the LDS row of a channel holds its fp16 weights followed by their low halves (w_lo); every activation fragment is
 // multiplied by both, so the layer computes with ~22-bit weights.  These layers are HBM-bound, the second MFMA is free.
 // OG: the instantiations of the output-gated epilogue (modes 7 / 8, nothing else) - kernels of their own, so that the gate's registers
@@ -723,21 +790,12 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(std::conditional_t<Y2, 
             }
             const int m_base = m0 + l15, n_first = n_chunk0 + sub + lq * 8;
             if constexpr (Y2) {
+                // (pw_gemm_kernel<.., Y2>: its two calls stay here - through pw_epilogue_mode<PT, OG_ALONE, true> these kernels allocate other registers)
                 const __amdgpu_buffer_rsrc_t rb_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, (unsigned)a.y_span_bytes, 0x00020000);
-                if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+                if (mode == EPI_OGATE_RES_RELU) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, &rb_y2);
                 else pw_epilogue<PT, VIP_ACT_NONE, true, false, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl, &rb_y2);
-            } else if constexpr (OG) {
-                if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
-                else pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc, m_base, n_first, rb_res, rb_y, gl);
-            } else
-            switch (mode) {
-                case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                case 3: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc, m_base, n_first, rb_res, rb_y); break;
-                default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc, m_base, n_first, rb_res, rb_y); break;
+            } else {
+                pw_epilogue_mode<PT, OG ? OG_ALONE : OG_UNKNOWN>(mode, a, acc, m_base, n_first, rb_res, rb_y, gl);
             }
         }
         if constexpr (PRE) {
@@ -754,8 +812,18 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(std::conditional_t<Y2, 
 // LDS of the output-gated streaming kernel's gate rows: 4 waves x OG_IMAGES images x nb_ch fp32
 constexpr size_t pw_og_lds(int nb_ch) { return (size_t)4 * 4 * nb_ch * 4; }
 
-template <int KS, int PT, bool HILO, bool OG = false>
-int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
+// the kernel argument of a launch: ConvArgs, or for the two-output instantiations ConvArgs2 with the second output
+template <bool Y2>
+std::conditional_t<Y2, ConvArgs2, ConvArgs> kernel_args(const ConvArgs& a, f16* y2) {
+    std::conditional_t<Y2, ConvArgs2, ConvArgs> ka;
+    static_cast<ConvArgs&>(ka) = a;
+    if constexpr (Y2) ka.y2 = y2;
+    return ka;
+}
+
+// OG / Y2: the output-gated instantiations and their two-output form (y2) - the same grid, and the same LDS and prefetch rule for both
+template <int KS, int PT, bool HILO, bool OG = false, bool Y2 = false>
+int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s, f16* y2 = nullptr) {
     // (the gated epilogue holds two more 16-byte loads per 8 channels: at KS = 3 it does not fit next to a prefetched tile without scratch)
     constexpr bool PRE = OG ? KS <= 2 : KS <= 3;
     const int n_tiles = (a.M + 64 * PT - 1) / (64 * PT);
@@ -763,34 +831,74 @@ int launch_pw(const ConvArgs& a, const Plan& p, hipStream_t s) {
     if (gx > n_tiles) gx = n_tiles;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO, OG>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO, OG, Y2>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO, OG>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
-                       (size_t)p.nb_ch * (p.lds_stride + 4) + (OG ? pw_og_lds(p.nb_ch) : 0), s, a, p.nb_ch, p.lds_stride, n_tiles, p.mode);
-    return vip_launch_status("vip_conv2d_nhwc_f16(pw)");
+    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO, OG, Y2>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
+                       (size_t)p.nb_ch * (p.lds_stride + 4) + (OG ? pw_og_lds(p.nb_ch) : 0), s, kernel_args<Y2>(a, y2), p.nb_ch, p.lds_stride,
+                       n_tiles, (int)p.mode);
+    return vip_launch_status(Y2 ? "vip_conv2d_out_gated2_nhwc_f16(pw)" : "vip_conv2d_nhwc_f16(pw)");
 }
 
-// the two-output form of the output-gated launch: the grid, the LDS and the prefetch rule of launch_pw<.., OG = true>
-template <int KS, int PT, bool HILO>
-int launch_pw_og2(const ConvArgs& a, const Plan& p, f16* y2, hipStream_t s) {
-    constexpr bool PRE = KS <= 2;
-    const int n_tiles = (a.M + 64 * PT - 1) / (64 * PT);
-    int gx = (2 * device_cus() + p.n_chunks - 1) / p.n_chunks;
-    if (gx > n_tiles) gx = n_tiles;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pw_gemm_kernel<KS, PT, PRE, HILO, true, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
+// ---- device code shared by the kernels that stream 64-k weight chunks through LDS (pwk_direct_kernel, pwx_body, pwk_gemm_kernel) and,
+// where named, gemm8p_kernel ----
+// The buffer descriptors of a pointwise kernel's operands: out-of-range offsets read as zero and drop stores, so tails and masked lanes
+// cost no branch (see conv_igemm_kernel).
+struct PwBuffers {
+    __amdgpu_buffer_rsrc_t w, x, res, y, bias;
+};
+__device__ __forceinline__ PwBuffers pw_buffers(const ConvArgs& a) {
+    PwBuffers b;
+    b.w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
+    b.x = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + a.cin_off), 0, (unsigned)min((long)0xFFFFFFF0L, a.x_span_bytes - 2L * a.cin_off),
+                                            0x00020000);
+    b.res = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_span_bytes : 0u, 0x00020000);
+    b.y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_span_bytes, 0x00020000);
+    b.bias = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)(a.bias_elems * 4) : 0u, 0x00020000);
+    return b;
+}
+
+// One k-step (ks = 0 / 1: 32 k, or the hi / lo plane of the packed storage) of a wave's MFMAs: the activation fragments xf of its PT
+// pixel tiles against the weight rows of its NG 64-channel groups in an LDS stage.  ws: the lane's fragment address in the first row
+// (stage + l15 * ROWB + lq * 16 + ks * 64).
+template <int NG, int PT, int ROWB>
+__device__ __forceinline__ void pw_mfma_step(f32x4 (&acc)[NG][PT][4], const char* ws, const U4H8 (&xf)[PT], int ks) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        U4H8 wf[4];
+        if constexpr (H2) {
+            // ks = 0: the x hi fragments against the weights' lo plane (wh + 64) and hi plane (wh); ks = 1: x lo against the hi
+            // plane (ws - 64: the caller's ks * 64 points at the lo plane)
+            const char* wh = ws - ks * 64;
+            U4H8 wl[4];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(wh + (g * 64 + nt * 16) * ROWB);
+            if (ks == 0) {
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) wl[nt].u = *reinterpret_cast<const uint4*>(wh + 64 + (g * 64 + nt * 16) * ROWB);
+            }
+            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int p = 0; p < PT; ++p) {
+                    if (ks == 0) acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
+                    acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
+                }
+            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
+            continue;
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(ws + (g * 64 + nt * 16) * ROWB);
+        if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int p = 0; p < PT; ++p)
+                acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
+        if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
     }
-    ConvArgs2 a2;
-    static_cast<ConvArgs&>(a2) = a;
-    a2.y2 = y2;
-    hipLaunchKernelGGL((pw_gemm_kernel<KS, PT, PRE, HILO, true, true>), dim3((unsigned)gx, (unsigned)p.n_chunks), dim3(256),
-                       (size_t)p.nb_ch * (p.lds_stride + 4) + pw_og_lds(p.nb_ch), s, a2, p.nb_ch, p.lds_stride, n_tiles, p.mode);
-    return vip_launch_status("vip_conv2d_out_gated2_nhwc_f16(pw)");
 }
 
 // ---- pointwise (1x1, stride 1) / dense layers, any K: activations direct to registers, weights through LDS ----
@@ -817,17 +925,12 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<O
     const int l15 = lane & 15, lq = lane >> 4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mb = bid / a.n_blocks, nb = bid - mb * a.n_blocks;
     const int m0 = mb * (64 * PT) + wave * (16 * PT);
     const int n0 = nb * NB;
 
+    // (pwk_direct_kernel: the descriptors stay single variables - as a PwBuffers the gated instantiations allocate registers differently)
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.w, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
@@ -839,6 +942,8 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<O
         __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)(a.bias_elems * 4) : 0u, 0x00020000);
 
     // weight staging: thread -> (LDS row j = tid/8 + 32 i, 16-byte chunk c = tid%8); row j holds channel perm(j)
+    // (pwk_direct_kernel: its own copy of the set-up it shares with pwk_gemm_kernel - as one struct with load / store members every
+    // instantiation of both kernels changed)
     const int wc = tid & 7;
     unsigned w_off[W_IT];
     int w_lds[W_IT];
@@ -934,7 +1039,8 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<O
     };
 
     f32x4 acc[NG][PT][4];
-    {   // bias is the C operand of the first MFMA of every accumulator
+    {   // bias is the C operand of the first MFMA of every accumulator  (pwk_direct_kernel: the loop stays a copy here, in pwx_body,
+        // pwk_gemm_kernel and gemm8p_kernel - as one function, forced inline or not, it changed the code of all four)
 #pragma unroll
         for (int g = 0; g < NG; ++g)
 #pragma unroll
@@ -955,42 +1061,7 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<O
     __syncthreads();
 
     auto compute = [&](int buf, int ks) {
-        const char* ws = smem + buf * STAGE + l15 * ROWB + lq * 16 + ks * 64;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            U4H8 wf[4];
-            if constexpr (H2) {
-                // ks = 0: the x hi fragments against the weights' lo plane (ws + 64) and hi plane (ws); ks = 1: x lo against the hi
-                // plane (ws - 64: the lambda's ks * 64 points at the lo plane)
-                const char* wh = ws - ks * 64;
-                U4H8 wl[4];
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(wh + (g * 64 + nt * 16) * ROWB);
-                if (ks == 0) {
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) wl[nt].u = *reinterpret_cast<const uint4*>(wh + 64 + (g * 64 + nt * 16) * ROWB);
-                }
-                if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                    for (int p = 0; p < PT; ++p) {
-                        if (ks == 0) acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt].h, xf[0][p].h, acc[g][p][nt], 0, 0, 0);
-                        acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[ks][p].h, acc[g][p][nt], 0, 0, 0);
-                    }
-                if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-                continue;
-            }
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(ws + (g * 64 + nt * 16) * ROWB);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[ks][p].h, acc[g][p][nt], 0, 0, 0);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-        }
+        pw_mfma_step<NG, PT, ROWB>(acc, smem + buf * STAGE + l15 * ROWB + lq * 16 + ks * 64, xf[ks], ks);
     };
 
     // One activation register set: the fragments of k-step ks are re-loaded for the NEXT chunk as soon as this
@@ -1034,43 +1105,27 @@ __global__ __launch_bounds__(256, 2) void pwk_direct_kernel(std::conditional_t<O
     // ~20 registers stay live through it (the loop is at the 256-VGPR limit of two waves per SIMD)
     int m_base = m0 + l15, n_lane = n0 + lq * 8;
     asm volatile("" : "+v"(m_base), "+v"(n_lane));
-    // (not a loop over g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be
-    // indexed dynamically, i.e. live in scratch)
+    // output gate: the instantiations without the INPUT gate alone (plan() sends no other one here with an output gate)
+    constexpr OutGateCases OG = OG2 ? OG_ALONE : H2 ? OG_UNKNOWN : GATED ? OG_IGNORED : OG_CARRIED;
     GateLds gl{};
-#if !VIP_GEMM_H2
-    if constexpr (!GATED) {
-        if (mode >= 7) {    // output gate: the weight stages are free after the loop's last barrier - the gate rows of the block's images go there
+    if constexpr (OG == OG_CARRIED || OG == OG_ALONE) {
+        if (mode >= EPI_OGATE_RES) {    // the weight stages are free after the loop's last barrier - the gate rows of the block's images go there
             float* g_lds = reinterpret_cast<float*>(smem);
             const int img0 = stage_out_gate(a, g_lds, NB, mb * (64 * PT), 64 * PT, n0, NB, (int)threadIdx.x, 256);
             __syncthreads();
             gl = GateLds{g_lds, img0, NB, n0};
         }
     }
-#endif
+    // (pwk_direct_kernel: the per-group call keeps its lambda - called through pw_epilogue_groups the gated instantiations allocate other
+    // registers in the k-loop)
     auto epi = [&](auto gtag) {
         constexpr int G_ = decltype(gtag)::value;
         const int n_first = n_lane + G_ * 64;
-#if !VIP_GEMM_H2
         if constexpr (OG2) {
             const __amdgpu_buffer_rsrc_t rb_y2 = __builtin_amdgcn_make_buffer_rsrc((void*)a.y2, 0, (unsigned)a.y_span_bytes, 0x00020000);
-            if (mode == 8) pw_epilogue<PT, VIP_ACT_NONE, true, true, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl, &rb_y2);
-            else pw_epilogue<PT, VIP_ACT_NONE, true, false, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl, &rb_y2);
-            return;
-        }
-#endif
-        switch (mode) {
-            case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 3: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-#if !VIP_GEMM_H2
-            // output gate: the instantiations without the INPUT gate alone (plan() sends no other one here in modes 7 / 8)
-            case 7: if constexpr (!GATED) pw_epilogue<PT, VIP_ACT_NONE, true, false, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl); break;
-            case 8: if constexpr (!GATED) pw_epilogue<PT, VIP_ACT_NONE, true, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y, gl); break;
-#endif
-            default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
+            pw_epilogue_mode<PT, OG, true>(mode, a, acc[G_], m_base, n_first, rb_res, rb_y, gl, &rb_y2);
+        } else {
+            pw_epilogue_mode<PT, OG>(mode, a, acc[G_], m_base, n_first, rb_res, rb_y, gl);
         }
     };
     epi(std::integral_constant<int, 0>{});
@@ -1103,24 +1158,10 @@ __device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
     const int l15 = lane & 15, lq = lane >> 4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
 
-    int bid = blockIdx.x;
-    {   // XCD-contiguous pixel tiles (as pwk_direct_kernel)
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);    // XCD-contiguous pixel tiles
     const int m0 = bid * (64 * PT) + wave * (16 * PT);
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.w, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.x + a.cin_off), 0, (unsigned)min((long)0xFFFFFFF0L, a.x_span_bytes - 2L * a.cin_off), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_res =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_span_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_span_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_bias =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)(a.bias_elems * 4) : 0u, 0x00020000);
+    const PwBuffers rb = pw_buffers(a);
 
     // weight staging: thread -> (LDS row j = tid/8 + 32 i, 16-byte chunk c = tid%8); row j holds channel n0 + perm(j)
     const int wc = tid & 7;
@@ -1139,7 +1180,7 @@ __device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
         for (int i = 0; i < W_IT; ++i) {
             const int ch = n0 + w_ch[i];
             wst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                   rw, (okk && ch < a.Cout_g) ? (unsigned)((ch * a.ldw + wc * 8) * 2) + kc * 128 : OOB, 0, 0));
+                                                   rb.w, (okk && ch < a.Cout_g) ? (unsigned)((ch * a.ldw + wc * 8) * 2) + kc * 128 : OOB, 0, 0));
         }
     };
     auto store_w = [&](int buf) {
@@ -1160,7 +1201,7 @@ __device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
             for (int ks = 0; ks < 2; ++ks) {
                 const bool ok = kc * 64 + (H2 ? lq * 16 + ks * 8 : ks * 32 + lq * 8) < a.K;
                 xf[2 * kc + ks][p].u = __builtin_bit_cast(
-                    uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? xo + kc * 128 + ks * (H2 ? 16 : 64) : OOB, 0, 0));
+                    uint4, __builtin_amdgcn_raw_buffer_load_b128(rb.x, ok ? xo + kc * 128 + ks * (H2 ? 16 : 64) : OOB, 0, 0));
             }
     }
     if constexpr (LN && !H2) {
@@ -1241,18 +1282,19 @@ __device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
     }
 
     f32x4 acc[NG][PT][4];
-    auto init_acc = [&](int n0) {     // bias is the C operand of the first MFMA of every accumulator
+    auto init_acc = [&](int n0) {     // bias is the C operand of the first MFMA of every accumulator  (pwx_body: a copy, see pwk_direct_kernel)
 #pragma unroll
         for (int g = 0; g < NG; ++g)
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const int n = n0 + g * 64 + (nt >> 1) * 32 + lq * 8 + (nt & 1) * 4;
                 const f32x4 bv = __builtin_bit_cast(
-                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb_bias, n < a.Cout_g ? (unsigned)(n * 4) : OOB, 0, 0));
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb.bias, n < a.Cout_g ? (unsigned)(n * 4) : OOB, 0, 0));
 #pragma unroll
                 for (int p = 0; p < PT; ++p) acc[g][p][nt] = bv;
             }
     };
+    // (pwx_body: its own copy of pw_mfma_step - with the shared one the packed build's pwx_kernel allocates other registers)
     auto compute = [&](int buf, int ks, const U4H8 (&xk)[2][PT]) {
         const char* ws = smem + buf * STAGE + l15 * ROWB + lq * 16 + ks * 64;
 #pragma unroll
@@ -1318,22 +1360,8 @@ __device__ __forceinline__ void pwx_body(const ConvArgs& a, int mode) {
             buf ^= 1;
         }
         int m_base = m0 + l15, n_lane = n0 + lq * 8;
-        asm volatile("" : "+v"(m_base), "+v"(n_lane));
-        auto epi = [&](auto gtag) {
-            constexpr int G_ = decltype(gtag)::value;
-            const int n_first = n_lane + G_ * 64;
-            switch (mode) {
-                case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 3: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            }
-        };
-        epi(std::integral_constant<int, 0>{});
-        epi(std::integral_constant<int, 1>{});
+        asm volatile("" : "+v"(m_base), "+v"(n_lane));      // (as in pwk_direct_kernel)
+        pw_epilogue_groups<NG, PT>(mode, a, acc, m_base, n_lane, rb.res, rb.y);
     }
 }
 
@@ -1353,168 +1381,6 @@ int launch_pwx(const ConvArgs& a, int mode, hipStream_t s) {
     else hipLaunchKernelGGL((pwx_kernel<KSC, PT>), dim3((unsigned)a.m_blocks), dim3(256), 0, s, a, mode);
     return vip_launch_status(LN ? "vip_ln_gemm_bias_act_f16" : "vip_conv2d_nhwc_f16(pwx)");
 }
-
-#if VIP_BUILD_EXPERIMENTS
-// ---- the direct kernel with the activation fragments requested TWO k-chunks ahead (round 3) ----------------------------------
-// EXPERIMENT (VIP_BUILD_EXPERIMENTS=1, selected per call with VIP_PWK_PF2=1) - a NEGATIVE result, kept for the record.
-// PMC of pwk_direct_kernel<2, false, 4> on its typical shapes (profiles/r03_pwk_pmc_*.txt): the matrix pipe is busy 30 % of the time,
-// a wave spends 47-62 % of its life in s_waitcnt, and a k-chunk takes ~6 000 cycles against 1 024 cycles of MFMAs.  Hypothesis: the
-// loop is a chain of memory round trips with too few bytes in flight.  This variant halves the wave tile to 32 pixels x 128 channels
-// (64 accumulator registers instead of 128) and spends the registers on a second activation register set: the fragments of chunk
-// kc + 2 are requested while chunk kc is multiplied (the k-loop is unrolled by two so that a chunk's register set is a compile-time
-// choice), 3 waves per SIMD instead of 2.  Bit-identical to the default kernel and SLOWER on 12 of 16 ensemble shapes (0.81-1.12x,
-// sum 680 vs 642 us; profiles/r03_pwk_deep_prefetch_ab.log): the 128-pixel block tile doubles the weight staging and the L2 -> CU
-// traffic per output (~7 TB/s chip-wide either way), which costs more than the extra loads in flight buy.
-template <int NG>
-__global__ __launch_bounds__(256, 3) void pwk_direct2_kernel(ConvArgs a, int mode) {
-    constexpr int PT = 2;
-    constexpr int NB = 64 * NG, ROWB = 160;
-    constexpr int STAGE = NB * ROWB;
-    constexpr int W_IT = NB / 32;
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, lq = lane >> 4;
-    constexpr unsigned OOB = 0xFFFFFFF0u;
-
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int mb = bid / a.n_blocks, nb = bid - mb * a.n_blocks;
-    const int m0 = mb * (64 * PT) + wave * (16 * PT);
-    const int n0 = nb * NB;
-
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.w, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.x + a.cin_off), 0, (unsigned)min((long)0xFFFFFFF0L, a.x_span_bytes - 2L * a.cin_off), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_res =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_span_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_span_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_bias =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)(a.bias_elems * 4) : 0u, 0x00020000);
-
-    const int wc = tid & 7;
-    unsigned w_off[W_IT];
-    int w_lds[W_IT];
-#pragma unroll
-    for (int i = 0; i < W_IT; ++i) {
-        const int j = (tid >> 3) + 32 * i;
-        const int t = (j >> 4) & 3, r = j & 15;
-        const int ch = n0 + (j & ~63) + (t >> 1) * 32 + (r >> 2) * 8 + (t & 1) * 4 + (r & 3);
-        w_off[i] = ch < a.Cout_g ? (unsigned)((ch * a.ldw + wc * 8) * 2) : OOB;
-        w_lds[i] = j * ROWB + wc * 16;
-    }
-    unsigned x_off[PT];
-#pragma unroll
-    for (int p = 0; p < PT; ++p) {
-        const int m = m0 + p * 16 + l15;
-        x_off[p] = m < a.M ? (unsigned)((m * a.ldx + lq * 8) * 2) : 0xFFFF0000u;
-    }
-    const int nk = (a.K + 63) >> 6;
-
-    uint4 wst[W_IT];
-    auto load_w = [&](int kc) {
-        const bool ok = kc * 64 + wc * 8 < a.K;
-#pragma unroll
-        for (int i = 0; i < W_IT; ++i)
-            wst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? w_off[i] + kc * 128 : OOB, 0, 0));
-    };
-    auto store_w = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < W_IT; ++i) *reinterpret_cast<uint4*>(smem + buf * STAGE + w_lds[i]) = wst[i];
-    };
-    U4H8 xf[2][2][PT];                                         // [register set = chunk parity][k-step][pixel tile]
-    auto load_x = [&](U4H8 (&dst)[PT], int kc, int ks) {
-        const bool ok = kc * 64 + ks * 32 + lq * 8 < a.K;       // also false for every chunk past the end of K: zeros, no traffic
-#pragma unroll
-        for (int p = 0; p < PT; ++p)
-            dst[p].u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? x_off[p] + kc * 128 + ks * 64 : OOB, 0, 0));
-    };
-
-    f32x4 acc[NG][PT][4];
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            const int n = n0 + g * 64 + (nt >> 1) * 32 + lq * 8 + (nt & 1) * 4;
-            const f32x4 bv = __builtin_bit_cast(
-                f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb_bias, n < a.Cout_g ? (unsigned)(n * 4) : OOB, 0, 0));
-#pragma unroll
-            for (int p = 0; p < PT; ++p) acc[g][p][nt] = bv;
-        }
-
-    load_w(0);
-    load_x(xf[0][0], 0, 0);
-    load_x(xf[0][1], 0, 1);
-    load_x(xf[1][0], 1, 0);
-    load_x(xf[1][1], 1, 1);
-    store_w(0);
-    __syncthreads();
-
-    auto compute = [&](int buf, const U4H8 (&xs)[PT], int ks) {
-        const char* ws = smem + buf * STAGE + l15 * ROWB + lq * 16 + ks * 64;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            U4H8 wf[4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(ws + (g * 64 + nt * 16) * ROWB);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xs[p].h, acc[g][p][nt], 0, 0, 0);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-        }
-    };
-    // one chunk on register set SET (compile time): its fragments are re-requested for chunk kc + 2 as soon as their MFMAs are issued
-#define VIP_PWK2_CHUNK(SET, KC)                               \
-    {                                                         \
-        const int buf = (KC) & 1;                             \
-        load_w((KC) + 1);                                     \
-        __builtin_amdgcn_sched_barrier(0);                    \
-        compute(buf, xf[SET][0], 0);                          \
-        __builtin_amdgcn_sched_barrier(0);                    \
-        load_x(xf[SET][0], (KC) + 2, 0);                      \
-        __builtin_amdgcn_sched_barrier(0);                    \
-        compute(buf, xf[SET][1], 1);                          \
-        __builtin_amdgcn_sched_barrier(0);                    \
-        load_x(xf[SET][1], (KC) + 2, 1);                      \
-        store_w(buf ^ 1);                                     \
-        __syncthreads();                                      \
-    }
-    for (int kc = 0; kc < nk; kc += 2) {
-        VIP_PWK2_CHUNK(0, kc)
-        if (kc + 1 < nk) VIP_PWK2_CHUNK(1, kc + 1)            // wave-uniform: nk comes from a kernel argument
-    }
-#undef VIP_PWK2_CHUNK
-
-    int m_base = m0 + l15, n_lane = n0 + lq * 8;
-    asm volatile("" : "+v"(m_base), "+v"(n_lane));
-    // (not a loop over g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be
-    // indexed dynamically, i.e. live in scratch)
-    auto epi = [&](auto gtag) {
-        constexpr int G_ = decltype(gtag)::value;
-        const int n_first = n_lane + G_ * 64;
-        switch (mode) {
-            case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 3: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-        }
-    };
-    epi(std::integral_constant<int, 0>{});
-    if constexpr (NG > 1) epi(std::integral_constant<int, 1>{});
-}
-
-#endif  // VIP_BUILD_EXPERIMENTS
 
 template <int NG, int WN, bool IM2COL>
 __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(ConvArgs a, int mode) {
@@ -1546,30 +1412,17 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
     const int l15 = lane & 15, lq = lane >> 4;
     constexpr unsigned OOB = 0xFFFFFFF0u;
 
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mb = bid / a.n_blocks, nb = bid - mb * a.n_blocks;
     const int mblk = mb * 256;                               // first pixel of the block tile
     const int m0 = mblk + wm * 64;                           // first pixel of this wave
     const int nblk = nb * NBLK;
     const int n0 = nblk + wn * NB;
 
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)a.w, 0, (unsigned)min((long)0xFFFFFFF0L, 2L * a.Cout_g * a.ldw), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.x + a.cin_off), 0, (unsigned)min((long)0xFFFFFFF0L, a.x_span_bytes - 2L * a.cin_off), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_res =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, a.res ? (unsigned)a.res_span_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_y = __builtin_amdgcn_make_buffer_rsrc((void*)a.y, 0, (unsigned)a.y_span_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_bias =
-        __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)(a.bias_elems * 4) : 0u, 0x00020000);
+    const PwBuffers rb = pw_buffers(a);
 
     // weight staging: thread -> (LDS row j = tid/8 + (NTHR/8) i, 16-byte chunk c = tid%8); row j holds channel perm(j)
+    // (pwk_gemm_kernel: pwk_direct_kernel's set-up with NTHR / 8 for 32 and nblk for n0, a copy for the reason given there)
     const int wc = tid & 7;
     unsigned w_off[W_IT];
     int w_lds[W_IT];
@@ -1619,7 +1472,7 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
         const bool ok = kc * 64 + wc * 8 < a.K;
 #pragma unroll
         for (int i = 0; i < W_IT; ++i)
-            wst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rw, ok ? w_off[i] + kc * 128 : OOB, 0, 0));
+            wst[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rb.w, ok ? w_off[i] + kc * 128 : OOB, 0, 0));
     };
     auto store_w = [&](int buf) {
 #pragma unroll
@@ -1638,14 +1491,14 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
                 const int hi = (hw0[i] >> 16) + tr, wi = (int)(short)(hw0[i] & 0xFFFF) + ts;
                 const bool ok = kok & ((unsigned)hi < (unsigned)a.H) & ((unsigned)wi < (unsigned)a.W);
                 const unsigned off = (unsigned)(((pix0[i] + hi * a.W + wi) * a.ldx + c) * 2);
-                xst[i].u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? off : OOB, 0, 0));
+                xst[i].u = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rb.x, ok ? off : OOB, 0, 0));
             }
         } else {
 #pragma unroll
             for (int i = 0; i < X_IT; ++i) {
                 const bool ok = kok & (mblk + xr + XROWS * i < a.M);
                 xst[i].u = __builtin_bit_cast(
-                    uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? x_base + i * x_rstep + kc * 128 : OOB, 0, 0));
+                    uint4, __builtin_amdgcn_raw_buffer_load_b128(rb.x, ok ? x_base + i * x_rstep + kc * 128 : OOB, 0, 0));
             }
         }
     };
@@ -1658,14 +1511,14 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
     const char* xs = ximg + wm * XS;
 
     f32x4 acc[NG][PT][4];
-    {   // bias is the C operand of the first MFMA of every accumulator
+    {   // bias is the C operand of the first MFMA of every accumulator  (pwk_gemm_kernel: a copy, see pwk_direct_kernel)
 #pragma unroll
         for (int g = 0; g < NG; ++g)
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const int n = n0 + g * 64 + (nt >> 1) * 32 + lq * 8 + (nt & 1) * 4;
                 const f32x4 bv = __builtin_bit_cast(
-                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb_bias, n < a.Cout_g ? (unsigned)(n * 4) : OOB, 0, 0));
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb.bias, n < a.Cout_g ? (unsigned)(n * 4) : OOB, 0, 0));
 #pragma unroll
                 for (int p = 0; p < PT; ++p) acc[g][p][nt] = bv;
             }
@@ -1682,42 +1535,10 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
         // computed from the lower half's weights - WN = 2 only, a shape gemm8p has taken since it exists unless K % 64 != 0)
         const char* ws = smem + buf * STAGE + (WN > 1 ? wn * NB * ROWB : 0) + l15 * ROWB + lq * 16 + ks * 64;
         const char* xl = xs + l15 * ROWB + lq * 16 + ks * 64;
-        U4H8 xf[PT];
+        U4H8 xf[PT];     // the fragments of the wave's activation image: the hi (ks = 0) / lo (ks = 1) plane of x on the packed storage
 #pragma unroll
         for (int p = 0; p < PT; ++p) xf[p].u = *reinterpret_cast<const uint4*>(xl + p * 16 * ROWB);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            U4H8 wf[4];
-            if constexpr (H2) {     // as in pwk_direct_kernel: xf is the hi (ks = 0) / lo (ks = 1) plane of x
-                const char* wh = ws - ks * 64;
-                U4H8 wl[4];
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(wh + (g * 64 + nt * 16) * ROWB);
-                if (ks == 0) {
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) wl[nt].u = *reinterpret_cast<const uint4*>(wh + 64 + (g * 64 + nt * 16) * ROWB);
-                }
-                if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                    for (int p = 0; p < PT; ++p) {
-                        if (ks == 0) acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
-                        acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
-                    }
-                if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-                continue;
-            }
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) wf[nt].u = *reinterpret_cast<const uint4*>(ws + (g * 64 + nt * 16) * ROWB);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    acc[g][p][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt].h, xf[p].h, acc[g][p][nt], 0, 0, 0);
-            if (VIP_MFMA_PRIO) __builtin_amdgcn_s_setprio(0);
-        }
+        pw_mfma_step<NG, PT, ROWB>(acc, ws, xf, ks);
     };
 
     // The next chunk's weights and activations are requested (global -> VGPR) before this chunk's math and written to
@@ -1740,52 +1561,26 @@ __global__ __launch_bounds__(256 * WN, WN == 1 ? 2 : 1) void pwk_gemm_kernel(Con
         __syncthreads();
     }
 
-    // opaque to the optimiser: otherwise the epilogue's address arithmetic is hoisted above the k-loop and its
-    // ~20 registers stay live through it (the loop is at the 256-VGPR limit of two waves per SIMD)
     int m_base = m0 + l15, n_lane = n0 + lq * 8;
-    asm volatile("" : "+v"(m_base), "+v"(n_lane));
-    // (not a loop over g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be
-    // indexed dynamically, i.e. live in scratch)
-    auto epi = [&](auto gtag) {
-        constexpr int G_ = decltype(gtag)::value;
-        const int n_first = n_lane + G_ * 64;
-        switch (mode) {
-            case 1: pw_epilogue<PT, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 2: pw_epilogue<PT, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 3: pw_epilogue<PT, VIP_ACT_GELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 4: pw_epilogue<PT, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 5: pw_epilogue<PT, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            case 6: pw_epilogue<PT, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            default: pw_epilogue<PT, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-        }
+    asm volatile("" : "+v"(m_base), "+v"(n_lane));      // (as in pwk_direct_kernel)
+    pw_epilogue_groups<NG, PT>(mode, a, acc, m_base, n_lane, rb.res, rb.y);
+}
+
+// Y2: the two-output instantiations of the output-gated epilogue (y2: the second output)
+template <int NG, bool Y2 = false>
+int launch_pwk_direct(const ConvArgs& a, const Plan& p, hipStream_t s, f16* y2 = nullptr) {
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, kernel_args<Y2>(a, y2), (int)p.mode);
     };
-    epi(std::integral_constant<int, 0>{});
-    if constexpr (NG > 1) epi(std::integral_constant<int, 1>{});
+    if constexpr (Y2) {
+        if (p.pt == 1) go(pwk_direct_kernel<NG, false, 1, true>);
+        else go(pwk_direct_kernel<NG, false, 4, true>);
+    } else {
+        if (p.pt == 1) p.gated ? go(pwk_direct_kernel<NG, true, 1>) : go(pwk_direct_kernel<NG, false, 1>);
+        else p.gated ? go(pwk_direct_kernel<NG, true, 4>) : go(pwk_direct_kernel<NG, false, 4>);
+    }
+    return vip_launch_status(Y2 ? "vip_conv2d_out_gated2_nhwc_f16(pwk-direct)" : "vip_conv2d_nhwc_f16(pwk-direct)");
 }
-
-template <int NG>
-int launch_pwk_direct(const ConvArgs& a, const Plan& p, hipStream_t s) {
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, a, p.mode); };
-    if (p.pt == 1) p.gated ? go(pwk_direct_kernel<NG, true, 1>) : go(pwk_direct_kernel<NG, false, 1>);
-#if VIP_BUILD_EXPERIMENTS
-    else if (p.pf2) go(pwk_direct2_kernel<NG>);
-#endif
-    else p.gated ? go(pwk_direct_kernel<NG, true, 4>) : go(pwk_direct_kernel<NG, false, 4>);
-    return vip_launch_status("vip_conv2d_nhwc_f16(pwk-direct)");
-}
-
-#if !VIP_GEMM_H2
-template <int NG>
-int launch_pwk_direct_og2(const ConvArgs& a, const Plan& p, f16* y2, hipStream_t s) {
-    ConvArgs2 a2;
-    static_cast<ConvArgs&>(a2) = a;
-    a2.y2 = y2;
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)(a.m_blocks * a.n_blocks)), dim3(256), 0, s, a2, p.mode); };
-    if (p.pt == 1) go(pwk_direct_kernel<NG, false, 1, true>);
-    else go(pwk_direct_kernel<NG, false, 4, true>);
-    return vip_launch_status("vip_conv2d_out_gated2_nhwc_f16(pwk-direct)");
-}
-#endif
 
 // IM2COL: the k x k form, one grid plane per group (the pointwise form is ungrouped)
 template <int NG, int WN, bool IM2COL>
@@ -1981,7 +1776,7 @@ int launch_igemm(const ConvArgs& a, int groups, hipStream_t s) {
 }  // namespace
 
 // ---- selection: which kernel, which template arguments, which tile grid.  Host code alone - every threshold and every selection
-// switch of the environment is read here (static: once per process; VIP_G8P_MINK, VIP_PWX, VIP_PWK_PF2 and VIP_LN_GEMM_ALL per call:
+// switch of the environment is read here (static: once per process; VIP_G8P_MINK, VIP_PWX and VIP_LN_GEMM_ALL per call:
 // their tests set them mid-process), and the selection's VIP_ERR_UNSUPPORTED exits are here (those of the argument checks stay in front).
 static void plan_blocks(Plan& p, const ConvArgs& a, int bm, int bn) {
     p.m_blocks = (a.M + bm - 1) / bm;
@@ -2026,11 +1821,6 @@ static int plan_pwk_direct(Plan& p, const ConvArgs& a) {
     static const int fill = getenv("VIP_PWK_FILL") ? atoi(getenv("VIP_PWK_FILL")) : 256;
     const long wg256 = (long)((a.M + 255) / 256) * ((a.Cout_g + 64 * p.ng - 1) / (64 * p.ng));
     p.pt = wg256 < fill ? 1 : 4;
-#if VIP_BUILD_EXPERIMENTS
-    if (p.pt == 4 && !a.gate && getenv("VIP_PWK_PF2") && atoi(getenv("VIP_PWK_PF2"))) {     // the two-chunks-ahead experiment (read per call)
-        p.pf2 = true; p.pt = 2;       // pwk_direct2_kernel's 128-pixel block tile
-    }
-#endif
     plan_blocks(p, a, 64 * p.pt, 64 * p.ng);
     return VIP_OK;
 }
@@ -2046,15 +1836,14 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
     const long M = a.M;
     const int cin_g = d->Cin / d->groups, cout_g = a.Cout_g;
     const bool residual = a.res, gate = a.gate, w_lo = a.w_lo;
-    // epilogue variants the pointwise kernels carry: act_pre alone, or residual (+ post-ReLU) with no act_pre
-    int mode = -1;
-    if (!residual && d->act_post == VIP_ACT_NONE) mode = d->act_pre;
-    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = 5;
-    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = 6;
+    EpiMode mode = EPI_OTHER;
+    if (!residual && d->act_post == VIP_ACT_NONE) mode = (EpiMode)d->act_pre;
+    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_NONE) mode = EPI_RES;
+    else if (residual && d->act_pre == VIP_ACT_NONE && d->act_post == VIP_ACT_RELU) mode = EPI_RES_RELU;
     p.mode = mode;
 #if !VIP_GEMM_H2
     if (a.ln_g) {     // vip_ln_gemm_bias_act_f16: the one kernel with the LayerNorm prologue, no fall-back (a missing kernel is an error)
-        VIP_REQUIRE(mode >= 0 && a.ln_b && !w_lo && !gate && !a.y_lo_off && !x_split && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 &&
+        VIP_REQUIRE(mode != EPI_OTHER && a.ln_b && !w_lo && !gate && !a.y_lo_off && !x_split && d->groups == 1 && d->kh == 1 && d->kw == 1 && d->sh == 1 &&
                         d->sw == 1 && d->pt == 0 && d->pl == 0 && d->Ho == d->H && d->Wo == d->W && d->cin_off == 0 &&
                         vip_ln_gemm_supported((int)M, a.K, cout_g, d->act_pre) && a.x_span_bytes < 0xFFFF0000L - 2L * a.K,
                     VIP_ERR_UNSUPPORTED,
@@ -2081,7 +1870,7 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
             return VIP_OK;
         }
         if (w_lo) {     // hi + lo weights: the streaming kernel is the one that carries them (any M)
-            VIP_REQUIRE(mode >= 0 && short_k && !gate && !a.y_lo_off, VIP_ERR_UNSUPPORTED,
+            VIP_REQUIRE(mode != EPI_OTHER && short_k && !gate && !a.y_lo_off, VIP_ERR_UNSUPPORTED,
                         "vip_conv2d_hilo_nhwc_f16: 1x1 stride-1 ungrouped, K <= 256, (activation) or (residual [+ReLU]) epilogue");
             return plan_pw(p, a);
         }
@@ -2091,20 +1880,20 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
             return VIP_OK;
         }
         VIP_REQUIRE(!a.y_lo_off && !x_split, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: at most 256 rows, N %% 4 == 0");
-        if (mode >= 0 && (pw_mode & 1) && short_k && M >= 65536 && !gate) return plan_pw(p, a);
+        if (mode != EPI_OTHER && (pw_mode & 1) && short_k && M >= 65536 && !gate) return plan_pw(p, a);
         // deep K, wide N: the LDS-DMA kernel (gemm8p.hpp).  VIP_G8P_MINK: smallest K it takes (0 = never).  1024: in isolation it
         // wins from K = 256 up (+6..+27 %), but it owns a CU (128 KB of LDS, 8 waves x 256 VGPRs, persistent) and the ensemble step
         // runs three member streams - with the K = 256-768 layers on it the STEP was 1.5-2 % slower (58.2 ms vs 57.1-57.4,
         // alternating runs on one box, profiles/r02_gemm8p_mink_streams_ab.log) and a single stream gained nothing either.
         const char* g8_env = getenv("VIP_G8P_MINK");     // read per call: the kernel's own tests lower it
         const int g8_min_k = g8_env ? atoi(g8_env) : 1024;
-        if (mode >= 0 && g8_min_k > 0 && !gate && a.K >= g8_min_k && gemm8p_eligible(a) && cout_g % 256 == 0 &&
+        if (mode != EPI_OTHER && g8_min_k > 0 && !gate && a.K >= g8_min_k && gemm8p_eligible(a) && cout_g % 256 == 0 &&
             (long)((M + 255) / 256) * (cout_g / 256) >= 128) {
             p.family = GEMM8P; p.pipe = a.K % 128 == 0;
             plan_blocks(p, a, 256, 256);
             return VIP_OK;
         }
-        if (mode >= 0 && (pw_mode & 2) && a.x_span_bytes < 0xFFFFFFF0L) {
+        if (mode != EPI_OTHER && (pw_mode & 2) && a.x_span_bytes < 0xFFFFFFF0L) {
             // (a 64 x 256 wave tile at one wave per SIMD - NG = 4 - measured 15-40 % slower than NG = 2 at two)
             static const int xl_min_k = getenv("VIP_PWK_XLK") ? atoi(getenv("VIP_PWK_XLK")) : 768;
             // (gated convolutions: only the direct kernel carries the gate pipeline - their deep-K cases are small launches)
@@ -2139,7 +1928,7 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
         // (ResNeSt's grouped 3x3: 585 -> 726, 721 -> 853 TF), except the 7 x 7-pixel stages (M = 12 544: 637 -> 497 TF),
         // which keep the tile kernel.  VIP_PWK_CONV: 1 = every eligible conv (tests), -1 = stems only.
         static const int im2col_all = getenv("VIP_PWK_CONV") ? atoi(getenv("VIP_PWK_CONV")) : 0;
-        if ((cin_g <= 16 || im2col_all > 0 || (im2col_all == 0 && M >= 32768)) && mode >= 0 && !gate && a.x_span_bytes < 0xFFFFFFF0L && d->H < 30000 &&
+        if ((cin_g <= 16 || im2col_all > 0 || (im2col_all == 0 && M >= 32768)) && mode != EPI_OTHER && !gate && a.x_span_bytes < 0xFFFFFFF0L && d->H < 30000 &&
             d->W < 30000 && d->pt < 16 && d->pl < 16) {
             p.family = IM2COL; p.ng = cout_g <= 64 ? 1 : 2;
             plan_blocks(p, a, 256, 64 * p.ng);
@@ -2157,28 +1946,21 @@ static int plan(const ConvArgs& a, const vip_conv_desc* d, bool x_split, Plan* o
 
 // ---- launch: the plan's instantiation.  What is read here depends on the device or changes nothing in the selection: the CU count that
 // caps the persistent grids, VIP_G8P_PERSIST, the once-per-kernel dynamic-LDS attributes.
-// y2: the second output of vip_conv2d_out_gated2_nhwc_f16 (modes 7 / 8 alone: the two-output instantiations), else NULL
+// y2: the second output of vip_conv2d_out_gated2_nhwc_f16, else NULL - it exists in the output-gated instantiations of two families alone
 static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s, f16* y2 = nullptr) {
     a.m_blocks = p.m_blocks; a.n_blocks = p.n_blocks;
-#if !VIP_GEMM_H2
-    if (y2) {
-        if (p.mode < 7) return (int)VIP_ERR_UNSUPPORTED;
-        if (p.family == PW_GEMM)
-            return with_const<1, 2, 3, 4>(p.ks, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                return p.hilo ? launch_pw_og2<KS, 4, true>(a, p, y2, s) : launch_pw_og2<KS, 4, false>(a, p, y2, s);
-            });
-        if (p.family == PWK_DIRECT) return p.ng == 1 ? launch_pwk_direct_og2<1>(a, p, y2, s) : launch_pwk_direct_og2<2>(a, p, y2, s);
-        return (int)VIP_ERR_UNSUPPORTED;
-    }
-#endif
+    const bool og = epi_out_gated(p.mode);
+    if (y2 && !(og && (p.family == PW_GEMM || p.family == PWK_DIRECT))) return VIP_ERR_UNSUPPORTED;
     switch (p.family) {
         case PW_GEMM:
             return with_const<1, 2, 3, 4, 6, 8>(p.ks, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value;
                 if constexpr (!H2 && KS <= 4)       // (K > 128: the gated epilogue would spill - conv2d_plan declines)
-                    if (p.mode >= 7) return p.hilo ? launch_pw<KS, 4, true, true>(a, p, s) : launch_pw<KS, 4, false, true>(a, p, s);
-                if (p.mode >= 7) return (int)VIP_ERR_UNSUPPORTED;
+                    if (og) {
+                        if (y2) return p.hilo ? launch_pw<KS, 4, true, true, true>(a, p, s, y2) : launch_pw<KS, 4, false, true, true>(a, p, s, y2);
+                        return p.hilo ? launch_pw<KS, 4, true, true>(a, p, s) : launch_pw<KS, 4, false, true>(a, p, s);
+                    }
+                if (og) return (int)VIP_ERR_UNSUPPORTED;
                 return p.hilo ? launch_pw<KS, 4, true>(a, p, s) : launch_pw<KS, 4, false>(a, p, s);
             });
         case ROWS_GEMM:
@@ -2192,7 +1974,11 @@ static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s, f16* y2 
 #endif
             if (p.pt == 2) return with_const<2, 3, 4>(p.ksc, [&](auto ksc) { return launch_pwx<decltype(ksc)::value, 2, false>(a, p.mode, s); });
             return with_const<6, 8>(p.ksc, [&](auto ksc) { return launch_pwx<decltype(ksc)::value, 1, false>(a, p.mode, s); });
-        case PWK_DIRECT: return p.ng == 1 ? launch_pwk_direct<1>(a, p, s) : launch_pwk_direct<2>(a, p, s);
+        case PWK_DIRECT:
+#if !VIP_GEMM_H2
+            if (y2) return p.ng == 1 ? launch_pwk_direct<1, true>(a, p, s, y2) : launch_pwk_direct<2, true>(a, p, s, y2);
+#endif
+            return p.ng == 1 ? launch_pwk_direct<1>(a, p, s) : launch_pwk_direct<2>(a, p, s);
         case PWK_GEMM:
             if (p.ng == 1) return launch_pwk<1, 1, false>(a, p.mode, groups, s);
             return p.wn == 1 ? launch_pwk<2, 1, false>(a, p.mode, groups, s) : launch_pwk<2, 2, false>(a, p.mode, groups, s);
@@ -2204,10 +1990,40 @@ static int launch(const Plan& p, ConvArgs a, int groups, hipStream_t s, f16* y2 
     return VIP_ERR_UNSUPPORTED;
 }
 
+// One call as its entry point states it: the operands every call has, and whatever else that entry point means (the rest keeps its default)
+struct ConvCall {
+    const void* x = nullptr;
+    const void* w = nullptr;
+    const float* bias = nullptr;
+    const void* residual = nullptr;
+    void* y = nullptr;
+    const vip_conv_desc* d = nullptr;
+    const void* gate = nullptr;         // per-image input-channel gate (ConvArgs::gate)
+    int y_lo_off = 0;                   // split output (ConvArgs::y_lo_off)
+    const void* w_lo = nullptr;         // second weight term
+    bool x_split = false;               // the rows are [M][2][K]: a hi and a lo plane
+    float out_scale = 1.f;              // packed storage: 1 / the weights' scale
+    int* status = nullptr;              // packed storage: the overflow word
+    const float* ln_g = nullptr;        // LayerNorm over the input row (pwx_ln_kernel)
+    const float* ln_b = nullptr;
+    float ln_eps = 0.f;
+    const void* out_gate = nullptr;     // per-image output-channel gate (ConvArgs::ogate)
+    void* y2 = nullptr;                 // second output of the output-gated epilogue
+};
+static ConvCall conv_call(const void* x, const void* w, const float* bias, const void* residual, void* y, const vip_conv_desc* d) {
+    ConvCall c;
+    c.x = x; c.w = w; c.bias = bias; c.residual = residual; c.y = y; c.d = d;
+    return c;
+}
+
 // the argument checks, the kernel arguments and the plan of one call
-static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
-                       const vip_conv_desc* d, const void* w_lo, bool x_split, float out_scale, int* status, const float* ln_g,
-                       const float* ln_b, float ln_eps, ConvArgs* args, Plan* p, const void* out_gate = nullptr) {
+static int conv2d_plan(const ConvCall& c, ConvArgs* args, Plan* p) {
+    const void *x = c.x, *w = c.w, *residual = c.residual, *gate = c.gate, *w_lo = c.w_lo, *out_gate = c.out_gate;
+    void* y = c.y;
+    const vip_conv_desc* d = c.d;
+    const int y_lo_off = c.y_lo_off;
+    const bool x_split = c.x_split;
+    const float* ln_g = c.ln_g;
     VIP_REQUIRE(x && w && y && d, VIP_ERR_BAD_ARG, "vip_conv2d_nhwc_f16: null pointer");
     VIP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kh > 0 && d->kw > 0 &&
                     d->sh > 0 && d->sw > 0 && d->Ho > 0 && d->Wo > 0 && d->groups > 0 && d->pt >= 0 && d->pl >= 0,
@@ -2233,7 +2049,7 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
     VIP_REQUIRE(M < (1L << 31) - 256, VIP_ERR_UNSUPPORTED, "vip_conv2d_nhwc_f16: B*Ho*Wo too large");
 
     ConvArgs& a = *args;
-    a.x = (const f16*)x; a.w = (const f16*)w; a.bias = bias; a.res = (const f16*)residual; a.y = (f16*)y;
+    a.x = (const f16*)x; a.w = (const f16*)w; a.bias = c.bias; a.res = (const f16*)residual; a.y = (f16*)y;
     a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo;
     // the INPUT side in halfs (H2: twice the logical channels - see the head of this file), the output side in logical channels
     a.Cin_g = cin_g * IN; a.Cout_g = cout_g;
@@ -2245,8 +2061,8 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
     a.y_span_bytes = (long)ESZ * M * d->ldy;
     a.res_span_bytes = (long)ESZ * M * d->ldr;
     a.bias_elems = d->Cout;
-    a.out_scale = out_scale;
-    a.status = status;
+    a.out_scale = c.out_scale;
+    a.status = c.status;
     VIP_REQUIRE(a.y_span_bytes < 0xFFFFFFE0L && a.res_span_bytes < 0xFFFFFFE0L, VIP_ERR_UNSUPPORTED,
                 "vip_conv2d_nhwc_f16: output or residual tensor exceeds the 4 GiB buffer-addressing range");
     VIP_REQUIRE(a.x_span_bytes < 0xFFFFFFF0L && 2L * d->Cout * d->ldw < 0xFFFFFFF0L, VIP_ERR_UNSUPPORTED,
@@ -2257,7 +2073,7 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
     a.gate = (const f16*)gate;
     a.gate_hw = d->Ho * d->Wo;
     a.y_lo_off = y_lo_off;
-    a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
+    a.ln_g = ln_g; a.ln_b = c.ln_b; a.ln_eps = c.ln_eps;
     a.ogate = (const f16*)out_gate;
     a.ogate_elems = 0;
     a.hw_magic = a.gate_hw > 1 ? (unsigned)((1L << 32) / a.gate_hw) : 0xFFFFFFFFu;
@@ -2276,22 +2092,19 @@ static int conv2d_plan(const void* x, const void* gate, int y_lo_off, const void
     // weight stages, 80 of them.)
     const bool pw_ok = p->family == PW_GEMM && p->ks <= 4 && 63 / a.gate_hw + 2 <= 4 &&
                        (size_t)p->nb_ch * (p->lds_stride + 4) + pw_og_lds(p->nb_ch) <= 80 * 1024;
-    const bool pwk_ok = p->family == PWK_DIRECT && !p->gated && !p->pf2 && (64 * p->pt - 1) / a.gate_hw + 2 <= 80;
-    VIP_REQUIRE((p->mode == 5 || p->mode == 6) && (pw_ok || pwk_ok), VIP_ERR_UNSUPPORTED,
+    const bool pwk_ok = p->family == PWK_DIRECT && !p->gated && (64 * p->pt - 1) / a.gate_hw + 2 <= 80;
+    VIP_REQUIRE((p->mode == EPI_RES || p->mode == EPI_RES_RELU) && (pw_ok || pwk_ok), VIP_ERR_UNSUPPORTED,
                 "vip_conv2d_out_gated_nhwc_f16: this shape's kernel carries no output gate (pw_gemm_kernel up to K = 128 and "
                 "pwk_direct_kernel do)");
-    p->mode += 2;
+    p->mode = p->mode == EPI_RES ? EPI_OGATE_RES : EPI_OGATE_RES_RELU;
     return VIP_OK;
 }
 
-static int conv2d_impl(const void* x, const void* gate, int y_lo_off, const void* w, const float* bias, const void* residual, void* y,
-                       const vip_conv_desc* d, void* stream, const void* w_lo = nullptr, bool x_split = false, float out_scale = 1.f,
-                       int* status = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
-                       const void* out_gate = nullptr, void* y2 = nullptr) {
+static int conv2d_impl(const ConvCall& c, void* stream) {
     ConvArgs a;
     Plan p;
-    const int st = conv2d_plan(x, gate, y_lo_off, w, bias, residual, y, d, w_lo, x_split, out_scale, status, ln_g, ln_b, ln_eps, &a, &p, out_gate);
-    return st != VIP_OK ? st : launch(p, a, d->groups, (hipStream_t)stream, (f16*)y2);
+    const int st = conv2d_plan(c, &a, &p);
+    return st != VIP_OK ? st : launch(p, a, c.d->groups, (hipStream_t)stream, (f16*)c.y2);
 }
 
 // vip_conv2d_kernel_name[_h2] / vip_conv2d_kernel_variant[_h2]: a dry run - the checks and the plan of the call the flags describe, and
@@ -2302,8 +2115,11 @@ static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, i
     static const char dummy[16] = {0};     // non-null stand-ins: nothing is dereferenced or launched in a dry run
     ConvArgs a;
     Plan p;
-    const int st = conv2d_plan(dummy, has_gate ? dummy : nullptr, 0, dummy, nullptr, has_residual ? dummy : nullptr, const_cast<char*>(dummy), d,
-                               has_w_lo ? dummy : nullptr, false, 1.f, nullptr, nullptr, nullptr, 0.f, &a, &p, out_gate ? dummy : nullptr);
+    ConvCall c = conv_call(dummy, dummy, nullptr, has_residual ? dummy : nullptr, const_cast<char*>(dummy), d);
+    if (has_gate) c.gate = dummy;
+    if (has_w_lo) c.w_lo = dummy;
+    if (out_gate) c.out_gate = dummy;
+    const int st = conv2d_plan(c, &a, &p);
     if (st != VIP_OK) return st;
     static const char* const kernel[] = {"pw_gemm_kernel",    "rows_gemm_kernel", "gemm8p_kernel",           "pwx_kernel",
                                          "pwk_direct_kernel", "pwk_gemm_kernel",  "pwk_gemm_kernel(im2col)", "conv_igemm_kernel"};
@@ -2312,13 +2128,12 @@ static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, i
         return VIP_OK;
     }
     switch (p.family) {
-        case PW_GEMM: snprintf(out, cap, "pw_gemm<KS=%d%s> %d x %d%s", p.ks, p.hilo ? ",hilo" : "", p.n_chunks, p.nb_ch, p.mode >= 7 ? " ogate" : ""); break;
+        case PW_GEMM: snprintf(out, cap, "pw_gemm<KS=%d%s> %d x %d%s", p.ks, p.hilo ? ",hilo" : "", p.n_chunks, p.nb_ch, epi_out_gated(p.mode) ? " ogate" : ""); break;
         case ROWS_GEMM: snprintf(out, cap, "rows_gemm%s", p.xsplit ? "<xsplit>" : ""); break;
         case GEMM8P: snprintf(out, cap, "gemm8p<%s> %d x %d", p.pipe ? "pipe" : "basic", p.m_blocks, p.n_blocks); break;
         case PWX: snprintf(out, cap, "%s<%d,%d>", p.ln ? "pwx_ln" : "pwx", p.ksc, p.pt); break;
         case PWK_DIRECT:
-            if (p.pf2) snprintf(out, cap, "pwk_direct2<%d>", p.ng);
-            else snprintf(out, cap, "pwk_direct<%d%s> PT=%d%s", p.ng, p.gated ? ",gated" : "", p.pt, p.mode >= 7 ? " ogate" : "");
+            snprintf(out, cap, "pwk_direct<%d%s> PT=%d%s", p.ng, p.gated ? ",gated" : "", p.pt, epi_out_gated(p.mode) ? " ogate" : "");
             break;
         case PWK_GEMM: snprintf(out, cap, "pwk_gemm<%d,%d> %d x %d", p.ng, p.wn, p.m_blocks, p.n_blocks); break;
         case IM2COL: snprintf(out, cap, "im2col<%d>", p.ng); break;
@@ -2333,7 +2148,9 @@ static int kernel_query(const char* who, bool variant, const vip_conv_desc* d, i
 extern "C" int vip_conv2d_nhwc_h2(const void* x, const void* w, const float* bias, const void* residual, void* y, const vip_conv_desc* d,
                                   float out_scale, int* status, void* stream) {
     VIP_REQUIRE(out_scale > 0.f, VIP_ERR_BAD_ARG, "vip_conv2d_nhwc_h2: out_scale must be positive");
-    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream, nullptr, false, out_scale, status);
+    ConvCall c = conv_call(x, w, bias, residual, y, d);
+    c.out_scale = out_scale; c.status = status;
+    return conv2d_impl(c, stream);
 }
 
 /* The same with a squeeze-excite gate folded into the activation operand: gate packed [B][Cin]; the product (x_hi + x_lo)(g_hi + g_lo) is
@@ -2345,7 +2162,9 @@ extern "C" int vip_conv2d_gated_nhwc_h2(const void* x, const void* gate, const v
     VIP_REQUIRE(out_scale > 0.f, VIP_ERR_BAD_ARG, "vip_conv2d_gated_nhwc_h2: out_scale must be positive");
     VIP_REQUIRE(d && d->cin_off == 0 && d->ldx == d->Cin, VIP_ERR_UNSUPPORTED,
                 "vip_conv2d_gated_nhwc_h2: the gate indexes the whole input channel axis (cin_off = 0, ldx = Cin)");
-    return conv2d_impl(x, gate, 0, w, bias, residual, y, d, stream, nullptr, false, out_scale, status);
+    ConvCall c = conv_call(x, w, bias, residual, y, d);
+    c.gate = gate; c.out_scale = out_scale; c.status = status;
+    return conv2d_impl(c, stream);
 }
 
 extern "C" int vip_conv2d_kernel_name_h2(const vip_conv_desc* d, int has_residual, char* name, size_t cap) {
@@ -2358,7 +2177,7 @@ extern "C" int vip_conv2d_kernel_variant_h2(const vip_conv_desc* d, int has_resi
 #else
 extern "C" int vip_conv2d_nhwc_f16(const void* x, const void* w, const float* bias, const void* residual, void* y,
                                    const vip_conv_desc* d, void* stream) {
-    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream);
+    return conv2d_impl(conv_call(x, w, bias, residual, y, d), stream);
 }
 
 extern "C" int vip_conv2d_gated_nhwc_f16(const void* x, const void* gate, const void* w, const float* bias,
@@ -2366,13 +2185,17 @@ extern "C" int vip_conv2d_gated_nhwc_f16(const void* x, const void* gate, const 
     VIP_REQUIRE(gate, VIP_ERR_BAD_ARG, "vip_conv2d_gated_nhwc_f16: null gate");
     VIP_REQUIRE(d && d->cin_off == 0 && d->ldx == d->Cin, VIP_ERR_UNSUPPORTED,
                 "vip_conv2d_gated_nhwc_f16: the gate indexes the whole input channel axis (cin_off = 0, ldx = Cin)");
-    return conv2d_impl(x, gate, 0, w, bias, residual, y, d, stream);
+    ConvCall c = conv_call(x, w, bias, residual, y, d);
+    c.gate = gate;
+    return conv2d_impl(c, stream);
 }
 
 extern "C" int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const void* w_lo, const float* bias,
                                         const void* residual, void* y, const vip_conv_desc* d, void* stream) {
     VIP_REQUIRE(w_lo, VIP_ERR_BAD_ARG, "vip_conv2d_hilo_nhwc_f16: null w_lo");
-    return conv2d_impl(x, nullptr, 0, w_hi, bias, residual, y, d, stream, w_lo);
+    ConvCall c = conv_call(x, w_hi, bias, residual, y, d);
+    c.w_lo = w_lo;
+    return conv2d_impl(c, stream);
 }
 
 /* y = act_post(conv(x) * g + residual), g = hi + lo of out_gate [B][2][Cout] fp16 (vip_se_gate_f16 with split): the squeeze-excite
@@ -2381,7 +2204,9 @@ extern "C" int vip_conv2d_hilo_nhwc_f16(const void* x, const void* w_hi, const v
 extern "C" int vip_conv2d_out_gated_nhwc_f16(const void* x, const void* w, const void* w_lo, const float* bias, const void* out_gate,
                                              const void* residual, void* y, const vip_conv_desc* d, void* stream) {
     VIP_REQUIRE(out_gate && residual, VIP_ERR_BAD_ARG, "vip_conv2d_out_gated_nhwc_f16: null gate or residual");
-    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream, w_lo, false, 1.f, nullptr, nullptr, nullptr, 0.f, out_gate);
+    ConvCall c = conv_call(x, w, bias, residual, y, d);
+    c.w_lo = w_lo; c.out_gate = out_gate;
+    return conv2d_impl(c, stream);
 }
 
 /* dry run of vip_conv2d_out_gated_nhwc_f16: VIP_OK and the instantiation ("pw_gemm<KS=2,hilo> 1 x 256 ogate") where the call is taken */
@@ -2396,7 +2221,9 @@ extern "C" int vip_conv2d_out_gated2_nhwc_f16(const void* x, const void* w, cons
                                               const void* residual, void* y, void* y2, int act2, const vip_conv_desc* d, void* stream) {
     VIP_REQUIRE(out_gate && residual && y2, VIP_ERR_BAD_ARG, "vip_conv2d_out_gated2_nhwc_f16: null gate, residual or second output");
     VIP_REQUIRE(act2 == VIP_ACT_SILU, VIP_ERR_UNSUPPORTED, "vip_conv2d_out_gated2_nhwc_f16: act2=%d (the second output is built for SiLU)", act2);
-    return conv2d_impl(x, nullptr, 0, w, bias, residual, y, d, stream, w_lo, false, 1.f, nullptr, nullptr, nullptr, 0.f, out_gate, y2);
+    ConvCall c = conv_call(x, w, bias, residual, y, d);
+    c.w_lo = w_lo; c.out_gate = out_gate; c.y2 = y2;
+    return conv2d_impl(c, stream);
 }
 
 /* dry run of vip_conv2d_out_gated2_nhwc_f16: the one-output call's selection with " y2" behind it ("pwk_direct<2> PT=4 ogate y2") */
@@ -2462,14 +2289,18 @@ extern "C" int vip_ln_gemm_bias_act_f16(const void* A, const float* ln_gamma, co
     VIP_REQUIRE(ln_gamma && ln_beta, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: null LayerNorm parameters");
     VIP_REQUIRE(ln_eps > 0.f, VIP_ERR_BAD_ARG, "vip_ln_gemm_bias_act_f16: eps must be positive");
     const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, ldc, ldr, act_pre, act_post);
-    return conv2d_impl(A, nullptr, 0, W, bias, residual, C, &d, stream, nullptr, false, 1.f, nullptr, ln_gamma, ln_beta, ln_eps);
+    ConvCall c = conv_call(A, W, bias, residual, C, &d);
+    c.ln_g = ln_gamma; c.ln_b = ln_beta; c.ln_eps = ln_eps;
+    return conv2d_impl(c, stream);
 }
 
 extern "C" int vip_gemm_split_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda,
                                   int ldw, int act, void* stream) {
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split_f16: M=%d (1..256 rows)", M);
     const vip_conv_desc d = gemm_desc(M, N, K, lda, ldw, 2 * N, 0, act, VIP_ACT_NONE);
-    return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream);
+    ConvCall c = conv_call(A, W, bias, nullptr, C, &d);
+    c.y_lo_off = N;
+    return conv2d_impl(c, stream);
 }
 
 extern "C" int vip_gemm_split2_hilo_f16(const void* A, const void* W, const void* W_lo, const float* bias, void* C, int M, int N, int K,
@@ -2478,7 +2309,9 @@ extern "C" int vip_gemm_split2_hilo_f16(const void* A, const void* W, const void
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split2_hilo_f16: M=%d (1..256 rows)", M);
     VIP_REQUIRE(K % 8 == 0, VIP_ERR_ALIGNMENT, "vip_gemm_split2_hilo_f16: K must be a multiple of 8");
     const vip_conv_desc d = gemm_desc(M, N, K, 2 * K, ldw, 2 * N, 0, act, VIP_ACT_NONE);
-    return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream, W_lo, true);
+    ConvCall c = conv_call(A, W, bias, nullptr, C, &d);
+    c.y_lo_off = N; c.w_lo = W_lo; c.x_split = true;
+    return conv2d_impl(c, stream);
 }
 
 extern "C" int vip_gemm_split2_f16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int ldw, int act,
@@ -2486,6 +2319,8 @@ extern "C" int vip_gemm_split2_f16(const void* A, const void* W, const float* bi
     VIP_REQUIRE(M > 0 && M <= 256, VIP_ERR_UNSUPPORTED, "vip_gemm_split2_f16: M=%d (1..256 rows)", M);
     VIP_REQUIRE(K % 8 == 0, VIP_ERR_ALIGNMENT, "vip_gemm_split2_f16: K must be a multiple of 8");
     const vip_conv_desc d = gemm_desc(M, N, K, 2 * K, ldw, 2 * N, 0, act, VIP_ACT_NONE);
-    return conv2d_impl(A, nullptr, N, W, bias, nullptr, C, &d, stream, nullptr, true);
+    ConvCall c = conv_call(A, W, bias, nullptr, C, &d);
+    c.y_lo_off = N; c.x_split = true;
+    return conv2d_impl(c, stream);
 }
 #endif  // VIP_GEMM_H2

@@ -1,6 +1,7 @@
 // Deep-K pointwise GEMM for gfx950: 256 pixels x 256 channels x 64 k block tiles, 8 waves, LDS-DMA staging with counted
 // vmcnt across raw barriers, four MFMA phases per k-tile.  Included by conv_igemm.hip (inside its anonymous namespace, after
-// ConvArgs / pw_epilogue); used for 1x1 stride-1 ungrouped convolutions / Dense layers with K % 64 == 0, K >= 384.
+// ConvArgs, xcd_remap and pw_epilogue_groups, which it shares with the other pointwise kernels); used for 1x1 stride-1 ungrouped
+// convolutions / Dense layers with K % 64 == 0, K >= 384.
 //
 // Why a separate kernel: in pwk_gemm_kernel a wave visits the MFMA pipe, the LDS pipe (fragment reads + staging writes) and
 // the vector-memory pipe (register staging) one after the other per 64-k chunk - three pipes of about equal load, ~30 % of
@@ -62,15 +63,10 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(ConvArgs a, int mode) {
     // (Measured: m-minor order and an XCD grid that splits the n-blocks so that each XCD keeps half of the weights are within
     // +-3 % of this order on every ensemble shape - the kernel is not L2-capacity bound.)
     const int n_tiles = a.m_blocks * a.n_blocks;
-    int tile;
-    {
-        const int bid = blockIdx.x, nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int tile_step = gridDim.x;
 
+    // (gemm8p_kernel: its own descriptors, not pw_buffers - rw / rx go without the 4 GiB clamp: gemm8p_eligible keeps the spans below 2 GiB)
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, (unsigned)(2L * a.Cout_g * a.ldw), 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + a.cin_off), 0,
                                                                         (unsigned)(a.x_span_bytes - 2L * a.cin_off), 0x00020000);
@@ -207,7 +203,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(ConvArgs a, int mode) {
     issue_prologue();
     while (true) {
         f32x4 acc[2][4][4];
-        {   // bias is the C operand of the first MFMA of every accumulator.  These are ordinary loads: hipcc waits vmcnt(0) before
+        {   // bias is the C operand of the first MFMA of every accumulator (gemm8p_kernel: a copy, see pwk_direct_kernel).  These are ordinary loads: hipcc waits vmcnt(0) before
             // their first use, which also retires the prologue DMA issued ahead of them - wanted here, the tile starts right after.
             const int n0 = nblk + wn * 128;
 #pragma unroll
@@ -320,23 +316,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(ConvArgs a, int mode) {
             setup_tile(tile);
             issue_prologue();                               // every wave is past the k-loop's last barrier: no fragment read is pending
         }
-        // (not a loop over g: with the packed-storage epilogue inlined seven times the unroller gives up and the accumulators would be
-        // indexed dynamically, i.e. live in scratch)
-        auto epi = [&](auto gtag) {
-            constexpr int G_ = decltype(gtag)::value;
-            const int n_first = n_lane + G_ * 64;
-            switch (mode) {
-                case 1: pw_epilogue<4, VIP_ACT_RELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 2: pw_epilogue<4, VIP_ACT_SILU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 3: pw_epilogue<4, VIP_ACT_GELU, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 4: pw_epilogue<4, VIP_ACT_SIGMOID, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 5: pw_epilogue<4, VIP_ACT_NONE, true, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                case 6: pw_epilogue<4, VIP_ACT_NONE, true, true>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-                default: pw_epilogue<4, VIP_ACT_NONE, false, false>(a, acc[G_], m_base, n_first, rb_res, rb_y); break;
-            }
-        };
-        epi(std::integral_constant<int, 0>{});
-        if constexpr (2 > 1) epi(std::integral_constant<int, 1>{});
+        pw_epilogue_groups<2, 4>(mode, a, acc, m_base, n_lane, rb_res, rb_y);
         if (!more) break;
     }
 #undef G8_DSR
