@@ -12,11 +12,9 @@
 // the B operand of O^T = V^T P^T, V^T fragments by ds_read_b64_tr_b16.  The table values (divided by the scale) are the MFMAs' C operand:
 // the accumulators are initialised with them BEFORE the first MFMA (the form that is correct next to MFMA-heavy co-runners, DESIGN.md
 // section 5).  Replaces the one-thread-per-query fp32 VALU kernels of strict_ops.hip for this storage.
-#include "common.hpp"
+#include "window_core.hpp"
 
 namespace {
-
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct AttnH2Args {
     const char* qkv;
@@ -46,18 +44,18 @@ struct AttnCfg {
 template <int HD>
 __device__ __forceinline__ int k_chunk(int row, int ch) {
     if constexpr (HD == 64) return ch ^ (row & 7);
-    else return ch ^ ((0x78u >> (2 * ((row >> 2) & 3))) & 3);          // pi = {0, 2, 3, 1}
+    else return win_k_slot(row, ch);
 }
 // V: 32-byte slots (one 16-channel output tile) swizzled so that the 8 rows a ds_read_b64_tr_b16 half-wave touches hit all banks
 template <int HD>
 __device__ __forceinline__ int v_chunk(int row, int ch) {
     if constexpr (HD == 64) return ((((ch >> 1) ^ ((row >> 1) & 3)) << 1) | (ch & 1));
-    else return ch ^ (((row >> 2) & 1) << 1);
+    else return win_v_chunk(row, ch);
 }
 template <int HD>
 __device__ __forceinline__ int v_slot(int row, int dt) {
     if constexpr (HD == 64) return dt ^ ((row >> 1) & 3);
-    else return dt ^ ((row >> 2) & 1);
+    else return win_v_half(row, dt);
 }
 
 // threads per workgroup: the hd = 64 item (ViT, 197 tokens) needs 115 KB of LDS, one workgroup per CU - with 4 waves that is ONE wave per

@@ -147,6 +147,15 @@ __device__ __forceinline__ float vip_act_strict(float v, int act) {
     }
 }
 
+// XCD-aware block remap: hardware deals workgroup ids round-robin to the 8 XCDs, so blocks b and b+8 share an XCD (and its L2); give
+// every XCD a contiguous run of logical blocks so that neighbours in the logical order (the n-blocks that re-read one activation tile,
+// the heads of one attention window) hit the same L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 union U4H8 {
     uint4 u;
     f16x8 h;

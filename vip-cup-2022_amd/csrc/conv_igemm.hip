@@ -279,14 +279,6 @@ __device__ __forceinline__ void epilogue(const ConvArgs& a, f32x4 (&acc)[MT][4],
     }
 }
 
-// XCD-aware block remap: hardware deals workgroup ids round-robin to the 8 XCDs, so blocks b and b+8 share an XCD (and its L2); give
-// every XCD a contiguous run of logical tiles so the n-blocks that re-read one activation tile hit the same L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
     constexpr int WAVES_N = BN / 64;

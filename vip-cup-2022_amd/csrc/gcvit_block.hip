@@ -6,14 +6,14 @@
 // y out).  It replaces four launches (LayerNorm, qkv Dense, attention core, proj Dense + residual) whose traffic at level 0 is
 // x + x^ + x^ + qkv + qkv + att + att + x + y = 15 N C halfs per window against 2 N C here.
 //
-// One WAVE per window (49 tokens as 4 MFMA tiles in the padded order row' = 8 ty + tx of window_attn.hip), persistent workgroups of
+// One WAVE per window (49 tokens as 4 MFMA tiles in the padded order row' = 8 ty + tx of window_core.hpp), persistent workgroups of
 // 4 waves; both weight matrices and the two heads' relative-position tables live in LDS for the whole kernel (44 KB), each wave has a
 // private 8 KB K / V image - no workgroup barrier inside the window loop.  Everything else stays in registers:
 //   * x fragments (MFMA B operand: lane = token, 8 consecutive channels) -> LayerNorm in place (in-lane sums + two lane exchanges,
 //     the expression of layernorm_kernel: the normalised row is rounded to fp16 where the separate launch rounded it);
 //   * per head: [q | k | v]^T = W x^T + b with the weight rows interleaved in LDS so that a lane ends up with 8 CONSECUTIVE head
 //     channels of its token - the packed fp16 result IS the B operand of S^T = K Q^T (q) or one 16-byte row chunk of the K / V image;
-//   * the attention core of window_attn.hip (bias table as the MFMA C operand, register-local softmax, V^T by transposed LDS reads),
+//   * the attention core of window_core.hpp, win_attn_tile (bias table as the MFMA C operand, register-local softmax, V^T by transposed LDS reads),
 //     whose normalised output O^T - head channels 4g..4g+3 and 16+4g..16+4g+3 in a lane - is the B operand of the proj MFMA as it
 //     stands, because the proj weight COLUMNS are stored in that order in LDS;
 //   * y^T accumulates over the two heads from the proj bias, then + x (re-read: L2), fp16, 16-byte stores.
@@ -28,11 +28,10 @@
 // (VALU + MFMA issue alone would be ~60 us).  Tried and dropped: the next window's rows requested into the dead x^ registers under
 // the last head's attention pass (124 -> 124 us: the x fetch is not what the waves wait for); two waves per window at C = 64 to get
 // under 128 VGPRs and four waves per SIMD (158 us: workgroup barriers and 37 spilled registers cost more than the occupancy buys).
-#include "common.hpp"
+#include "window_core.hpp"
+#include "frag.hpp"
 
 namespace {
-
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct GbArgs {
     const f16* x;
@@ -51,12 +50,12 @@ struct GbArgs {
     float scale_log2e, inv_scale;
 };
 
-constexpr int GB_WS = 7;
-constexpr int GB_NKT = 4;                                      // 64 key rows (8 x 8 padded grid)
-constexpr int GB_TW = 16, GB_KSTEP = 32, GB_KCMAX = GB_KSTEP * GB_NKT, GB_NEGSZ = GB_KCMAX + 4, GB_TOFF = GB_NEGSZ + GB_KCMAX;
-constexpr int GB_TROWS = 2 * GB_WS - 1, GB_TBF = GB_TOFF + GB_TROWS * GB_TW;      // floats per head (window_attn.hip WinCfg<7, 8, 3, 1>)
-constexpr int GB_KVB = 64;                                     // K / V row: 32 halfs
-constexpr int GB_KV_WIN = 2 * 64 * GB_KVB;                     // K + V image of one window (one head at a time)
+using GbWin = WinCfg<7, 8, 3, 1>;                              // one wave per window, the padded order row' = 8 ty + tx
+constexpr int GB_WS = GbWin::WIN;
+constexpr int GB_TBF = GbWin::TB_FLOATS;                       // table-image floats per head
+constexpr int GB_KVB = GbWin::ROWB;                            // K / V row: 32 halfs
+constexpr int GB_KV_WIN = 2 * GbWin::RP * GB_KVB;              // K + V image of one window (one head at a time)
+static_assert(GbWin::NKT == 4 && GB_TBF == 468 && GB_KV_WIN == 8192, "64 key rows; 468 table floats per head; 8 KB K / V image");
 
 template <int HEADS>
 struct GbCfg {
@@ -72,154 +71,8 @@ struct GbCfg {
     static constexpr int KV_OFF = (TB_OFF + HEADS * GB_TBF * 4 + 15) / 16 * 16;
     static constexpr int SMEM = KV_OFF + 4 * GB_KV_WIN;
 };
-
-// LDS row j of a 32-row group holds channel (r >> 2) * 8 + t * 4 + (r & 3), t = j >> 4, r = j & 15: MFMA row tiles 2m, 2m + 1 then
-// leave lane group g with channels 8g .. 8g + 7 of the group (mlp_fused.hip)
-__device__ __forceinline__ int gb_frag32(int j) {
-    const int t = (j >> 4) & 1, r = j & 15;
-    return (r >> 2) * 8 + t * 4 + (r & 3);
-}
-__device__ __forceinline__ int gb_k_slot(int row, int ch) {
-    const int q = (row >> 2) & 3;
-    return ch ^ ((0x78 >> (q * 2)) & 3);        // window_attn.hip k_slot
-}
-
-// LayerNorm of one 16-token tile held as fragments: lane (l15 = token, g) has channels 32 ks + 8 g .. + 7, ks < CK (mlp_fused.hip
-// ln_fragments)
-template <int CK>
-__device__ __forceinline__ void gb_layernorm(U4H8 (&xf)[CK], const float* __restrict__ gam, const float* __restrict__ bet, float eps,
-                                             int g) {
-    constexpr int GB_C = 32 * CK;
-    float v[CK][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < CK; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            v[ks][j] = (float)xf[ks].e[j];
-            sum += v[ks][j];
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float mean = sum / (float)GB_C;
-    float sq = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < CK; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d = v[ks][j] - mean;
-            sq += d * d;
-        }
-    sq += __shfl_xor(sq, 16, 64);
-    sq += __shfl_xor(sq, 32, 64);
-    const float rstd = rsqrtf(sq / (float)GB_C + eps);
-#pragma unroll
-    for (int ks = 0; ks < CK; ++ks) {
-        const float4 g0 = *reinterpret_cast<const float4*>(gam + ks * 32 + g * 8), g1 = *reinterpret_cast<const float4*>(gam + ks * 32 + g * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(bet + ks * 32 + g * 8), b1 = *reinterpret_cast<const float4*>(bet + ks * 32 + g * 8 + 4);
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[ks].e[j] = (f16)((v[ks][j] - mean) * rstd * gg[j] + bb[j]);
-    }
-}
-
-// One 16-query tile against the wave's K / V image: S^T = K Q^T + bias (table values are the C operand), softmax over the keys,
-// O^T = V^T P^T, normalised and packed as the proj MFMA's B operand.  The arithmetic of window_attn.hip win_query_tile<7, 8, 3, 1>;
-// the query of a lane is (qy, qx) of the PADDED order here (no division).
-__device__ __forceinline__ U4H8 gb_attn_tile(const U4H8& qfrag, const char* k_lds, const char* v_lds, const float* tb, int qy, int qx,
-                                             int l15, int g, float sc) {
-    const int lane_term = (g >> 1) * GB_TW + 4 * (g & 1);
-    const int tr_q = l15 >> 2, tr_p = l15 & 3;
-    const float* tbase = tb + (GB_TOFF + qy * GB_TW + qx + (GB_WS - 1) * (GB_TW + 1) - lane_term - GB_KCMAX);
-    f32x4 acc[GB_NKT];
-#pragma unroll
-    for (int t = 0; t < GB_NKT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int mask = 0;                       // lane groups whose key slot (t, r) is padding (compile-time)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int kp = 16 * t + 4 * gg + r;
-                if (((kp & 7) >= GB_WS) || ((kp >> 3) >= GB_WS)) mask |= 1 << gg;
-            }
-            if (mask == 15) {
-                acc[t][r] = -1.0e30f;
-            } else {
-                const int imm = GB_KCMAX - (GB_KSTEP * t + r);
-                const float* bp = (mask == 0) ? tbase : (((mask >> g) & 1) ? tb : tbase);
-                acc[t][r] = bp[imm];
-            }
-        }
-    U4H8 kf[GB_NKT];
-#pragma unroll
-    for (int t = 0; t < GB_NKT; ++t) {
-        const int row = t * 16 + l15;
-        kf[t].u = *reinterpret_cast<const uint4*>(k_lds + row * GB_KVB + gb_k_slot(row, g) * 16);
-    }
-#pragma unroll
-    for (int t = 0; t < GB_NKT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t].h, qfrag.h, acc[t], 0, 0, 0);
-    float m = -1.0e30f;
-#pragma unroll
-    for (int t = 0; t < GB_NKT; ++t) {
-        m = fmaxf(fmaxf(m, acc[t][0]), acc[t][1]);
-        m = fmaxf(fmaxf(m, acc[t][2]), acc[t][3]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const f32x2 nm = {-m * sc, -m * sc};
-    f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < GB_NKT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-            const f32x2 e = (f32x2){acc[t][r], acc[t][r + 1]} * sc + nm;
-            const f32x2 p = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-            acc[t][r] = p.x;
-            acc[t][r + 1] = p.y;
-            ls2 += p;
-        }
-    float lsum = ls2.x + ls2.y;
-    lsum += __shfl_xor(lsum, 16, 64);
-    lsum += __shfl_xor(lsum, 32, 64);
-
-    f32x4 o[2];
-    o[0] = o[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    U4H8 pfa[GB_NKT / 2];
-    union VF {
-        fp16x4_t t[2];
-        f16x8 v;
-    } vfa[GB_NKT / 2][2];
-#pragma unroll
-    for (int s = 0; s < GB_NKT / 2; ++s) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pfa[s].e[j] = (f16)acc[2 * s][j];
-            pfa[s].e[4 + j] = (f16)acc[2 * s + 1][j];
-        }
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int row = 32 * s + 16 * hh + 4 * g + tr_q;
-                const int half = dt ^ ((row >> 2) & 1);
-                vfa[s][dt].t[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                    (__attribute__((address_space(3))) fp16x4_t*)(v_lds + row * GB_KVB + half * 32 + tr_p * 8));
-            }
-    }
-#pragma unroll
-    for (int s = 0; s < GB_NKT / 2; ++s)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfa[s][dt].v, pfa[s].h, o[dt], 0, 0, 0);
-    const float inv = 1.f / lsum;
-    U4H8 of;                                    // k-slot (g, j): head channel 4g + j (j < 4) / 16 + 4g + (j - 4)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        of.e[r] = (f16)(o[0][r] * inv);
-        of.e[4 + r] = (f16)(o[1][r] * inv);
-    }
-    return of;
-}
+static_assert(GbCfg<2>::KV_OFF == 44704 && GbCfg<2>::SMEM == 77472 && GbCfg<4>::KV_OFF == 118080 && GbCfg<4>::SMEM == 150848,
+              "LDS plan of the two configurations");
 
 template <int HEADS, bool GLOBALQ>
 __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void gcvit_attn_block_kernel(GbArgs a) {
@@ -235,31 +88,27 @@ __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void 
     const int l15 = lane & 15, g = lane >> 4;
     const int slot = wave / WPW, sub = wave % WPW;                 // window slot of the workgroup pass; which token tiles of it
     char* k_lds = smem + Cfg::KV_OFF + slot * GB_KV_WIN;
-    char* v_lds = k_lds + 64 * GB_KVB;
+    char* v_lds = k_lds + GbWin::RP * GB_KVB;
 
     // ---- once per workgroup: weights (fragment-ordered) and the heads' bias tables ----
     constexpr int CPR = C / 8;                                     // 16-byte chunks per weight row
     for (int i = tid; i < NQ * C * CPR; i += NTHR) {
         const int j = i / CPR, c = i - j * CPR;
-        const int ch = (j & ~31) + gb_frag32(j & 31);              // rows of [part][head][32] = consecutive groups of 32
+        const int ch = frag_channel(j);              // rows of [part][head][32] = consecutive groups of 32
         *reinterpret_cast<uint4*>(wq + j * WROWB + c * 16) = *reinterpret_cast<const uint4*>(a.wqkv + (long)ch * a.ldwq + c * 8);
     }
     if constexpr (Cfg::WP_LDS) {
         for (int i = tid; i < C * CPR; i += NTHR) {
             const int j = i / CPR, c = i - j * CPR;                // chunk c = head * 4 + lane group
-            const int ch = (j & ~31) + gb_frag32(j & 31);
+            const int ch = frag_channel(j);
             const f16* src = a.wproj + (long)ch * a.ldwp + (c >> 2) * 32 + 4 * (c & 3);
             const uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
             *reinterpret_cast<uint4*>(wp + j * WROWB + c * 16) = make_uint4(lo.x, lo.y, hi.x, hi.y);
         }
     }
     for (int i = tid; i < HEADS * GB_TBF; i += NTHR) {
-        const int head = i / GB_TBF, ii = i - head * GB_TBF;
-        const int e = ii - GB_TOFF;
-        const int ry = e / GB_TW, rx = e - ry * GB_TW;
-        const bool in_tab = (ii >= GB_TOFF) & (rx < GB_TROWS);
-        const float t = a.table[in_tab ? (ry * GB_TROWS + rx) * HEADS + head : 0];
-        tbs[i] = in_tab ? t * a.inv_scale : (ii < GB_TOFF ? -1.0e30f : 0.f);
+        const int head = i / GB_TBF;
+        tbs[i] = win_table_value<GbWin, false>(a.table, HEADS, head, i - head * GB_TBF, a.inv_scale);
     }
     __syncthreads();
 
@@ -275,7 +124,7 @@ __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void 
     // proj weight rows of this lane's fragments when they come from global: LDS-image row 16 ct + l15 = channel ...
     int pch[NCT];
 #pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) pch[ct] = ((16 * ct + l15) & ~31) + gb_frag32((16 * ct + l15) & 31);
+    for (int ct = 0; ct < NCT; ++ct) pch[ct] = frag_channel(16 * ct + l15);
 
     // One wave per window: waves walk their own windows.  Two waves per window: the workgroup walks window quartets in step (barriers
     // inside), a wave whose window is past the end works on out-of-range offsets (loads give zeros, stores are dropped).
@@ -312,7 +161,7 @@ __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void 
             U4H8 col[CK];
 #pragma unroll
             for (int ks = 0; ks < CK; ++ks) col[ks] = xf[ks][tt];
-            gb_layernorm<CK>(col, a.ln_g, a.ln_b, a.ln_eps, g);
+            ln_fragments<CK>(col, a.ln_g, a.ln_b, a.ln_eps, g);
 #pragma unroll
             for (int ks = 0; ks < CK; ++ks) xf[ks][tt] = col[ks];
         }
@@ -361,7 +210,8 @@ __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void 
                     }
                     const int row = (sub * TT + tt) * 16 + l15;
                     if (!GLOBALQ && part == 0) qf[tt] = pk;
-                    else if (part == NQ - 2) *reinterpret_cast<uint4*>(k_lds + row * GB_KVB + gb_k_slot(row, g) * 16) = pk.u;
+                    else if (part == NQ - 2) *reinterpret_cast<uint4*>(k_lds + row * GB_KVB + win_k_slot(row, g) * 16) = pk.u;
+                    // chunk win_v_chunk(row, g), written out: as a call here the kernels' code changes
                     else *reinterpret_cast<uint4*>(v_lds + row * GB_KVB + ((g ^ (((row >> 2) & 1) << 1)) * 16)) = pk.u;
                 }
             }
@@ -399,7 +249,7 @@ __global__ __launch_bounds__(GbCfg<HEADS>::NWAVE * 64, HEADS == 2 ? 2 : 1) void 
             const float* tb = tbs + head * GB_TBF;
 #pragma unroll
             for (int qt = 0; qt < TT; ++qt) {
-                const U4H8 of = gb_attn_tile(qf[qt], k_lds, v_lds, tb, qyv[qt], tx < GB_WS ? tx : GB_WS - 1, l15, g, sc);
+                const U4H8 of = win_attn_tile<GbWin, true, true>(qf[qt], k_lds, v_lds, tb, qyv[qt], tx < GB_WS ? tx : GB_WS - 1, l15, g, sc);
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct)
                     yacc[ct][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pwf[ct].h, of.h, yacc[ct][qt], 0, 0, 0);

@@ -9,18 +9,17 @@
 //     fragments stay in registers (64 VGPRs) for all heads;
 //   * per head (loop NOT unrolled): the head's q | k | v weight rows (96 x 256, 51 KB) and its relative-position table are staged in
 //     LDS; every wave computes q, k, v for its own tokens - q stays in registers, k and v go to the workgroup's K / V image in the
-//     padded order row' = 16 ty + tx of window_attn.hip - then runs the attention core of window_attn.hip<14> on its own query tiles;
+//     padded order row' = 16 ty + tx of window_core.hpp - then runs win_attn_tile of window_core.hpp on its own query tiles;
 //   * the normalised head output O_h (8 halfs per lane and tile) is parked in the rows of y this lane will write anyway (the same 16
 //     bytes it later overwrites with the result: a private scratch that costs no memory) - 8 heads of accumulators or outputs do not
 //     fit next to the core in 256 registers;
 //   * after the last head: proj weight columns of two heads at a time through the same LDS buffer, y^T += Wp O^T for both tiles from
 //     the parked fragments, + bias + x, 16-byte stores.
 // A block with a global query takes q from q_global [B, 196, C] and computes k, v only.
-#include "common.hpp"
+#include "window_core.hpp"
+#include "frag.hpp"
 
 namespace {
-
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct Gb14Args {
     const f16* x;
@@ -41,10 +40,9 @@ struct Gb14Args {
 
 constexpr int G14_WS = 14, G14_C = 256, G14_HEADS = 8, G14_CK = 8, G14_N = G14_WS * G14_WS;
 constexpr int G14_NT = 13;                                      // 16-token tiles of the dense order
-constexpr int G14_RP = 224, G14_NKT = 14;                       // key rows of the padded order (14 rows of 16 slots)
-constexpr int G14_TW = 48, G14_KSTEP = 48, G14_KCMAX = G14_KSTEP * G14_NKT, G14_NEGSZ = G14_KCMAX + 4, G14_TOFF = G14_NEGSZ + G14_KCMAX;
-constexpr int G14_TROWS = 2 * G14_WS - 1, G14_TBF = G14_TOFF + G14_TROWS * G14_TW;   // window_attn.hip WinCfg<14, 16, 4, 4>
-constexpr int G14_KVB = 64;
+using G14Win = WinCfg<14, 16, 4, 4>;                            // the padded order row' = 16 ty + tx
+constexpr int G14_RP = G14Win::RP, G14_TBF = G14Win::TB_FLOATS, G14_KVB = G14Win::ROWB;
+static_assert(G14_RP == 224 && G14Win::NKT == 14 && G14_TBF == 2644, "14 key tiles of the padded order; 2644 table floats");
 constexpr int G14_WROWB = 2 * G14_C + 32;                       // qkv weight row in LDS (stride = 32 mod 64)
 constexpr int G14_PROWB = 2 * 64 + 32;                          // proj weight row of a head PAIR (64 columns)
 constexpr int G14_W_OFF = 0;
@@ -53,147 +51,7 @@ constexpr int G14_KV_OFF = G14_W_OFF + G14_W_BYTES;
 constexpr int G14_TB_OFF = G14_KV_OFF + 2 * G14_RP * G14_KVB;
 constexpr int G14_SMEM = G14_TB_OFF + (G14_TBF * 4 + 15) / 16 * 16;
 static_assert(256 * G14_PROWB <= G14_W_BYTES, "proj pair image fits the weight buffer");
-
-__device__ __forceinline__ int g14_frag32(int j) {              // gcvit_block.hip gb_frag32
-    const int t = (j >> 4) & 1, r = j & 15;
-    return (r >> 2) * 8 + t * 4 + (r & 3);
-}
-__device__ __forceinline__ int g14_k_slot(int row, int ch) {
-    const int q = (row >> 2) & 3;
-    return ch ^ ((0x78 >> (q * 2)) & 3);
-}
-
-// LayerNorm of one 16-token tile held as fragments (mlp_fused.hip ln_fragments, C = 256)
-__device__ __forceinline__ void g14_layernorm(U4H8 (&xf)[G14_CK], const float* __restrict__ gam, const float* __restrict__ bet, float eps,
-                                              int g) {
-    float v[G14_CK][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < G14_CK; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            v[ks][j] = (float)xf[ks].e[j];
-            sum += v[ks][j];
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float mean = sum / (float)G14_C;
-    float sq = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < G14_CK; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d = v[ks][j] - mean;
-            sq += d * d;
-        }
-    sq += __shfl_xor(sq, 16, 64);
-    sq += __shfl_xor(sq, 32, 64);
-    const float rstd = rsqrtf(sq / (float)G14_C + eps);
-#pragma unroll
-    for (int ks = 0; ks < G14_CK; ++ks) {
-        const float4 g0 = *reinterpret_cast<const float4*>(gam + ks * 32 + g * 8), g1 = *reinterpret_cast<const float4*>(gam + ks * 32 + g * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(bet + ks * 32 + g * 8), b1 = *reinterpret_cast<const float4*>(bet + ks * 32 + g * 8 + 4);
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xf[ks].e[j] = (f16)((v[ks][j] - mean) * rstd * gg[j] + bb[j]);
-    }
-}
-
-// One 16-query tile against the workgroup's K / V image (window_attn.hip win_query_tile<14, 16, 4, 4>: S^T = K Q^T with the bias
-// table as the C operand, softmax over the 224 key slots, O^T = V^T P^T), normalised and packed for the proj MFMA: k-slot (g, j) =
-// head channel 4g + j (j < 4) / 16 + 4g + (j - 4).  (qy, qx): the lane's query in the window, clamped for the padding lanes.
-__device__ __forceinline__ U4H8 g14_attn_tile(const U4H8& qfrag, const char* k_lds, const char* v_lds, const float* tb, int qy, int qx,
-                                              int l15, int g, float sc) {
-    constexpr int NKT = G14_NKT;
-    const int lane_term = 4 * g;
-    const int tr_q = l15 >> 2, tr_p = l15 & 3;
-    const float* tbase = tb + (G14_TOFF + qy * G14_TW + qx + (G14_WS - 1) * (G14_TW + 1) - lane_term - G14_KCMAX);
-    f32x4 acc[NKT];
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            int mask = 0;                       // lane groups whose key slot (t, r) is padding (compile-time)
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const int kp = 16 * t + 4 * gg + r;
-                if (((kp & 15) >= G14_WS) || ((kp >> 4) >= G14_WS)) mask |= 1 << gg;
-            }
-            if (mask == 15) {
-                acc[t][r] = -1.0e30f;
-            } else {
-                const int imm = G14_KCMAX - (G14_KSTEP * t + r);
-                const float* bp = (mask == 0) ? tbase : (((mask >> g) & 1) ? tb : tbase);
-                acc[t][r] = bp[imm];
-            }
-        }
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-        const int row = t * 16 + l15;
-        U4H8 kf;
-        kf.u = *reinterpret_cast<const uint4*>(k_lds + row * G14_KVB + g14_k_slot(row, g) * 16);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf.h, qfrag.h, acc[t], 0, 0, 0);
-    }
-    float m = -1.0e30f;
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-        m = fmaxf(fmaxf(m, acc[t][0]), acc[t][1]);
-        m = fmaxf(fmaxf(m, acc[t][2]), acc[t][3]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const f32x2 nm = {-m * sc, -m * sc};
-    f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-            const f32x2 e = (f32x2){acc[t][r], acc[t][r + 1]} * sc + nm;
-            const f32x2 p = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-            acc[t][r] = p.x;
-            acc[t][r + 1] = p.y;
-            ls2 += p;
-        }
-    float lsum = ls2.x + ls2.y;
-    lsum += __shfl_xor(lsum, 16, 64);
-    lsum += __shfl_xor(lsum, 32, 64);
-
-    f32x4 o[2];
-    o[0] = o[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NKT / 2; ++s) {
-        U4H8 pf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            pf.e[j] = (f16)acc[2 * s][j];
-            pf.e[4 + j] = (f16)acc[2 * s + 1][j];
-        }
-        union {
-            fp16x4_t t[2];
-            f16x8 v;
-        } vf[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int row = 32 * s + 16 * hh + 4 * g + tr_q;
-                const int half = dt ^ ((row >> 2) & 1);
-                vf[dt].t[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                    (__attribute__((address_space(3))) fp16x4_t*)(v_lds + row * G14_KVB + half * 32 + tr_p * 8));
-            }
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[dt].v, pf.h, o[dt], 0, 0, 0);
-    }
-    const float inv = 1.f / lsum;
-    U4H8 of;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        of.e[r] = (f16)(o[0][r] * inv);
-        of.e[4 + r] = (f16)(o[1][r] * inv);
-    }
-    return of;
-}
+static_assert(G14_KV_OFF == 52224 && G14_TB_OFF == 80896 && G14_SMEM == 91472, "LDS plan");
 
 template <bool GLOBALQ>
 __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) {
@@ -259,7 +117,7 @@ __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) 
             U4H8 col[CK];
 #pragma unroll
             for (int ks = 0; ks < CK; ++ks) col[ks] = xf[ks][s];
-            g14_layernorm(col, a.ln_g, a.ln_b, a.ln_eps, g);
+            ln_fragments<CK>(col, a.ln_g, a.ln_b, a.ln_eps, g);
 #pragma unroll
             for (int ks = 0; ks < CK; ++ks) xf[ks][s] = col[ks];
         }
@@ -270,16 +128,10 @@ __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) 
             // the barrier that closed its attention pass ----
             for (int i = tid; i < NQ * 32 * (C / 8); i += NTHR) {
                 const int j = i >> 5, c = i & 31;                                 // LDS row (part * 32 + jj), 16-byte chunk
-                const int row = (j >> 5) * C + head * 32 + g14_frag32(j & 31);
+                const int row = (j >> 5) * C + head * 32 + frag_channel32(j & 31);
                 *reinterpret_cast<uint4*>(wbuf + j * G14_WROWB + c * 16) = *reinterpret_cast<const uint4*>(a.wqkv + (long)row * a.ldwq + c * 8);
             }
-            for (int i = tid; i < G14_TBF; i += NTHR) {
-                const int e = i - G14_TOFF;
-                const int ry_ = e / G14_TW, rx_ = e - ry_ * G14_TW;
-                const bool in_tab = (i >= G14_TOFF) & (rx_ < G14_TROWS);
-                const float t = a.table[in_tab ? (ry_ * G14_TROWS + rx_) * G14_HEADS + head : 0];
-                tb[i] = in_tab ? t * a.inv_scale : (i < G14_TOFF ? -1.0e30f : 0.f);
-            }
+            win_table_fill_loop<G14Win>(tb, a.table, G14_HEADS, head, a.inv_scale, tid, NTHR);
             __syncthreads();
 
             // ---- [q | k | v]^T = W x^T + b for this wave's tokens ----
@@ -315,9 +167,9 @@ __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) 
                     const int row = krow[s];
                     if (!GLOBALQ && part == 0) qf[s] = pk;
                     else if (part == NQ - 2) {
-                        if (tok_ok[s]) *reinterpret_cast<uint4*>(k_lds + row * G14_KVB + g14_k_slot(row, g) * 16) = pk.u;
+                        if (tok_ok[s]) *reinterpret_cast<uint4*>(k_lds + row * G14_KVB + win_k_slot(row, g) * 16) = pk.u;
                     } else {
-                        if (tok_ok[s]) *reinterpret_cast<uint4*>(v_lds + row * G14_KVB + ((g ^ (((row >> 2) & 1) << 1)) * 16)) = pk.u;
+                        if (tok_ok[s]) *reinterpret_cast<uint4*>(v_lds + row * G14_KVB + win_v_chunk(row, g) * 16) = pk.u;
                     }
                 }
             }
@@ -335,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) 
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 if (!tile_ok[s]) continue;
-                const U4H8 of = g14_attn_tile(qf[s], k_lds, v_lds, tb, qyv[s], qxv[s], l15, g, sc);
+                const U4H8 of = win_attn_tile<G14Win, false, false>(qf[s], k_lds, v_lds, tb, qyv[s], qxv[s], l15, g, sc);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, of.u),
                                                        ry, xoff[s] == OOB ? OOB : xoff[s] + (head * 32 + g * 8) * 2, 0, 0);
             }
@@ -354,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void gcvit_attn_block14_kernel(Gb14Args a) 
         for (int hp = 0; hp < G14_HEADS / 2; ++hp) {
             for (int i = tid; i < C * 8; i += NTHR) {
                 const int j = i >> 3, c = i & 7;                                  // LDS row, chunk = head-in-pair * 4 + lane group
-                const int ch = (j & ~31) + g14_frag32(j & 31);
+                const int ch = frag_channel(j);
                 const f16* src = a.wproj + (long)ch * a.ldwp + (2 * hp + (c >> 2)) * 32 + 4 * (c & 3);
                 const uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
                 *reinterpret_cast<uint4*>(wbuf + j * G14_PROWB + c * 16) = make_uint4(lo.x, lo.y, hi.x, hi.y);

@@ -11,28 +11,26 @@
 //   region(Y, X) = 3 r(Y, Hp) + r(X, Wp), r(t, L) = [t >= L - ws] + [t >= L - shift] on rolled, padded coordinates (shift > 0 only).
 //
 // fp16 storage (swin_attn_kernel): work item = (image, window, head), one wave per item, four items per workgroup; head_dim 32.
-// Tokens are re-indexed as row' = 8 ty + tx (the P = 8 re-indexing of window_attn.hip), so ws <= 8 gives four 16-key tiles; ws 8 is
+// Tokens are re-indexed as row' = 8 ty + tx (the P = 8 re-indexing of window_core.hpp), so ws <= 8 gives four 16-key tiles; ws 8 is
 // the dense case, ws < 8 leaves DEAD slots (ty >= ws or tx >= ws: no token at all, unlike a padded token), killed by value: their
 // accumulators start at -1e30.  K is normalised in fp32 while it is staged into LDS, Q (times tau) as its fragments are loaded.
 // S^T = Kn Qn^T with v_mfma_f32_16x16x32_f16 and the table entry plus the mask term as the MFMA's C OPERAND (the concurrency rule at
-// the top of window_attn.hip: no "MFMA with C = 0, LDS read, packed add" sequence), softmax over keys register-local plus two
+// the top of window_core.hpp: no "MFMA with C = 0, LDS read, packed add" sequence), softmax over keys register-local plus two
 // cross-lane exchanges, O^T = V^T P^T with V^T fragments from transposed LDS reads - the LDS images and fragment reads of
-// window_attn.hip.  Wrapped gathers, v_bias rows and skipped stores are plain C++ addressing.  No atomics: every output is a function
+// window_core.hpp.  Wrapped gathers, v_bias rows and skipped stores are plain C++ addressing.  No atomics: every output is a function
 // of its own window alone, in a fixed order - bit-reproducible and independent of the batch.
 //
 // packed and fp32 storages (swin_attn_strict_kernel): one fp32 VALU template, the conventions of sattn_kernel (strict_ops.hip) - one
 // thread per query token, Kn / V of the item in LDS as fp32, online softmax with libm expf, true divisions.
-#include "common.hpp"
+#include "window_core.hpp"
 #include <math.h>
 
 namespace {
 
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
 constexpr int SW_MAX_WS = 8;
 constexpr int SW_HD = 32;
 constexpr int SW_ROWS = 64;                        // key slots: 8 x 8
-constexpr int SW_ROWB = 64;                        // bytes per fp16 row
+constexpr int SW_ROWB = WIN_ROWB;                  // bytes per fp16 row
 constexpr int SW_TB = 232;                         // (2 * 8 - 1)^2 = 225 table floats per head, rounded up
 constexpr int SW_ITEM_BYTES = 2 * SW_ROWS * SW_ROWB + SW_TB * 4;
 constexpr float SW_EPS = 1e-6f;
@@ -58,11 +56,6 @@ __device__ __forceinline__ int sw_pix(const SwinArgs& a, int wy, int wx, int ty,
     if (y >= a.Hp) y -= a.Hp;
     if (x >= a.Wp) x -= a.Wp;
     return (y < a.H && x < a.W) ? y * a.W + x : -1;
-}
-
-__device__ __forceinline__ int sw_k_slot(int row, int ch) {
-    const int q = (row >> 2) & 3;
-    return ch ^ ((0x78 >> (q * 2)) & 3);  // pi = {0,2,3,1}: conflict-free ds_read_b128 fragment reads (window_attn.hip)
 }
 
 __global__ __launch_bounds__(256) void swin_attn_kernel(SwinArgs a) {
@@ -144,7 +137,8 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(SwinArgs a) {
                 for (int j = 0; j < 8; ++j) vr.e[j] = (f16)a.vbias[head * SW_HD + ch * 8 + j];
             }
         }
-        *reinterpret_cast<uint4*>(k_lds + row * SW_ROWB + sw_k_slot(row, ch) * 16) = kn.u;
+        *reinterpret_cast<uint4*>(k_lds + row * SW_ROWB + win_k_slot(row, ch) * 16) = kn.u;
+        // chunk win_v_chunk(row, ch), written out: as a call here the kernel's code changes
         *reinterpret_cast<uint4*>(v_lds + row * SW_ROWB + (ch ^ (((row >> 2) & 1) << 1)) * 16) = vr.u;
     }
     for (int i = lane; i < tw * tw; i += 64) tb[i] = a.table[(long)i * a.heads + head];
@@ -173,7 +167,9 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(SwinArgs a) {
         const int rq = shift ? 3 * sw_r(wy * ws + qy, a.Hp, ws, shift) + sw_r(wx * ws + qx, a.Wp, ws, shift) : 0;
         const int tbase = (qy + ws - 1) * tw + (qx + ws - 1);
         // S^T tiles: rows = keys 16 t + 4 g + r, column = this lane's query.  The accumulators START as table + mask (dead slots:
-        // -1e30) and go in as the C operand of S^T = Kn Qn^T + C.
+        // -1e30) and go in as the C operand of S^T = Kn Qn^T + C.  From the K fragment reads to the store this mirrors win_attn_tile
+        // <.., true, true> of window_core.hpp with its own start, softmax expression and store; as calls into pieces of that function
+        // the kernel's code changes, so the text stays here.
         f32x4 acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -187,18 +183,11 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(SwinArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int row = t * 16 + l15;
-            kf[t].u = *reinterpret_cast<const uint4*>(k_lds + row * SW_ROWB + sw_k_slot(row, g) * 16);
+            kf[t].u = *reinterpret_cast<const uint4*>(k_lds + row * SW_ROWB + win_k_slot(row, g) * 16);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t].h, qf[qt].h, acc[t], 0, 0, 0);
-        float m = SW_DEAD;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            m = fmaxf(fmaxf(m, acc[t][0]), acc[t][1]);
-            m = fmaxf(fmaxf(m, acc[t][2]), acc[t][3]);
-        }
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        const float m = win_score_max<4>(acc);
         float lsum = 0.f;
 #pragma unroll
         for (int t = 0; t < 4; ++t)

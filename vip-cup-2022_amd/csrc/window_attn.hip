@@ -22,8 +22,8 @@
 //
 // LDS images (64-byte rows, no padding): K chunk c of row r at slot c ^ pi[(r>>2)&3], pi = {0,2,3,1}
 // (conflict-free ds_read_b128 fragment reads); V 32-byte halves swapped on rows with bit 2 set
-// (conflict-free transposed reads).
-#include "common.hpp"
+// (conflict-free transposed reads).  Geometry (WinCfg), swizzles, the table image and the softmax pieces: window_core.hpp.
+#include "window_core.hpp"
 #include <stdlib.h>
 
 // CONCURRENCY NOTE (round 3, tools/stress_determinism.py -> bisect_determinism.py -> race_matrix.py).  Rounds 1-2 computed S^T with a
@@ -36,16 +36,8 @@
 // accumulators and go in as the MFMA's C operand - the "MFMA with C = 0, LDS read, v_pk_add_f32 on the MFMA result" sequence no
 // longer exists (and the tile saves its 28 packed adds).  40 of 40 launches bit-identical under every co-runner, both window
 // sizes, with or without scheduling fences around the MFMAs (profiles/r03_attn_race_*.log); speed unchanged (42.7 vs 42.5 us at L2).
-// WA_PV_OPERANDS_FIRST: the P.V MFMAs take all their operands (P^T fragments, V^T fragments) from registers that are complete before
-// the first of them issues (1), or convert / read them step by step between the MFMAs as rounds 1-2 did (0).
-#ifndef WA_PV_OPERANDS_FIRST
-#define WA_PV_OPERANDS_FIRST 1
-#endif
-
 
 namespace {
-
-typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct WinArgs {
     const f16* qkv;
@@ -58,36 +50,9 @@ struct WinArgs {
     float scale_log2e, inv_scale;
 };
 
-template <int WS, int P, int LOG2P, int WPI>
-struct WinCfg {
-    static constexpr int RP = (WS * P + 31) / 32 * 32;  // key rows (64 / 224)
-    static constexpr int NKT = RP / 16;                 // 16-key tiles
-    static constexpr int NQT = (WS * WS + 15) / 16;     // 16-query tiles over the DENSE token order (4 / 13)
-    static constexpr int IPW = 4 / WPI;
-    static constexpr int ROWB = 64;
-    // bias-table row stride (floats).  ws 14: 48, not 32 - with a 32-float stride the two token rows a query tile
-    // spans land on the same LDS banks (2-way conflicts on 28 % of the table reads); 48 shifts them by 16 banks.
-    static constexpr int TW = (P == 16) ? 48 : 2 * P;
-    static constexpr int KSTEP = TW * 16 / P;           // table-offset step of one 16-key tile
-    static constexpr int KCMAX = KSTEP * NKT;
-    static constexpr int NEGSZ = KCMAX + 4;
-    static constexpr int TOFF = NEGSZ + KCMAX;
-    static constexpr int TROWS = 2 * WS - 1;
-    static constexpr int TB_FLOATS = TOFF + TROWS * TW;
-    static constexpr int K_OFF = 0;
-    static constexpr int V_OFF = RP * ROWB;
-    static constexpr int T_OFF = 2 * RP * ROWB;
-    static constexpr int ITEM_BYTES = (T_OFF + TB_FLOATS * 4 + 15) / 16 * 16;
-    static constexpr int SMEM = ITEM_BYTES * IPW;
-    static constexpr int QPW = (NQT + WPI - 1) / WPI;   // query tiles per wave
-};
-
-__device__ __forceinline__ int k_slot(int row, int ch) {
-    const int q = (row >> 2) & 3;
-    return ch ^ ((0x78 >> (q * 2)) & 3);  // pi = {0,2,3,1}
-}
-
-// One 16-query tile of one (window, head) item: S^T = K Q^T, bias, softmax, O^T = V^T P^T, store.  Shared by both kernels.
+// One 16-query tile of one (window, head) item: S^T = K Q^T, bias, softmax, O^T = V^T P^T, store.  Shared by both kernels.  Up to the
+// store this is win_attn_tile<Cfg, true, true> of window_core.hpp, kept as its own text: built on that function (or on pieces of it) all
+// three kernels' code changes.
 template <int WS, int P, int LOG2P, int WPI>
 __device__ __forceinline__ void win_query_tile(const WinArgs& a, const U4H8& qfrag, const char* k_lds, const char* v_lds,
                                                const float* tb, int qt, int l15, int g, bool item_ok, long img_pix, int wy,
@@ -133,40 +98,17 @@ __device__ __forceinline__ void win_query_tile(const WinArgs& a, const U4H8& qfr
 #pragma unroll
         for (int t = 0; t < NKT; ++t) {
             const int row = t * 16 + l15;
-            kf[t].u = *reinterpret_cast<const uint4*>(k_lds + row * Cfg::ROWB + k_slot(row, g) * 16);
+            kf[t].u = *reinterpret_cast<const uint4*>(k_lds + row * Cfg::ROWB + win_k_slot(row, g) * 16);
         }
 #pragma unroll
         for (int t = 0; t < NKT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[t].h, qfrag.h, acc[t], 0, 0, 0);
-        float m = -1.0e30f;
-#pragma unroll
-        for (int t = 0; t < NKT; ++t) {
-            m = fmaxf(fmaxf(m, acc[t][0]), acc[t][1]);   // v_max3_f32
-            m = fmaxf(fmaxf(m, acc[t][2]), acc[t][3]);
-        }
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        const f32x2 nm = {-m * sc, -m * sc};
-        f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < NKT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-                const f32x2 e = (f32x2){acc[t][r], acc[t][r + 1]} * sc + nm;      // v_pk_fma_f32
-                const f32x2 p = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-                acc[t][r] = p.x;
-                acc[t][r + 1] = p.y;
-                ls2 += p;                                                         // v_pk_add_f32
-            }
-        }
-        float lsum = ls2.x + ls2.y;
-        lsum += __shfl_xor(lsum, 16, 64);
-        lsum += __shfl_xor(lsum, 32, 64);
+        const float m = win_score_max<NKT>(acc);
+        const float lsum = win_softmax_exp2<NKT>(acc, m, sc);
 
         // O^T = V^T P^T : A = V^T (two 16-wide head-dim tiles) via transposed LDS reads, B = P^T from the
         // accumulators: MFMA k-slot (g, j) carries key 32s + 4g + j (j < 4) / 32s + 16 + 4g + (j-4).
         f32x4 o[2];
         o[0] = o[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#if WA_PV_OPERANDS_FIRST
         U4H8 pfa[NKT / 2];
         union VF {
             fp16x4_t t[2];
@@ -193,34 +135,9 @@ __device__ __forceinline__ void win_query_tile(const WinArgs& a, const U4H8& qfr
         for (int s = 0; s < NKT / 2; ++s)
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vfa[s][dt].v, pfa[s].h, o[dt], 0, 0, 0);
-#else
-#pragma unroll
-        for (int s = 0; s < NKT / 2; ++s) {
-            U4H8 pf;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                pf.e[j] = (f16)acc[2 * s][j];
-                pf.e[4 + j] = (f16)acc[2 * s + 1][j];
-            }
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                union {
-                    fp16x4_t t[2];
-                    f16x8 v;
-                } vf;
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const int row = 32 * s + 16 * hh + 4 * g + tr_q;
-                    const int half = dt ^ ((row >> 2) & 1);  // = dt ^ (g & 1): 32-byte halves swapped on odd row quads
-                    vf.t[hh] = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                        (__attribute__((address_space(3))) fp16x4_t*)(v_lds + row * Cfg::ROWB + half * 32 + tr_p * 8));
-                }
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf.v, pf.h, o[dt], 0, 0, 0);
-            }
-        }
-#endif
 
-        // store: lane owns query qn, head-dim d = 16*dt + 4g + (0..3).  Lane pairs (g, g^1) swap one 8-byte half so
+        // store (the same lines as swin_attn.hip's: as one shared function returning the 16-byte value both files' code changes):
+        // lane owns query qn, head-dim d = 16*dt + 4g + (0..3).  Lane pairs (g, g^1) swap one 8-byte half so
         // that every lane holds 8 CONSECUTIVE channels and the four lanes of a token write its whole 64-byte head
         // slice with one 16-byte store each (two 8-byte stores per lane left 32-byte fragments in every line).
         {
@@ -264,13 +181,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_kernel(WinArgs a) {
     const int lt = tid - slot * WPI * 64;
     // XCD-aware block order: consecutive logical blocks (the heads of one window: neighbouring 64-byte slices of the
     // same 128-byte lines) run on the same XCD and share its L2, instead of each XCD fetching the line for itself
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     int item = bid * Cfg::IPW + slot;
     const bool item_ok = item < a.items;
     if (!item_ok) item = a.items - 1;
@@ -333,7 +244,8 @@ __global__ __launch_bounds__(256, 2) void window_attn_kernel(WinArgs a) {
             const int rem = s - arr * (RP * 4);
             const int row = rem >> 2, ch = rem & 3;
             if (s < NSLOT) {
-                const int pch = (arr == 0) ? k_slot(row, ch) : (ch ^ (((row >> 2) & 1) << 1));
+                // V: chunk win_v_chunk(row, ch), written out: as a call here the kernels' code changes
+                const int pch = (arr == 0) ? win_k_slot(row, ch) : (ch ^ (((row >> 2) & 1) << 1));
                 *reinterpret_cast<uint4*>((arr == 0 ? k_lds : v_lds) + row * Cfg::ROWB + pch * 16) = st[it];
             }
         }
@@ -343,13 +255,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_kernel(WinArgs a) {
         float tv[TIT];
 #pragma unroll
         for (int it = 0; it < TIT; ++it) {
-            const int i = lt + it * NTHR;
-            const int e = i - Cfg::TOFF;
-            const int ry = e / Cfg::TW, rx = e - ry * Cfg::TW;
-            const bool in_tab = (i >= Cfg::TOFF) & (i < Cfg::TB_FLOATS) & (rx < Cfg::TROWS);
-            const int gi = in_tab ? (ry * Cfg::TROWS + rx) * a.heads + head : 0;
-            const float t = a.table[gi];
-            tv[it] = in_tab ? t * a.inv_scale : (i < Cfg::TOFF ? -1.0e30f : 0.f);
+            tv[it] = win_table_value<Cfg, true>(a.table, a.heads, head, lt + it * NTHR, a.inv_scale);
         }
 #pragma unroll
         for (int it = 0; it < TIT; ++it) {
@@ -401,13 +307,9 @@ __global__ __launch_bounds__(256, 2) void window_attn_pipe_kernel(WinArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    int lb = blockIdx.x;
     const int nblk = gridDim.x;
-    {   // XCD-aware order: consecutive logical blocks = the heads of one window (neighbouring 64-byte slices of the same lines)
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = lb & 7, idx = lb >> 3;
-        lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // XCD-aware order: consecutive logical blocks = the heads of one window (neighbouring 64-byte slices of the same lines)
+    const int lb = xcd_remap(blockIdx.x, nblk);
     const int head = lb % a.heads;                               // the same for every item of this block (nblk % heads == 0)
     const int ldq = a.nq * a.C;
 
@@ -425,7 +327,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_pipe_kernel(WinArgs a) {
             const int j = wave + 4 * i;
             const int arr = j / (RP / 16), ty = j - arr * (RP / 16);
             const int row = ty * 16 + tx;
-            const int ch = arr == 0 ? k_slot(row, pc) : (pc ^ (((row >> 2) & 1) << 1));     // both swizzles are involutions
+            const int ch = arr == 0 ? win_k_slot(row, pc) : win_v_chunk(row, pc);     // both swizzles are involutions
             const bool valid = (tx < WS) & (ty < WS);
             rel[i] = valid ? (unsigned)(((ty * a.Wp + tx) * ldq + (a.nq - 2 + arr) * a.C + head * 32 + ch * 8) * 2) : OOB;
             dlds[i] = (unsigned)(arr * RP * Cfg::ROWB + ty * 1024);
@@ -478,15 +380,7 @@ __global__ __launch_bounds__(256, 2) void window_attn_pipe_kernel(WinArgs a) {
         constexpr int TIT = (Cfg::TB_FLOATS + 255) / 256;
         float tv[TIT];
 #pragma unroll
-        for (int it = 0; it < TIT; ++it) {
-            const int i = tid + it * 256;
-            const int e = i - Cfg::TOFF;
-            const int ry = e / Cfg::TW, rx = e - ry * Cfg::TW;
-            const bool in_tab = (i >= Cfg::TOFF) & (i < Cfg::TB_FLOATS) & (rx < Cfg::TROWS);
-            const int gi = in_tab ? (ry * Cfg::TROWS + rx) * a.heads + head : 0;
-            const float t = a.table[gi];
-            tv[it] = in_tab ? t * a.inv_scale : (i < Cfg::TOFF ? -1.0e30f : 0.f);
-        }
+        for (int it = 0; it < TIT; ++it) tv[it] = win_table_value<Cfg, true>(a.table, a.heads, head, tid + it * 256, a.inv_scale);
 #pragma unroll
         for (int it = 0; it < TIT; ++it) {
             const int i = tid + it * 256;
@@ -546,6 +440,8 @@ int launch_win_pipe(const WinArgs& a, hipStream_t s) {
 }
 
 #endif  // VIP_BUILD_EXPERIMENTS
+
+static_assert(WinCfg<7, 8, 3, 1>::SMEM == 4 * 10064 && WinCfg<14, 16, 4, 4>::SMEM == 39248, "LDS per workgroup of the two window sizes");
 
 template <int WS, int P, int LOG2P, int WPI>
 int launch_win(const WinArgs& a, hipStream_t s) {
