@@ -1265,6 +1265,32 @@ int vip_swin_attn_fwd_s32(const float* qkv, const float* v_bias, const float* ta
 int vip_swin_attn_fwd_h2(const void* qkv, const float* v_bias, const float* tau, const float* bias_table, void* out, int B, int H, int W,
                          int C, int heads, int ws, int shift, int* status, void* stream);
 
+/* ---- Neighbourhood attention (csrc/nat_attn.hip) ------------------------------------------------------------------------------------
+ * Everything between the `qkv` Dense and the `output` Dense of kecam nat/nat.py:65-116 (`neighborhood_attention` with
+ * `MultiHeadRelativePositionalKernelBias`) in one launch on the UNPADDED map, on the three storages (_f16: fp16, _s32: fp32, _h2: packed
+ * (hi, lo) pairs with the status word of the other packed producers).
+ *   qkv [B][H][W][3C], channels (q|k|v, head, 32) - the output of the layer's qkv Dense as it stands; out [B][H][W][C];
+ *   kv_pad fp32 [2C] (k | v) or NULL (zeros): the key and value of a PADDED token - the k | v part of the qkv Dense's bias, since the
+ *   layer zero-pads a map below the kernel BEFORE that Dense;
+ *   table fp32 [heads][(2K-1)^2]: the layer's `positional_embedding`; K = kernel_size in {3, 5, 7}.
+ * With r = K / 2, Hp = max(H, K), Wp = max(W, K) the query at (y, x), y < H, x < W, attends to the K x K block with the origin
+ *   sy = clamp(y - r, 0, Hp - K), sx = clamp(x - r, 0, Wp - K):
+ *   logit(ky, kx) = 2^-2.5 q . k[ky, kx] + table[head][(ky - y + K - 1)(2K - 1) + (kx - x + K - 1)]     (ky, kx) in [sy, sy+K) x [sx, sx+K)
+ *   out[b, y, x, head 32 + :] = softmax over the K^2 keys of the block (logit) . v
+ * The table index is the absolute key-minus-query offset, not the key's position inside the clamped block.  A token with ky >= H or
+ * kx >= W (only when the map is below the kernel) is padded: k | v = kv_pad, it is a key of every block that holds it, never a query,
+ * never stored.  No atomics: bit-reproducible, independent of the batch.  K outside {3, 5, 7}, C != 32 heads, sizes beyond the plan's
+ * range: VIP_ERR_UNSUPPORTED. */
+/* dry run on the host, nothing is launched: 1 and *Hp, *Wp (the padded map), *items = B * ceil(H / 8) * ceil(W / 8) * heads (the work
+ * items of a launch: 8 x 8 query tiles per head), or 0 when the launch would be refused */
+int vip_nat_attn_plan(int B, int H, int W, int heads, int kernel_size, int* Hp, int* Wp, int* items);
+int vip_nat_attn_fwd_f16(const void* qkv, const float* kv_pad, const float* table, void* out, int B, int H, int W, int C, int heads,
+                         int kernel_size, void* stream);
+int vip_nat_attn_fwd_s32(const float* qkv, const float* kv_pad, const float* table, float* out, int B, int H, int W, int C, int heads,
+                         int kernel_size, void* stream);
+int vip_nat_attn_fwd_h2(const void* qkv, const float* kv_pad, const float* table, void* out, int B, int H, int W, int C, int heads,
+                        int kernel_size, int* status, void* stream);
+
 /* Which kernel vip_conv2d_nhwc_f16 / _gated_ / _hilo_ would launch for this descriptor ("pw_gemm_kernel",
  * "pwk_direct_kernel", "pwk_gemm_kernel", "pwk_gemm_kernel(im2col)", "rows_gemm_kernel", "conv_igemm_kernel"):
  * the dispatcher itself in a dry run, nothing is launched.  Used to label profiler records (bench.py roofline). */

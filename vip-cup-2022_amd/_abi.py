@@ -234,6 +234,11 @@ SIGNATURES = {
     "vip_swin_attn_fwd_f16": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     "vip_swin_attn_fwd_s32": (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     "vip_swin_attn_fwd_h2": (_i, [_vp] * 5 + [_i] * 7 + [_vp, _vp]),
+    # neighbourhood attention: csrc/nat_attn.hip
+    "vip_nat_attn_plan": (_i, [_i] * 5 + [C.POINTER(_i)] * 3),
+    "vip_nat_attn_fwd_f16": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    "vip_nat_attn_fwd_s32": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    "vip_nat_attn_fwd_h2": (_i, [_vp] * 4 + [_i] * 6 + [_vp, _vp]),
     "vip_conv2d_kernel_name": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_conv2d_kernel_variant": (_i, [C.POINTER(ConvDesc), _i, _i, _i, C.c_char_p, _sz]),
     "vip_workspace_bytes": (_sz, [_i, C.POINTER(C.c_int64), _i]),

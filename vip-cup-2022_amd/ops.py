@@ -184,6 +184,7 @@ _KIND_OPS = {
     "window_attn_fwd": (_ALL_KINDS, True),
     "global_local_filter_nhwc": (_ALL_KINDS, True),
     "swin_attn_fwd": (_ALL_KINDS, True),
+    "nat_attn_fwd": (_ALL_KINDS, True),
     "cam": ({"f16": "f32", "s32": "s32", "h2": "h2"}, False),
     "scale_add_act": (_STRICT_KINDS, True),
     "radix_combine": (_STRICT_KINDS, True),
@@ -1651,6 +1652,43 @@ def make_swin_bias_table(meta1_kernel, meta1_bias, meta2_kernel, ws: int, pos_sc
     k1, b1, k2 = (t.detach().to("cpu", torch.float64) for t in (meta1_kernel, meta1_bias, meta2_kernel))
     t = torch.relu(c @ k1 + b1) @ k2
     return (16.0 * torch.sigmoid(t)).to(torch.float32).contiguous().to(device)
+
+
+NAT_KERNEL_SIZES = (3, 5, 7)
+
+
+def nat_attention(qkv, kv_pad, table, heads: int, kernel_size: int = 7):
+    """kecam ``neighborhood_attention`` between its ``qkv`` and ``output`` Dense layers (nat/nat.py:65-116) as one launch on the unpadded
+    map: qkv ``[B,H,W,3C]`` (channels (q|k|v, head, 32), the qkv Dense's output as it stands) -> ``[B,H,W,C]``.  Every query attends to
+    the ``kernel_size`` x ``kernel_size`` block around it, clamped at the map's edge, under ``table`` fp32 ``[heads, (2K-1)^2]`` (the
+    layer's ``positional_embedding``) indexed by the key-minus-query offset.  ``kv_pad`` fp32 ``[2C]`` or None (zeros): k | v of a padded
+    token where the map is below the kernel - the k | v part of the qkv Dense's bias.  Patch extraction, replicate padding, the bias
+    gather and the crop are addressing inside the kernel (include/vipcup_hip.h has the formulas)."""
+    kind = _kind(qkv, "nat_attention.qkv")
+    B, H, W, C3 = qkv.shape
+    Cc = C3 // 3
+    _chk32(table, "nat_attention.table")
+    if kv_pad is not None:
+        _chk32(kv_pad, "nat_attention.kv_pad")
+    if C3 != 3 * Cc or tuple(table.shape) != (heads, (2 * kernel_size - 1) ** 2) or (kv_pad is not None and tuple(kv_pad.shape) != (2 * Cc,)):
+        raise _abi.VipError(f"nat_attention: qkv {tuple(qkv.shape)} with {heads} heads and kernel_size {kernel_size} needs table "
+                            f"({heads}, {(2 * kernel_size - 1) ** 2}) and kv_pad ({2 * Cc},) or None, got {tuple(table.shape)}, "
+                            f"{None if kv_pad is None else tuple(kv_pad.shape)}")
+    out = torch.empty((B, H, W, Cc), dtype=qkv.dtype, device=qkv.device)
+
+    def prof():
+        return ("nat_attn_kernel", B * H * W * heads * 4.0 * kernel_size ** 2 * 32, B * H * W * 4.0 * Cc * 2,
+                f"nat attn k{kernel_size} C={Cc} heads={heads} map={H}x{W}")
+    _launch_kind("nat_attn_fwd", kind, _p(qkv), _p(kv_pad), _p(table), _p(out), B, H, W, Cc, heads, kernel_size,
+                 prof=prof if kind == "f16" else None)
+    return out
+
+
+def nat_attn_plan(B: int, H: int, W: int, heads: int, kernel_size: int = 7):
+    """dry run of ``nat_attention``: (Hp, Wp, work items = B * 8 x 8 query tiles * heads), None when the launch would be refused"""
+    hp, wp, items = C.c_int(0), C.c_int(0), C.c_int(0)
+    ok = _abi.lib().vip_nat_attn_plan(B, H, W, heads, kernel_size, C.byref(hp), C.byref(wp), C.byref(items))
+    return (hp.value, wp.value, items.value) if ok == 1 else None
 
 
 def make_dw_weight(depthwise_kernel_hwc1: torch.Tensor, scale: Optional[torch.Tensor] = None, device="cuda") -> torch.Tensor:

@@ -11,7 +11,7 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import gcvit, hornet, kecam_models as km, resnet_rs, swin_v2, tfimm_models as tm
+from . import gcvit, hornet, kecam_models as km, nat, resnet_rs, swin_v2, tfimm_models as tm
 
 
 @dataclass
@@ -26,7 +26,7 @@ class MemberSpec:
     gmac_per_image: float  # algorithmic GMAC / image
     head: str = "predictions"  # Keras name of the classifier Dense
     family: str = ""           # constructor-argument dialect for checkpoint variants (variant_kwargs): `oracle` when empty; given
-                               # explicitly by a family that has no module under oracle/ ("swin_v2")
+                               # explicitly by a family that has no module under oracle/ ("swin_v2", "nat")
 
 
 MEMBERS: Dict[str, MemberSpec] = {
@@ -88,6 +88,18 @@ MEMBERS: Dict[str, MemberSpec] = {
         lambda seed: swin_v2.synth_params(swin_v2.CONFIGS["swin_transformer_v2_base_window8"], seed, input_hw=224),
         lambda p, **kw: swin_v2.SwinV2(p, **swin_v2.CONFIGS["swin_transformer_v2_base_window8"], input_hw=224, **kw), "",
         round(swin_v2.gmac_per_image(swin_v2.CONFIGS["swin_transformer_v2_base_window8"], 224), 3), family="swin_v2"),
+    # Neighbourhood Attention Transformer (nat.py:182-207): built for the manifest's resolution - whether a stack's blocks pad follows
+    # from its map (50, 25, 13, 7 at 200 pixels; 56, 28, 14, 7 at 224: no stack is below the 7 x 7 kernel).  gmac_per_image =
+    # nat.gmac_per_image(cfg, input_hw): the stem's two convolutions, per block and token (4 + 2 r) C^2 + 98 C, 9 C_in C_out per
+    # downsampled token, C * classes for the head
+    "nat_mini": MemberSpec("nat_mini", "NAT_Mini-200x200", 200, 1038,
+        lambda seed: nat.synth_params(nat.CONFIGS["nat_mini"], seed, input_hw=200),
+        lambda p, **kw: nat.NAT(p, **nat.CONFIGS["nat_mini"], input_hw=200, **kw), "",
+        round(nat.gmac_per_image(nat.CONFIGS["nat_mini"], 200), 3), family="nat"),
+    "nat_base": MemberSpec("nat_base", "NAT_Base-224x224", 224, 1039,
+        lambda seed: nat.synth_params(nat.CONFIGS["nat_base"], seed, input_hw=224),
+        lambda p, **kw: nat.NAT(p, **nat.CONFIGS["nat_base"], input_hw=224, **kw), "",
+        round(nat.gmac_per_image(nat.CONFIGS["nat_base"], 224), 3), family="nat"),
     "gcvit_base": MemberSpec("gcvit_base", "GCViTBase-224x224", 224, 1022,
                              lambda seed: gcvit.synth_params(gcvit.NAME2CONFIG["gcvit_base"], seed),
                              lambda p, **kw: gcvit.GCViT(p, **gcvit.NAME2CONFIG["gcvit_base"], **kw), "gcvit_ref", 14.3, "head"),
@@ -417,8 +429,8 @@ def variant_kwargs(spec: MemberSpec, info: dict) -> dict:
         if classes is not None and "nb_classes" not in kw:
             kw["nb_classes"] = classes
         return kw
-    if fam == "swin_v2":                                # a 4x4 stride-4 patch stem: no first_strides argument, nothing to identify
-        fs = None
+    if fam in ("swin_v2", "nat"):                       # a 4x4 stride-4 patch stem / a fixed two-convolution stem: no first_strides
+        fs = None                                       # argument, nothing to identify
     elif fs is None and "stem_strides" in info:
         # the constructor argument behind the stem convolution's stride: HorNet's stem runs at first_strides * 2 (kecam
         # hornet/hornet.py:144), every other family's at first_strides itself (resnet_rs_model.py:97-104, aotnet.py:326,
@@ -430,7 +442,7 @@ def variant_kwargs(spec: MemberSpec, info: dict) -> dict:
             fs = ss // 2
         else:
             fs = ss
-    if fs is None and info.get("n_layers", 0) > 1 and fam not in ("gcvit_ref", "swin_v2"):
+    if fs is None and info.get("n_layers", 0) > 1 and fam not in ("gcvit_ref", "swin_v2", "nat"):
         raise ValueError(f"{spec.ckpt_name}: the checkpoint's model_config lists {info['n_layers']} layers but no stem convolution with "
                          "strides could be identified - refusing to assume first_strides")
     if classes is not None and classes != 1:
