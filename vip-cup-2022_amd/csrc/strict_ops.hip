@@ -66,8 +66,10 @@ __global__ __launch_bounds__(256) void spool2d_kernel(const void* __restrict__ x
                     ++cnt;
                 }
                 if (mode == 0) {
+                    // the NaN-propagating maximum (v_maximum3_f32, one instruction like v_max_f32): fmaxf drops a NaN tap, and the
+                    // range check of the store below would never see it
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = fmaxf(acc[j], v[j]);
+                    for (int j = 0; j < 4; ++j) acc[j] = __builtin_elementwise_maximum(acc[j], v[j]);
                 } else {
                     acc += v;
                 }

@@ -264,6 +264,14 @@ def score_files(jpegs_for: Callable[[int, int], List[bytes]], n_images: int, mem
             for j, m in enumerate(midx):
                 chunks.setdefault((s, m), []).append(rows[j])
     local = {k: torch.cat(v) for k, v in chunks.items()}
+    if scorer is None:
+        from . import ops
+        if any(model is not None and member_dtype(model) == ops.PACKED for _, model in members):
+            # packed strict members: no activation of any batch left the fp16 range of the storage.  The word is sticky, so ONE read
+            # after the last batch covers them all, and the copy to the host below synchronises anyway: read-ahead and stream overlap
+            # are untouched.  With several ranks the one that overflowed raises HERE, before the collective below, like any exception
+            # in the middle of a run: the launcher ends the job, the other ranks do not get scores either
+            ops.h2_check("score_files")
     dev = None
     if not local:
         dev = torch.device("cuda" if (scorer is None and torch.cuda.is_available()) else "cpu")

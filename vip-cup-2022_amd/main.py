@@ -537,8 +537,11 @@ def main(argv=None):
                          "image (one model per GPU); hybrid = LPT packing by measured ms/image.  One all-gather in every mode.")
     ap.add_argument("--precision", default=None, choices=["fast", "strict", "f32"],
                     help="fast (default; env VIP_PRECISION): fp16 storage, the throughput path - member logits at the fp16 storage floor "
-                         "(7e-4 ... 8e-3 vs an fp32 run).  strict: fp32 storage and fp32 matrix arithmetic, what the reference's "
-                         "TensorFlow run computes in (main.py:107-109): every member's logit within 1e-3 of it, ~3.5x slower.")
+                         "(7e-4 ... 8e-3 vs an fp32 run).  strict: every activation and weight stored as a pair of fp16 values (hi, lo: "
+                         "22 significant bits), fp32 accumulation - every member's logit within 1e-3 of the reference's fp32 "
+                         "TensorFlow run (main.py:107-109); a value must satisfy |v| <= 65504, and a run in which an activation "
+                         "leaves that range ends with an error that says to switch to f32.  f32: fp32 storage and fp32 matrix "
+                         "arithmetic, no range limit, the slowest of the three.")
     ap.add_argument("--calibration-images", default=None, metavar="DIR",
                     help="fast mode: a directory of JPEGs (up to 32 are read) for the bias calibration of the fp16 weights instead of the "
                          "built-in seeded synthetic batch - use real images with real checkpoints (the correction needs typical "

@@ -1734,11 +1734,13 @@ def build_dataset(paths, labels=None, batch_size=32, cache=True, decode_fn=None,
                    drop_remainder, seed, num_classes, device, threads, ops.act_dtype(mode))
 
 
-def predict_dataset(predict_batch, dataset, steps=None, verbose=0) -> np.ndarray:
+def predict_dataset(predict_batch, dataset, steps=None, verbose=0, precision=None) -> np.ndarray:
     """``tf.keras.Model.predict(dataset, steps)`` (main.py:109): run ``predict_batch`` over ``ceil(steps)`` batches of the
     iterable (Keras' data handler keeps stepping while ``step < steps``, so the reference's fractional
     ``steps = max(tta * n / batch, 1)`` means its ceiling; ``None`` = until the dataset ends) and return the concatenated
-    predictions as a numpy array ``[sum of batch sizes, C]`` - the caller slices off what the repeat padded (main.py:110)."""
+    predictions as a numpy array ``[sum of batch sizes, C]`` - the caller slices off what the repeat padded (main.py:110).
+    ``precision`` "strict" (the model's): the packed storage's status word is read once, after the last batch and before the copy to the
+    host (``ops.h2_check``: it raises when an activation left the fp16 range and names ``--precision f32``)."""
     import itertools
     import math
     limit = None if steps is None else int(math.ceil(float(steps)))
@@ -1754,6 +1756,9 @@ def predict_dataset(predict_batch, dataset, steps=None, verbose=0) -> np.ndarray
         print()
     if not outs:
         return np.zeros((0, 1), dtype=np.float32)
+    if precision == "strict":
+        from . import ops
+        ops.h2_check("predict(dataset)")
     return torch.cat([o.float() for o in outs], 0).cpu().numpy()
 
 
@@ -1773,7 +1778,7 @@ def keras_predict(cls):
     def predict(self, x, steps=None, verbose=0, **_keras_kwargs):
         if isinstance(x, torch.Tensor):
             return checked(self, x)
-        return predict_dataset(lambda t: checked(self, t), x, steps, verbose)
+        return predict_dataset(lambda t: checked(self, t), x, steps, verbose, precision=getattr(self, "precision", None))
     predict.__doc__ = batch_predict.__doc__
     cls.predict = predict
     return cls
